@@ -12,6 +12,11 @@ ViT (CLIP-L/14 @224) -> mlp2x_gelu projector -> splice -> Qwen2.5-7B-class decod
 -> DiT-B diffusion loss (4 repeats) -> backward -> [RCCL gradient all-reduce] -> global-norm clip -> fused AdamW.
 Random-init weights at the REAL shapes (no checkpoints offline), bf16 compute with fp32 master weights,
 fp32 action head; nothing is skipped inside the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the `--steps` steps and prints the line (`value` episodes/s, `ms_per_step`).  `--full`
+adds what takes runs or instrumentation of its own: the live GEMM roofline over the timed steps, the reference recipe 8 x 2,
+the 8-rank emulated step, action-inference latency, the CPU baseline and the secondary workloads (the `--no-*` options skip
+single ones).  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -342,6 +347,24 @@ def secondary_workloads(timeout_s: float = 150.0) -> dict:
     return out
 
 
+DUMP_SAMPLE = 1 << 21      # arena positions --dump-outputs samples (8 MB per fp32 array)
+
+
+def dump_outputs(out_dir: str, trainer, loss: torch.Tensor, with_grad: bool) -> None:
+    """what the last timed step hands its caller, as float32 .npy files: ``loss`` (the value trainer.step returned),
+    ``master_sample`` (the fp32 master weights AdamW just wrote) and, with ``with_grad``, ``grad_sample`` (the gradients it
+    read), both at the same DUMP_SAMPLE positions of the flat arena drawn with a fixed seed (the arena holds 8 G values)"""
+    os.makedirs(out_dir, exist_ok=True)
+    store = trainer.store
+    store.wait_pending()
+    idx = torch.from_numpy(np.unique(np.random.default_rng(0).integers(0, store.total, DUMP_SAMPLE))).to(store.device)
+    arrays = {"loss": loss.detach().float().reshape(()), "master_sample": store.master[idx]}
+    if with_grad:
+        arrays["grad_sample"] = (store.gradc if store.bf16_grads else store.grad)[idx].float()
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -351,6 +374,13 @@ def main():
     ap.add_argument("--views", type=int, default=1)
     ap.add_argument("--s-text", dest="s_text", type=int, default=32)
     ap.add_argument("--dtype", default="bfloat16", choices=["bfloat16", "float32"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also measure the live GEMM roofline (HIP events inside the timed steps), the "
+                         "reference recipe, the 8-rank emulated step, action-inference latency, the CPU baseline and the secondary "
+                         "workloads.  Off: only the headline figure")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's loss, updated master weights and gradients (a fixed, "
+                         "seeded sample of the arena) as DIR/<name>.npy")
     ap.add_argument("--llm-layers", dest="llm_layers", type=int, default=28)
     ap.add_argument("--vit-layers", dest="vit_layers", type=int, default=24)
     ap.add_argument("--force-reducer", action="store_true",
@@ -429,6 +459,9 @@ def main():
     # whole process throttled; DXA_HOST_THREADS=0 leaves torch's default for an A/B)
     from dexbotic_amd import hostcpu
     host_threads = hostcpu.limit_host_threads()
+    # the diffusion draws (noise, timesteps, CFG drops) come from torch's generators, which an unseeded process seeds at
+    # random: seeded here, so that equal arguments give equal inputs on every run
+    torch.manual_seed(0)
     model, cfg, llm, vis = build_model(args, device)
     model.train()
     if args.recompute:
@@ -467,7 +500,7 @@ def main():
     # dominant kernel: gemm_pp_kernel, whose three instantiations carry every large product of the step:
     # NT (forward linears, bf16 out), NN (dX = dY W, bf16 out), TN (dW = dY^T X, fp32 out into the gradient arena)
     prof_keys = {"NT fwd": (L.NT, in_dt, in_dt), "NN dX": (L.NN, in_dt, in_dt), "TN dW": (L.TN, in_dt, L.F32)}
-    prof = K.GemmProfile(*set(prof_keys.values()), stride=args.profile_stride)
+    prof = K.GemmProfile(*set(prof_keys.values()), stride=args.profile_stride) if args.full else None
     K.GEMM_PROFILE = prof if rank == 0 else None
     cg0 = hostcpu.throttle_stats()
     t0 = time.perf_counter()
@@ -477,6 +510,10 @@ def main():
     dt = time.perf_counter() - t0
     cg1 = hostcpu.throttle_stats()
     K.GEMM_PROFILE = None
+    if args.dump_outputs:
+        trainer.consolidate()               # (sharded step: every rank's fp32 masters up to date; all ranks take part)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, trainer, loss, with_grad=world == 1)
     comm_stats = None
     if trainer.reducer is not None and not trainer.reducer.local_only:
         # (before the recipe figure below runs more optimizer steps through the same reducer)
@@ -495,7 +532,7 @@ def main():
                                          if trainer.sharded else "replicated: reduce-scatter + all-gather of gradients, full adamw per rank"),
                       "weights_gathered_gb_per_step": round(red.bytes_gathered / n_opt / 1e9, 3) if trainer.sharded else None}
     recipe = None
-    if not args.no_recipe and args.accum == 1 and args.batch % 2 == 0 and not args.static_batch:
+    if args.full and not args.no_recipe and args.accum == 1 and args.batch % 2 == 0 and not args.static_batch:
         # second figure: the reference recipe, 8 episodes x 2 accumulation steps per GPU per optimizer
         # step (cogact_exp.py:41-46), measured twice: pass by pass (half-height GEMM grids; the linears' dW is one product over both
         # micro-batches' (dY, X) pairs) and with the group coalesced into one pass
@@ -539,8 +576,8 @@ def main():
     loss_val = float(loss.item())
     peak_main = torch.cuda.max_memory_allocated(device)
     dp_emu = None
-    if world == 1 and not args.no_dp_emulation and not args.force_reducer and args.dtype == "bfloat16" and args.accum == 1 \
-            and not args.overlap:
+    if args.full and world == 1 and not args.no_dp_emulation and not args.force_reducer and args.dtype == "bfloat16" \
+            and args.accum == 1 and not args.overlap:
         # what ONE rank of an 8-rank data-parallel step does locally, on the one GPU there is (SCALE runs need an 8-GPU node this
         # repo never had): the RCCL collectives of the real sequence over the whole slices at world size 1 (bf16 exchange, SUM) on
         # the communication stream under the backward, the sum of squares, AdamW — sharded: over rank 0's 1/8 of the arena, then
@@ -620,7 +657,7 @@ def main():
     if dp_emu is not None:
         result["dp8_emulated_ms_per_step"] = dp_emu.get("sharded_ms_per_step")
         result["dp8_emulated"] = dp_emu
-    if rank == 0:
+    if rank == 0 and args.full:
         n, ms, fl, by = prof.summary()
         ach = fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
         # HBM bytes per launch of that kernel come from the committed rocprofv3 PMC passes over this same command
@@ -717,6 +754,7 @@ def main():
             gc.collect()
             torch.cuda.empty_cache()
             result["secondary"] = secondary_workloads()
+    if rank == 0:
         print(json.dumps(result), flush=True)
     if dist.is_initialized():
         dist.barrier()

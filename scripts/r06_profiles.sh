@@ -7,8 +7,8 @@ B="python $R/bench.py --no-cpu-baseline --no-latency --no-secondary --no-recipe 
 for w in $what; do case $w in
 tests)   # the GPU suite
   timeout 1500 python -m pytest tests -m gpu -q 2>&1 | grep -v "^ROCm version\|^Hostname\|^Librccl\|^RCCL\|^HIP version" | tail -6 | tee gpurun_out/r06_gpu_tests.txt ;;
-bench)   # the default driver-style line
-  timeout 1200 python bench.py > gpurun_out/r06_bench_default.log 2>&1; grep "^{" gpurun_out/r06_bench_default.log > gpurun_out/r06_bench.json; cut -c1-700 gpurun_out/r06_bench.json ;;
+bench)   # the whole bench line with every secondary figure (--full), written straight to profiles/
+  timeout 1200 python bench.py --full > profiles/r06_bench_default.log 2>&1; grep "^{" profiles/r06_bench_default.log > profiles/r06_bench.json; cut -c1-700 profiles/r06_bench.json ;;
 trace)   # exact per-step kernel table of the headline step: difference of a 4- and a 10-step trace
   cd /tmp; export TMPDIR=/tmp
   for n in 3 9; do rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof -o tr$n -- $B --steps $n --warmup 1 > $R/gpurun_out/r06_trace_$n.log 2>&1; done
