@@ -1294,14 +1294,9 @@ __global__ __launch_bounds__(64 * NW, (D <= 128 && NW == 4 ? 2 : 1)) void attn_b
   // grid (kv head, batch, key tile): the key tile is the SLOWEST dimension of the dispatch order.  Under the causal mask key tile 0
   // is seen by every query tile and the last one by one (G x 5, 4, .. 1 iterations at S = 287): dealt tile-fastest, as until round
   // 5, a compute unit that drew a light workgroup first got a heavy one behind it (makespan 42 units for 26 of work); heaviest
-  // tiles first, the light ones fill in behind them (35)
-#if defined(DXA_ATTN_OLD_ORDER)        // tuning build: the grid of rounds 1-4 (scripts/build_variant.sh, profiles/r05_attn_order.txt)
-  const int b = blockIdx.z, hk = blockIdx.y;
-  const int key0 = blockIdx.x * 64;
-#else
+  // tiles first, the light ones fill in behind them (35; profiles/r05_attn_order.txt)
   const int b = blockIdx.y, hk = blockIdx.x;
   const int key0 = blockIdx.z * 64;
-#endif
   const int G = p.Hq / p.Hkv;
   const int key = key0 + (HS == 1 ? wave : (wave & 3)) * 16 + l16;
   const int di0 = HS == 1 ? 0 : (wave >> 2) * DIW;              // first 16-column block of dK / dV this wave accumulates
@@ -1479,17 +1474,15 @@ static bool wide_tiles(const dxa_attn_desc* d) {
 
 // the forward on row-major V tiles (attn_fwd_tr_k: the default since round 5, same results bit for bit — profiles/r05_attn_variants.txt:
 // head_dim 256 344 -> 198 us, 128 65 -> 52, 64 37.5 -> 27.7) loads V rows 16 bytes at a time; a V that is only 8-byte aligned
-// stays on attn_fwd_flash_k (DXA_ATTN_FWD_TR=0 sends everything there: A/B and the fallback's tests)
+// stays on attn_fwd_flash_k
 static bool fwd_tr_ok(const dxa_attn_desc* d) {
-  static const int on = getenv("DXA_ATTN_FWD_TR") ? atoi(getenv("DXA_ATTN_FWD_TR")) : 1;
-  return on && d->v_ss % 8 == 0 && d->v_sb % 8 == 0 && d->v_sh % 8 == 0 && al(d->v, 16);
+  return d->v_ss % 8 == 0 && d->v_sb % 8 == 0 && d->v_sh % 8 == 0 && al(d->v, 16);
 }
 
 // fp32 head-sized attention (attn_fwd_small_f32_k): the [16][Sk] score slab of a workgroup has to fit the LDS
 static bool fwd_small_f32_ok(const dxa_attn_desc* d) {
-  static const bool off = getenv("DXA_ATTN_NO_SMALL") != nullptr;
   auto s4 = [](int64_t a, int64_t b, int64_t c) { return a % 4 == 0 && b % 4 == 0 && c % 4 == 0; };
-  return !off && !d->force_generic && !d->drop_mask && d->dtype == DXA_F32 && (d->D == 32 || d->D == 64 || d->D == 96 || d->D == 128) &&
+  return !d->force_generic && !d->drop_mask && d->dtype == DXA_F32 && (d->D == 32 || d->D == 64 || d->D == 96 || d->D == 128) &&
          d->Sk <= 2048 && d->B <= 65535 && d->Hq <= 65535 && s4(d->q_sb, d->q_sh, d->q_ss) && s4(d->k_sb, d->k_sh, d->k_ss) &&
          s4(d->o_sb, d->o_sh, d->o_ss) && al(d->q, 16) && al(d->k, 16) && al(d->o, 16);
 }
@@ -1507,8 +1500,7 @@ static bool fwd_materialise(const dxa_attn_desc* d) {
 // EIGHT workgroups of the flash kernel, each walking 13 key tiles in sequence — 70 us): the keys are cut into ranges, one
 // workgroup per (query tile, head, batch, range), and the ranges' normalised partials are folded by their log-sum-exps.
 static int fwd_flash_splits(const dxa_attn_desc* d) {
-  static const int off = getenv("DXA_ATTN_NO_KSPLIT") != nullptr;
-  if (off || !fwd_flash_ok(d) || d->Sk < 512 || d->D == 72) return 1;      // (a 300-key decode step measured the same cut or whole: 4.63 vs 4.57 ms/token)
+  if (!fwd_flash_ok(d) || d->Sk < 512 || d->D == 72) return 1;      // (a 300-key decode step measured the same cut or whole: 4.63 vs 4.57 ms/token)
   const int64_t wgs = (int64_t)((d->Sq + 63) / 64) * d->Hq * d->B;
   if (wgs > 64) return 1;
   const int tiles = (d->Sk + 63) / 64;
@@ -1605,9 +1597,8 @@ extern "C" int dxa_attn_fwd(const dxa_attn_desc* d, dxa_stream_t stream) {
   const bool flash_ok = fwd_flash_ok(d);
   if (flash_ok) {
     // 8-wave workgroups (128 queries per staged K/V tile) for head_dim 256 once there are enough queries to fill the chip that way
-    static const int nw_env = getenv("DXA_ATTN_FWD_NW") ? atoi(getenv("DXA_ATTN_FWD_NW")) : 0;
     const int64_t wgs8 = (int64_t)((d->Sq + 127) / 128) * d->Hq * d->B;
-    const int nw = nw_env ? nw_env : (wide_tiles(d) && wgs8 >= 256 ? 8 : 4);
+    const int nw = wide_tiles(d) && wgs8 >= 256 ? 8 : 4;
     dim3 grid((unsigned)((d->Sq + 16 * nw - 1) / (16 * nw)), (unsigned)d->Hq, (unsigned)d->B);
     if (fwd_tr_ok(d)) {
 #define LAUNCH_TR(D_, DV_)                                                                            \
@@ -1705,20 +1696,14 @@ extern "C" int dxa_attn_bwd(const dxa_attn_desc* d, void* workspace, size_t work
     bp.dq = (char*)d->dq; bp.dq_sb = d->dq_sb; bp.dq_sh = d->dq_sh; bp.dq_ss = d->dq_ss;
     bp.dk = (char*)d->dk; bp.dk_sb = d->dk_sb; bp.dk_sh = d->dk_sh; bp.dk_ss = d->dk_ss;
     bp.dv = (char*)d->dv; bp.dv_sb = d->dv_sb; bp.dv_sh = d->dv_sh; bp.dv_ss = d->dv_ss;
-    static const int nwq_env = getenv("DXA_ATTN_DQ_NW") ? atoi(getenv("DXA_ATTN_DQ_NW")) : 0;
     const int64_t wgs8 = (int64_t)((d->Sq + 127) / 128) * d->Hq * d->B;
-    const int nwq = nwq_env ? nwq_env : (wide_tiles(d) && wgs8 >= 256 ? 8 : 4);
+    const int nwq = wide_tiles(d) && wgs8 >= 256 ? 8 : 4;
     dim3 gq((unsigned)((d->Sq + 16 * nwq - 1) / (16 * nwq)), (unsigned)d->Hq, (unsigned)d->B);
-#if defined(DXA_ATTN_OLD_ORDER)
-    dim3 gk((unsigned)((d->Sk + 63) / 64), (unsigned)d->Hkv, (unsigned)d->B);
-#else
     dim3 gk((unsigned)d->Hkv, (unsigned)d->B, (unsigned)((d->Sk + 63) / 64));
-#endif
     // head_dim 256, dK / dV: 0 = 4 waves, no register prefetch (rounds 2-4); 1 = 4 waves + prefetch (416 registers); 2 = 8 waves,
     // the d range of dK / dV cut over wave pairs, + prefetch (256 registers, 7 spilled); 3 = 8 waves without the prefetch (248
     // registers): dQ + dK/dV at B 16 x 8 heads x 816 keys 735 / 753 / 714 / 685 us (profiles/r05_attn_variants.txt; same results
     // bit for bit) -> 3
-    static const int dkv256 = getenv("DXA_ATTN_DKV256") ? atoi(getenv("DXA_ATTN_DKV256")) : 3;
 #define LAUNCH_DKV(D_, DV_, NW_, PF_)                                                                             \
   do {                                                                                                            \
     constexpr int lds_ = 2 * FlashTile<D_>::RM_BYTES + 3 * 64 * (int)sizeof(float);                               \
@@ -1737,17 +1722,13 @@ extern "C" int dxa_attn_bwd(const dxa_attn_desc* d, void* workspace, size_t work
   } while (0)
     if (d->D == 256) {
       LAUNCH_BWD(256, 256);
-      if (dkv256 == 2) LAUNCH_DKV(256, 256, 8, true);
-      else if (dkv256 == 3) LAUNCH_DKV(256, 256, 8, false);
-      else if (dkv256 == 1) LAUNCH_DKV(256, 256, 4, true);
-      else LAUNCH_DKV(256, 256, 4, false);
+      LAUNCH_DKV(256, 256, 8, false);
     } else if (d->D == 128) {
       // the 8-wave cut at head_dim 128 (182 registers without spills against 256 + 2 spilled): dQ + dK/dV of the decoder layer
       // 177.5 -> 172.5 and 175.2 -> 166.5 us in two sessions, the one-request shape 194.5 -> 186 (profiles/r05_attn_variants.txt,
-      // r05_attn_nw_probe.txt; same results bit for bit); DXA_ATTN_DKV128=0: the 4-wave kernel of rounds 1-4
-      static const int dkv128 = getenv("DXA_ATTN_DKV128") ? atoi(getenv("DXA_ATTN_DKV128")) : 2;
+      // r05_attn_nw_probe.txt; same results bit for bit)
       LAUNCH_BWD(128, 128);
-      if (dkv128 == 2) LAUNCH_DKV(128, 128, 8, true); else LAUNCH_DKV(128, 128, 4, true);
+      LAUNCH_DKV(128, 128, 8, true);
     }
     else if (d->D == 72) { LAUNCH_BWD(128, 72); LAUNCH_DKV(128, 72, 4, true); }
     else { LAUNCH_BWD(64, 64); LAUNCH_DKV(64, 64, 4, true); }
@@ -1756,9 +1737,8 @@ extern "C" int dxa_attn_bwd(const dxa_attn_desc* d, void* workspace, size_t work
     DXA_CHECK_LAUNCH();
     return DXA_OK;
   }
-  // head-sized fp32 attention without masks (the DiT heads' training backward): one launch (DXA_ATTN_NO_SMALL_BWD: the generic path)
-  static const bool small_bwd_off = getenv("DXA_ATTN_NO_SMALL_BWD") != nullptr;
-  if (!small_bwd_off && !d->force_generic && d->dtype == DXA_F32 && d->Hq == d->Hkv && !d->causal && !d->kv_start && !d->kv_end &&
+  // head-sized fp32 attention without masks (the DiT heads' training backward): one launch
+  if (!d->force_generic && d->dtype == DXA_F32 && d->Hq == d->Hkv && !d->causal && !d->kv_start && !d->kv_end &&
       !d->q_limit && !d->key_valid && !d->drop_mask && d->Sq <= SB_MAXQ && d->Sk <= 4096 && d->D <= SB_MAXD && d->D % 4 == 0 &&
       d->lse && d->Hq <= 65535 && d->B <= 65535 &&
       ((uintptr_t)d->q % 16 == 0) && ((uintptr_t)d->k % 16 == 0) && ((uintptr_t)d->v % 16 == 0) && ((uintptr_t)d->d_o % 16 == 0) &&
@@ -1772,10 +1752,9 @@ extern "C" int dxa_attn_bwd(const dxa_attn_desc* d, void* workspace, size_t work
     bp.dq = (char*)d->dq; bp.dq_sb = d->dq_sb; bp.dq_sh = d->dq_sh; bp.dq_ss = d->dq_ss;
     bp.dk = (char*)d->dk; bp.dk_sb = d->dk_sb; bp.dk_sh = d->dk_sh; bp.dk_ss = d->dk_ss;
     bp.dv = (char*)d->dv; bp.dv_sb = d->dv_sb; bp.dv_sh = d->dv_sh; bp.dv_ss = d->dv_ss;
-    // more than one chunk of queries: the register-blocked kernel (16-byte aligned dq / dk / dv rows; DXA_ATTN_SMALL_BWD_V1=1: the
+    // more than one chunk of queries: the register-blocked kernel (16-byte aligned dq / dk / dv rows; otherwise the
     // one-element-per-thread kernel at 1024 threads, rounds 6a-b)
-    static const bool v1_only = getenv("DXA_ATTN_SMALL_BWD_V1") != nullptr;
-    const bool v2_ok = !v1_only && ((uintptr_t)d->dq % 16 == 0) && ((uintptr_t)d->dk % 16 == 0) && ((uintptr_t)d->dv % 16 == 0) &&
+    const bool v2_ok = ((uintptr_t)d->dq % 16 == 0) && ((uintptr_t)d->dk % 16 == 0) && ((uintptr_t)d->dv % 16 == 0) &&
                        d->dq_ss % 4 == 0 && d->dk_ss % 4 == 0 && d->dv_ss % 4 == 0 && d->dq_sh % 4 == 0 && d->dk_sh % 4 == 0 &&
                        d->dv_sh % 4 == 0 && d->dq_sb % 4 == 0 && d->dk_sb % 4 == 0 && d->dv_sb % 4 == 0;
     if (d->Sq > SB_MAXT && v2_ok) {

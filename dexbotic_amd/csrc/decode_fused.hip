@@ -192,23 +192,14 @@ __device__ __forceinline__ float wave_rows(const DSmem& s, const bf16_t* __restr
       u32x4_t wv[RG];
 #pragma unroll
       for (int i = 0; i < RG; ++i)
-#if defined(DXA_DEC_PLAINLD)
-        wv[i] = *reinterpret_cast<const u32x4_t*>(W + rows[i] * ldw + k);
-#else
         wv[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(W + rows[i] * ldw + k));
-#endif
 #pragma unroll
       for (int i = 0; i < RG; ++i)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-#if defined(DXA_DEC_FMA)
-          acc[i] += __uint_as_float(wv[i][e] << 16) * __uint_as_float(hv[e] << 16);
-          acc[i] += __uint_as_float(wv[i][e] & 0xffff0000u) * __uint_as_float(hv[e] & 0xffff0000u);
-#else
           // (inline asm: __builtin_amdgcn_fdot2_f32_bf16 on elements of a 4 x u32 vector came out of hipcc 7.2 with ONE register for
           //  all four activation words and repeated weight words — results off by O(1), found by scripts/probes/decode_step_debug.py)
           asm volatile("v_dot2c_f32_bf16 %0, %1, %2" : "+v"(acc[i]) : "v"(wv[i][e]), "v"(hv[e]));
-#endif
         }
     }
   }
@@ -589,9 +580,7 @@ extern "C" int dxa_decode_step(const dxa_decode_desc* q, dxa_stream_t stream) {
     DXA_CHECK_ARG(per_cu >= 1, "dxa_decode_step: the kernel does not fit on this device");
     resident = prop.multiProcessorCount;          // one workgroup per CU: the weight stream wants every CU's load queue, not more waves
   }
-  int grid = resident;
-  static const int grid_cap = getenv("DXA_DECODE_GRID") ? atoi(getenv("DXA_DECODE_GRID")) : 0;   // tuning aid
-  if (grid_cap > 0 && grid > grid_cap) grid = grid_cap;
+  const int grid = resident;
   DXA_CHECK_ARG(q->Hq <= grid, "dxa_decode_step: %d attention heads need at least as many workgroups (%d)", q->Hq, grid);
   hipLaunchKernelGGL(decode_step_k, dim3(grid), dim3(512), sizeof(DSmem), st, p);
   DXA_CHECK_LAUNCH();

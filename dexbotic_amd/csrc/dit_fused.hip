@@ -36,7 +36,6 @@ struct DitP {
   int M, N, T1, H, heads, I, depth;
   int s_proj, s_fc2;
   float eps, scale;
-  int dbg;   // tuning aid (wrong results): 1 = barriers only, 2 = work only, 3 = no attention, 5 = no weight loads, 6 = no activation loads
 };
 
 struct alignas(16) Smem {
@@ -70,11 +69,6 @@ typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 // activation access is an agent-scope (sc1) buffer access — stores write through, loads miss in the private caches —
 // so the barrier needs no cache-wide write-back / invalidate and the weights stay cached.
 constexpr int SC1 = 16;
-#if defined(DXA_DIT_CACHED_LOADS)
-constexpr int A_AUX = 0;      // tuning build: the A operand through the XCD's L2
-#else
-constexpr int A_AUX = SC1;
-#endif
 struct Act {
   __amdgpu_buffer_rsrc_t r;
   __device__ __forceinline__ Act(float* p, size_t floats)
@@ -92,12 +86,7 @@ struct Act {
   // cached load: data complete before the last device-wide barrier (whose acquire dropped stale lines); the 20+
   // workgroups of an XCD then share one copy in its L2 instead of each pulling the matrix from the memory side
   __device__ __forceinline__ float4 ld4c(size_t idx) const {
-#if !defined(DXA_DIT_CACHED_LOADS)
     return ld4(idx);     // measured: the cached variant (+ acquire at every barrier) is 8 % slower end to end
-#else
-    const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)(idx * 4), 0, 0);
-    return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
-#endif
   }
   __device__ __forceinline__ float ld1(size_t idx) const {
     return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, (int)(idx * 4), 0, SC1));
@@ -220,10 +209,10 @@ __device__ __forceinline__ void gemm_phase_u(const DitP& p, Smem& s, const Act& 
         const uint32_t koff = (uint32_t)hb * 128u;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          wv[u][j] = __builtin_amdgcn_raw_buffer_load_b128(Wr, (int)(live && p.dbg != 5 ? woff + koff + 64u * j : OOB), 0, 0);
+          wv[u][j] = __builtin_amdgcn_raw_buffer_load_b128(Wr, (int)(live ? woff + koff + 64u * j : OOB), 0, 0);
 #pragma unroll
           for (int mb = 0; mb < MB; ++mb)
-            av[u][mb][j] = __builtin_amdgcn_raw_buffer_load_b128(A.r, (int)(live && aoff[mb] != OOB && p.dbg != 6 ? aoff[mb] + koff + 64u * j : OOB), 0, A_AUX);
+            av[u][mb][j] = __builtin_amdgcn_raw_buffer_load_b128(A.r, (int)(live && aoff[mb] != OOB ? aoff[mb] + koff + 64u * j : OOB), 0, SC1);
         }
       }
       __builtin_amdgcn_sched_barrier(0);        // every load of the trip is in flight before the first MFMA (the scheduler otherwise
@@ -403,35 +392,34 @@ __device__ __forceinline__ void attention_phase(const DitP& p, Smem& s, const Ac
 // the `depth` blocks of one denoising call; `base` = blocks walked by this launch before (the split-K tile counters count on)
 __device__ __forceinline__ void walk_blocks(const DitP& p, Smem& s, unsigned& epoch, unsigned nblk, unsigned base, const Act& h,
                                             const Act& qkv, const Act& o, const Act& a, const Act& part) {
-  const bool work = p.dbg != 1, sync = p.dbg != 2;
   for (int blk = 0; blk < p.depth; ++blk) {
     const float* const* w = p.w + blk * 8;
     DIT_STAMP(s, 0);
-    if (work) gemm_phase<true, EPI_BIAS>(p, s, h, p.H, w[0], w[1], qkv, 3 * p.H, 3 * p.H, p.H, 1, nullptr, 0, part);
+    gemm_phase<true, EPI_BIAS>(p, s, h, p.H, w[0], w[1], qkv, 3 * p.H, 3 * p.H, p.H, 1, nullptr, 0, part);
     DIT_STAMP(s, 3);
-    if (sync) grid_sync(p.bar, nblk, epoch, p.dbg != 4, &s);
+    grid_sync(p.bar, nblk, epoch, true, &s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 0, 5);
     DIT_STAMP(s, 0);
-    if (work && p.dbg != 3) attention_phase(p, s, qkv, o);
+    attention_phase(p, s, qkv, o);
     DIT_STAMP(s, 1); DIT_STAMP(s, 2); DIT_STAMP(s, 3);
-    if (sync) grid_sync(p.bar, nblk, epoch, p.dbg != 4, &s);
+    grid_sync(p.bar, nblk, epoch, true, &s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 1, 5);
     DIT_STAMP(s, 0);
-    if (work) gemm_phase<false, EPI_RESADD>(p, s, o, p.H, w[2], w[3], h, p.H, p.H, p.H, p.s_proj, p.cnt_proj,
-                                            (base + (unsigned)blk + 1u) * p.s_proj, part);
+    gemm_phase<false, EPI_RESADD>(p, s, o, p.H, w[2], w[3], h, p.H, p.H, p.H, p.s_proj, p.cnt_proj,
+                                  (base + (unsigned)blk + 1u) * p.s_proj, part);
     DIT_STAMP(s, 3);
-    if (sync) grid_sync(p.bar, nblk, epoch, p.dbg != 4, &s);
+    grid_sync(p.bar, nblk, epoch, true, &s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 2, 5);
     DIT_STAMP(s, 0);
-    if (work) gemm_phase<true, EPI_GELU>(p, s, h, p.H, w[4], w[5], a, p.I, p.I, p.H, 1, nullptr, 0, part);
+    gemm_phase<true, EPI_GELU>(p, s, h, p.H, w[4], w[5], a, p.I, p.I, p.H, 1, nullptr, 0, part);
     DIT_STAMP(s, 3);
-    if (sync) grid_sync(p.bar, nblk, epoch, p.dbg != 4, &s);
+    grid_sync(p.bar, nblk, epoch, true, &s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 3, 5);
     DIT_STAMP(s, 0);
-    if (work) gemm_phase<false, EPI_RESADD>(p, s, a, p.I, w[6], w[7], h, p.H, p.H, p.I, p.s_fc2, p.cnt_fc2,
-                                            (base + (unsigned)blk + 1u) * p.s_fc2, part);
+    gemm_phase<false, EPI_RESADD>(p, s, a, p.I, w[6], w[7], h, p.H, p.H, p.I, p.s_fc2, p.cnt_fc2,
+                                  (base + (unsigned)blk + 1u) * p.s_fc2, part);
     DIT_STAMP(s, 3);
-    if (sync) grid_sync(p.bar, nblk, epoch, p.dbg != 4, &s);
+    grid_sync(p.bar, nblk, epoch, true, &s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 4, 5);
   }
 }
@@ -684,8 +672,6 @@ int setup_blocks(DitP& p, int* grid_out, float* h, const float* const* weights, 
   p.M = M; p.N = N; p.T1 = T1; p.H = H; p.heads = heads; p.I = I; p.depth = depth;
   p.eps = eps;
   p.scale = 1.f / sqrtf((float)HD);
-  static const int dbg = getenv("DXA_DIT_DBG") ? atoi(getenv("DXA_DIT_DBG")) : 0;
-  p.dbg = dbg;
   // every workgroup must be resident at once (device-wide barrier): one per 16 columns of the widest product,
   // never more than the 256 CUs can hold
   int grid = I / 16;
@@ -704,13 +690,8 @@ int setup_blocks(DitP& p, int* grid_out, float* h, const float* const* weights, 
     DXA_CHECK_ARG(resident >= 1, "%s: the kernel does not fit on this device", who);
   }
   if (grid > resident) grid = resident;
-  static const int grid_cap = getenv("DXA_DIT_GRID") ? atoi(getenv("DXA_DIT_GRID")) : 0;   // tuning aid
-  if (grid_cap > 0 && grid > grid_cap) grid = grid_cap;
-  static const int no_slice = getenv("DXA_DIT_NO_SLICE") ? 1 : 0;
-  p.s_proj = no_slice ? 1 : pick_slices(H / 16, H / 64, grid);
-  p.s_fc2 = no_slice ? 1 : pick_slices(H / 16, I / 64, grid);
-  static const int proj_cap = getenv("DXA_DIT_PROJ_SLICES") ? atoi(getenv("DXA_DIT_PROJ_SLICES")) : 0;      // tuning aid
-  if (proj_cap > 0 && p.s_proj > proj_cap && (H / 64) % proj_cap == 0) p.s_proj = proj_cap;
+  p.s_proj = pick_slices(H / 16, H / 64, grid);
+  p.s_fc2 = pick_slices(H / 16, I / 64, grid);
   *grid_out = grid;
   return DXA_OK;
 }
@@ -816,7 +797,6 @@ struct DitBfP {
   int P, wstride;
   int s_proj, s_fc2;
   float eps, scale;
-  int dbg;
 };
 
 struct BfBufs {
@@ -901,10 +881,10 @@ __device__ __forceinline__ void gemm_bf_u(const DitBfP& p, Smem& s, const BfBufs
       for (int u = 0; u < U; ++u) {
         const int pc = base + wave + 8 * u;
         const bool live = pc < pc_hi;
-        wv[u] = __builtin_amdgcn_raw_buffer_load_b128(Wr, (int)(live && p.dbg != 5 ? woff + (uint32_t)pc * 1024u : OOB), 0, 0);
+        wv[u] = __builtin_amdgcn_raw_buffer_load_b128(Wr, (int)(live ? woff + (uint32_t)pc * 1024u : OOB), 0, 0);
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb)
-          av[u][mb] = A.ld16(live && aoff[mb] != OOB && p.dbg != 6 ? aoff[mb] + (uint32_t)(pc * Mp) * 64u : OOB);
+          av[u][mb] = A.ld16(live && aoff[mb] != OOB ? aoff[mb] + (uint32_t)(pc * Mp) * 64u : OOB);
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -1211,57 +1191,54 @@ __device__ __forceinline__ void per_attention_bf(const DitBfP& p, Smem& s, const
 }
 
 __device__ __forceinline__ void walk_blocks_bf(const DitBfP& p, Smem& s, const BfBufs& b, unsigned& epoch, unsigned nblk, unsigned base) {
-  const bool work = p.dbg != 1, sync = p.dbg != 2;
   for (int blk = 0; blk < p.depth; ++blk) {
     const void* const* w = p.w + blk * p.wstride;
     const bool per = p.P > 0;
     // the K-sliced output projections count arrivals per column block: with perceptual attention TWO products per block use cnt_proj
     const unsigned tgt_proj = per ? (2u * (base + (unsigned)blk) + 1u) * p.s_proj : (base + (unsigned)blk + 1u) * p.s_proj;
     DIT_STAMP(s, 0);
-    if (work) gemm_bf<BF_QKV>(p, s, b, b.hb, p.H, w[0], w[1], w[8], 3 * p.H, 1, nullptr, 0);
+    gemm_bf<BF_QKV>(p, s, b, b.hb, p.H, w[0], w[1], w[8], 3 * p.H, 1, nullptr, 0);
     DIT_STAMP(s, 3);
-    if (sync) grid_sync(p.bar, nblk, epoch, true, &s);
+    grid_sync(p.bar, nblk, epoch, true, &s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 0, 5);
     DIT_STAMP(s, 0);
-    if (work && p.dbg != 3) attention_bf(p, s, b);
+    attention_bf(p, s, b);
     DIT_STAMP(s, 1); DIT_STAMP(s, 2); DIT_STAMP(s, 3);
-    if (sync) grid_sync(p.bar, nblk, epoch, true, &s);
+    grid_sync(p.bar, nblk, epoch, true, &s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 1, 5);
     DIT_STAMP(s, 0);
-    if (work) gemm_bf<BF_RES>(p, s, b, b.ob, p.H, w[2], w[3], nullptr, p.H, p.s_proj, p.cnt_proj, tgt_proj);
+    gemm_bf<BF_RES>(p, s, b, b.ob, p.H, w[2], w[3], nullptr, p.H, p.s_proj, p.cnt_proj, tgt_proj);
     DIT_STAMP(s, 3);
-    if (sync) grid_sync(p.bar, nblk, epoch, true, &s);
+    grid_sync(p.bar, nblk, epoch, true, &s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 2, 5);
     if (per) {
       // x + MHA(norm3 x, per, per): q = (norm3 folded into the packed q rows of in_proj) | attention over the cached keys / values | out_proj
-      if (work) gemm_bf<BF_QKV>(p, s, b, b.hb, p.H, w[10], w[11], w[12], p.H, 1, nullptr, 0);
+      gemm_bf<BF_QKV>(p, s, b, b.hb, p.H, w[10], w[11], w[12], p.H, 1, nullptr, 0);
       // the keys / values of this workgroup's first attention item: in flight (or, for the workgroups without a projection tile,
       // already here) when the barrier opens — a cold 128 KB of them costs 5 us after it (profiles/r06_memvla_sampler.txt)
       const float* kvb = p.kv + (size_t)blk * p.N * p.P * 2 * p.H;
       PerOperands ops;
       bool pre = false;
-      if (work && p.dbg != 3 && p.dbg != 7) {
-        int n_, hd_, r0_, nr_;
-        if (per_decode(p, per_first_item(p), n_, hd_, r0_, nr_)) { per_load(p, kvb, n_, hd_, ops); pre = true; }
-      }
-      if (sync) grid_sync(p.bar, nblk, epoch, true, &s);
+      int n_, hd_, r0_, nr_;
+      if (per_decode(p, per_first_item(p), n_, hd_, r0_, nr_)) { per_load(p, kvb, n_, hd_, ops); pre = true; }
+      grid_sync(p.bar, nblk, epoch, true, &s);
       DIT_STAMP(s, 0);
-      if (work && p.dbg != 3) per_attention_bf(p, s, b, kvb, ops, pre);
+      per_attention_bf(p, s, b, kvb, ops, pre);
       DIT_STAMP(s, 5);
-      if (sync) grid_sync(p.bar, nblk, epoch, true, &s);
+      grid_sync(p.bar, nblk, epoch, true, &s);
       DIT_STAMP(s, 6); DIT_STAMP_FOLD(s, 5, 6);
-      if (work) gemm_bf<BF_RES>(p, s, b, b.ob, p.H, w[13], w[14], nullptr, p.H, p.s_proj, p.cnt_proj, tgt_proj + (unsigned)p.s_proj);
-      if (sync) grid_sync(p.bar, nblk, epoch, true, &s);
+      gemm_bf<BF_RES>(p, s, b, b.ob, p.H, w[13], w[14], nullptr, p.H, p.s_proj, p.cnt_proj, tgt_proj + (unsigned)p.s_proj);
+      grid_sync(p.bar, nblk, epoch, true, &s);
     }
     DIT_STAMP(s, 0);
-    if (work) gemm_bf<BF_FC1>(p, s, b, b.hb, p.H, w[4], w[5], w[9], p.I, 1, nullptr, 0);
+    gemm_bf<BF_FC1>(p, s, b, b.hb, p.H, w[4], w[5], w[9], p.I, 1, nullptr, 0);
     DIT_STAMP(s, 3);
-    if (sync) grid_sync(p.bar, nblk, epoch, true, &s);
+    grid_sync(p.bar, nblk, epoch, true, &s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 3, 5);
     DIT_STAMP(s, 0);
-    if (work) gemm_bf<BF_RES>(p, s, b, b.ab, p.I, w[6], w[7], nullptr, p.H, p.s_fc2, p.cnt_fc2, (base + (unsigned)blk + 1u) * p.s_fc2);
+    gemm_bf<BF_RES>(p, s, b, b.ab, p.I, w[6], w[7], nullptr, p.H, p.s_fc2, p.cnt_fc2, (base + (unsigned)blk + 1u) * p.s_fc2);
     DIT_STAMP(s, 3);
-    if (sync) grid_sync(p.bar, nblk, epoch, true, &s);
+    grid_sync(p.bar, nblk, epoch, true, &s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 4, 5);
   }
 }
@@ -1546,8 +1523,6 @@ int sample_bf16_launch(const char* who, float* x, const float* z_emb, const floa
   p.kv = per_kv; p.P = P; p.wstride = P > 0 ? 16 : 10;
   p.M = M; p.Mp = (M + 1) & ~1; p.N = N; p.T1 = T1; p.H = H; p.heads = heads; p.I = I; p.depth = depth;
   p.eps = eps; p.scale = 1.f / sqrtf((float)HD);
-  static const int dbg = getenv("DXA_DIT_DBG") ? atoi(getenv("DXA_DIT_DBG")) : 0;
-  p.dbg = dbg;
   int grid = I / 16;
   if (3 * H / 16 > grid) grid = 3 * H / 16;
   static int resident = 0;
@@ -1561,16 +1536,11 @@ int sample_bf16_launch(const char* who, float* x, const float* z_emb, const floa
     DXA_CHECK_ARG(resident >= 1, "%s: the kernel does not fit on this device", who);
   }
   if (grid > resident) grid = resident;
-  static const int grid_cap = getenv("DXA_DIT_GRID") ? atoi(getenv("DXA_DIT_GRID")) : 0;
-  if (grid_cap > 0 && grid > grid_cap) grid = grid_cap;
-  static const int no_slice = getenv("DXA_DIT_NO_SLICE") ? 1 : 0;
-  p.s_proj = no_slice ? 1 : pick_slices(H / 16, H / 64, grid);
-  p.s_fc2 = no_slice ? 1 : pick_slices(H / 16, I / 64, grid);
+  p.s_fc2 = pick_slices(H / 16, I / 64, grid);
   // the output projection is NOT K-sliced here: with bf16 operands a workgroup's whole K = 768 slab is 25 KB of weights + 52 KB of
   // activations (the qkv phase's load), while a sliced product pays the partial exchange — store, acknowledge, tile counter, gather by
   // the last arrival — after its MFMAs: 3.90 ms per sample with 4 slices, 3.82 with 2, 3.70 with 1 (profiles/r04_proj_slices.txt)
-  static const int proj_cap = getenv("DXA_DIT_PROJ_SLICES") ? atoi(getenv("DXA_DIT_PROJ_SLICES")) : 1;
-  if (proj_cap > 0 && p.s_proj > proj_cap && (H / 64) % proj_cap == 0) p.s_proj = proj_cap;
+  p.s_proj = 1;
   sp.x = x; sp.ze = z_emb; sp.te = t_emb; sp.pos = pos; sp.xw = x_w; sp.xb = x_b; sp.fw = final_w; sp.fb = final_b; sp.coef = coef;
   sp.steps = steps; sp.A = A; sp.nb = nb; sp.use_cfg = use_cfg; sp.cfg_scale = cfg_scale;
   sp.xpp = extra; sp.eps = extra + 2 * MAXM * MAXA;

@@ -477,15 +477,8 @@ __global__ __launch_bounds__(256 + 64 * WS) void gemm_nt_t128_kernel(const GemmP
     }
 #endif
 }
-template __global__ void gemm_nt_t128_kernel<bf16_t, 2, 0>(const GemmP);
-template __global__ void gemm_nt_t128_kernel<float, 2, 0>(const GemmP);
-template __global__ void gemm_nt_t128_kernel<bf16_t, 4, 0>(const GemmP);
-template __global__ void gemm_nt_t128_kernel<float, 4, 0>(const GemmP);
 template __global__ void gemm_nt_t128_kernel<bf16_t, 4, 4>(const GemmP);
 template __global__ void gemm_nt_t128_kernel<float, 4, 4>(const GemmP);
-template __global__ void gemm_nt_t128_kernel<bf16_t, 4, 8>(const GemmP);
-template __global__ void gemm_nt_t128_kernel<float, 4, 8>(const GemmP);
-template __global__ void gemm_nt_t128_kernel<float, 4, 4, float>(const GemmP);
 
 // =====================================================================================================
 // Few-row NN product (M <= 8): out[M, N] = A[M, K] W[K, N] with W as it lies — the dX of a linear layer applied to a handful
@@ -895,11 +888,7 @@ __global__ __launch_bounds__(512) void gemm_nt_ring_kernel(const GemmP p) {
   const uint32_t abase1 = lds0 + (wm * (BMR / 2) + l32) * 64 + (((2 + lh) ^ sw) << 4);
   const uint32_t bbase0 = lds0 + A_ST + (wn * 64 + l32) * 64 + (((0 + lh) ^ sw) << 4);
   const uint32_t bbase1 = lds0 + A_ST + (wn * 64 + l32) * 64 + (((2 + lh) ^ sw) << 4);
-#if defined(DXA_ABL) && DXA_ABL == 3
-#define DS_READ(dst, addr, imm) asm volatile("" : "+v"(dst) : "v"(addr))
-#else
 #define DS_READ(dst, addr, imm) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(imm) : "memory")
-#endif
 #define RD_SET(A_, B_, abase, bbase, soff)                                                      \
   do {                                                                                          \
     const uint32_t ax_ = (abase) + (soff), bx_ = (bbase) + (soff);                              \
@@ -907,21 +896,13 @@ __global__ __launch_bounds__(512) void gemm_nt_ring_kernel(const GemmP p) {
     if constexpr (AI > 3) DS_READ(A_[3], ax_, 6144);                                            \
     DS_READ(B_[0], bx_, 0); DS_READ(B_[1], bx_, 2048);                                          \
   } while (0)
-#if defined(DXA_ABL) && DXA_ABL == 4
-#define MFMA1(A_, B_, i, j) asm volatile("" : "+v"(acc[i][j]) : "v"(A_[i]), "v"(B_[j]))
-#else
 #define MFMA1(A_, B_, i, j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, B_[j]), __builtin_bit_cast(bf16x8_t, A_[i]), acc[i][j], 0, 0, 0)
-#endif
 #define SB() __builtin_amdgcn_sched_barrier(0)
 
   RD_SET(a0, b0, abase0, bbase0, 0u);       // k-step 0 of slab 0
   for (int t = 0; t < nk; ++t) {
     const uint32_t soff = (uint32_t)((t & 3) * STAGE), soff_n = (uint32_t)(((t + 1) & 3) * STAGE);
-#if defined(DXA_ABL) && DXA_ABL == 1
-    const bool dma = false;
-#else
     const bool dma = t + 3 < nk;
-#endif
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     SB();
     MFMA1(a0, b0, 0, 0); MFMA1(a0, b0, 0, 1);
@@ -950,9 +931,7 @@ __global__ __launch_bounds__(512) void gemm_nt_ring_kernel(const GemmP p) {
     SB();
     if (dma) WAIT_PREV_SLAB();                                   // my pieces of slab t+2 have landed
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#if !(defined(DXA_ABL) && DXA_ABL == 2)
     __builtin_amdgcn_s_barrier();
-#endif
     SB();
   }
 #undef DMA_A
@@ -996,7 +975,7 @@ template __global__ void gemm_nt_ring_kernel<float, 3, float>(const GemmP);
 // groups of ds_read_b128 over a 32-row fragment column hit 16 distinct 16-byte slots of the 256-byte bank row.  The DMA
 // writes LDS lane-linearly (8 rows x 128 B per instruction), so the swizzle is applied to the per-lane SOURCE chunk;
 // each row is still fetched as one whole 128-byte line.
-// Ablations on 8192^3 (scripts/ablate_gemm.sh): everything 832 us; without LDS-DMA 574 (1.92 PF/s); without MFMA 607;
+// Ablations on 8192^3 (round-3 ablation builds): everything 832 us; without LDS-DMA 574 (1.92 PF/s); without MFMA 607;
 // without ds_read 628; 2 phases per K tile instead of 4 (half the barriers) 819 — the L2->LDS feed (~27 B/clk/CU
 // achieved, 32 needed at the MFMA peak for a 256x256 tile) and its interference with the fragment reads are what is
 // left, not the barriers.
@@ -1107,11 +1086,6 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
   const uint32_t ktileA = A_KS ? 64u * (uint32_t)p.lda * 2u : 0u, ktileB = B_KS ? 64u * (uint32_t)p.ldb * 2u : 0u;
 #define PP_DMA(rsrc, vo, ldsoff, buf, soff)                                                                             \
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)(smem + (buf) * BUF + (ldsoff)), 16, vo, soff, 0, 0)
-#if (DXA_PPV & 1)
-#define PP_LOOP(x) do { } while (0)
-#else
-#define PP_LOOP(x) x
-#endif
 #define PP_DMA_A1(h, j, buf, tile)                                                                          \
   do {                                                                                                      \
     if constexpr (A_KS && B_KS) {                                                                           \
@@ -1165,13 +1139,8 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
                            : (lds0 + REG + (wn * 64 + l32) * 128) | (uint32_t)((lh ^ sw) << 4);
   u32x4_t af[2][4], bq[2][4];            // B fragments of both halves stay in registers: B0 serves phases 0 and 3
   typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-#if (DXA_PPV & 2)
-#define PP_READ(dst, addr, imm) asm volatile("" : "+v"(dst) : "v"(addr))
-#define PP_READ_TR(dst, addr, imm) asm volatile("" : "+v"(dst) : "v"(addr))
-#else
 #define PP_READ(dst, addr, imm) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(imm) : "memory")
 #define PP_READ_TR(dst, addr, imm) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(imm) : "memory")
-#endif
   // one fragment (8 k of one tile row per lane) of a k-strided operand: k 0..3 | k 4..7
 #define PP_FRAG_TR(dst, addr, imm)                                                       \
   do {                                                                                   \
@@ -1209,12 +1178,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
       PP_READ(bq[j][2], b2_, (j) * 4096); PP_READ(bq[j][3], b3_, (j) * 4096);                               \
     }                                                                                                       \
   } while (0)
-#if (DXA_PPV & 4)
-#define PP_MFMA2(ii, ks, i, j, jr) asm volatile("" : "+v"(acc[i][j]) : "v"(bq[jr][ks]), "v"(af[ii][ks]))
-#else
-#define PP_MFMA2(ii, ks, i, j, jr) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, bq[jr][ks]), __builtin_bit_cast(bf16x8_t, af[ii][ks]), acc[i][j], 0, 0, 0)
-#endif
-#define PP_MFMA(ii, ks, i, j) PP_MFMA2(ii, ks, i, j, j)
+#define PP_MFMA(ii, ks, i, j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, bq[j][ks]), __builtin_bit_cast(bf16x8_t, af[ii][ks]), acc[i][j], 0, 0, 0)
 #define PP_SB() __builtin_amdgcn_sched_barrier(0)
 #define PP_BAR() do { PP_SB(); __builtin_amdgcn_s_barrier(); PP_SB(); } while (0)
   // compute cluster of quadrant (A half h, B half j): the two accumulators alternate so dependent MFMAs are 2 apart
@@ -1249,26 +1213,6 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
       PP_READ(bq[j][ks], b_, (j) * 4096);                                                                   \
     }                                                                                                       \
   } while (0)
-  // the same with the register set named apart from the B half (DXA_PPR=2: the two sets swap roles every K tile)
-#define PP_RDK_B2(cur, j, jr, ks)                                                                           \
-  do {                                                                                                      \
-    if constexpr (B_KS) {                                                                                   \
-      const uint32_t b0_ = yb ^ (uint32_t)((cur) * BUF + (j) * 16384);                                      \
-      PP_FRAG_TR(bq[jr][ks], b0_, 4096 * (ks));                                                             \
-    } else {                                                                                                \
-      const uint32_t b_ = yb ^ (uint32_t)((cur) * BUF + 32 * (ks));                                         \
-      PP_READ(bq[jr][ks], b_, (j) * 4096);                                                                  \
-    }                                                                                                       \
-  } while (0)
-#define PP_COMPUTE_R2(h, j, jr, R)                                                                \
-  do {                                                                                            \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                            \
-    PP_SB();                                                                                      \
-    PP_MFMA2(0, 0, 2 * (h), j, jr); PP_MFMA2(1, 0, 2 * (h) + 1, j, jr); PP_SB(); R(0); PP_SB();   \
-    PP_MFMA2(0, 1, 2 * (h), j, jr); PP_MFMA2(1, 1, 2 * (h) + 1, j, jr); PP_SB(); R(1); PP_SB();   \
-    PP_MFMA2(0, 2, 2 * (h), j, jr); PP_MFMA2(1, 2, 2 * (h) + 1, j, jr); PP_SB(); R(2); PP_SB();   \
-    PP_MFMA2(0, 3, 2 * (h), j, jr); PP_MFMA2(1, 3, 2 * (h) + 1, j, jr); PP_SB(); R(3); PP_SB();   \
-  } while (0)
   // compute cluster with the NEXT cluster's fragment reads in its gaps: after the two MFMAs of k-step ks their operand registers are
   // dead, R(ks) refills them (the data lands tens of cycles after the MFMAs have read their sources)
 #define PP_COMPUTE_R(h, j, R)                                                                     \
@@ -1281,50 +1225,11 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
     PP_MFMA(0, 3, 2 * (h), j); PP_MFMA(1, 3, 2 * (h) + 1, j); PP_SB(); R(3); PP_SB();             \
   } while (0)
 #define PP_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-  // one K tile in buffer `cur = t & 1`.  LDS-DMA runs SIX pieces (96 KiB) ahead of the reads, in the two 64 KiB buffers
-  // alone: the B0 fragments stay in registers from phase 0 to phase 3, so every piece is read from LDS in exactly one
-  // memory cluster (A0, B0: M0; B1: M1; A1: M2; M3 reads nothing) and its bytes are free again two phases later.  The global
-  // issue order is A0(0) B0(0) B1(0) A1(0) A0(1) B0(1) | B1(t+1) A1(t+1) A0(t+2) B0(t+2) in phases 0..3 of tile t: each
-  // piece is issued 5-6 phases (~1.5 K tiles, > 1.5 us) before its read instead of 2-3 — the loaded L2 -> LDS latency no
-  // longer stalls the MFMA clusters.  A piece read in M_q is waited for at the END of M_{q-1} by every wave (vmcnt(8): the
-  // four younger pieces stay in flight); both groups' M_{q-1} end before the interval in which the first M_q starts, so
-  // wait + barrier order the DMA before every read.  Reads of M_q have completed for BOTH staggered groups two phases on
-  // (group 1's reads of M_q retire in barrier interval 2q+2, group 0 issues M_{q+2} in interval 2q+4): a piece may be
-  // overwritten from phase q+2 onward — A0(t+2) in phase 2, B0(t+2) in phase 3 of tile t (read in M0 of tile t), B1(t+1) /
-  // A1(t+1) in phases 0 / 1 of tile t (read in M1 / M2 of tile t-1).
-#if (DXA_PPV & 64)   /* tuning variant: LDS-DMA issue ahead of the fragment reads of the same memory cluster */
-#define PP_M(reads, dma) do { dma; PP_SB(); reads; PP_SB(); } while (0)
-#else
-#define PP_M(reads, dma) do { reads; PP_SB(); dma; PP_SB(); } while (0)
-#endif
-  // The eight LDS-DMA instructions a wave issues per K tile, in their (fixed) order: slots 0-1 = B1(t+1), 2-3 = A1(t+1) into
-  // the other buffer, 4-5 = A0(t+2), 6-7 = B0(t+2) into this one.  They are dealt to the four memory clusters as PPD0..PPD3
-  // instructions: M0 already carries 12 fragment reads, M1 4, M2 8 and M3 none, and a memory cluster longer than the other
-  // group's compute cluster (8 MFMAs = 256 cycles) stalls the MFMA pipe — so the DMA issue goes where the reads are few
-  // (default 1, 2, 2, 3; DXA_PPD=2222 is the even deal).  Slots 4-7 overwrite bytes read in M0 of this tile: not before M2.
-#ifndef DXA_PPD
-#define DXA_PPD 1223
-#endif
-  constexpr int PPD0 = DXA_PPD / 1000, PPD1 = DXA_PPD / 100 % 10, PPD2 = DXA_PPD / 10 % 10, PPD3 = DXA_PPD % 10;
-  static_assert(PPD0 + PPD1 + PPD2 + PPD3 == 8 && PPD0 + PPD1 <= 4, "eight LDS-DMA instructions per K tile; slots 4-7 from phase 2 on");
-#define PP_SLOT(k, cur, t)                                                                                  \
-  do {                                                                                                      \
-    if ((k) < 4 ? more1 : more2) {                                                                          \
-      if ((k) == 0) PP_LOOP(PP_DMA_B1(1, 0, (cur) ^ 1, (t) + 1));                                           \
-      else if ((k) == 1) PP_LOOP(PP_DMA_B1(1, 1, (cur) ^ 1, (t) + 1));                                      \
-      else if ((k) == 2) PP_LOOP(PP_DMA_A1(1, 0, (cur) ^ 1, (t) + 1));                                      \
-      else if ((k) == 3) PP_LOOP(PP_DMA_A1(1, 1, (cur) ^ 1, (t) + 1));                                      \
-      else if ((k) == 4) PP_LOOP(PP_DMA_A1(0, 0, cur, (t) + 2));                                            \
-      else if ((k) == 5) PP_LOOP(PP_DMA_A1(0, 1, cur, (t) + 2));                                            \
-      else if ((k) == 6) PP_LOOP(PP_DMA_B1(0, 0, cur, (t) + 2));                                            \
-      else PP_LOOP(PP_DMA_B1(0, 1, cur, (t) + 2));                                                          \
-    }                                                                                                       \
-  } while (0)
-#define PP_SLOTS(from, to, cur, t) do { _Pragma("unroll") for (int k_ = (from); k_ < (to); ++k_) PP_SLOT(k_, cur, t); } while (0)
-#define PP_VMCNT_N(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
-  // tuning variant DXA_PPV & 128: s_memtime after every barrier of a K tile (8 stamps, read once per tile where no LDS read is
+  // one K tile in buffer `cur = t & 1` of two 64 KiB LDS buffers; the two wave groups run staggered by one barrier interval, a
+  // compute cluster C_q of one group beside the memory cluster M_q (LDS-DMA issue) of the other.
+  // stamp build (-DDXA_PP_STAMPS): s_memtime after every barrier of a K tile (8 stamps, read once per tile where no LDS read is
   // outstanding); the eight barrier-to-barrier intervals are summed per wave and stored over the first bytes of C
-#if (DXA_PPV & 128)
+#if defined(DXA_PP_STAMPS)
   uint64_t ts_[8];
   uint32_t iv_[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}, ts_last_ = 0u;
 #define PP_STAMP(i) asm volatile("s_memtime %0" : "=s"(ts_[i]))
@@ -1341,49 +1246,8 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
 #define PP_STAMP(i) do { } while (0)
 #define PP_STAMPS_FOLD() do { } while (0)
 #endif
-#ifndef DXA_PPR
-#define DXA_PPR 1
-#endif
-#if DXA_PPR == 2
-  // Round 4 schedule, second form (DXA_PPR=2, default).  DXA_PPR=1 below moved every fragment read into the gaps of the compute cluster
-  // BEFORE the one that needs it; its stamps (profiles/r04_pp_stamps_after.txt) then showed the barrier intervals that hold a C3 —
-  // 12 reads in its gaps (24 ds_read_b64_tr_b16 for TN): A0(t+1) and B0(t+1) — at 360 / 410 cycles (TN 427 / 500) against 270-340 for
-  // the others, while C2 carried none: A1 and B0 are both still live in C2, so nothing could be refilled there.  Here the two B
-  // register sets swap roles every K tile (the loop is unrolled by two, so the set index is a compile-time constant): in tile t set
-  // s0 = t & 1 holds B0(t) and set s1 = s0 ^ 1 receives B1(t) in C0; C2 (A1 x B1) consumes s1 k-step by k-step and refills it with
-  // B0(t+1) — which is then already where tile t+1 (s0' = s1) expects it — and C3 (A1 x B0, set s0) refills only the A registers
-  // with A0(t+1).  Reads per compute cluster 4 / 8 / 4 / 8 instead of 4 / 8 / 0 / 12.
-  //   C0 (A0 x B0) reads B1(t);  C1 (A0 x B1) reads A1(t);  C2 (A1 x B1) reads B0(t+1);  C3 (A1 x B0) reads A0(t+1).
-  // B0(t+1) is needed one phase earlier than before, so the LDS-DMA order swaps A0 and B0:  M0 A1(t+1) -> other buffer, M1 B0(t+2),
-  // M2 A0(t+2), M3 B1(t+2) -> this buffer (the bytes they overwrite were read in C1(t-1), C2(t-1), C3(t-1), C0(t): at least one full
-  // barrier interval before, for both groups).  In-order issue per wave (2 instructions each):
-  //   ... A1(t) | B0(t+1) | A0(t+1) | B1(t+1) | A1(t+1) | B0(t+2) | A0(t+2) | B1(t+2) ...
-  // A piece read in C_q is waited for at the end of M_{q-1} by every wave: always the piece issued four phases earlier = vmcnt(8).
-#define PP_R2_B1(ks) PP_RDK_B2(cur_, 1, cur_ ^ 1, ks)
-#define PP_R2_A1(ks) PP_RDK_A(cur_, 1, ks)
-#define PP_R2_B0N(ks) do { if (more1) { PP_RDK_B2(cur_ ^ 1, 0, cur_ ^ 1, ks); } } while (0)
-#define PP_R2_A0N(ks) do { if (more1) { PP_RDK_A(cur_ ^ 1, 0, ks); } } while (0)
-#define PP_TILE(cur, t)                                                                                     \
-  do {                                                                                                      \
-    constexpr int cur_ = (cur);                                                                             \
-    const bool more1 = (t) + 1 < nk, more2 = (t) + 2 < nk;                                                  \
-    /* phase 0 */                                                                                           \
-    if (more1) { PP_LOOP(PP_DMA_A(1, cur_ ^ 1, (t) + 1)); PP_SB(); PP_VMCNT(8); } else { PP_VMCNT(0); }     \
-    PP_BAR(); PP_STAMP(0); PP_COMPUTE_R2(0, 0, cur_, PP_R2_B1); PP_BAR(); PP_STAMP(1);                      \
-    /* phase 1 */                                                                                           \
-    if (more2) { PP_LOOP(PP_DMA_B(0, cur_, (t) + 2)); PP_SB(); PP_VMCNT(8); } else if (more1) { PP_VMCNT(6); } \
-    PP_BAR(); PP_STAMP(2); PP_COMPUTE_R2(0, 1, cur_ ^ 1, PP_R2_A1); PP_BAR(); PP_STAMP(3);                  \
-    /* phase 2 */                                                                                           \
-    if (more2) { PP_LOOP(PP_DMA_A(0, cur_, (t) + 2)); PP_SB(); PP_VMCNT(8); } else if (more1) { PP_VMCNT(4); } \
-    PP_BAR(); PP_STAMP(4); PP_COMPUTE_R2(1, 1, cur_ ^ 1, PP_R2_B0N); PP_BAR(); PP_STAMP(5);                 \
-    /* phase 3 */                                                                                           \
-    if (more2) { PP_LOOP(PP_DMA_B(1, cur_, (t) + 2)); PP_SB(); PP_VMCNT(8); } else if (more1) { PP_VMCNT(2); } \
-    PP_BAR(); PP_STAMP(6); PP_COMPUTE_R2(1, 0, cur_, PP_R2_A0N); PP_BAR(); PP_STAMP(7);                     \
-    PP_STAMPS_FOLD();                                                                                       \
-  } while (0)
-#elif DXA_PPR
-  // Round 4 schedule (DXA_PPR=1, default): NO fragment read is left in a memory cluster.  The stamp build (DXA_PPV=128,
-  // profiles/r04_pp_stamps_before.txt) showed the two barrier intervals in which a group runs M0 — 12 ds_read_b128 (24
+  // Round 4 schedule: NO fragment read is left in a memory cluster.  The stamp build (DXA_PP_STAMPS,
+  // profiles/r04_pp_stamps_before.txt) of the round-3 schedule showed the two barrier intervals in which a group runs M0 — 12 ds_read_b128 (24
   // ds_read_b64_tr_b16 when both operands are k-strided) — at 440 cycles (TN 540) against 285 for the other six: the compute
   // cluster of the other group finishes its 256 cycles of MFMAs and waits.  Now every fragment is read in the gaps of the compute
   // cluster BEFORE the one that needs it, into the operand registers its MFMAs have just consumed:
@@ -1402,79 +1266,41 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
     constexpr int cur_ = (cur);                                                                             \
     const bool more1 = (t) + 1 < nk, more2 = (t) + 2 < nk;                                                  \
     /* phase 0 */                                                                                           \
-    if (more1) { PP_LOOP(PP_DMA_A(1, cur_ ^ 1, (t) + 1)); PP_SB(); PP_VMCNT(8); } else { PP_VMCNT(0); }     \
+    if (more1) { PP_DMA_A(1, cur_ ^ 1, (t) + 1); PP_SB(); PP_VMCNT(8); } else { PP_VMCNT(0); }              \
     PP_BAR(); PP_STAMP(0); PP_COMPUTE_R(0, 0, PP_R_B1); PP_BAR(); PP_STAMP(1);                              \
     /* phase 1 */                                                                                           \
-    if (more2) { PP_LOOP(PP_DMA_A(0, cur_, (t) + 2)); PP_SB(); }                                            \
+    if (more2) { PP_DMA_A(0, cur_, (t) + 2); PP_SB(); }                                                     \
     PP_BAR(); PP_STAMP(2); PP_COMPUTE_R(0, 1, PP_R_A1); PP_BAR(); PP_STAMP(3);                              \
     /* phase 2 */                                                                                           \
-    if (more2) { PP_LOOP(PP_DMA_B(0, cur_, (t) + 2)); PP_SB(); PP_VMCNT(8); } else if (more1) { PP_VMCNT(4); } \
+    if (more2) { PP_DMA_B(0, cur_, (t) + 2); PP_SB(); PP_VMCNT(8); } else if (more1) { PP_VMCNT(4); }       \
     PP_BAR(); PP_STAMP(4); PP_COMPUTE(1, 1); PP_BAR(); PP_STAMP(5);                                         \
     /* phase 3 */                                                                                           \
-    if (more2) { PP_LOOP(PP_DMA_B(1, cur_, (t) + 2)); PP_SB(); PP_VMCNT(8); } else if (more1) { PP_VMCNT(2); } \
+    if (more2) { PP_DMA_B(1, cur_, (t) + 2); PP_SB(); PP_VMCNT(8); } else if (more1) { PP_VMCNT(2); }       \
     PP_BAR(); PP_STAMP(6); PP_COMPUTE_R(1, 0, PP_R_NEXT); PP_BAR(); PP_STAMP(7);                            \
     PP_STAMPS_FOLD();                                                                                       \
   } while (0)
-#else
-#define PP_TILE(cur, t)                                                                                     \
-  do {                                                                                                      \
-    const bool more1 = (t) + 1 < nk, more2 = (t) + 2 < nk;                                                  \
-    /* phase 0 */                                                                                           \
-    PP_M(PP_RD_A(cur, 0); PP_RD_B(cur, 0), PP_SLOTS(0, PPD0, cur, t));                                      \
-    /* B1(t) landed: younger = A1(t) (2) + A0, B0 of t+1 (4) + this tile's slots so far */                  \
-    if (more1) { PP_VMCNT_N(6 + PPD0); } else { PP_VMCNT(2); }                                              \
-    PP_BAR(); PP_STAMP(0); PP_COMPUTE(0, 0); PP_BAR(); PP_STAMP(1);                                         \
-    /* phase 1 */                                                                                           \
-    PP_M(PP_RD_B(cur, 1), PP_SLOTS(PPD0, PPD0 + PPD1, cur, t));                                             \
-    if (more1) { PP_VMCNT_N(4 + PPD0 + PPD1); } else { PP_VMCNT(0); }     /* A1(t) landed */               \
-    PP_BAR(); PP_STAMP(2); PP_COMPUTE(0, 1); PP_BAR(); PP_STAMP(3);                                         \
-    /* phase 2 */                                                                                           \
-    PP_M(PP_RD_A(cur, 1), PP_SLOTS(PPD0 + PPD1, PPD0 + PPD1 + PPD2, cur, t));                               \
-    PP_BAR(); PP_STAMP(4); PP_COMPUTE(1, 1); PP_BAR(); PP_STAMP(5);                                         \
-    /* phase 3: B0 fragments are still in bq[0] */                                                          \
-    PP_M(, PP_SLOTS(PPD0 + PPD1 + PPD2, 8, cur, t));                                                        \
-    if (more2) { PP_VMCNT(8); } else if (more1) { PP_VMCNT(4); }      /* A0(t+1), B0(t+1) landed */         \
-    PP_BAR(); PP_STAMP(6); PP_COMPUTE(1, 0); PP_BAR(); PP_STAMP(7);                                         \
-    PP_STAMPS_FOLD();                                                                                       \
-  } while (0)
-#endif
 
-#if DXA_PPR
   // ---- prologue: the four pieces of tile 0 and A0, B0, B1 of tile 1 in the steady state's issue order; A0(0), B0(0), B1(0) landed
   //      for every wave before the first read; tile 0's A0 / B0 fragments are read here (C3 of "tile -1")
   PP_DMA_A(0, 0, 0); PP_DMA_B(0, 0, 0); PP_DMA_B(1, 0, 0); PP_DMA_A(1, 0, 0);
-#if DXA_PPR == 2
-  if (nk > 1) { PP_DMA_B(0, 1, 1); PP_DMA_A(0, 1, 1); PP_DMA_B(1, 1, 1); }
-#else
   if (nk > 1) { PP_DMA_A(0, 1, 1); PP_DMA_B(0, 1, 1); PP_DMA_B(1, 1, 1); }
-#endif
   PP_SB();
   if (nk > 1) { PP_VMCNT(8); } else { PP_VMCNT(2); }
   PP_BAR();
   PP_RD_A(0, 0); PP_RD_B(0, 0);
   PP_SB();
-#else
-  // ---- prologue: the four pieces of tile 0 and the first two of tile 1; A0(0) and B0(0) landed for every wave before
-  //      the first read
-  PP_DMA_A(0, 0, 0); PP_DMA_B(0, 0, 0); PP_DMA_B(1, 0, 0); PP_DMA_A(1, 0, 0);
-  if (nk > 1) { PP_DMA_A(0, 1, 1); PP_DMA_B(0, 1, 1); }
-  PP_SB();
-  if (nk > 1) { PP_VMCNT(8); } else { PP_VMCNT(4); }
-  PP_BAR();
-#endif
-  if (!(DXA_PPV & 16) && wm == 1) PP_BAR();    // group 1 runs one barrier interval behind group 0
+  if (wm == 1) PP_BAR();    // group 1 runs one barrier interval behind group 0
   for (int t = 0; t < nk; t += 2) {
     PP_TILE(0, t);
     if (t + 1 < nk) PP_TILE(1, t + 1);
   }
-  if (!(DXA_PPV & 16) && wm == 0) PP_BAR();    // every wave has now passed the same number of barriers
-#if (DXA_PPV & 128)
+  if (wm == 0) PP_BAR();    // every wave has now passed the same number of barriers
+#if defined(DXA_PP_STAMPS)
   const uint32_t iv0_ = iv_[0], iv1_ = iv_[1], iv2_ = iv_[2], iv3_ = iv_[3], iv4_ = iv_[4], iv5_ = iv_[5], iv6_ = iv_[6], iv7_ = iv_[7];
 #endif
 #undef PP_A_ROW0
 #undef PP_B_ROW0
 #undef PP_DMA
-#undef PP_LOOP
 #undef PP_DMA_A
 #undef PP_DMA_B
 #undef PP_READ
@@ -1488,37 +1314,23 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
 #undef PP_COMPUTE
 #undef PP_VMCNT
 #undef PP_TILE
-#undef PP_SLOT
-#undef PP_SLOTS
-#undef PP_VMCNT_N
 #undef PP_DMA_A1
 #undef PP_DMA_B1
-#undef PP_M
 #undef PP_STAMP
 #undef PP_STAMPS_FOLD
 #undef PP_RDK_A
 #undef PP_RDK_B
 #undef PP_COMPUTE_R
-#undef PP_COMPUTE_R2
-#undef PP_RDK_B2
-#undef PP_MFMA2
-#if DXA_PPR == 2
-#undef PP_R2_B1
-#undef PP_R2_A1
-#undef PP_R2_B0N
-#undef PP_R2_A0N
-#elif DXA_PPR
 #undef PP_R_B1
 #undef PP_R_A1
 #undef PP_R_NEXT
-#endif
 
   if constexpr (LEAN) {
     if (!tile_split_exchange<4>(p, acc, tid, split_j, split_s, tail_i)) return;
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (FUSE == 1) sk_epilogue_swiglu<4>(p, acc, smem + wave * 4096, lane, wm, wn, m0i, n0i);
     else sk_epilogue<TO, TE>(p, acc, smem + wave * 4096, lane, wm, wn, m0i, n0i, reinterpret_cast<float*>(smem + 8 * 4096), bid);
-#if (DXA_PPV & 128)
+#if defined(DXA_PP_STAMPS)
     __syncthreads();
     if (m0i == 0 && n0i == 0 && lane == 0) {          // the first tile's waves: [wave][8 intervals + K tiles] over the head of C
       uint32_t* o_ = reinterpret_cast<uint32_t*>(p.C) + wave * 16;
@@ -1831,10 +1643,6 @@ inline int num_cus() {
   }
   return n;
 }
-inline bool skinny_off_g() {
-  static const bool off = getenv("DXA_GEMM_NO_SKINNY") != nullptr;
-  return off;
-}
 inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 inline bool strides_mult(const int64_t s[3], int64_t m) { return s[0] % m == 0 && s[1] % m == 0 && s[2] % m == 0; }
 
@@ -1901,8 +1709,7 @@ int gemm_dispatch(const dxa_gemm_desc* d, dxa_stream_t stream, bool* mirrored, b
   //      large bf16 NT / NN product to the generic kernel (3x slower): K = K0 + K1 with K0 = K - K % 64 on the MFMA fast path
   //      (bias / residual epilogue applied there) and the < 64-deep tail accumulated on top by the generic kernel.  With a bf16
   //      C the partial result is rounded once more than a single pass would (one extra bf16 rounding of the output).
-  static const bool ksplit_off = getenv("DXA_GEMM_NO_KTAIL") != nullptr;
-  if (!ksplit_off && d->in_dtype == DXA_BF16 && nbatch == 1 && d->layout != DXA_TN && d->K % 64 != 0 && d->K >= 1024 &&
+  if (d->in_dtype == DXA_BF16 && nbatch == 1 && d->layout != DXA_TN && d->K % 64 != 0 && d->K >= 1024 &&
       d->M >= 256 && d->N >= 256 && d->act == DXA_ACT_NONE && !d->aux_out && !d->mulgrad && !d->sumsq && !d->mirror && !d->epi_f32) {
     const int64_t K0 = d->K - d->K % 64;
     dxa_gemm_desc head = *d, tail = *d;
@@ -1968,8 +1775,6 @@ int gemm_dispatch(const dxa_gemm_desc* d, dxa_stream_t stream, bool* mirrored, b
   //      k-contiguous A, TN takes any K
   const int64_t bytesA = (a_ks ? (d->K - 1) * d->lda + d->M : (d->M - 1) * d->lda + d->K) * 2;
   const int64_t bytesB = (b_ks ? (d->K - 1) * d->ldb + d->N : (d->N - 1) * d->ldb + d->K) * 2;
-  static const bool fast_off = getenv("DXA_GEMM_NO_FAST") != nullptr;
-  static const bool ks_off = getenv("DXA_GEMM_NO_KS") != nullptr;
   const bool ks_layout = d->layout != DXA_NT;
   const int64_t cpl = 16 / (int64_t)os;
   // the lean epilogue: C = alpha * acc + bias (+ residual) (+ C) made of whole 16-byte accesses
@@ -1978,35 +1783,26 @@ int gemm_dispatch(const dxa_gemm_desc* d, dxa_stream_t stream, bool* mirrored, b
                        d->act == DXA_ACT_NONE && (!d->bias || aligned_to(d->bias, cpl * ees)) &&
                        (!d->residual || (aligned_to(d->residual, cpl * ees) && d->ldr % cpl == 0 &&
                                          ((d->M - 1) * d->ldr + d->N) * (int64_t)ees < (1ll << 31)));
-  const bool ks_ok = (d->layout == DXA_NN ? (d->out_dtype == DXA_BF16 || lean_ok) : lean_ok) && !d->epi_f32 && ks_layout && !ks_off && aligned_to(d->A, 16) && aligned_to(d->B, 16) && d->lda % 8 == 0 && d->ldb % 8 == 0 &&
+  const bool ks_ok = (d->layout == DXA_NN ? (d->out_dtype == DXA_BF16 || lean_ok) : lean_ok) && !d->epi_f32 && ks_layout && aligned_to(d->A, 16) && aligned_to(d->B, 16) && d->lda % 8 == 0 && d->ldb % 8 == 0 &&
                      (d->layout == DXA_TN || d->K % 64 == 0) && d->K >= 64;
   // ---- few-row NT products (batch-1 prefill, ViT on a couple of images): 128x128 tiles fill the chip where 256-row tiles
   //      cannot; any epilogue of the bf16 menu
-  static const bool t128_off = getenv("DXA_GEMM_NO_T128") != nullptr;
-  static const int t128_max_m = getenv("DXA_GEMM_T128_MAX_M") ? atoi(getenv("DXA_GEMM_T128_MAX_M")) : 1024;
   // measured (scripts/gemm_bench.py pre, M = 543 / 514): wins where its tiles fit one round of the 256 CUs and K is short
   // (qkv 45 vs 50 us, o_proj 44 vs 52, ViT fc1 20 vs 31); loses to the 192-row ring kernel + split-K tail on wide N or deep K
   // (gate_up 211 vs 181, down 181 vs 120): an LDS-DMA instruction costs its wave 60-180 issue cycles, and a 128x128 tile
   // needs twice as many of them per MFMA as a 256x256 tile
   const int64_t t128_tiles = (int64_t)dxa_cdiv(d->M, 128) * dxa_cdiv(d->N, 128);
-  static const bool t128_all = getenv("DXA_GEMM_T128_NS") != nullptr;     // tuning: every admissible shape
-  // (epi_f32 = the split-bf16 fp32 products of the action head: M = 64 x 17 rows, K' = 3K up to 9216 — their 128x128 tiles fill
-  //  54-216 CUs where the 192-row ring kernel's fill 18-72)
-  // opt-in (DXA_GEMM_T128_F32EPI=1): parity-green, but the step measured the same with it (255.6 vs 256.2 ms on one box)
-  static const bool t128_f32epi = getenv("DXA_GEMM_T128_F32EPI") && atoi(getenv("DXA_GEMM_T128_F32EPI")) != 0;
-  if (!fast_off && !t128_off && d->fuse == DXA_FUSE_NONE && d->layout == DXA_NT && d->in_dtype == DXA_BF16 && nbatch == 1 && (!d->epi_f32 || t128_f32epi) &&
-      d->M >= 64 && d->M <= (d->epi_f32 ? 2048 : t128_max_m) && d->N >= 64 && d->K >= 64 && d->K % 64 == 0 && p.vecA && p.vecB &&
-      bytesA < (1ll << 31) && bytesB < (1ll << 31) &&
-      (t128_all || (t128_tiles >= 32 && t128_tiles <= NUM_CU && (d->K <= 4096 || d->epi_f32)))) {
+  // (the split-bf16 fp32 products of the action head, epi_f32, measured the same on these tiles: they stay on the 256-row kernels)
+  if (d->fuse == DXA_FUSE_NONE && d->layout == DXA_NT && d->in_dtype == DXA_BF16 && nbatch == 1 && !d->epi_f32 &&
+      d->M >= 64 && d->M <= 1024 && d->N >= 64 && d->K >= 64 && d->K % 64 == 0 && p.vecA && p.vecB &&
+      bytesA < (1ll << 31) && bytesB < (1ll << 31) && t128_tiles >= 32 && t128_tiles <= NUM_CU && d->K <= 4096) {
     p.tm = dxa_cdiv(d->M, 128);
     p.tn = dxa_cdiv(d->N, 128);
     // few tiles over a deep K: cut K so that every CU gets a workgroup (>= 8 K tiles of 64 per slice, <= 4 slices)
-    static const bool t128_nosplit = getenv("DXA_GEMM_NO_SPLIT") != nullptr;
     int t_split = 1;
     // (120 tiles x K 1024 measured slower cut in two: 21.2 vs 18.7 us; up to half the CUs over a deep K it pays: the decoder's
     //  qkv / o_proj at 287 rows are 108 / 84 tiles of K 3584, each CU's feed rate being the bound)
-    static const int t128_deepk = getenv("DXA_GEMM_T128_DEEPK") ? atoi(getenv("DXA_GEMM_T128_DEEPK")) : 2048;
-    if (!t128_nosplit && (t128_tiles <= NUM_CU / 4 || (t128_tiles <= NUM_CU / 2 && t128_deepk > 0 && d->K >= t128_deepk)))
+    if (t128_tiles <= NUM_CU / 4 || (t128_tiles <= NUM_CU / 2 && d->K >= 2048))
       t_split = (int)std::min<int64_t>(std::min<int64_t>(4, NUM_CU / t128_tiles), (d->K / 64) / 8);
     if (t_split >= 2) {
       SplitWs w;
@@ -2016,35 +1812,18 @@ int gemm_dispatch(const dxa_gemm_desc* d, dxa_stream_t stream, bool* mirrored, b
       p.split_s = 1;
     }
     dim3 tgrid((unsigned)(p.tm * p.tn * p.split_s));
-    // two stages (64 KiB): two workgroups share a CU and hide each other's LDS-DMA issue and barriers; four stages when a CU
-    // gets one workgroup anyway
-    static const int force_ns = getenv("DXA_GEMM_T128_NS") ? atoi(getenv("DXA_GEMM_T128_NS")) : 0;
-    const int ns = force_ns ? force_ns : (p.tm * p.tn > NUM_CU ? 2 : 4);
-#define LAUNCH_T128(TO_, NS_, WS_)                                                                                   \
+    // four stages (a CU gets one workgroup: the tile count is <= NUM_CU), four dedicated loader waves
+#define LAUNCH_T128(TO_)                                                                                             \
   do {                                                                                                               \
     static bool attr_set = false;                                                                                    \
     if (!attr_set) {                                                                                                 \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_t128_kernel<TO_, NS_, WS_>),                  \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, NS_ * 32768);                            \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_t128_kernel<TO_, 4, 4>),                      \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 32768);                              \
       attr_set = true;                                                                                               \
     }                                                                                                                \
-    hipLaunchKernelGGL((gemm_nt_t128_kernel<TO_, NS_, WS_>), tgrid, dim3(256 + 64 * WS_), NS_ * 32768, st, p);       \
+    hipLaunchKernelGGL((gemm_nt_t128_kernel<TO_, 4, 4>), tgrid, dim3(512), 4 * 32768, st, p);                        \
   } while (0)
-    // wave-specialised build: DXA_GEMM_T128_WS = number of dedicated loader waves (0: every wave loads and computes, 4, 8)
-    static const int t128_ws = getenv("DXA_GEMM_T128_WS") ? atoi(getenv("DXA_GEMM_T128_WS")) : 4;
-    if (d->epi_f32) {
-      static bool attr_f32 = false;
-      if (!attr_f32) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_t128_kernel<float, 4, 4, float>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 32768);
-        attr_f32 = true;
-      }
-      hipLaunchKernelGGL((gemm_nt_t128_kernel<float, 4, 4, float>), tgrid, dim3(512), 4 * 32768, st, p);
-    } else
-    if (ns == 2) { if (d->out_dtype == DXA_BF16) LAUNCH_T128(bf16_t, 2, 0); else LAUNCH_T128(float, 2, 0); }
-    else if (t128_ws == 8) { if (d->out_dtype == DXA_BF16) LAUNCH_T128(bf16_t, 4, 8); else LAUNCH_T128(float, 4, 8); }
-    else if (t128_ws == 4) { if (d->out_dtype == DXA_BF16) LAUNCH_T128(bf16_t, 4, 4); else LAUNCH_T128(float, 4, 4); }
-    else { if (d->out_dtype == DXA_BF16) LAUNCH_T128(bf16_t, 4, 0); else LAUNCH_T128(float, 4, 0); }
+    if (d->out_dtype == DXA_BF16) LAUNCH_T128(bf16_t); else LAUNCH_T128(float);
 #undef LAUNCH_T128
     DXA_CHECK_LAUNCH();
     return DXA_OK;
@@ -2054,7 +1833,7 @@ int gemm_dispatch(const dxa_gemm_desc* d, dxa_stream_t stream, bool* mirrored, b
   if (d->K2 > 0) {
     DXA_CHECK_ARG(d->layout == DXA_TN && d->A2 && d->B2 && nbatch == 1, "dxa_gemm: A2 / B2 / K2 need an unbatched TN product");
     const int64_t bytesA2 = ((d->K2 - 1) * d->lda + d->M) * 2, bytesB2 = ((d->K2 - 1) * d->ldb + d->N) * 2;
-    const bool seg_fast = !fast_off && d->in_dtype == DXA_BF16 && ks_ok && d->M >= 64 && d->N >= 64 &&
+    const bool seg_fast = d->in_dtype == DXA_BF16 && ks_ok && d->M >= 64 && d->N >= 64 &&
                           (int64_t)d->M * d->N >= 128 * 128 && bytesA < (1ll << 31) && bytesB < (1ll << 31) &&
                           bytesA2 < (1ll << 31) && bytesB2 < (1ll << 31) && aligned_to(d->A2, 16) && aligned_to(d->B2, 16);
     if (!seg_fast) {
@@ -2068,32 +1847,26 @@ int gemm_dispatch(const dxa_gemm_desc* d, dxa_stream_t stream, bool* mirrored, b
     }
     p.A2 = (const char*)d->A2; p.B2 = (const char*)d->B2; p.K2 = d->K2;
   }
-  if (!fast_off && d->in_dtype == DXA_BF16 && nbatch == 1 &&
+  if (d->in_dtype == DXA_BF16 && nbatch == 1 &&
       ((d->layout == DXA_NT && d->K >= 32 && d->K % 32 == 0 && p.vecA && p.vecB) || ks_ok) &&
       d->M >= 64 && d->N >= 64 && (int64_t)d->M * d->N >= 128 * 128 && bytesA < (1ll << 31) && bytesB < (1ll << 31)) {
     // 192-row tiles when they trim the padded row count by more than 8% (they run ~6% below the 256-row tile's rate)
-    static const int force_ai = getenv("DXA_GEMM_RING_AI") ? atoi(getenv("DXA_GEMM_RING_AI")) : 0;
     const int64_t pad256 = (int64_t)dxa_cdiv(d->M, 256) * 256, pad192 = (int64_t)dxa_cdiv(d->M, 192) * 192;
-    const int ai = ks_layout ? 4 : (force_ai ? force_ai : (pad192 * 27 < pad256 * 25 ? 3 : 4));
+    const int ai = ks_layout ? 4 : (pad192 * 27 < pad256 * 25 ? 3 : 4);
     p.tm = dxa_cdiv(d->M, ai * 64);
     p.tn = dxa_cdiv(d->N, 256);
     const int nt = p.tm * p.tn, nk_tot = (int)((d->K + d->K2 + 31) / 32);
     p.full = nt; p.tail_r = 0; p.split_s = 1;
-    static const int group_m = getenv("DXA_GEMM_GROUP_M") ? atoi(getenv("DXA_GEMM_GROUP_M")) : 4;
-    p.group_m = group_m;
-    static const bool split_off = getenv("DXA_GEMM_NO_SPLIT") != nullptr;
+    p.group_m = 4;
     const int tail = nt % NUM_CU;
-    if (!split_off && tail > 0) {
-      // the last round would leave NUM_CU - tail CUs idle: cut its tiles along K (>= 16 slabs per piece)
-      // (measured: each fp32 partial slot costs ~0.25 us of write-through traffic, so short K does not pay)
-      static const int min_nk = getenv("DXA_SPLIT_MIN_NK") ? atoi(getenv("DXA_SPLIT_MIN_NK")) : 64;
-      // (min_piece: K slabs of 32 per piece.  16 — rounds 1 - 6 — cut the tail tiles of the step's products and the fp32 head's dW products
+    if (tail > 0) {
+      // the last round would leave NUM_CU - tail CUs idle: cut its tiles along K into <= 8 pieces of >= 32 slabs, when K has
+      // >= 64 slabs (measured: each fp32 partial slot costs ~0.25 us of write-through traffic, so short K does not pay)
+      // (32 slabs per piece: 16 — rounds 1 - 6 — cut the tail tiles of the step's products and the fp32 head's dW products
       //  into up to 6 - 7 pieces of 512-deep K; at >= 32 slabs (1024-deep pieces, <= 3 of them at K = 3584) the step is 1.8 - 2.6 ms
       //  shorter, MemVLA's 2.8 ms, the 287-row request's gate/up 126 -> 119 us: a piece's fp32 partial costs its write-through and read-back
       //  whoever adds it up (profiles/r06_split_dist.txt).  24: -1.0 ms, 48: -1.3, 64: level, no split at all: +7.5 — profiles/r06_split_knobs.txt)
-      static const int min_piece = getenv("DXA_SPLIT_MIN_PIECE") ? atoi(getenv("DXA_SPLIT_MIN_PIECE")) : 32;
-      static const int max_split = getenv("DXA_SPLIT_MAX") ? atoi(getenv("DXA_SPLIT_MAX")) : 8;
-      const int s = nk_tot >= min_nk ? std::min(std::min(NUM_CU / tail, max_split), nk_tot / min_piece) : 1;
+      const int s = nk_tot >= 64 ? std::min(std::min(NUM_CU / tail, 8), nk_tot / 32) : 1;
       if (s >= 2) {
         SplitWs w;
         if (int rc = get_split_ws(st, &w)) return rc;
@@ -2113,9 +1886,7 @@ int gemm_dispatch(const dxa_gemm_desc* d, dxa_stream_t stream, bool* mirrored, b
     hipLaunchKernelGGL((gemm_nt_ring_kernel<TO_, AI_, TE_>), fgrid, dim3(512), RING_LDS, st, p);                \
   } while (0)
     // ---- ping-pong main loop: 256-row tiles, K % 64 == 0; the lean epilogue when it is made of whole 16-byte accesses
-    static const bool pp_off = getenv("DXA_GEMM_NO_PP") != nullptr;
-    static const bool pp3_on = !(getenv("DXA_GEMM_PP3") && atoi(getenv("DXA_GEMM_PP3")) == 0);
-    const bool pp = ks_layout || (!pp_off && ai == 4 && d->K % 64 == 0);
+    const bool pp = ks_layout || (ai == 4 && d->K % 64 == 0);
     const bool lean = pp && lean_ok;
 #define LAUNCH_PP(TO_, TE_, LEAN_, AKS_, BKS_)                                                                  \
   do {                                                                                                          \
@@ -2165,8 +1936,8 @@ int gemm_dispatch(const dxa_gemm_desc* d, dxa_stream_t stream, bool* mirrored, b
       else LAUNCH_PP(float, bf16_t, false, false, false);
     }
 #undef LAUNCH_PP
-    // ---- 192-row tiles on the ping-pong schedule (round 4): K % 64 == 0; DXA_GEMM_PP3=0: the ring kernel
-    else if (ai == 3 && pp3_on && d->K % 64 == 0 && d->layout == DXA_NT) {
+    // ---- 192-row tiles on the ping-pong schedule (round 4): K % 64 == 0
+    else if (ai == 3 && d->K % 64 == 0 && d->layout == DXA_NT) {
 #define LAUNCH_PP3(TO_, TE_, LEAN_)                                                                             \
   do {                                                                                                          \
     static bool attr_set = false;                                                                               \
@@ -2189,12 +1960,11 @@ int gemm_dispatch(const dxa_gemm_desc* d, dxa_stream_t stream, bool* mirrored, b
     DXA_CHECK_LAUNCH();
     return DXA_OK;
   }
-  DXA_CHECK_ARG(d->fuse == DXA_FUSE_NONE, "dxa_gemm: fuse is only implemented on the bf16 NT MFMA fast path (DXA_GEMM_NO_FAST set?)");
+  DXA_CHECK_ARG(d->fuse == DXA_FUSE_NONE, "dxa_gemm: fuse is only implemented on the bf16 NT MFMA fast path (K %% 32 == 0, M, N >= 64, 16-byte aligned rows, no batching)");
   DXA_CHECK_ARG(!d->epi_f32, "dxa_gemm: epi_f32 is only implemented on the bf16 NT fast path (K %% 32 == 0, M, N >= 64, "
                               "16-byte aligned rows, no batching)");
   // ---- few-row NN (dX of a linear on <= 8 tokens): a stream over W as it lies, K cut into slices, partials in the split scratch
-  static const bool gemv_off = getenv("DXA_GEMM_NO_GEMV") != nullptr;
-  if (!gemv_off && d->layout == DXA_NN && d->in_dtype == DXA_BF16 && nbatch == 1 && d->M <= GV_MAXM && d->K >= 64 &&
+  if (d->layout == DXA_NN && d->in_dtype == DXA_BF16 && nbatch == 1 && d->M <= GV_MAXM && d->K >= 64 &&
       d->N >= 64 && d->N % 8 == 0 && d->ldb % 8 == 0 && aligned_to(d->B, 16) && !d->bias && !d->residual && !d->aux_out &&
       !d->mulgrad && d->act == DXA_ACT_NONE && !d->accumulate && !d->epi_f32) {
     const int nbn = dxa_cdiv(d->N, 2048);
@@ -2221,16 +1991,13 @@ int gemm_dispatch(const dxa_gemm_desc* d, dxa_stream_t stream, bool* mirrored, b
     }
   }
   // ---- skinny bf16 path: M <= 64 (KV-cached decode, few-row products): a stream over the weights
-  if (!skinny_off_g() && d->layout == DXA_NT && d->in_dtype == DXA_BF16 && nbatch == 1 && d->M <= 64 && d->K >= 64 &&
+  if (d->layout == DXA_NT && d->in_dtype == DXA_BF16 && nbatch == 1 && d->M <= 64 && d->K >= 64 &&
       d->K % 64 == 0 && p.vecA && p.vecB) {
     // few column tiles (<= 128) over a deep K: K cut across workgroups (>= 8 blocks of 64 k per range), as for the fp32 twin
-    static const int skb_target = getenv("DXA_SKINNY_TARGET") ? atoi(getenv("DXA_SKINNY_TARGET")) : 256;
-    static const int skb_maxtiles = getenv("DXA_SKINNY_BF16_MAXTILES") ? atoi(getenv("DXA_SKINNY_BF16_MAXTILES")) : NUM_CU / 2;
-    static const int skb_unroll = getenv("DXA_SKINNY_BF16_UNROLL") ? atoi(getenv("DXA_SKINNY_BF16_UNROLL")) : 4;
     const int64_t skb_tiles = dxa_cdiv(d->N, 16);
     int skb_split = 1;
-    if (skb_target > 0 && skb_tiles <= skb_maxtiles)
-      skb_split = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8, (d->K / 64) / 8), dxa_cdiv(skb_target, skb_tiles)));
+    if (skb_tiles <= NUM_CU / 2)
+      skb_split = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8, (d->K / 64) / 8), dxa_cdiv(256, skb_tiles)));
     p.split_s = 1;
     if (skb_split >= 2) {
       SplitWs w;
@@ -2239,36 +2006,27 @@ int gemm_dispatch(const dxa_gemm_desc* d, dxa_stream_t stream, bool* mirrored, b
     }
     dim3 sgrid((unsigned)(skb_tiles * p.split_s));
     const int mb = dxa_cdiv(d->M, 16);
-#define LAUNCH_SK(MB_)                                                                                              \
+    // one row (the decode step): 4 blocks of 64 k in flight per wave, 2 for more rows
+#define LAUNCH_SK(MB_, U_)                                                                                          \
   do {                                                                                                              \
-    if (d->out_dtype == DXA_BF16) hipLaunchKernelGGL((gemm_skinny_bf16_kernel<MB_, bf16_t>), sgrid, dim3(512), 0, st, p); \
-    else hipLaunchKernelGGL((gemm_skinny_bf16_kernel<MB_, float>), sgrid, dim3(512), 0, st, p);                   \
+    if (d->out_dtype == DXA_BF16) hipLaunchKernelGGL((gemm_skinny_bf16_kernel<MB_, bf16_t, U_>), sgrid, dim3(512), 0, st, p); \
+    else hipLaunchKernelGGL((gemm_skinny_bf16_kernel<MB_, float, U_>), sgrid, dim3(512), 0, st, p);               \
   } while (0)
-    if (mb == 1 && skb_unroll != 2) {            // one row (the decode step): 4 blocks in flight; DXA_SKINNY_BF16_UNROLL=1: rounds 2-4
-#define LAUNCH_SK1(U_)                                                                                              \
-  do {                                                                                                              \
-    if (d->out_dtype == DXA_BF16) hipLaunchKernelGGL((gemm_skinny_bf16_kernel<1, bf16_t, U_>), sgrid, dim3(512), 0, st, p); \
-    else hipLaunchKernelGGL((gemm_skinny_bf16_kernel<1, float, U_>), sgrid, dim3(512), 0, st, p);                 \
-  } while (0)
-      if (skb_unroll == 1) LAUNCH_SK1(1); else LAUNCH_SK1(4);
-#undef LAUNCH_SK1
-    } else if (mb == 1) LAUNCH_SK(1); else if (mb == 2) LAUNCH_SK(2); else if (mb == 3) LAUNCH_SK(3); else LAUNCH_SK(4);
+    if (mb == 1) LAUNCH_SK(1, 4); else if (mb == 2) LAUNCH_SK(2, 2); else if (mb == 3) LAUNCH_SK(3, 2); else LAUNCH_SK(4, 2);
 #undef LAUNCH_SK
     DXA_CHECK_LAUNCH();
     return DXA_OK;
   }
   // ---- skinny fp32 path: M <= 64 (DiT head at inference), weights streamed by N/16 workgroups of 8 K-splitting waves
-  if (!skinny_off_g() && d->layout == DXA_NT && d->in_dtype == DXA_F32 && d->out_dtype == DXA_F32 && nbatch == 1 &&
+  if (d->layout == DXA_NT && d->in_dtype == DXA_F32 && d->out_dtype == DXA_F32 && nbatch == 1 &&
       d->M <= 64 && d->K >= 64 && d->K % 64 == 0 && p.vecA && p.vecB) {
     // few column tiles (<= 128) over a deep K: cut K so that ~256 workgroups share the exact-fp32 MFMAs (32 cycles apiece: 64
     // workgroups walking K 4096 are MFMA-bound, DiT-L fc2 33 -> 19 us cut in four); each of a range's 8 waves keeps >= 1 block of
     // 64 k.  192+ tiles measured slower cut (15.1 vs 12.1 us)
-    static const int sk_target = getenv("DXA_SKINNY_TARGET") ? atoi(getenv("DXA_SKINNY_TARGET")) : 256;
-    static const int sk_minkb = getenv("DXA_SKINNY_MINKB") ? std::max(1, atoi(getenv("DXA_SKINNY_MINKB"))) : 8;
     const int64_t sk_tiles = dxa_cdiv(d->N, 16);
     int sk_split = 1;
-    if (sk_target > 0 && sk_tiles <= NUM_CU / 2)
-      sk_split = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8, (d->K / 64) / sk_minkb), dxa_cdiv(sk_target, sk_tiles)));
+    if (sk_tiles <= NUM_CU / 2)
+      sk_split = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8, (d->K / 64) / 8), dxa_cdiv(256, sk_tiles)));
     p.split_s = 1;
     if (sk_split >= 2) {
       SplitWs w;

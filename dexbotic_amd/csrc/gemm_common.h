@@ -279,12 +279,6 @@ __device__ __forceinline__ void tile_finish(const GemmP& p, f32x16_t (&acc)[AI][
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
-// Tuning builds (scripts/ablate_gemm.sh): -DDXA_PPV=<bits> removes parts of the main loop (results are garbage, timings are
-// not): 1 no LDS-DMA in the loop, 2 no ds_read, 4 no MFMA, 8 s_setprio around the MFMA clusters, 16 no stagger,
-// 32 no epilogue stores.
-#ifndef DXA_PPV
-#define DXA_PPV 0
-#endif
 // origin of tile t of the grouped order (group_m row tiles x all column tiles per group)
 __device__ __forceinline__ void sk_tile_origin(const GemmP& p, int t, int& m0, int& n0) {
   const int width = p.group_m * p.tn;
@@ -414,7 +408,6 @@ __device__ __forceinline__ float sk_epilogue_rows(const GemmP& p, f32x16_t (&acc
 #pragma unroll
           for (int e = 0; e < CPL; ++e) v[e] += c0[e];
         }
-#if !(DXA_PPV & 32)
         SkIO<TO>::template st<CPL>(v, rC, oc);
         if constexpr (sizeof(TO) == 2) {
           if (want_ssq && ok) {                                // bf16 gradient arena: the norm is taken over what is stored
@@ -433,7 +426,6 @@ __device__ __forceinline__ float sk_epilogue_rows(const GemmP& p, f32x16_t (&acc
             __builtin_amdgcn_raw_buffer_store_b64(o2, rM, ok ? (offC0 + rr * ldcB) >> 1 : 0x80000000u, 0, 0);
           }
         }
-#endif
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();

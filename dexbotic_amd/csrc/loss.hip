@@ -207,8 +207,7 @@ extern "C" int dxa_argmax_rows(const void* x, int64_t ld, int64_t* out, int64_t 
   const size_t es = dtype == DXA_BF16 ? 2 : 4;
   const bool vec = cols % 4 == 0 && ld % 4 == 0 && al(x, 4 * es);
   dim3 grid((unsigned)rows);
-  static const bool wide_off = getenv("DXA_ARGMAX_NO_WIDE") != nullptr;
-  if (!wide_off && dtype == DXA_BF16 && rows <= 64 && cols >= 16384 && cols < (1ll << 31) && cols % 8 == 0 && ld % 8 == 0 && al(x, 16)) {
+  if (dtype == DXA_BF16 && rows <= 64 && cols >= 16384 && cols < (1ll << 31) && cols % 8 == 0 && ld % 8 == 0 && al(x, 16)) {
     hipLaunchKernelGGL(argmax_rows_wide_k, grid, dim3(1024), 0, ST, (const bf16_t*)x, ld, out, (int)cols);
     DXA_CHECK_LAUNCH();
     return DXA_OK;

@@ -716,15 +716,14 @@ bool launch_norm_bwd_fast(const void* dy, const void* x, const void* w, const fl
   int64_t g = (rows + 3) / 4;
   if (g > NORM_BWD_MAX_BLOCKS) g = NORM_BWD_MAX_BLOCKS;
   dim3 grid((unsigned)g);
-  static const bool split_off = getenv("DXA_NORM_BWD_NO_SPLIT") != nullptr;      // A/B: profiles/r05_norm_bwd_split.txt
-  if (!LN && !split_off && vec_ok && dtype == DXA_BF16 && cols % 16 == 0 && cols <= 8192 && (cols * 4) % 16 == 0 &&
+  // the row split between two waves (A/B against the one-wave-per-row kernels below: profiles/r05_norm_bwd_split.txt)
+  if (!LN && vec_ok && dtype == DXA_BF16 && cols % 16 == 0 && cols <= 8192 && (cols * 4) % 16 == 0 &&
       (!partial || (reinterpret_cast<uintptr_t>(partial) & 15) == 0)) {
-    // DXA_NORM_BWD_ROWS=3: three rows per workgroup pass (384 threads, 168 registers: no spill) instead of four (512 threads at
-    // 128 registers: a dozen spilled dwords) — tuning switch, profiles/r05_norm_bwd_split.txt
-    static const int ns = getenv("DXA_NORM_BWD_ROWS") ? atoi(getenv("DXA_NORM_BWD_ROWS")) : 4;
+    // four rows per workgroup pass (512 threads at 128 registers: a dozen spilled dwords); the three-row form (384 threads, 168
+    // registers, no spill) against it: profiles/r05_norm_bwd_split.txt
 #define LAUNCH_SPLIT(TW_, NIT_, NS_) hipLaunchKernelGGL((rmsnorm_bwd_split_k<TW_, NIT_, NS_>), grid, dim3(NS_ * 128), 0, st, (const bf16_t*)dy, (const bf16_t*)x, (const TW_*)w, rstd, (bf16_t*)dx, (const bf16_t*)res, partial, rows, cols)
-    if (w_dtype == DXA_BF16) { if (cols > 4096) LAUNCH_SPLIT(bf16_t, 8, 4); else if (ns == 3) LAUNCH_SPLIT(bf16_t, 4, 3); else LAUNCH_SPLIT(bf16_t, 4, 4); }
-    else { if (cols > 4096) LAUNCH_SPLIT(float, 8, 4); else if (ns == 3) LAUNCH_SPLIT(float, 4, 3); else LAUNCH_SPLIT(float, 4, 4); }
+    if (w_dtype == DXA_BF16) { if (cols > 4096) LAUNCH_SPLIT(bf16_t, 8, 4); else LAUNCH_SPLIT(bf16_t, 4, 4); }
+    else { if (cols > 4096) LAUNCH_SPLIT(float, 8, 4); else LAUNCH_SPLIT(float, 4, 4); }
 #undef LAUNCH_SPLIT
     return true;
   }
@@ -979,9 +978,8 @@ extern "C" int dxa_colsum(const void* x, int64_t ld, float* out, int64_t rows, i
     DXA_CHECK_LAUNCH();
     return DXA_OK;
   }
-  static const bool two_stage = getenv("DXA_COLSUM_TWO_STAGE") != nullptr;
   int* cnt = nullptr;
-  if (!two_stage && grid.x <= COLSUM_CNT) {
+  if (grid.x <= COLSUM_CNT) {
     if (int rc = colsum_counters(st, &cnt)) return rc;
   }
   if (cnt != nullptr) {

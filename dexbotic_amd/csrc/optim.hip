@@ -254,9 +254,7 @@ extern "C" int dxa_adamw(const dxa_adamw_desc* d, dxa_stream_t stream) {
   a.state = d->chunk_state;
   a.cms = d->chunk_mv_start;
   a.n_chunks = (int)d->n_chunks;
-  // DXA_ADAMW_GRID=<n>: at most n workgroups, each walking chunks n apart (the overlapped update's footprint on the CUs)
-  static const int grid_cap = getenv("DXA_ADAMW_GRID") ? atoi(getenv("DXA_ADAMW_GRID")) : 0;
-  const unsigned grid = grid_cap > 0 && (int64_t)grid_cap < d->n_chunks ? (unsigned)grid_cap : (unsigned)d->n_chunks;
+  const unsigned grid = (unsigned)d->n_chunks;
   if (d->g_dtype == DXA_BF16) hipLaunchKernelGGL(adamw_k<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(adamw_k<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
   DXA_CHECK_LAUNCH();

@@ -68,9 +68,6 @@ class Slot:
     bucket: int = 0
 
 
-_HOOK_JOINS = __import__('os').environ.get('DXA_JOIN_AT_BUCKET', '0') != '1'     # 1: rounds-4 behaviour (A/B)
-
-
 class ParamStore:
     """Owns the arenas.  ``specs``: ordered list of groups; a group is a list of (name, shape) packed
     contiguously; ``bucket`` ids follow registration order (= forward order) and are the unit of the
@@ -318,7 +315,7 @@ class ParamStore:
                     # stream of its own (the norm tracker, the reducer) orders THAT stream behind the side stream
                     # (wait_side); anything else makes the compute stream wait here — which stalls the dX chain for a bias
                     # column sum that nothing downstream of it needs (18 us per decoder layer, profiles/r05_step_timeline.txt)
-                    if not (_HOOK_JOINS and getattr(getattr(self.on_bucket_ready, "__self__", None), "joins_side", False)):
+                    if not getattr(getattr(self.on_bucket_ready, "__self__", None), "joins_side", False):
                         self.join_wgrad()
                     self.on_bucket_ready(b)
 
@@ -740,8 +737,7 @@ class FusedAdamW:
         self.stream = None
         if self.overlap:
             import bisect
-            prio = int(__import__("os").environ.get("DXA_OPT_STREAM_PRIO", "0"))
-            self.stream = torch.cuda.Stream(device=dev, priority=prio)
+            self.stream = torch.cuda.Stream(device=dev)
             i0, buckets, elems = 0, [], 0
             for b, (lo, hi) in enumerate(store.bucket_ranges):
                 if hi <= lo:

@@ -16,7 +16,6 @@ order: bit-identical gradients) — ~0.75 GB -> 33 MB kept per decoder layer at 
 """
 from __future__ import annotations
 
-import os
 
 from dataclasses import dataclass
 from typing import Optional, Tuple
@@ -195,25 +194,18 @@ def _wgrad_product(st: ParamStore, names, dy2d: torch.Tensor, x2d: torch.Tensor,
         K.mm_tn(dy2d, x2d, out=out, accumulate=accumulate, mirror=mirror, sumsq=ssq, **kw2)
 
 
-_SKIP_BGRAD = os.environ.get("DXA_TUNE_SKIP_BGRAD") == "1"
-_NO_DEFER_BGRAD = os.environ.get("DXA_NO_DEFER_BGRAD") == "1"      # A/B: one column sum per consumer of a bias (rounds 1 - 6a)
-
-
 def _bgrad(st: ParamStore, names, dy2d: torch.Tensor) -> None:
     names = _names(names)
     if not all(st.trainable(n) for n in names):
         return
     n = sum(st.slots[nm].numel for nm in names)
-    if _SKIP_BGRAD:            # tuning only (WRONG gradients): what the step would cost if the bias column sums were free
-        st.mark_written(*names)
-        return
     # a bias applied k times in one forward (MemVLA's per-sample retrieval blocks: 16 samples x 2 roles x 11 linears): the k dY are
     # collected like the weight's (dY, X) pairs (_wgrad) and ONE column sum over all their rows writes db once — k - 1 launches of the
     # backward's host-bound stretch less per bias (profiles/r06_host_uploads.txt: the bank's backward is issued at 21 us a launch)
     key = tuple(names)
     pending = st._uses.get(names[0], 0)
     acc0 = None
-    if st.defer_wgrad and not _NO_DEFER_BGRAD and (pending > 1 or key in st._bg_stash):
+    if st.defer_wgrad and (pending > 1 or key in st._bg_stash):
         ent = st._bg_stash.get(key)
         if ent is None:
             ent = st._bg_stash[key] = {"acc0": st.accum_flag(*names), "dy": []}
@@ -410,9 +402,8 @@ class VitBlockSpec:
 def _padded_head_dim(D: int, dtype) -> int:
     """head width the MFMA attention kernels run at for a model head_dim D (bf16 only; fp32 uses the generic kernels)"""
     # 72 (SigLIP-So400m) runs natively on the 128-wide tiles since round 5: only its 72 real columns are loaded / stored
-    # (DXA_ATTN_PAD72=1: the round-3/4 zero-padded copies, kept for the A/B of profiles/r05_pi0_hd72.txt)
-    native = (64, 128, 256) if os.environ.get("DXA_ATTN_PAD72") == "1" else (64, 72, 128, 256)
-    if dtype != torch.bfloat16 or D in native or D > 256 or D % 8 != 0:
+    # (the round-3/4 zero-padded copies: profiles/r05_pi0_hd72.txt)
+    if dtype != torch.bfloat16 or D in (64, 72, 128, 256) or D > 256 or D % 8 != 0:
         return D
     return 64 if D < 64 else (128 if D < 128 else 256)
 
@@ -517,7 +508,7 @@ def _ln_bwd(st: ParamStore, dy, x, wn: Optional[str], bn: Optional[str], mean, r
         dx, _, _ = K.layernorm_bwd(dy, x, None, mean, rstd, residual=residual)
         return dx
     tr = st.trainable(wn)
-    if tr and bn is not None and st.defer_wgrad and not _NO_DEFER_BGRAD and (st._uses.get(wn, 0) > 1 or (wn, bn) in st._bg_stash) and \
+    if tr and bn is not None and st.defer_wgrad and (st._uses.get(wn, 0) > 1 or (wn, bn) in st._bg_stash) and \
             st.slots[bn].offset == st.slots[wn].offset + st.slots[wn].numel:
         # an affine LayerNorm applied k times per forward (MemVLA's retrieval blocks): the kernel's per-row-block partial sums
         # [blocks, dw | db] of the k calls are folded by ONE column sum when the last one arrives (_bgrad's stash) instead of one per call

@@ -95,19 +95,11 @@ def split3_t(x: torch.Tensor, pad_to: int, side: int) -> torch.Tensor:
     return out
 
 
-_NO_SPLIT_PAIR = __import__("os").environ.get("DXA_NO_SPLIT_PAIR") == "1"
-
-
 def split3_pair(a: torch.Tensor, a_t: bool, b: torch.Tensor, b_t: bool, pad_to: int = 1, a_dims=None, b_dims=None
                 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """both operands of one bf16x3 product in ONE launch (dxa_split3_pair): ``a`` as the A operand (hi | hi | lo), ``b`` as the B operand
     (hi | lo | hi); ``*_t``: the split of the TRANSPOSE ([R, C] -> [C, 3 Rp], Rp = R rounded up to ``pad_to``) as split3_t writes it;
     ``*_dims`` = (rows, cols, ld) of an operand that is not simply a row-major 2-D tensor (gemm()'s explicit extents)"""
-    if _NO_SPLIT_PAIR:                                 # A/B: one launch per operand (rounds 2 - 6b)
-        res = []
-        for x, t, side, dims in ((a, a_t, 0, a_dims), (b, b_t, 1, b_dims)):
-            res.append(split3_t(x, pad_to, side) if t else split3(x, *(dims if dims is not None else (x.shape[0], x.shape[1], _row_major(x, "x"))), side))
-        return res[0], res[1]
     ops, outs = [], []
     for x, t, side, dims in ((a, a_t, 0, a_dims), (b, b_t, 1, b_dims)):
         R, C_, ld = dims if dims is not None else (x.shape[0], x.shape[1], _row_major(x, "x"))
@@ -320,13 +312,11 @@ def swiglu_gemm_supported(x: torch.Tensor, w: torch.Tensor, keep_pre: bool = Fal
     F % 8 == 0, F >= 128.  Default: the serving paths (no pre-activations kept: one output stream); the training forward, which also
     stores the [M, 2F] pre-activations from the epilogue (three 8-byte store streams and 87 M SiLUs that nothing overlaps), measured
     235.5 against 236.1 ms per step with it — inside the noise, and the product's own rate drops — so it stays on the two-launch
-    form unless DXA_SWIGLU_FUSE=1 (profiles/r06_swiglu_fuse_ab.txt).  DXA_SWIGLU_FUSE=0: two launches everywhere."""
-    import os
+    form (profiles/r06_swiglu_fuse_ab.txt)."""
+    if keep_pre:
+        return False
     M, K_ = x.shape
     F_ = w.shape[0] // 2
-    mode = os.environ.get("DXA_SWIGLU_FUSE", "")
-    if mode == "0" or (keep_pre and mode != "1"):
-        return False
     return (x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and x.is_cuda and
             M >= 129 and K_ % 64 == 0 and K_ >= 64 and F_ % 8 == 0 and F_ >= 128 and w.shape[0] % 2 == 0 and
             x.is_contiguous() and w.is_contiguous() and x.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0 and

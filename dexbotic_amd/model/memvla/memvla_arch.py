@@ -19,7 +19,6 @@ import math
 import os
 from typing import Dict, List, Optional, Tuple
 
-import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -362,9 +361,7 @@ class MemVLAForCausalLM(CogACTForCausalLM):
         loss = None
         if attention_mask is not None and actions is not None:
             plan = self.model._last_plan
-            pageable = os.environ.get("DXA_MEMVLA_PAGEABLE_UPLOAD", "0") == "1"       # (measurement switch: the round-5 uploads)
-            idx = plan.dev(hidden.device)["last_flat"] if not pageable else \
-                torch.from_numpy(np.arange(B, dtype=np.int64) * S + plan.last_index).to(hidden.device)
+            idx = plan.dev(hidden.device)["last_flat"]
             cog = Fn.GatherRowsFn.apply(hidden.reshape(B * S, d), idx).to(hidden.dtype).view(B, 1, d)
             per = self.model.per_compr(vision_proj.reshape(B, -1, d))
             eids = [tuple(int(v) for v in item[:2]) for item in indexes]
@@ -372,7 +369,7 @@ class MemVLAForCausalLM(CogACTForCausalLM):
             # forward, that throws away the 60 ms the launching thread is ahead and leaves the bank's ~2,400 small launches
             # host-bound (profiles/r06_host_uploads.txt)
             ts = torch.tensor([float(item[2]) for item in indexes], dtype=torch.float32)
-            ts = ts.to(hidden.device, non_blocking=True) if pageable else hostcpu.upload(ts, hidden.device)
+            ts = hostcpu.upload(ts, hidden.device)
             bank = self.model.per_cog_mem_bank
             cog = bank.process_batch_cog(cog, eids, ts)
             per = bank.process_batch_per(per, eids, ts)

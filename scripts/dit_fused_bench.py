@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Times the persistent DiT-block kernel at DiT-B size (12 blocks, 2 x 17 rows) against the block-by-block kernels.
-    python scripts/dit_fused_bench.py           (DXA_DIT_GRID=n caps the grid of the fused kernel)"""
+    python scripts/dit_fused_bench.py"""
 import os
 import sys
 

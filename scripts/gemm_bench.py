@@ -1,9 +1,8 @@
 #!/usr/bin/env python
 """GEMM micro-benchmark for kernel tuning: times dxa_gemm on the shapes of the DB-CogACT step.
 
-    python scripts/gemm_bench.py                 # default (fast path where eligible)
-    DXA_GEMM_NO_FAST=1 python scripts/gemm_bench.py
-    DXA_GEMM_FAST_BN=128 python scripts/gemm_bench.py
+    python scripts/gemm_bench.py                 # every shape
+    python scripts/gemm_bench.py "pre,gate_up dW" # the shapes whose names contain one of the comma-separated filters
 Random bf16 operands (uniform [-1,1): zero-filled inputs clock ~20 % higher, cdna guide rule 25)."""
 import os
 import sys

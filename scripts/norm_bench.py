@@ -1,7 +1,6 @@
 #!/usr/bin/env python
 """RMSNorm backward on the decoder's rows ([16 x 287, 3584] bf16, residual added, weight gradient wanted): time per call and, against a
-float64 torch reference, the error of dx and dw.  The kernel variant is picked by the environment (read once per process):
-    DXA_NORM_BWD_NO_SPLIT=1   round-4 kernel (one wave per row);  default: the split kernel;  DXA_NORM_BWD_ROWS=3: its 384-thread form"""
+float64 torch reference, the error of dx and dw."""
 import os
 import sys
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""Reads the barrier-to-barrier intervals the stamp build of the ping-pong kernel leaves in C (scripts/ablate_gemm.sh
-stamp:"-DDXA_PPV=128"; run with DXA_LIB=_abl/lib_stamp.so).  Interval i of a wave = cycles between its barrier exits i and i+1
+"""Reads the barrier-to-barrier intervals the stamp build of the ping-pong kernel leaves in C (scripts/build_variant.sh
+stamp -DDXA_PP_STAMPS; run with DXA_LIB=_abl/lib_stamp.so).  Interval i of a wave = cycles between its barrier exits i and i+1
 within a K tile (0: C0, 1: M1, 2: C1, 3: M2, 4: C2, 5: M3, 6: C3, 7: M0 of the next tile), averaged over the K tiles."""
 import os
 import sys

@@ -46,8 +46,8 @@ def main():
             run()
         e1.record()
         torch.cuda.synchronize()
-        print(f"DiT-L sampler, one launch, perceptual attention {per}: {e0.elapsed_time(e1) / 10:.3f} ms per sample (10 steps, {depth} blocks)"
-              f"  dbg={os.environ.get('DXA_DIT_DBG', '0')}", flush=True)
+        print(f"DiT-L sampler, one launch, perceptual attention {per}: {e0.elapsed_time(e1) / 10:.3f} ms per sample (10 steps, {depth} blocks)",
+              flush=True)
     assert not K.dit_blocks_timed_out()
     if os.environ.get("STAMPS"):          # tuning build (SRC=dit_fused.hip scripts/build_variant.sh ditstamp0 -DDXA_DIT_STAMPS=0; DXA_LIB=_abl/lib_ditstamp0.so)
         import ctypes

@@ -198,8 +198,8 @@ def test_gemm_pingpong_strided_operands(case):
 def test_gemm_ring_192_row_tiles(shape, f32out):
     """bf16 NT products on 192-row tiles (chosen when they trim the row padding: the B=1 prefill shapes): the ping-pong 192-row
     kernel (round 4: gemm_pp3_kernel, K % 64 == 0 — lean epilogue, or the generic one where N is ragged) and the ring kernel
-    (K % 64 != 0); with and without the split-K tail, ragged M and N edges.  scripts/pp3_check.py: the two kernels agree bit for bit
-    wherever they cut K at the same places (profiles/r04_pp3_vs_ring.txt)"""
+    (K % 64 != 0); with and without the split-K tail, ragged M and N edges.  The two kernels agree bit for bit wherever they
+    cut K at the same places (profiles/r04_pp3_vs_ring.txt)"""
     M, N, Kd = shape
     assert -(-M // 192) * 192 * 27 < -(-M // 256) * 256 * 25          # dispatch takes the 192-row variant
     a, w = rnd(M, Kd, dtype=torch.bfloat16, seed=25), rnd(N, Kd, dtype=torch.bfloat16, seed=26, scale=0.1)
@@ -1132,7 +1132,7 @@ def test_attention_dropout_mask(dtype):
 def test_gemm_contraction_not_multiple_of_64_takes_the_fast_path_plus_tail():
     """K = 4304 (SigLIP-So400m's MLP width): NT with bias + residual (fc2 forward) and NN (fc1 dX) run as K0 = 4288 on the
     MFMA fast path + a 16-deep tail accumulated by the generic kernel; against fp64, and against the single generic pass
-    (DXA_GEMM_NO_KTAIL semantics are exercised by the small-M call, which stays on the generic kernel)"""
+    (exercised by the small-M call, which stays on the generic kernel)"""
     M, N, Kd = 1024, 1152, 4304
     a = rnd(M, Kd, dtype=torch.bfloat16, seed=170)
     w = rnd(N, Kd, dtype=torch.bfloat16, seed=171, scale=0.05)
