@@ -1627,37 +1627,31 @@ extern "C" int dxa_attn_fwd(const dxa_attn_desc* d, dxa_stream_t stream) {
     const int srow = 16 * ((d->Sk + 15) / 16) + 4;
     const size_t lds_s = (size_t)16 * srow * sizeof(float);
     dim3 grid((unsigned)((d->Sq + 15) / 16), (unsigned)d->Hq, (unsigned)d->B);
-#define LAUNCH_SMALL(D_)                                                                                          \
-  do {                                                                                                            \
-    static size_t attr_ = 48 * 1024;                                                                              \
-    if (lds_s > attr_) {                                                                                          \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_small_f32_k<D_>),                         \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 16 * (2048 + 4) * 4);                 \
-      attr_ = 16 * (2048 + 4) * 4;                                                                                \
-    }                                                                                                             \
-    hipLaunchKernelGGL((attn_fwd_small_f32_k<D_>), grid, dim3(256), lds_s, st, p, srow);                          \
-  } while (0)
-    if (d->D == 32) LAUNCH_SMALL(32); else if (d->D == 64) LAUNCH_SMALL(64); else if (d->D == 96) LAUNCH_SMALL(96); else LAUNCH_SMALL(128);
-#undef LAUNCH_SMALL
+    constexpr int SMALL_LDS = 16 * (2048 + 4) * 4;      // Sk <= 2048
+    int rc;
+    if (d->D == 32) rc = dxa_launch_lds<attn_fwd_small_f32_k<32>>(SMALL_LDS, grid, dim3(256), lds_s, st, p, srow);
+    else if (d->D == 64) rc = dxa_launch_lds<attn_fwd_small_f32_k<64>>(SMALL_LDS, grid, dim3(256), lds_s, st, p, srow);
+    else if (d->D == 96) rc = dxa_launch_lds<attn_fwd_small_f32_k<96>>(SMALL_LDS, grid, dim3(256), lds_s, st, p, srow);
+    else rc = dxa_launch_lds<attn_fwd_small_f32_k<128>>(SMALL_LDS, grid, dim3(256), lds_s, st, p, srow);
+    if (rc) return rc;
     DXA_CHECK_LAUNCH();
     return DXA_OK;
   }
+  constexpr int GENERIC_LDS = 160 * 1024;
   const size_t lds = 4 * (size_t)(d->D + d->Sk) * sizeof(float);
-  DXA_CHECK_ARG(lds <= 160 * 1024, "dxa_attn_fwd: generic kernel supports Sk+D <= 10240 (got %d)", d->Sk + d->D);
+  DXA_CHECK_ARG(lds <= GENERIC_LDS, "dxa_attn_fwd: generic kernel supports Sk+D <= 10240 (got %d)", d->Sk + d->D);
   const int64_t rows = (int64_t)d->B * d->Hq * d->Sq;
   dim3 grid((unsigned)((rows + 3) / 4));
   const size_t es = d->dtype == DXA_BF16 ? 2 : 4;
   const bool vec = d->D % 4 == 0 && d->k_ss % 4 == 0 && d->k_sb % 4 == 0 && d->k_sh % 4 == 0 && al(d->k, 4 * es);
-#define LAUNCH_GENERIC(T, V)                                                                                      \
-  do {                                                                                                            \
-    if (lds > 48 * 1024)                                                                                          \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_generic_k<T, V>),                         \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                            \
-    hipLaunchKernelGGL((attn_fwd_generic_k<T, V>), grid, dim3(256), lds, st, p);                                  \
-  } while (0)
-  if (d->dtype == DXA_BF16) { if (vec) LAUNCH_GENERIC(bf16_t, 4); else LAUNCH_GENERIC(bf16_t, 1); }
-  else { if (vec) LAUNCH_GENERIC(float, 4); else LAUNCH_GENERIC(float, 1); }
-#undef LAUNCH_GENERIC
+  int rc;
+  if (d->dtype == DXA_BF16)
+    rc = vec ? dxa_launch_lds<attn_fwd_generic_k<bf16_t, 4>>(GENERIC_LDS, grid, dim3(256), lds, st, p)
+             : dxa_launch_lds<attn_fwd_generic_k<bf16_t, 1>>(GENERIC_LDS, grid, dim3(256), lds, st, p);
+  else
+    rc = vec ? dxa_launch_lds<attn_fwd_generic_k<float, 4>>(GENERIC_LDS, grid, dim3(256), lds, st, p)
+             : dxa_launch_lds<attn_fwd_generic_k<float, 1>>(GENERIC_LDS, grid, dim3(256), lds, st, p);
+  if (rc) return rc;
   DXA_CHECK_LAUNCH();
   return DXA_OK;
 }
@@ -1679,6 +1673,12 @@ extern "C" size_t dxa_attn_bwd_workspace(const dxa_attn_desc* d) {
   const size_t n = (size_t)d->B * d->Hq * d->Sq * d->Sk;
   const size_t es = d->dtype == DXA_BF16 ? 2 : 4;
   return align_up(n * 4, 256) + 2 * align_up(n * es, 256) + align_up((size_t)d->B * d->Hq * d->Sq * 4, 256);
+}
+
+template <int D, int DV, int NW, bool PF>
+static int launch_dkv(dim3 grid, hipStream_t st, const AttnBwdP& bp) {
+  constexpr int lds = 2 * FlashTile<D>::RM_BYTES + 3 * 64 * (int)sizeof(float);
+  return dxa_launch_lds<attn_bwd_dkv_k<D, DV, NW, PF>>(lds, grid, dim3(64 * NW), lds, st, bp);
 }
 
 extern "C" int dxa_attn_bwd(const dxa_attn_desc* d, void* workspace, size_t workspace_bytes, dxa_stream_t stream) {
@@ -1704,17 +1704,6 @@ extern "C" int dxa_attn_bwd(const dxa_attn_desc* d, void* workspace, size_t work
     // the d range of dK / dV cut over wave pairs, + prefetch (256 registers, 7 spilled); 3 = 8 waves without the prefetch (248
     // registers): dQ + dK/dV at B 16 x 8 heads x 816 keys 735 / 753 / 714 / 685 us (profiles/r05_attn_variants.txt; same results
     // bit for bit) -> 3
-#define LAUNCH_DKV(D_, DV_, NW_, PF_)                                                                             \
-  do {                                                                                                            \
-    constexpr int lds_ = 2 * FlashTile<D_>::RM_BYTES + 3 * 64 * (int)sizeof(float);                               \
-    static bool attr_ = false;                                                                                    \
-    if (!attr_ && lds_ > 48 * 1024) {                                                                             \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv_k<D_, DV_, NW_, PF_>),                \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_);                                \
-      attr_ = true;                                                                                               \
-    }                                                                                                             \
-    hipLaunchKernelGGL((attn_bwd_dkv_k<D_, DV_, NW_, PF_>), gk, dim3(64 * NW_), lds_, st, bp);                    \
-  } while (0)
 #define LAUNCH_BWD(D_, DV_)                                                                                      \
   do {                                                                                                            \
     if (nwq == 8) hipLaunchKernelGGL((attn_bwd_dq_k<D_, 8, DV_>), gq, dim3(512), 0, st, bp);                      \
@@ -1722,18 +1711,21 @@ extern "C" int dxa_attn_bwd(const dxa_attn_desc* d, void* workspace, size_t work
   } while (0)
     if (d->D == 256) {
       LAUNCH_BWD(256, 256);
-      LAUNCH_DKV(256, 256, 8, false);
+      if (int rc = launch_dkv<256, 256, 8, false>(gk, st, bp)) return rc;
     } else if (d->D == 128) {
       // the 8-wave cut at head_dim 128 (182 registers without spills against 256 + 2 spilled): dQ + dK/dV of the decoder layer
       // 177.5 -> 172.5 and 175.2 -> 166.5 us in two sessions, the one-request shape 194.5 -> 186 (profiles/r05_attn_variants.txt,
       // r05_attn_nw_probe.txt; same results bit for bit)
       LAUNCH_BWD(128, 128);
-      LAUNCH_DKV(128, 128, 8, true);
+      if (int rc = launch_dkv<128, 128, 8, true>(gk, st, bp)) return rc;
+    } else if (d->D == 72) {
+      LAUNCH_BWD(128, 72);
+      if (int rc = launch_dkv<128, 72, 4, true>(gk, st, bp)) return rc;
+    } else {
+      LAUNCH_BWD(64, 64);
+      if (int rc = launch_dkv<64, 64, 4, true>(gk, st, bp)) return rc;
     }
-    else if (d->D == 72) { LAUNCH_BWD(128, 72); LAUNCH_DKV(128, 72, 4, true); }
-    else { LAUNCH_BWD(64, 64); LAUNCH_DKV(64, 64, 4, true); }
 #undef LAUNCH_BWD
-#undef LAUNCH_DKV
     DXA_CHECK_LAUNCH();
     return DXA_OK;
   }
@@ -1758,12 +1750,9 @@ extern "C" int dxa_attn_bwd(const dxa_attn_desc* d, void* workspace, size_t work
                        d->dq_ss % 4 == 0 && d->dk_ss % 4 == 0 && d->dv_ss % 4 == 0 && d->dq_sh % 4 == 0 && d->dk_sh % 4 == 0 &&
                        d->dv_sh % 4 == 0 && d->dq_sb % 4 == 0 && d->dk_sb % 4 == 0 && d->dv_sb % 4 == 0;
     if (d->Sq > SB_MAXT && v2_ok) {
-      static bool attr_set = false;
-      if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_small2_f32_k), hipFuncAttributeMaxDynamicSharedMemorySize, S2_LDS_BYTES);
-        attr_set = true;
-      }
-      hipLaunchKernelGGL(attn_bwd_small2_f32_k, dim3((unsigned)d->Hq, (unsigned)d->B), dim3(1024), S2_LDS_BYTES, (hipStream_t)stream, bp);
+      if (int rc = dxa_launch_lds<attn_bwd_small2_f32_k>(S2_LDS_BYTES, dim3((unsigned)d->Hq, (unsigned)d->B), dim3(1024), S2_LDS_BYTES,
+                                                         (hipStream_t)stream, bp))
+        return rc;
     } else if (d->Sq > SB_MAXT) hipLaunchKernelGGL(attn_bwd_small_f32_k<1024>, dim3((unsigned)d->Hq, (unsigned)d->B), dim3(1024), 0, (hipStream_t)stream, bp);
     else hipLaunchKernelGGL(attn_bwd_small_f32_k<256>, dim3((unsigned)d->Hq, (unsigned)d->B), dim3(256), 0, (hipStream_t)stream, bp);
     DXA_CHECK_LAUNCH();

@@ -5,6 +5,10 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <map>
+#include <mutex>
+#include <utility>
+
 #include "../../include/dexbotic_amd.h"
 
 typedef unsigned short bf16_t;  // raw bfloat16 bits
@@ -200,4 +204,55 @@ static inline int dxa_grid1d(int64_t n, int block, int cap = 256 * 16) {
   if (g < 1) g = 1;
   if (g > cap) g = cap;
   return (int)g;
+}
+
+// A zeroed device block of `bytes` per (device, stream), allocated on first use and kept for the process.  Every user owns its
+// StreamBlock, so no two users share a block.  The allocation cannot happen under stream capture: get() then returns DXA_OK with a
+// null block, and the caller decides what that means.
+class StreamBlock {
+ public:
+  explicit StreamBlock(size_t bytes) : bytes_(bytes) {}
+  template <typename T>
+  int get(hipStream_t st, T** out) {
+    int dev = 0;
+    DXA_CHECK_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(mu_);
+    auto it = tab_.find({dev, st});
+    if (it == tab_.end()) {
+      *out = nullptr;
+      hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+      if (st != nullptr && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) return DXA_OK;
+      void* p = nullptr;
+      DXA_CHECK_HIP(hipMalloc(&p, bytes_));
+      DXA_CHECK_HIP(hipMemset(p, 0, bytes_));
+      DXA_CHECK_HIP(hipDeviceSynchronize());
+      it = tab_.emplace(std::make_pair(dev, st), p).first;
+    }
+    *out = static_cast<T*>(it->second);
+    return DXA_OK;
+  }
+
+ private:
+  const size_t bytes_;
+  std::mutex mu_;
+  std::map<std::pair<int, hipStream_t>, void*> tab_;
+};
+
+// Kernels that take more dynamic LDS than the default ceiling: the first call for a kernel raises its ceiling to `max_lds`, the most
+// any launch of it asks for.
+template <auto kernel>
+int dxa_raise_lds(int max_lds) {
+  static const hipError_t e =
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+  if (e != hipSuccess) {
+    dxa_set_error("raising a kernel's dynamic LDS ceiling to %d bytes: %s", max_lds, hipGetErrorString(e));
+    return DXA_ERR_HIP;
+  }
+  return DXA_OK;
+}
+template <auto kernel, typename... Args>
+int dxa_launch_lds(int max_lds, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+  if (int rc = dxa_raise_lds<kernel>(max_lds)) return rc;
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+  return DXA_OK;
 }

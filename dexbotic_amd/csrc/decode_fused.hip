@@ -11,7 +11,7 @@
 // workgroups (one per CU) walks the five phases of every layer
 //     [RMSNorm] qkv GEMV + bias | RoPE + cache append + attention over the cache | o GEMV + residual |
 //     [RMSNorm] gate/up GEMV + SiLU * up | down GEMV + residual
-// with a device-wide barrier between them (the dit_fused.hip barrier: 16 spread arrival counters, bounded spin, abort word).
+// with a device-wide barrier between them (persistent.h: 16 spread arrival counters, bounded spin, abort word).
 // A workgroup owns N / grid output rows of a product (18 / 14 / 74 pairs / 14 at the 7B widths on 256 CUs: no tail).  Its 8
 // waves split K in 512-wide blocks (block b -> wave b % 8): a lane's 16-byte load is 8 consecutive k of one weight row, the
 // activation vector sits in LDS as bf16 (the rounding point of the unfused path: every activation between two ops is a bf16
@@ -22,16 +22,11 @@
 // GEMM epilogue): bf16 after the norm, after bias, after each RoPE product, after silu, after the gate product, after
 // the residual add.  Attention is fp32 from bf16 q / k / v (the flash kernel of the unfused path rounds the probabilities
 // to bf16 for its MFMA; this one does not), so the two paths agree to bf16 rounding, not bit for bit.
-#include <map>
-#include <mutex>
-
 #include "common.h"
+#include "persistent.h"
 
 namespace {
 
-constexpr int SC1 = 16;            // buffer-instruction cache policy: agent scope (gfx94x / gfx95x)
-constexpr unsigned NCTR = 16;      // arrival counters of the device-wide barrier
-constexpr unsigned SPIN_LIMIT = 1u << 21;
 constexpr int MAXR = 160;          // rows (a gate / up pair counts 2) a workgroup folds per pass
 constexpr int ACT_MAX = 32768;     // longest activation vector (elements) staged in LDS: 64 KiB of bf16
 constexpr int T_MAX = ACT_MAX / 2 - 1;   // cached keys per sequence (descriptor sizes and loop counters are 32-bit; nothing is staged per key)
@@ -95,34 +90,9 @@ __device__ unsigned long long g_dec_wg[5][256];     // work cycles of EVERY work
 #define DEC_PHASE_SYNC() do { } while (0)
 #define DEC_PHASE_END(ph_) do { } while (0)
 #endif
-// the barrier of dit_fused.hip (see there for the measurements behind the 16 counters)
 // (round 6 A/B, profiles/r06_decode_prefetch_ab.txt: requesting the next product's first weight block in front of the barrier made
 //  the token 6 % SLOWER — the 28 MB burst of 256 workgroups sits in front of the small activation loads every phase starts with;
 //  the stream is bandwidth-bound, a prefetch adds no bandwidth.  Removed.)
-__device__ __forceinline__ void grid_sync(unsigned* bar, unsigned nblk, unsigned& epoch) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  epoch += 1;
-  if (threadIdx.x < 64) {
-    unsigned* abortw = bar + 56;
-    if (threadIdx.x == 0)
-      (void)__hip_atomic_fetch_add(bar + 1024u * (blockIdx.x % NCTR + 1u), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned g = threadIdx.x % NCTR;
-    const unsigned target = epoch * ((nblk + NCTR - 1u - g) / NCTR);
-    const unsigned* mine = bar + 1024u * (g + 1u);
-    unsigned spins = 0;
-    while (true) {
-      const unsigned v = threadIdx.x < NCTR ? __hip_atomic_load(mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : target;
-      if (__builtin_amdgcn_ballot_w64(v < target) == 0ull) break;
-      __builtin_amdgcn_s_sleep(1);
-      if ((++spins & 15u) == 0u) {
-        if (spins >= SPIN_LIMIT && threadIdx.x == 0) __hip_atomic_store(abortw, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (__hip_atomic_load(abortw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) || spins >= SPIN_LIMIT) break;
-      }
-    }
-  }
-  __syncthreads();
-}
 
 __device__ __forceinline__ float block_reduce(float v, float* wred, bool is_max) {
   v = is_max ? wave_max(v) : wave_sum(v);
@@ -488,41 +458,10 @@ __global__ __launch_bounds__(512) void decode_step_k(const DecP p) {
     for (int c = threadIdx.x * 8; c < p.d; c += 512 * 8)
       *reinterpret_cast<u32x4_t*>(p.out + c) = *reinterpret_cast<const u32x4_t*>(&s.act[c]);
   }
-  // leave the barrier state zeroed for the next launch on this stream (see dit_fused.hip: atomics, not a memset node)
-  if (threadIdx.x == 0) {
-    unsigned* exit_cnt = p.bar + 48;
-    const unsigned outn = __hip_atomic_fetch_add(exit_cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
-    if (outn == nwg) {
-      for (unsigned g = 0; g < NCTR; ++g)
-        __hip_atomic_store(p.bar + 1024u * (g + 1u), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(exit_cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  grid_exit(p.bar, nwg);
 }
 
-constexpr size_t SYNC_BYTES = 4096 * (NCTR + 1);
-int get_sync_block(hipStream_t st, unsigned** out) {
-  static std::mutex mu;
-  static std::map<std::pair<int, hipStream_t>, unsigned*> tab;
-  int dev = 0;
-  DXA_CHECK_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = tab.find({dev, st});
-  if (it == tab.end()) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (st != nullptr && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
-      dxa_set_error("dxa_decode_step: first use on a stream allocates its sync block and cannot happen under stream capture");
-      return DXA_ERR_BAD_ARG;
-    }
-    unsigned* p = nullptr;
-    DXA_CHECK_HIP(hipMalloc((void**)&p, SYNC_BYTES));
-    DXA_CHECK_HIP(hipMemset(p, 0, SYNC_BYTES));
-    DXA_CHECK_HIP(hipDeviceSynchronize());
-    it = tab.emplace(std::make_pair(dev, st), p).first;
-  }
-  *out = it->second;
-  return DXA_OK;
-}
+StreamBlock sync_blocks(SYNC_BYTES);
 size_t ws_elems(int d, int Hq, int Hkv, int D, int F) {
   auto up = [](size_t v) { return (v + 127) / 128 * 128; };
   return up((size_t)d) + up((size_t)(Hq + 2 * Hkv) * D) + up((size_t)Hq * D) + up((size_t)F);
@@ -563,24 +502,16 @@ extern "C" int dxa_decode_step(const dxa_decode_desc* q, dxa_stream_t stream) {
   p.qkv = p.xres + up((size_t)q->d);
   p.ao = p.qkv + up((size_t)(q->Hq + 2 * q->Hkv) * q->D);
   p.act = p.ao + up((size_t)q->Hq * q->D);
-  if (int rc = get_sync_block(st, &p.bar)) return rc;
+  if (int rc = sync_block(sync_blocks, st, &p.bar, "dxa_decode_step")) return rc;
   p.L = q->n_layers; p.d = q->d; p.Hq = q->Hq; p.Hkv = q->Hkv; p.D = q->D; p.F = q->F;
   p.slot = q->slot; p.kv_lo = q->kv_lo; p.max_len = q->max_len;
   p.eps = q->eps; p.scale = 1.f / sqrtf((float)q->D);
   // every workgroup must be resident at once (device-wide barrier): one per CU, at least one per attention head
-  static int resident = 0;
-  if (resident == 0) {
-    int dev = 0, per_cu = 0;
-    hipDeviceProp_t prop;
-    DXA_CHECK_HIP(hipGetDevice(&dev));
-    DXA_CHECK_HIP(hipGetDeviceProperties(&prop, dev));
-    DXA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_step_k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)sizeof(DSmem)));
-    DXA_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_step_k, 512, sizeof(DSmem)));
-    DXA_CHECK_ARG(per_cu >= 1, "dxa_decode_step: the kernel does not fit on this device");
-    resident = prop.multiProcessorCount;          // one workgroup per CU: the weight stream wants every CU's load queue, not more waves
-  }
-  const int grid = resident;
+  if (int rc = dxa_raise_lds<decode_step_k>((int)sizeof(DSmem))) return rc;      // before the occupancy query
+  Residency r;
+  if (int rc = residency(reinterpret_cast<const void*>(&decode_step_k), sizeof(DSmem), &r)) return rc;
+  DXA_CHECK_ARG(r.per_cu >= 1, "dxa_decode_step: the kernel does not fit on this device");
+  const int grid = r.cus;          // one workgroup per CU: the weight stream wants every CU's load queue, not more waves
   DXA_CHECK_ARG(q->Hq <= grid, "dxa_decode_step: %d attention heads need at least as many workgroups (%d)", q->Hq, grid);
   hipLaunchKernelGGL(decode_step_k, dim3(grid), dim3(512), sizeof(DSmem), st, p);
   DXA_CHECK_LAUNCH();
@@ -608,17 +539,5 @@ extern "C" int dxa_decode_debug_stamps(unsigned long long* out) {
 // 1 if a decode launch on this stream gave up at a device-wide barrier since the last call (its output is garbage); the barrier
 // state is re-armed.  Synchronises the stream.
 extern "C" int dxa_decode_status(dxa_stream_t stream, int* timed_out) {
-  DXA_CHECK_ARG(timed_out != nullptr, "dxa_decode_status: null output");
-  hipStream_t st = (hipStream_t)stream;
-  unsigned* tail = nullptr;
-  if (int rc = get_sync_block(st, &tail)) return rc;
-  unsigned word = 0;
-  DXA_CHECK_HIP(hipMemcpyAsync(&word, tail + 56, sizeof(word), hipMemcpyDeviceToHost, st));
-  DXA_CHECK_HIP(hipStreamSynchronize(st));
-  *timed_out = word != 0;
-  if (word != 0) {
-    DXA_CHECK_HIP(hipMemsetAsync(tail, 0, SYNC_BYTES, st));
-    DXA_CHECK_HIP(hipStreamSynchronize(st));
-  }
-  return DXA_OK;
+  return sync_status(sync_blocks, stream, timed_out, "dxa_decode_status");
 }

@@ -7,18 +7,17 @@
 // and drain latency.  Here ONE launch runs every block: a grid of co-resident workgroups walks the phases
 //     [row statistics] qkv = LN(h) Wqkv^T + b | attention | h += o Wproj^T + b |
 //     [row statistics] a = gelu_tanh(LN(h) W1^T + b1) | h += a W2^T + b2
-// with a device-wide barrier between them (one agent-scope counter; release/acquire fences make the few hundred KB of
-// activations visible across the 8 XCD L2s).  The products are the skinny fp32 decomposition of gemm.hip: a
-// workgroup owns 16 output columns, its 8 waves split K in 64-deep blocks straight from L2/HBM into exact fp32
-// MFMA (v_mfma_f32_16x16x4_f32), partials folded through LDS.  LayerNorm is applied on the fly to the A operand.
+// with a device-wide barrier between them (persistent.h: the few hundred KB of activations are write-through agent-scope
+// accesses, visible across the 8 XCD L2s without fences or cache maintenance).  The products are the skinny fp32
+// decomposition of gemm.hip: a workgroup owns 16 output columns, its 8 waves split K in 64-deep blocks straight from
+// L2/HBM into exact fp32 MFMA (v_mfma_f32_16x16x4_f32), partials folded through LDS.  LayerNorm is applied on the fly to the A operand.
 // fp32 throughout, same arithmetic as the unfused kernels (held to them by tests/test_kernels_gpu.py).
 #include <stdlib.h>
 
-#include <map>
-#include <mutex>
-#include <utility>
+#include <algorithm>
 
 #include "common.h"
+#include "persistent.h"
 
 namespace {
 
@@ -65,10 +64,7 @@ __device__ unsigned long long g_dit_stamps[6][8];
 
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
-// Activations travel between workgroups on different XCDs, whose L2s are not coherent with each other: every
-// activation access is an agent-scope (sc1) buffer access — stores write through, loads miss in the private caches —
-// so the barrier needs no cache-wide write-back / invalidate and the weights stay cached.
-constexpr int SC1 = 16;
+// Every activation access is an agent-scope (sc1) buffer access (the protocol of persistent.h)
 struct Act {
   __amdgpu_buffer_rsrc_t r;
   __device__ __forceinline__ Act(float* p, size_t floats)
@@ -83,8 +79,8 @@ struct Act {
     const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, SC1);
     return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
   }
-  // cached load: data complete before the last device-wide barrier (whose acquire dropped stale lines); the 20+
-  // workgroups of an XCD then share one copy in its L2 instead of each pulling the matrix from the memory side
+  // data complete before the last device-wide barrier: a cached load would let the 20+ workgroups of an XCD share one copy in
+  // its L2, but needs an acquire at every barrier to drop stale lines
   __device__ __forceinline__ float4 ld4c(size_t idx) const {
     return ld4(idx);     // measured: the cached variant (+ acquire at every barrier) is 8 % slower end to end
   }
@@ -100,44 +96,10 @@ struct Act {
   }
 };
 
-// Device-wide barrier over workgroups that must all be resident.  The launch is a plain one sized by the occupancy query
-// (a cooperative launch adds 15-19 us per forward and enforces nothing more, MI355X_MICROARCH.md "coop-launch"), so
-// co-residency holds only while nothing else occupies CUs for long: the spin is BOUNDED (~2 s).  A workgroup that gives up
-// raises a sticky abort word; every later barrier of every workgroup then falls through, the launch drains in
-// microseconds with a garbage result, and dxa_dit_blocks_status() reports it to the host, which re-runs the request on
-// the unfused path (persistent kernel needs a watchdog).
-constexpr unsigned SPIN_LIMIT = 1u << 21;
-// Round 4: SIXTEEN arrival counters, one 4 KiB apart from the next (bar + 1024 (g + 1) words), workgroup b arrives at counter b % 16
-// with a no-return atomic and lanes 0-15 of wave 0 poll one counter each until every counter shows its whole group.  The single
-// counter + flag of rounds 1-3 cost 1.0 us + 10 ns per WORKGROUP (2.97 us at 192, 1.06 us at 8: `profiles/r04_barrier_vs_grid.txt`) —
-// device-scope atomics on one address are applied one after the other at the memory side, and the flag hop is a second dependent
-// round trip behind them; spread over 16 lines in 16 places the same arrivals take 1.27 us and nobody waits for a publisher
-// (`scripts/probes/sync_probe.hip` modes 4 / 16: `profiles/r04_barrier_split.txt`).
-constexpr unsigned NCTR = 16;
-__device__ __forceinline__ void grid_sync(unsigned* bar, unsigned nblk, unsigned& epoch, bool sleep, Smem* sst = nullptr) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wave's write-through stores have been acknowledged
-  __syncthreads();
-  if (sst) DIT_STAMP(*sst, 4);
-  epoch += 1;                                                // every thread keeps the count (wave 0's lanes need it)
-  if (threadIdx.x < 64) {
-    unsigned* abortw = bar + 56;
-    if (threadIdx.x == 0)
-      (void)__hip_atomic_fetch_add(bar + 1024u * (blockIdx.x % NCTR + 1u), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned g = threadIdx.x % NCTR;
-    const unsigned target = epoch * ((nblk + NCTR - 1u - g) / NCTR);      // workgroups b < nblk with b % NCTR == g, `epoch` times
-    const unsigned* mine = bar + 1024u * (g + 1u);
-    unsigned spins = 0;
-    while (true) {
-      const unsigned v = threadIdx.x < NCTR ? __hip_atomic_load(mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : target;
-      if (__builtin_amdgcn_ballot_w64(v < target) == 0ull) break;
-      if (sleep) __builtin_amdgcn_s_sleep(1);
-      if ((++spins & 15u) == 0u) {            // the abort word: every 16th poll (a launch that was aborted drains in milliseconds)
-        if (spins >= SPIN_LIMIT && threadIdx.x == 0) __hip_atomic_store(abortw, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (__hip_atomic_load(abortw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) || spins >= SPIN_LIMIT) break;
-      }
-    }
-  }
-  __syncthreads();
+// the device-wide barrier of the block phases, with the tuning build's stamp 4 (stores acknowledged, workgroup assembled)
+template <typename S>
+__device__ __forceinline__ void phase_sync(unsigned* bar, unsigned nblk, unsigned& epoch, S& s) {
+  grid_sync(bar, nblk, epoch, [&] { DIT_STAMP(s, 4); });
 }
 
 enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_RESADD = 2 };
@@ -397,48 +359,42 @@ __device__ __forceinline__ void walk_blocks(const DitP& p, Smem& s, unsigned& ep
     DIT_STAMP(s, 0);
     gemm_phase<true, EPI_BIAS>(p, s, h, p.H, w[0], w[1], qkv, 3 * p.H, 3 * p.H, p.H, 1, nullptr, 0, part);
     DIT_STAMP(s, 3);
-    grid_sync(p.bar, nblk, epoch, true, &s);
+    phase_sync(p.bar, nblk, epoch, s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 0, 5);
     DIT_STAMP(s, 0);
     attention_phase(p, s, qkv, o);
     DIT_STAMP(s, 1); DIT_STAMP(s, 2); DIT_STAMP(s, 3);
-    grid_sync(p.bar, nblk, epoch, true, &s);
+    phase_sync(p.bar, nblk, epoch, s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 1, 5);
     DIT_STAMP(s, 0);
     gemm_phase<false, EPI_RESADD>(p, s, o, p.H, w[2], w[3], h, p.H, p.H, p.H, p.s_proj, p.cnt_proj,
                                   (base + (unsigned)blk + 1u) * p.s_proj, part);
     DIT_STAMP(s, 3);
-    grid_sync(p.bar, nblk, epoch, true, &s);
+    phase_sync(p.bar, nblk, epoch, s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 2, 5);
     DIT_STAMP(s, 0);
     gemm_phase<true, EPI_GELU>(p, s, h, p.H, w[4], w[5], a, p.I, p.I, p.H, 1, nullptr, 0, part);
     DIT_STAMP(s, 3);
-    grid_sync(p.bar, nblk, epoch, true, &s);
+    phase_sync(p.bar, nblk, epoch, s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 3, 5);
     DIT_STAMP(s, 0);
     gemm_phase<false, EPI_RESADD>(p, s, a, p.I, w[6], w[7], h, p.H, p.H, p.I, p.s_fc2, p.cnt_fc2,
                                   (base + (unsigned)blk + 1u) * p.s_fc2, part);
     DIT_STAMP(s, 3);
-    grid_sync(p.bar, nblk, epoch, true, &s);
+    phase_sync(p.bar, nblk, epoch, s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 4, 5);
   }
 }
 
-// Leave the counters zeroed for the next launch on this stream (see the comment at the end of dit_blocks_fused_k)
-__device__ __forceinline__ void leave_clean(const DitP& p, unsigned nblk) {
-  if (threadIdx.x == 0) {
-    unsigned* exit_cnt = p.bar + 48;
-    const unsigned out = __hip_atomic_fetch_add(exit_cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
-    if (out == nblk) {
-      for (int i = 0; i < 64; ++i) {
-        __hip_atomic_store(p.cnt_proj + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(p.cnt_fc2 + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      for (unsigned g = 0; g < NCTR; ++g)
-        __hip_atomic_store(p.bar + 1024u * (g + 1u), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(exit_cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+// Leave the sync block zeroed for the next launch on this stream (persistent.h grid_exit), the split-K tile counters included
+template <typename P>
+__device__ __forceinline__ void leave_clean(const P& p, unsigned nblk) {
+  grid_exit(p.bar, nblk, [&] {
+    for (int i = 0; i < SYNC_NTILE; ++i) {
+      __hip_atomic_store(p.cnt_proj + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(p.cnt_fc2 + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-  }
+  });
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -521,7 +477,7 @@ __global__ __launch_bounds__(512) void dit_sample_fused_k(const DitSampleP sp) {
       }
       h.st1(idx, v + sp.pos[(size_t)t * H + c]);
     }
-    grid_sync(p.bar, nblk, epoch, true);
+    grid_sync(p.bar, nblk, epoch);
     walk_blocks(p, s, epoch, nblk, (unsigned)step * (unsigned)p.depth, h, qkv, o, a, part);
     // ---- final layer on the action tokens: one wave per row, rows spread over the workgroups
     for (int m = blockIdx.x * 8 + wave; m < p.M; m += gridDim.x * 8) {
@@ -546,7 +502,7 @@ __global__ __launch_bounds__(512) void dit_sample_fused_k(const DitSampleP sp) {
         if (lane == 0) epsg.st1((size_t)m * MAXA + k, d + sp.fb[k]);
       }
     }
-    grid_sync(p.bar, nblk, epoch, true);
+    grid_sync(p.bar, nblk, epoch);
   }
   if (blockIdx.x == 0) load_x(sp.steps);                                  // the last update, written to x
   leave_clean(p, nblk);
@@ -567,38 +523,15 @@ __global__ __launch_bounds__(512) void dit_blocks_fused_k(const DitP p) {
   __syncthreads();
   if (blockIdx.x == DXA_DIT_STAMPS && threadIdx.x < 48) g_dit_stamps[threadIdx.x / 8][threadIdx.x % 8] = s.stamp[threadIdx.x / 8][threadIdx.x % 8];
 #endif
-  // Leave the counters zeroed for the next launch on this stream (like the split-K flags of the ring GEMM): every
-  // workgroup has passed the last barrier when it gets here, so the LAST one out may clear them.  Agent-scope atomic
-  // stores, not a host-side memset: under HIP-graph replay a memset node's zeros were not reliably what the next
-  // kernel's atomics saw (the sampler hung), atomics are performed at the memory side and always are.
   leave_clean(p, nblk);
 }
 
-// Exit counter, abort word and the two per-tile counter arrays (H / 16 <= 64 entries each) in the first KiB, the 16 arrival counters
-// of the device-wide barrier 4 KiB apart behind it: one 68 KiB block per (device, stream), zeroed when it is created and left
-// zeroed by every launch.
-constexpr size_t SYNC_BYTES = 4096 * (NCTR + 1);      // the first KiB: exit counter, abort word, tile counters; then the arrival counters
-int get_sync_block(hipStream_t st, unsigned** out) {
-  static std::mutex mu;
-  static std::map<std::pair<int, hipStream_t>, unsigned*> tab;
-  int dev = 0;
-  DXA_CHECK_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = tab.find({dev, st});
-  if (it == tab.end()) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (st != nullptr && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
-      dxa_set_error("dxa_dit_blocks_fwd: first use on a stream allocates its sync block and cannot happen under stream "
-                    "capture: run the request once eagerly on this stream first");
-      return DXA_ERR_BAD_ARG;
-    }
-    unsigned* p = nullptr;
-    DXA_CHECK_HIP(hipMalloc((void**)&p, SYNC_BYTES));
-    DXA_CHECK_HIP(hipMemset(p, 0, SYNC_BYTES));
-    DXA_CHECK_HIP(hipDeviceSynchronize());
-    it = tab.emplace(std::make_pair(dev, st), p).first;
-  }
-  *out = it->second;
+StreamBlock sync_blocks(SYNC_BYTES);      // shared by the three kernels of this file
+template <typename P>
+int get_sync_block(hipStream_t st, P& p, const char* who) {
+  unsigned* blk = nullptr;
+  if (int rc = sync_block(sync_blocks, st, &blk, who)) return rc;
+  p.bar = blk; p.cnt_proj = blk + SYNC_TILES_PROJ; p.cnt_fc2 = blk + SYNC_TILES_FC2;
   return DXA_OK;
 }
 size_t act_bytes_for(int M, int H, int I) {
@@ -615,19 +548,7 @@ int pick_slices(int ncb, int nkb, int grid) {
 // 1 if a launch on this stream gave up at a device-wide barrier since the last call (its result is garbage); the sync block
 // is re-armed.  Synchronises the stream: call it where the host waits for the result anyway.
 extern "C" int dxa_dit_blocks_status(dxa_stream_t stream, int* timed_out) {
-  DXA_CHECK_ARG(timed_out != nullptr, "dxa_dit_blocks_status: null output");
-  hipStream_t st = (hipStream_t)stream;
-  unsigned* tail = nullptr;
-  if (int rc = get_sync_block(st, &tail)) return rc;
-  unsigned word = 0;
-  DXA_CHECK_HIP(hipMemcpyAsync(&word, tail + 56, sizeof(word), hipMemcpyDeviceToHost, st));
-  DXA_CHECK_HIP(hipStreamSynchronize(st));
-  *timed_out = word != 0;
-  if (word != 0) {
-    DXA_CHECK_HIP(hipMemsetAsync(tail, 0, SYNC_BYTES, st));
-    DXA_CHECK_HIP(hipStreamSynchronize(st));
-  }
-  return DXA_OK;
+  return sync_status(sync_blocks, stream, timed_out, "dxa_dit_blocks_status");
 }
 
 #if defined(DXA_DIT_STAMPS)
@@ -663,11 +584,7 @@ int setup_blocks(DitP& p, int* grid_out, float* h, const float* const* weights, 
   p.o = p.qkv + (size_t)M * 3 * H;
   p.a = p.o + (size_t)M * H;
   p.part = p.a + (size_t)M * I;
-  unsigned* tail = nullptr;          // first use on a stream allocates: must not happen under stream capture
-  if (int rc = get_sync_block(st, &tail)) return rc;
-  p.bar = tail;
-  p.cnt_proj = tail + 64;
-  p.cnt_fc2 = tail + 128;
+  if (int rc = get_sync_block(st, p, who)) return rc;
   p.w = weights;
   p.M = M; p.N = N; p.T1 = T1; p.H = H; p.heads = heads; p.I = I; p.depth = depth;
   p.eps = eps;
@@ -677,18 +594,11 @@ int setup_blocks(DitP& p, int* grid_out, float* h, const float* const* weights, 
   int grid = I / 16;
   if (3 * H / 16 > grid) grid = 3 * H / 16;
   // ... and never more than fit on the device at once (registers allow one 512-thread workgroup per CU)
-  static int resident = 0;
-  if (resident == 0) {
-    int dev = 0, per_cu = 0, per_cu2 = 0;
-    hipDeviceProp_t prop;
-    DXA_CHECK_HIP(hipGetDevice(&dev));
-    DXA_CHECK_HIP(hipGetDeviceProperties(&prop, dev));
-    DXA_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dit_blocks_fused_k, 512, 0));
-    DXA_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu2, dit_sample_fused_k, 512, 0));
-    if (per_cu2 < per_cu) per_cu = per_cu2;
-    resident = per_cu * prop.multiProcessorCount;
-    DXA_CHECK_ARG(resident >= 1, "%s: the kernel does not fit on this device", who);
-  }
+  Residency r1, r2;
+  if (int rc = residency(reinterpret_cast<const void*>(&dit_blocks_fused_k), 0, &r1)) return rc;
+  if (int rc = residency(reinterpret_cast<const void*>(&dit_sample_fused_k), 0, &r2)) return rc;
+  const int resident = std::min(r1.per_cu, r2.per_cu) * r1.cus;
+  DXA_CHECK_ARG(resident >= 1, "%s: the kernel does not fit on this device", who);
   if (grid > resident) grid = resident;
   p.s_proj = pick_slices(H / 16, H / 64, grid);
   p.s_fc2 = pick_slices(H / 16, I / 64, grid);
@@ -1199,17 +1109,17 @@ __device__ __forceinline__ void walk_blocks_bf(const DitBfP& p, Smem& s, const B
     DIT_STAMP(s, 0);
     gemm_bf<BF_QKV>(p, s, b, b.hb, p.H, w[0], w[1], w[8], 3 * p.H, 1, nullptr, 0);
     DIT_STAMP(s, 3);
-    grid_sync(p.bar, nblk, epoch, true, &s);
+    phase_sync(p.bar, nblk, epoch, s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 0, 5);
     DIT_STAMP(s, 0);
     attention_bf(p, s, b);
     DIT_STAMP(s, 1); DIT_STAMP(s, 2); DIT_STAMP(s, 3);
-    grid_sync(p.bar, nblk, epoch, true, &s);
+    phase_sync(p.bar, nblk, epoch, s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 1, 5);
     DIT_STAMP(s, 0);
     gemm_bf<BF_RES>(p, s, b, b.ob, p.H, w[2], w[3], nullptr, p.H, p.s_proj, p.cnt_proj, tgt_proj);
     DIT_STAMP(s, 3);
-    grid_sync(p.bar, nblk, epoch, true, &s);
+    phase_sync(p.bar, nblk, epoch, s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 2, 5);
     if (per) {
       // x + MHA(norm3 x, per, per): q = (norm3 folded into the packed q rows of in_proj) | attention over the cached keys / values | out_proj
@@ -1221,24 +1131,24 @@ __device__ __forceinline__ void walk_blocks_bf(const DitBfP& p, Smem& s, const B
       bool pre = false;
       int n_, hd_, r0_, nr_;
       if (per_decode(p, per_first_item(p), n_, hd_, r0_, nr_)) { per_load(p, kvb, n_, hd_, ops); pre = true; }
-      grid_sync(p.bar, nblk, epoch, true, &s);
+      phase_sync(p.bar, nblk, epoch, s);
       DIT_STAMP(s, 0);
       per_attention_bf(p, s, b, kvb, ops, pre);
       DIT_STAMP(s, 5);
-      grid_sync(p.bar, nblk, epoch, true, &s);
+      phase_sync(p.bar, nblk, epoch, s);
       DIT_STAMP(s, 6); DIT_STAMP_FOLD(s, 5, 6);
       gemm_bf<BF_RES>(p, s, b, b.ob, p.H, w[13], w[14], nullptr, p.H, p.s_proj, p.cnt_proj, tgt_proj + (unsigned)p.s_proj);
-      grid_sync(p.bar, nblk, epoch, true, &s);
+      phase_sync(p.bar, nblk, epoch, s);
     }
     DIT_STAMP(s, 0);
     gemm_bf<BF_FC1>(p, s, b, b.hb, p.H, w[4], w[5], w[9], p.I, 1, nullptr, 0);
     DIT_STAMP(s, 3);
-    grid_sync(p.bar, nblk, epoch, true, &s);
+    phase_sync(p.bar, nblk, epoch, s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 3, 5);
     DIT_STAMP(s, 0);
     gemm_bf<BF_RES>(p, s, b, b.ab, p.I, w[6], w[7], nullptr, p.H, p.s_fc2, p.cnt_fc2, (base + (unsigned)blk + 1u) * p.s_fc2);
     DIT_STAMP(s, 3);
-    grid_sync(p.bar, nblk, epoch, true, &s);
+    phase_sync(p.bar, nblk, epoch, s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 4, 5);
   }
 }
@@ -1315,7 +1225,7 @@ __global__ __launch_bounds__(512) void dit_sample_bf16_k(const DitSampleBfP sp) 
       }
       write_h(p, b, m, c, make_float4(v[0], v[1], v[2], v[3]), valid, q == 0, 1, 2);
     }
-    grid_sync(p.bar, nblk, epoch, true);
+    grid_sync(p.bar, nblk, epoch);
     walk_blocks_bf(p, s, b, epoch, nblk, (unsigned)step * (unsigned)p.depth);
     // ---- final layer on the action tokens (fp32, from the fp32 residual stream): one wave per row
     for (int m = blockIdx.x * 8 + wave; m < p.M; m += gridDim.x * 8) {
@@ -1340,26 +1250,14 @@ __global__ __launch_bounds__(512) void dit_sample_bf16_k(const DitSampleBfP sp) 
         if (lane == 0) epsg.st1((size_t)m * MAXA + k, d + sp.fb[k]);
       }
     }
-    grid_sync(p.bar, nblk, epoch, true);
+    grid_sync(p.bar, nblk, epoch);
   }
   if (blockIdx.x == 0) load_x(sp.steps);
 #if defined(DXA_DIT_STAMPS)
   __syncthreads();
   if (blockIdx.x == DXA_DIT_STAMPS && threadIdx.x < 48) g_dit_stamps[threadIdx.x / 8][threadIdx.x % 8] = s.stamp[threadIdx.x / 8][threadIdx.x % 8];
 #endif
-  if (threadIdx.x == 0) {                 // leave_clean
-    unsigned* exit_cnt = p.bar + 48;
-    const unsigned out = __hip_atomic_fetch_add(exit_cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
-    if (out == nblk) {
-      for (int i = 0; i < 64; ++i) {
-        __hip_atomic_store(p.cnt_proj + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(p.cnt_fc2 + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      for (unsigned g = 0; g < NCTR; ++g)
-        __hip_atomic_store(p.bar + 1024u * (g + 1u), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(exit_cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  leave_clean(p, nblk);
 }
 
 // ---- weight packing: one workgroup per (block, matrix, 16 output columns); thread (r = tid / 16, t = tid % 16) walks row nb * 16 + r
@@ -1516,25 +1414,17 @@ int sample_bf16_launch(const char* who, float* x, const float* z_emb, const floa
   p.part = reinterpret_cast<float*>(ws + off[3]); p.hb = reinterpret_cast<bf16_t*>(ws + off[4]); p.ob = reinterpret_cast<bf16_t*>(ws + off[5]);
   p.ab = reinterpret_cast<bf16_t*>(ws + off[6]);
   float* extra = reinterpret_cast<float*>(ws + off[7]);
-  unsigned* tail = nullptr;
-  if (int rc = get_sync_block(st, &tail)) return rc;
-  p.bar = tail; p.cnt_proj = tail + 64; p.cnt_fc2 = tail + 128;
+  if (int rc = get_sync_block(st, p, who)) return rc;
   p.w = packed_table;
   p.kv = per_kv; p.P = P; p.wstride = P > 0 ? 16 : 10;
   p.M = M; p.Mp = (M + 1) & ~1; p.N = N; p.T1 = T1; p.H = H; p.heads = heads; p.I = I; p.depth = depth;
   p.eps = eps; p.scale = 1.f / sqrtf((float)HD);
   int grid = I / 16;
   if (3 * H / 16 > grid) grid = 3 * H / 16;
-  static int resident = 0;
-  if (resident == 0) {
-    int dev = 0, per_cu = 0;
-    hipDeviceProp_t prop;
-    DXA_CHECK_HIP(hipGetDevice(&dev));
-    DXA_CHECK_HIP(hipGetDeviceProperties(&prop, dev));
-    DXA_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dit_sample_bf16_k, 512, 0));
-    resident = per_cu * prop.multiProcessorCount;
-    DXA_CHECK_ARG(resident >= 1, "%s: the kernel does not fit on this device", who);
-  }
+  Residency r;
+  if (int rc = residency(reinterpret_cast<const void*>(&dit_sample_bf16_k), 0, &r)) return rc;
+  const int resident = r.per_cu * r.cus;
+  DXA_CHECK_ARG(resident >= 1, "%s: the kernel does not fit on this device", who);
   if (grid > resident) grid = resident;
   p.s_fc2 = pick_slices(H / 16, I / 64, grid);
   // the output projection is NOT K-sliced here: with bf16 operands a workgroup's whole K = 768 slab is 25 KB of weights + 52 KB of

@@ -20,9 +20,6 @@
 #include "gemm_common.h"
 
 #include <algorithm>
-#include <map>
-#include <mutex>
-#include <utility>
 
 namespace {
 
@@ -1604,45 +1601,25 @@ int launch(const GemmP& p, int layout, dim3 grid, hipStream_t st) {
 // first use (so the first dxa_gemm on a stream must not run under stream capture) and kept for the process.
 constexpr int NUM_CU = 256;
 static_assert(NUM_CU == NUM_CU_D, "split-K scratch sizing");
+constexpr size_t SPLIT_WS_BYTES = (size_t)NUM_CU * 256 * 256 * 4;
 struct SplitWs { float* ws; int* flags; };
 int get_split_ws(hipStream_t st, SplitWs* out) {
-  static std::mutex mu;
-  static std::map<std::pair<int, hipStream_t>, SplitWs> tab;
-  int dev = 0;
-  DXA_CHECK_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = tab.find({dev, st});
-  if (it == tab.end()) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (st != nullptr && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
-      dxa_set_error("dxa_gemm: first split-K product on a stream allocates its scratch and cannot happen under stream "
-                    "capture: run the request once eagerly on this stream first");
-      return DXA_ERR_BAD_ARG;
-    }
-    char* base = nullptr;
-    const size_t ws_bytes = (size_t)NUM_CU * 256 * 256 * 4;
-    DXA_CHECK_HIP(hipMalloc((void**)&base, ws_bytes + NUM_CU * sizeof(int)));
-    DXA_CHECK_HIP(hipMemset(base + ws_bytes, 0, NUM_CU * sizeof(int)));
-    DXA_CHECK_HIP(hipDeviceSynchronize());
-    it = tab.emplace(std::make_pair(dev, st), SplitWs{(float*)base, (int*)(base + ws_bytes)}).first;
-  }
-  *out = it->second;
+  static StreamBlock blocks(SPLIT_WS_BYTES + NUM_CU * sizeof(int));
+  char* base = nullptr;
+  if (int rc = blocks.get(st, &base)) return rc;
+  DXA_CHECK_ARG(base != nullptr, "dxa_gemm: first split-K product on a stream allocates its scratch and cannot happen under stream "
+                "capture: run the request once eagerly on this stream first");
+  *out = SplitWs{(float*)base, (int*)(base + SPLIT_WS_BYTES)};
   return DXA_OK;
 }
 
-// persistent kernels launch one workgroup per compute unit
-inline int num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-      n = prop.multiProcessorCount;
-    else
-      n = NUM_CU;
-  }
-  return n;
+// the ring / ping-pong kernels: 512 threads, max(4 x 32 KiB ring, 8 waves x 64 x 272 B epilogue slabs) of LDS
+constexpr int RING_LDS = 139264;
+template <auto kernel>
+int launch_ring(dim3 grid, hipStream_t st, const GemmP& p) {
+  return dxa_launch_lds<kernel>(RING_LDS, grid, dim3(512), RING_LDS, st, p);
 }
+
 inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 inline bool strides_mult(const int64_t s[3], int64_t m) { return s[0] % m == 0 && s[1] % m == 0 && s[2] % m == 0; }
 
@@ -1813,18 +1790,11 @@ int gemm_dispatch(const dxa_gemm_desc* d, dxa_stream_t stream, bool* mirrored, b
     }
     dim3 tgrid((unsigned)(p.tm * p.tn * p.split_s));
     // four stages (a CU gets one workgroup: the tile count is <= NUM_CU), four dedicated loader waves
-#define LAUNCH_T128(TO_)                                                                                             \
-  do {                                                                                                               \
-    static bool attr_set = false;                                                                                    \
-    if (!attr_set) {                                                                                                 \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_t128_kernel<TO_, 4, 4>),                      \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 32768);                              \
-      attr_set = true;                                                                                               \
-    }                                                                                                                \
-    hipLaunchKernelGGL((gemm_nt_t128_kernel<TO_, 4, 4>), tgrid, dim3(512), 4 * 32768, st, p);                        \
-  } while (0)
-    if (d->out_dtype == DXA_BF16) LAUNCH_T128(bf16_t); else LAUNCH_T128(float);
-#undef LAUNCH_T128
+    constexpr int T128_LDS = 4 * 32768;
+    const int rc = d->out_dtype == DXA_BF16
+                       ? dxa_launch_lds<gemm_nt_t128_kernel<bf16_t, 4, 4>>(T128_LDS, tgrid, dim3(512), T128_LDS, st, p)
+                       : dxa_launch_lds<gemm_nt_t128_kernel<float, 4, 4>>(T128_LDS, tgrid, dim3(512), T128_LDS, st, p);
+    if (rc) return rc;
     DXA_CHECK_LAUNCH();
     return DXA_OK;
   }
@@ -1874,89 +1844,49 @@ int gemm_dispatch(const dxa_gemm_desc* d, dxa_stream_t stream, bool* mirrored, b
       }
     }
     dim3 fgrid((unsigned)(p.full + p.tail_r * p.split_s));
-    constexpr int RING_LDS = 139264;   // max(4 x 32 KiB ring, 8 waves x 64 x 272 B epilogue slabs)
-#define LAUNCH_RING(TO_, AI_, TE_)                                                                              \
-  do {                                                                                                          \
-    static bool attr_set = false;                                                                               \
-    if (!attr_set) {                                                                                            \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_ring_kernel<TO_, AI_, TE_>),             \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, RING_LDS);                          \
-      attr_set = true;                                                                                          \
-    }                                                                                                           \
-    hipLaunchKernelGGL((gemm_nt_ring_kernel<TO_, AI_, TE_>), fgrid, dim3(512), RING_LDS, st, p);                \
-  } while (0)
     // ---- ping-pong main loop: 256-row tiles, K % 64 == 0; the lean epilogue when it is made of whole 16-byte accesses
     const bool pp = ks_layout || (ai == 4 && d->K % 64 == 0);
     const bool lean = pp && lean_ok;
-#define LAUNCH_PP(TO_, TE_, LEAN_, AKS_, BKS_)                                                                  \
-  do {                                                                                                          \
-    static bool attr_set = false;                                                                               \
-    if (!attr_set) {                                                                                            \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pp_kernel<TO_, TE_, LEAN_, AKS_, BKS_>),    \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, RING_LDS);                          \
-      attr_set = true;                                                                                          \
-    }                                                                                                           \
-    hipLaunchKernelGGL((gemm_pp_kernel<TO_, TE_, LEAN_, AKS_, BKS_>), fgrid, dim3(512), RING_LDS, st, p);       \
-  } while (0)
+    const bool bf = d->out_dtype == DXA_BF16;
     if (lean) { p.mirror = (char*)d->mirror; *mirrored = d->mirror != nullptr; }
     if (lean) { p.sumsq = d->sumsq; *summed = d->sumsq != nullptr; }
+    int rc;
     if (d->layout == DXA_NN) {          // dX = dY W: bf16 out (lean, or with the activation-gradient epilogue), fp32 out lean
-      if (d->out_dtype == DXA_BF16) { if (lean) LAUNCH_PP(bf16_t, bf16_t, true, false, true); else LAUNCH_PP(bf16_t, bf16_t, false, false, true); }
-      else LAUNCH_PP(float, bf16_t, true, false, true);
+      if (bf) rc = lean ? launch_ring<gemm_pp_kernel<bf16_t, bf16_t, true, false, true>>(fgrid, st, p)
+                        : launch_ring<gemm_pp_kernel<bf16_t, bf16_t, false, false, true>>(fgrid, st, p);
+      else rc = launch_ring<gemm_pp_kernel<float, bf16_t, true, false, true>>(fgrid, st, p);
     } else if (d->layout == DXA_TN) {   // dW = dY^T X: fp32 (accumulating) or bf16 out, plain epilogue
-      if (d->out_dtype == DXA_BF16) LAUNCH_PP(bf16_t, bf16_t, true, true, true); else LAUNCH_PP(float, bf16_t, true, true, true);
+      rc = bf ? launch_ring<gemm_pp_kernel<bf16_t, bf16_t, true, true, true>>(fgrid, st, p)
+              : launch_ring<gemm_pp_kernel<float, bf16_t, true, true, true>>(fgrid, st, p);
     } else if (d->fuse == DXA_FUSE_SWIGLU && ai == 4) {
-#define LAUNCH_PPF(FUSE_)                                                                                       \
-  do {                                                                                                          \
-    static bool attr_set = false;                                                                               \
-    if (!attr_set) {                                                                                            \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pp_kernel<bf16_t, bf16_t, true, false, false, FUSE_>), \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, RING_LDS);                          \
-      attr_set = true;                                                                                          \
-    }                                                                                                           \
-    hipLaunchKernelGGL((gemm_pp_kernel<bf16_t, bf16_t, true, false, false, FUSE_>), fgrid, dim3(512), RING_LDS, st, p); \
-  } while (0)
-      LAUNCH_PPF(1);
-#undef LAUNCH_PPF
+      rc = launch_ring<gemm_pp_kernel<bf16_t, bf16_t, true, false, false, 1>>(fgrid, st, p);
     } else if (d->fuse == DXA_FUSE_SWIGLU) {                   // 192-row tiles
-      static bool attr_f = false;
-      if (!attr_f) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pp3_kernel<bf16_t, bf16_t, true, 1>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, RING_LDS);
-        attr_f = true;
-      }
-      hipLaunchKernelGGL((gemm_pp3_kernel<bf16_t, bf16_t, true, 1>), fgrid, dim3(512), RING_LDS, st, p);
+      rc = launch_ring<gemm_pp3_kernel<bf16_t, bf16_t, true, 1>>(fgrid, st, p);
     } else if (pp && lean) {
-      if (d->epi_f32) LAUNCH_PP(float, float, true, false, false);
-      else if (d->out_dtype == DXA_BF16) LAUNCH_PP(bf16_t, bf16_t, true, false, false);
-      else LAUNCH_PP(float, bf16_t, true, false, false);
+      if (d->epi_f32) rc = launch_ring<gemm_pp_kernel<float, float, true, false, false>>(fgrid, st, p);
+      else if (bf) rc = launch_ring<gemm_pp_kernel<bf16_t, bf16_t, true, false, false>>(fgrid, st, p);
+      else rc = launch_ring<gemm_pp_kernel<float, bf16_t, true, false, false>>(fgrid, st, p);
     } else if (pp) {
-      if (d->epi_f32) LAUNCH_PP(float, float, false, false, false);
-      else if (d->out_dtype == DXA_BF16) LAUNCH_PP(bf16_t, bf16_t, false, false, false);
-      else LAUNCH_PP(float, bf16_t, false, false, false);
+      if (d->epi_f32) rc = launch_ring<gemm_pp_kernel<float, float, false, false, false>>(fgrid, st, p);
+      else if (bf) rc = launch_ring<gemm_pp_kernel<bf16_t, bf16_t, false, false, false>>(fgrid, st, p);
+      else rc = launch_ring<gemm_pp_kernel<float, bf16_t, false, false, false>>(fgrid, st, p);
     }
-#undef LAUNCH_PP
     // ---- 192-row tiles on the ping-pong schedule (round 4): K % 64 == 0
     else if (ai == 3 && d->K % 64 == 0 && d->layout == DXA_NT) {
-#define LAUNCH_PP3(TO_, TE_, LEAN_)                                                                             \
-  do {                                                                                                          \
-    static bool attr_set = false;                                                                               \
-    if (!attr_set) {                                                                                            \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pp3_kernel<TO_, TE_, LEAN_>),               \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, RING_LDS);                          \
-      attr_set = true;                                                                                          \
-    }                                                                                                           \
-    hipLaunchKernelGGL((gemm_pp3_kernel<TO_, TE_, LEAN_>), fgrid, dim3(512), RING_LDS, st, p);                  \
-  } while (0)
-      if (d->epi_f32) { if (lean_ok) LAUNCH_PP3(float, float, true); else LAUNCH_PP3(float, float, false); }
-      else if (lean_ok) { if (d->out_dtype == DXA_BF16) LAUNCH_PP3(bf16_t, bf16_t, true); else LAUNCH_PP3(float, bf16_t, true); }
-      else { if (d->out_dtype == DXA_BF16) LAUNCH_PP3(bf16_t, bf16_t, false); else LAUNCH_PP3(float, bf16_t, false); }
-#undef LAUNCH_PP3
+      if (d->epi_f32) rc = lean_ok ? launch_ring<gemm_pp3_kernel<float, float, true>>(fgrid, st, p)
+                                   : launch_ring<gemm_pp3_kernel<float, float, false>>(fgrid, st, p);
+      else if (lean_ok) rc = bf ? launch_ring<gemm_pp3_kernel<bf16_t, bf16_t, true>>(fgrid, st, p)
+                                : launch_ring<gemm_pp3_kernel<float, bf16_t, true>>(fgrid, st, p);
+      else rc = bf ? launch_ring<gemm_pp3_kernel<bf16_t, bf16_t, false>>(fgrid, st, p)
+                   : launch_ring<gemm_pp3_kernel<float, bf16_t, false>>(fgrid, st, p);
     }
-    else if (d->epi_f32) { if (ai == 3) LAUNCH_RING(float, 3, float); else LAUNCH_RING(float, 4, float); }
-    else if (ai == 3) { if (d->out_dtype == DXA_BF16) LAUNCH_RING(bf16_t, 3, bf16_t); else LAUNCH_RING(float, 3, bf16_t); }
-    else { if (d->out_dtype == DXA_BF16) LAUNCH_RING(bf16_t, 4, bf16_t); else LAUNCH_RING(float, 4, bf16_t); }
-#undef LAUNCH_RING
+    else if (d->epi_f32) rc = ai == 3 ? launch_ring<gemm_nt_ring_kernel<float, 3, float>>(fgrid, st, p)
+                                      : launch_ring<gemm_nt_ring_kernel<float, 4, float>>(fgrid, st, p);
+    else if (ai == 3) rc = bf ? launch_ring<gemm_nt_ring_kernel<bf16_t, 3, bf16_t>>(fgrid, st, p)
+                              : launch_ring<gemm_nt_ring_kernel<float, 3, bf16_t>>(fgrid, st, p);
+    else rc = bf ? launch_ring<gemm_nt_ring_kernel<bf16_t, 4, bf16_t>>(fgrid, st, p)
+                 : launch_ring<gemm_nt_ring_kernel<float, 4, bf16_t>>(fgrid, st, p);
+    if (rc) return rc;
     DXA_CHECK_LAUNCH();
     return DXA_OK;
   }

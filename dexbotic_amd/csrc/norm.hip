@@ -5,10 +5,6 @@
 // (L2 resident), reduced afterwards by dxa_colsum: deterministic, no atomics.
 #include <stdlib.h>
 
-#include <map>
-#include <mutex>
-#include <utility>
-
 #include "common.h"
 
 namespace {
@@ -928,30 +924,9 @@ extern "C" int dxa_layernorm_bwd(const void* dy, const void* x, const void* w, c
 
 namespace {
 // arrival counters of colsum_fused_k: COLSUM_CNT ints per (device, stream), zeroed once (the kernel leaves them zeroed),
-// allocated on first use — so the first column sum on a stream must not run under stream capture
+// allocated on first use; under capture before they exist the counters are null and the two-launch form, which needs none, runs
 constexpr int COLSUM_CNT = 4096;
-int colsum_counters(hipStream_t st, int** out) {
-  static std::mutex mu;
-  static std::map<std::pair<int, hipStream_t>, int*> tab;
-  int dev = 0;
-  DXA_CHECK_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = tab.find({dev, st});
-  if (it == tab.end()) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (st != nullptr && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
-      *out = nullptr;                      // under capture before the counters exist: the two-launch form needs none
-      return DXA_OK;
-    }
-    int* p = nullptr;
-    DXA_CHECK_HIP(hipMalloc((void**)&p, COLSUM_CNT * sizeof(int)));
-    DXA_CHECK_HIP(hipMemset(p, 0, COLSUM_CNT * sizeof(int)));
-    DXA_CHECK_HIP(hipDeviceSynchronize());
-    it = tab.emplace(std::make_pair(dev, st), p).first;
-  }
-  *out = it->second;
-  return DXA_OK;
-}
+StreamBlock colsum_counters(COLSUM_CNT * sizeof(int));
 }  // namespace
 
 extern "C" int dxa_colsum(const void* x, int64_t ld, float* out, int64_t rows, int64_t cols, int dtype,
@@ -980,7 +955,7 @@ extern "C" int dxa_colsum(const void* x, int64_t ld, float* out, int64_t rows, i
   }
   int* cnt = nullptr;
   if (grid.x <= COLSUM_CNT) {
-    if (int rc = colsum_counters(st, &cnt)) return rc;
+    if (int rc = colsum_counters.get(st, &cnt)) return rc;
   }
   if (cnt != nullptr) {
     if (dtype == DXA_BF16)
