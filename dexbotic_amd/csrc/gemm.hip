@@ -960,16 +960,19 @@ template __global__ void gemm_nt_ring_kernel<float, 3, float>(const GemmP);
 // w+4 share a SIMD) run ONE barrier interval apart and alternate roles:
 //     group 0:       | M0 | C0 | M1 | C1 | ...          M = memory cluster: ds_read_b128 fragment loads of the
 //     group 1:  | -- | M0 | C0 | M1 | C1 | ...              quadrant computed next + 2 LDS-DMA instructions + counted vmcnt
-//                                                        C = compute cluster: 8 x v_mfma_f32_32x32x16_bf16 (256 clk)
+//                                                        C = compute cluster: 16 x v_mfma_f32_16x16x32_bf16 (256 clk)
 // so in every interval each SIMD has one wave feeding the matrix pipe and one wave on the LDS / L2 side
 // (measured: the stagger alone is worth 13 %; s_setprio around the clusters nothing).  A K tile is 4 phases = the 4
 // quadrants (64 rows x 32 cols) of the wave's 128 x 64 output:
 //     phase 0: reads A0,B0 -> Q(A0,B0) | 1: reads B1 -> Q(A0,B1) | 2: reads A1 -> Q(A1,B1) | 3: reads B0 -> Q(A1,B0)
 // (A0/A1 = 64-row halves of the wave's rows, B0/B1 = 32-column halves of its columns): 24 ds_read_b128 per wave per
-// K tile for 32 MFMAs.  The next K tile arrives as 4 DMA "pieces" of 16 KiB, one per phase (each piece = that half for
+// K tile for 64 MFMAs.  The fragments are 16x16x32 since round 7 (was 32x32x16; scripts/gemm_bench.py on random data,
+// profiles/r07_mfma16_gemm_ab.txt: gate_up / down forward, the NN and TN shapes and 8192^3 +3 to +7 %, qkv forward level,
+// o_proj forward level to slower; counters in profiles/r07_mfma16_pmc.txt).  The next K tile arrives as 4 DMA "pieces" of 16 KiB, one per phase (each piece = that half for
 // ALL waves: 2 x 1 KiB instructions per wave).
-// LDS image: rows of 128 bytes (64 k), 16-byte chunk c of row r stored at chunk c ^ ((r >> 1) & 7): the 16-lane
-// groups of ds_read_b128 over a 32-row fragment column hit 16 distinct 16-byte slots of the 256-byte bank row.  The DMA
+// LDS image: rows of 128 bytes (64 k), 16-byte chunk c of row r stored at chunk c ^ ((r >> 1) & 7): each of the four
+// lane groups of a ds_read_b128 over a 16-row fragment (rows of two k-chunks 4 ks + g) hits 16 distinct 16-byte slots of
+// the 256-byte bank row.  The DMA
 // writes LDS lane-linearly (8 rows x 128 B per instruction), so the swizzle is applied to the per-lane SOURCE chunk;
 // each row is still fetched as one whole 128-byte line.
 // Ablations on 8192^3 (round-3 ablation builds): everything 832 us; without LDS-DMA 574 (1.92 PF/s); without MFMA 607;
@@ -987,7 +990,8 @@ template __global__ void gemm_nt_ring_kernel<float, 3, float>(const GemmP);
 // [64 k][128 tile rows of that half] with 256-byte LDS rows (4 k-rows per DMA instruction, every 128 / 64 contiguous
 // source bytes a whole / half line), and the MFMA fragment (8 consecutive k of ONE tile row per lane) is gathered with
 // two ds_read_b64_tr_b16: a 16-lane group reads a [4 k][16 rows] block and lane i receives the 4 k of row i.  The four
-// k-rows of such a block would share banks (256-byte pitch): 64-byte chunk q of k-row t sits at chunk q ^ (t & 3).
+// k-rows of such a block would share banks (256-byte pitch): 64-byte chunk q of k-row t sits at chunk q ^ (t & 3), and its
+// two 32-byte halves swap places when bit 3 of t is set (the two 16-lane groups of a 32-lane bank cycle read k-rows 8 apart).
 // No transposed copy of anything is ever made: the W^T shadow arena and the per-GEMM activation transposes are gone.
 // K need not be a multiple of 64 when every operand is k-strided (rows past K are out of the buffer's range: zeros).
 // FUSE = 1 (DXA_FUSE_SWIGLU, bf16 NT lean only): B = [gate ; up] of a gated MLP; the tile's 256 B rows are 128 gate rows and the 128
@@ -1034,7 +1038,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
 #define PP_A_ROW0(h, j) ((((wave * 2 + (j)) & 7) * 8) + (((wave * 2 + (j)) >> 3) * 128) + 64 * (h))
 #define PP_B_ROW0(h, j) ((((wave * 2 + (j)) >> 2) * 64) + (((wave * 2 + (j)) & 3) * 8) + 32 * (h))
   // k-strided operand: DMA instruction (h, j) of a wave covers k-rows 4 (2 wave + j) .. +3 of piece h; lane -> (k-row =
-  // + lane / 16, LDS slot s = lane % 16 of the 256-byte row, source slot = s ^ ((k-row & 3) << 2)); source slot sigma ->
+  // + lane / 16, LDS slot s = lane % 16 of the 256-byte row, source slot = s ^ ((k-row & 3) << 2) ^ (((k-row >> 3) & 1) << 1)); source slot sigma ->
   // tile row: A: (sigma >> 3) * 128 + 64 h + 8 (sigma & 7) (two 128-byte segments: the A-h rows of wm = 0, 1)
   //           B: (sigma >> 2) * 64 + 32 h + 8 (sigma & 3)  (four 64-byte segments: the B-h columns of wn = 0..3)
   uint32_t voA[2][2], voB[2][2];
@@ -1046,7 +1050,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int krow = (wave * 2 + j) * 4 + (lane >> 4);
-        const int sig = (lane & 15) ^ ((krow & 3) << 2);
+        const int sig = (lane & 15) ^ ((krow & 3) << 2) ^ (((krow >> 3) & 1) << 1);
         if constexpr (A_KS) {
           const int ga = m0i + (sig >> 3) * 128 + 64 * h + 8 * (sig & 7);
           voA[h][j] = ga < (int)p.M ? (uint32_t)krow * lda2 + (uint32_t)ga * 2u : 0x80000000u;
@@ -1112,29 +1116,31 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
 #define PP_DMA_A(h, buf, tile) do { PP_DMA_A1(h, 0, buf, tile); PP_DMA_A1(h, 1, buf, tile); } while (0)
 #define PP_DMA_B(h, buf, tile) do { PP_DMA_B1(h, 0, buf, tile); PP_DMA_B1(h, 1, buf, tile); } while (0)
 
-  f32x16_t acc[4][2];
+  f32x4_t acc[8][4];                       // AccL<4, 16>: acc[i][j] = 16x16 block (16-row block i, 16-column block j)
 #pragma unroll
-  for (int i = 0; i < 4; ++i)
+  for (int i = 0; i < 8; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 
-  // fragment read addresses: A block i (32 rows) of k-step ks: row = wm*128 + 32 i + l32, chunk c = 2 ks + lh at slot
-  // c ^ sw.  2 ks + lh = (ks << 1) ^ lh, the row base has zero bits below 128 and buffer 1 starts at bit 16, so
-  // address = ya ^ (ks << 5) ^ (cur << 16) with ONE per-lane register ya = row base | ((lh ^ sw) << 4) per operand.
+  // v_mfma_f32_16x16x32_bf16 fragment: lane (i16 = lane % 16, g = lane / 16) holds tile row i16 of a 16-row block, k 8 g .. 8 g + 7
+  // of a 32-k step ks (two per K tile).
+  // K-contiguous operand: row r0 + i16, chunk c = 4 ks + g at slot c ^ sw (sw = (i16 >> 1) & 7).  4 ks + g = (ks << 2) ^ g, the row
+  // base has zero bits below 128 and buffer 1 starts at bit 16, so address = ya ^ (ks << 6) ^ (cur << 16), + 2048 per 16-row block
+  // as immediate, with ONE per-lane register ya = row base | ((g ^ sw) << 4) per operand.  Each of the four lane groups of a
+  // ds_read_b128 (4 + 4 + 8 lanes of two values of g) meets 16 distinct 16-byte slots of the bank row: conflict-free.
   const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  const int sw = (l32 >> 1) & 7;
-  // k-strided operand: lane (i = lane % 16, half-group (lane >> 4) & 1, lh) passes the address of 4 consecutive tile rows
-  // (8 bytes) of k-row t = 8 lh + (i >> 2) [+ 16 ks + 4 r as immediate] of its [4 k][16 rows] block and receives row i's
-  // 4 k; the wave's 64-byte chunk of the 256-byte piece row is q = 2 wm + ii (A) / wn (B), stored at q ^ (t & 3).
-  const int i16 = lane & 15, tq = (i16 >> 2) & 3, tk = 8 * lh + (i16 >> 2);
-  const uint32_t ks_lane = (uint32_t)(tk * 256 + ((lane >> 4) & 1) * 32 + (i16 & 3) * 8);
+  const int i16 = lane & 15, g = lane >> 4, sw = (i16 >> 1) & 7, tq = (i16 >> 2) & 3;
+  // k-strided operand: lane passes the address of 4 consecutive tile rows (8 bytes) of k-row t = 8 g + (i16 >> 2) [+ 32 ks, + 4 for
+  // k 4..7: immediates] of its [4 k][16 rows] block and receives row i16's 4 k.  16-row block b of the A half (B half) is 32-byte
+  // half b & 1 of the 64-byte chunk q = 2 wm + (b >> 1) (A) / wn (B) of the 256-byte piece row, stored at chunk q ^ (t & 3), half
+  // (b & 1) ^ ((t >> 3) & 1) (the DMA's source slot swizzle): the two 16-lane groups of a 32-lane bank cycle read k-rows 8 apart,
+  // which the half swap puts on different banks.  address = y ^ (32 b) ^ (cur << 16), + 16384 h + 8192 ks as immediate.
+  const uint32_t ks_lane = (uint32_t)((8 * g + (i16 >> 2)) * 256 + (g & 1) * 32 + (i16 & 3) * 8);
   const uint32_t ya = A_KS ? lds0 + ks_lane + (uint32_t)(((wm * 2) ^ tq) << 6)
-                           : (lds0 + (wm * 128 + l32) * 128) | (uint32_t)((lh ^ sw) << 4);
+                           : (lds0 + (wm * 128 + i16) * 128) | (uint32_t)((g ^ sw) << 4);
   const uint32_t yb = B_KS ? lds0 + REG + ks_lane + (uint32_t)((wn ^ tq) << 6)
-                           : (lds0 + REG + (wn * 64 + l32) * 128) | (uint32_t)((lh ^ sw) << 4);
-  u32x4_t af[2][4], bq[2][4];            // B fragments of both halves stay in registers: B0 serves phases 0 and 3
+                           : (lds0 + REG + (wn * 64 + i16) * 128) | (uint32_t)((g ^ sw) << 4);
+  u32x4_t af[4][2], bq[2][2][2];         // af[b][ks]: A half in use; bq[j][b][ks]: both B halves stay in registers (B0 serves phases 0 and 3)
   typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 #define PP_READ(dst, addr, imm) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(imm) : "memory")
 #define PP_READ_TR(dst, addr, imm) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(imm) : "memory")
@@ -1145,82 +1151,35 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
     PP_READ_TR(lo_, addr, imm); PP_READ_TR(hi_, addr, (imm) + 1024);                     \
     dst = (u32x4_t){lo_[0], lo_[1], hi_[0], hi_[1]};                                     \
   } while (0)
-#define PP_RD_A(cur, h)                                                                                     \
+  // fragment (block b, k-step ks) of A half h / B half j
+#define PP_RDF_A(cur, h, b, ks)                                                                             \
   do {                                                                                                      \
-    if constexpr (A_KS) {                                                                                   \
-      const uint32_t a0_ = ya ^ (uint32_t)((cur) * BUF + (h) * 16384), a1_ = a0_ ^ 64u;                     \
-      PP_FRAG_TR(af[0][0], a0_, 0); PP_FRAG_TR(af[1][0], a1_, 0);                                           \
-      PP_FRAG_TR(af[0][1], a0_, 4096); PP_FRAG_TR(af[1][1], a1_, 4096);                                     \
-      PP_FRAG_TR(af[0][2], a0_, 8192); PP_FRAG_TR(af[1][2], a1_, 8192);                                     \
-      PP_FRAG_TR(af[0][3], a0_, 12288); PP_FRAG_TR(af[1][3], a1_, 12288);                                   \
-    } else {                                                                                                \
-      const uint32_t a0_ = ya ^ (uint32_t)((cur) * BUF), a1_ = ya ^ (uint32_t)((cur) * BUF + 32),           \
-                     a2_ = ya ^ (uint32_t)((cur) * BUF + 64), a3_ = ya ^ (uint32_t)((cur) * BUF + 96);      \
-      PP_READ(af[0][0], a0_, (2 * (h)) * 4096); PP_READ(af[1][0], a0_, (2 * (h) + 1) * 4096);              \
-      PP_READ(af[0][1], a1_, (2 * (h)) * 4096); PP_READ(af[1][1], a1_, (2 * (h) + 1) * 4096);              \
-      PP_READ(af[0][2], a2_, (2 * (h)) * 4096); PP_READ(af[1][2], a2_, (2 * (h) + 1) * 4096);              \
-      PP_READ(af[0][3], a3_, (2 * (h)) * 4096); PP_READ(af[1][3], a3_, (2 * (h) + 1) * 4096);              \
-    }                                                                                                       \
+    if constexpr (A_KS) PP_FRAG_TR(af[b][ks], ya ^ (uint32_t)((cur) * BUF + 32 * (b)), (h) * 16384 + (ks) * 8192); \
+    else PP_READ(af[b][ks], ya ^ (uint32_t)((cur) * BUF + 64 * (ks)), (4 * (h) + (b)) * 2048);            \
   } while (0)
-#define PP_RD_B(cur, j)                                                                                     \
+#define PP_RDF_B(cur, j, b, ks)                                                                             \
   do {                                                                                                      \
-    if constexpr (B_KS) {                                                                                   \
-      const uint32_t b0_ = yb ^ (uint32_t)((cur) * BUF + (j) * 16384);                                      \
-      PP_FRAG_TR(bq[j][0], b0_, 0); PP_FRAG_TR(bq[j][1], b0_, 4096);                                        \
-      PP_FRAG_TR(bq[j][2], b0_, 8192); PP_FRAG_TR(bq[j][3], b0_, 12288);                                    \
-    } else {                                                                                                \
-      const uint32_t b0_ = yb ^ (uint32_t)((cur) * BUF), b1_ = yb ^ (uint32_t)((cur) * BUF + 32),           \
-                     b2_ = yb ^ (uint32_t)((cur) * BUF + 64), b3_ = yb ^ (uint32_t)((cur) * BUF + 96);      \
-      PP_READ(bq[j][0], b0_, (j) * 4096); PP_READ(bq[j][1], b1_, (j) * 4096);                               \
-      PP_READ(bq[j][2], b2_, (j) * 4096); PP_READ(bq[j][3], b3_, (j) * 4096);                               \
-    }                                                                                                       \
+    if constexpr (B_KS) PP_FRAG_TR(bq[j][b][ks], yb ^ (uint32_t)((cur) * BUF + 32 * (b)), (j) * 16384 + (ks) * 8192); \
+    else PP_READ(bq[j][b][ks], yb ^ (uint32_t)((cur) * BUF + 64 * (ks)), (2 * (j) + (b)) * 2048);         \
   } while (0)
-#define PP_MFMA(ii, ks, i, j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, bq[j][ks]), __builtin_bit_cast(bf16x8_t, af[ii][ks]), acc[i][j], 0, 0, 0)
+#define PP_MFMA(h, j, b, jb, ks)                                                                                            \
+  acc[4 * (h) + (b)][2 * (j) + (jb)] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(                                           \
+      __builtin_bit_cast(bf16x8_t, bq[j][jb][ks]), __builtin_bit_cast(bf16x8_t, af[b][ks]), acc[4 * (h) + (b)][2 * (j) + (jb)], 0, 0, 0)
 #define PP_SB() __builtin_amdgcn_sched_barrier(0)
 #define PP_BAR() do { PP_SB(); __builtin_amdgcn_s_barrier(); PP_SB(); } while (0)
-  // compute cluster of quadrant (A half h, B half j): the two accumulators alternate so dependent MFMAs are 2 apart
-#define PP_COMPUTE(h, j)                                                                          \
-  do {                                                                                            \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                            \
-    PP_SB();                                                                                      \
-    PP_MFMA(0, 0, 2 * (h), j); PP_MFMA(1, 0, 2 * (h) + 1, j);                                     \
-    PP_MFMA(0, 1, 2 * (h), j); PP_MFMA(1, 1, 2 * (h) + 1, j);                                     \
-    PP_MFMA(0, 2, 2 * (h), j); PP_MFMA(1, 2, 2 * (h) + 1, j);                                     \
-    PP_MFMA(0, 3, 2 * (h), j); PP_MFMA(1, 3, 2 * (h) + 1, j);                                     \
-    PP_SB();                                                                                      \
-  } while (0)
-  // k-step ks of A half h / B half j alone (round 4: the fragment reads ride in the gaps of the PREVIOUS compute cluster's MFMAs)
-#define PP_RDK_A(cur, h, ks)                                                                                \
-  do {                                                                                                      \
-    if constexpr (A_KS) {                                                                                   \
-      const uint32_t a0_ = ya ^ (uint32_t)((cur) * BUF + (h) * 16384), a1_ = a0_ ^ 64u;                     \
-      PP_FRAG_TR(af[0][ks], a0_, 4096 * (ks)); PP_FRAG_TR(af[1][ks], a1_, 4096 * (ks));                     \
-    } else {                                                                                                \
-      const uint32_t a_ = ya ^ (uint32_t)((cur) * BUF + 32 * (ks));                                         \
-      PP_READ(af[0][ks], a_, (2 * (h)) * 4096); PP_READ(af[1][ks], a_, (2 * (h) + 1) * 4096);              \
-    }                                                                                                       \
-  } while (0)
-#define PP_RDK_B(cur, j, ks)                                                                                \
-  do {                                                                                                      \
-    if constexpr (B_KS) {                                                                                   \
-      const uint32_t b0_ = yb ^ (uint32_t)((cur) * BUF + (j) * 16384);                                      \
-      PP_FRAG_TR(bq[j][ks], b0_, 4096 * (ks));                                                              \
-    } else {                                                                                                \
-      const uint32_t b_ = yb ^ (uint32_t)((cur) * BUF + 32 * (ks));                                         \
-      PP_READ(bq[j][ks], b_, (j) * 4096);                                                                   \
-    }                                                                                                       \
-  } while (0)
-  // compute cluster with the NEXT cluster's fragment reads in its gaps: after the two MFMAs of k-step ks their operand registers are
-  // dead, R(ks) refills them (the data lands tens of cycles after the MFMAs have read their sources)
+  // compute cluster of quadrant (A half h, B half j): 16 MFMAs, the k-step outermost so that the quadrant's 8 accumulators lie
+  // between two MFMAs on one accumulator.  R(ks, b) runs after the two MFMAs of A block b in k-step ks: af[b][ks] is dead from there
+  // on, and R refills registers with the NEXT cluster's fragments (the data lands tens of cycles after the MFMAs have read their
+  // sources).
+#define PP_MFMA2(h, j, b, ks, R) do { PP_MFMA(h, j, b, 0, ks); PP_MFMA(h, j, b, 1, ks); PP_SB(); R(ks, b); PP_SB(); } while (0)
 #define PP_COMPUTE_R(h, j, R)                                                                     \
   do {                                                                                            \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                            \
     PP_SB();                                                                                      \
-    PP_MFMA(0, 0, 2 * (h), j); PP_MFMA(1, 0, 2 * (h) + 1, j); PP_SB(); R(0); PP_SB();             \
-    PP_MFMA(0, 1, 2 * (h), j); PP_MFMA(1, 1, 2 * (h) + 1, j); PP_SB(); R(1); PP_SB();             \
-    PP_MFMA(0, 2, 2 * (h), j); PP_MFMA(1, 2, 2 * (h) + 1, j); PP_SB(); R(2); PP_SB();             \
-    PP_MFMA(0, 3, 2 * (h), j); PP_MFMA(1, 3, 2 * (h) + 1, j); PP_SB(); R(3); PP_SB();             \
+    PP_MFMA2(h, j, 0, 0, R); PP_MFMA2(h, j, 1, 0, R); PP_MFMA2(h, j, 2, 0, R); PP_MFMA2(h, j, 3, 0, R); \
+    PP_MFMA2(h, j, 0, 1, R); PP_MFMA2(h, j, 1, 1, R); PP_MFMA2(h, j, 2, 1, R); PP_MFMA2(h, j, 3, 1, R); \
   } while (0)
+#define PP_R_NONE(ks, b) do { } while (0)
 #define PP_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
   // one K tile in buffer `cur = t & 1` of two 64 KiB LDS buffers; the two wave groups run staggered by one barrier interval, a
   // compute cluster C_q of one group beside the memory cluster M_q (LDS-DMA issue) of the other.
@@ -1255,9 +1214,18 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
   // C1(t-1), C3(t-1), C3(t-1), C0(t): at least one full barrier interval before, for both groups).  In-order issue per wave:
   //   ... A1(t) | A0(t+1) | B0(t+1) | B1(t+1) | A1(t+1) | A0(t+2) | B0(t+2) | B1(t+2) ...   (2 instructions each)
   // end of M0: A1(t) landed = vmcnt(8);  end of M2: A0(t+1), B0(t+1) = vmcnt(8);  end of M3: B1(t+1) = vmcnt(8)  (4 phases ahead).
-#define PP_R_B1(ks) PP_RDK_B(cur_, 1, ks)
-#define PP_R_A1(ks) PP_RDK_A(cur_, 1, ks)
-#define PP_R_NEXT(ks) do { if (more1) { PP_RDK_A(cur_ ^ 1, 0, ks); PP_RDK_B(cur_ ^ 1, 0, ks); } } while (0)
+  // In the 16-MFMA clusters: B1(t) one fragment after blocks 1 and 3 of each k-step; A1(t) and A0(t+1) fragment (b, ks) right after
+  // the two MFMAs that consumed the register; B0(t+1) k-step 0 after blocks 0 and 1 of k-step 1, k-step 1 after the last MFMA.
+#define PP_R_B1(ks, b) do { if constexpr (((b) & 1) != 0) PP_RDF_B(cur_, 1, (b) >> 1, ks); } while (0)
+#define PP_R_A1(ks, b) PP_RDF_A(cur_, 1, b, ks)
+#define PP_R_NEXT(ks, b)                                                                                    \
+  do {                                                                                                      \
+    if (more1) {                                                                                            \
+      PP_RDF_A(cur_ ^ 1, 0, b, ks);                                                                         \
+      if constexpr ((ks) == 1 && (b) < 2) PP_RDF_B(cur_ ^ 1, 0, (b) & 1, 0);                                \
+      if constexpr ((ks) == 1 && (b) == 3) { PP_RDF_B(cur_ ^ 1, 0, 0, 1); PP_RDF_B(cur_ ^ 1, 0, 1, 1); }    \
+    }                                                                                                       \
+  } while (0)
 #define PP_TILE(cur, t)                                                                                     \
   do {                                                                                                      \
     constexpr int cur_ = (cur);                                                                             \
@@ -1270,7 +1238,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
     PP_BAR(); PP_STAMP(2); PP_COMPUTE_R(0, 1, PP_R_A1); PP_BAR(); PP_STAMP(3);                              \
     /* phase 2 */                                                                                           \
     if (more2) { PP_DMA_B(0, cur_, (t) + 2); PP_SB(); PP_VMCNT(8); } else if (more1) { PP_VMCNT(4); }       \
-    PP_BAR(); PP_STAMP(4); PP_COMPUTE(1, 1); PP_BAR(); PP_STAMP(5);                                         \
+    PP_BAR(); PP_STAMP(4); PP_COMPUTE_R(1, 1, PP_R_NONE); PP_BAR(); PP_STAMP(5);                                         \
     /* phase 3 */                                                                                           \
     if (more2) { PP_DMA_B(1, cur_, (t) + 2); PP_SB(); PP_VMCNT(8); } else if (more1) { PP_VMCNT(2); }       \
     PP_BAR(); PP_STAMP(6); PP_COMPUTE_R(1, 0, PP_R_NEXT); PP_BAR(); PP_STAMP(7);                            \
@@ -1284,7 +1252,9 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
   PP_SB();
   if (nk > 1) { PP_VMCNT(8); } else { PP_VMCNT(2); }
   PP_BAR();
-  PP_RD_A(0, 0); PP_RD_B(0, 0);
+  PP_RDF_A(0, 0, 0, 0); PP_RDF_A(0, 0, 1, 0); PP_RDF_A(0, 0, 2, 0); PP_RDF_A(0, 0, 3, 0);
+  PP_RDF_A(0, 0, 0, 1); PP_RDF_A(0, 0, 1, 1); PP_RDF_A(0, 0, 2, 1); PP_RDF_A(0, 0, 3, 1);
+  PP_RDF_B(0, 0, 0, 0); PP_RDF_B(0, 0, 1, 0); PP_RDF_B(0, 0, 0, 1); PP_RDF_B(0, 0, 1, 1);
   PP_SB();
   if (wm == 1) PP_BAR();    // group 1 runs one barrier interval behind group 0
   for (int t = 0; t < nk; t += 2) {
@@ -1303,30 +1273,29 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
 #undef PP_READ
 #undef PP_READ_TR
 #undef PP_FRAG_TR
-#undef PP_RD_A
-#undef PP_RD_B
+#undef PP_RDF_A
+#undef PP_RDF_B
 #undef PP_MFMA
+#undef PP_MFMA2
 #undef PP_SB
 #undef PP_BAR
-#undef PP_COMPUTE
+#undef PP_R_NONE
 #undef PP_VMCNT
 #undef PP_TILE
 #undef PP_DMA_A1
 #undef PP_DMA_B1
 #undef PP_STAMP
 #undef PP_STAMPS_FOLD
-#undef PP_RDK_A
-#undef PP_RDK_B
 #undef PP_COMPUTE_R
 #undef PP_R_B1
 #undef PP_R_A1
 #undef PP_R_NEXT
 
   if constexpr (LEAN) {
-    if (!tile_split_exchange<4>(p, acc, tid, split_j, split_s, tail_i)) return;
+    if (!tile_split_exchange<4, 16>(p, acc, tid, split_j, split_s, tail_i)) return;
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (FUSE == 1) sk_epilogue_swiglu<4>(p, acc, smem + wave * 4096, lane, wm, wn, m0i, n0i);
-    else sk_epilogue<TO, TE>(p, acc, smem + wave * 4096, lane, wm, wn, m0i, n0i, reinterpret_cast<float*>(smem + 8 * 4096), bid);
+    if constexpr (FUSE == 1) sk_epilogue_swiglu<4, 16>(p, acc, smem + wave * 4096, lane, wm, wn, m0i, n0i);
+    else sk_epilogue<TO, TE, 4, 16>(p, acc, smem + wave * 4096, lane, wm, wn, m0i, n0i, reinterpret_cast<float*>(smem + 8 * 4096), bid);
 #if defined(DXA_PP_STAMPS)
     __syncthreads();
     if (m0i == 0 && n0i == 0 && lane == 0) {          // the first tile's waves: [wave][8 intervals + K tiles] over the head of C
@@ -1336,7 +1305,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
     }
 #endif
   } else {
-    tile_finish<TO, 4, TE>(p, acc, smem, tid, lane, wave, wm, wn, l32, lh, m0, n0, split_j, split_s, tail_i);
+    tile_finish<TO, 4, TE, false, 16>(p, acc, smem, tid, lane, wave, wm, wn, l32, lh, m0, n0, split_j, split_s, tail_i);
   }
 #endif  // __HIP_DEVICE_COMPILE__
 }

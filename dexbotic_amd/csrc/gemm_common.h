@@ -120,13 +120,53 @@ __device__ __forceinline__ void epilogue4(const GemmP& p, TO* C, TO* AUX, const 
 
 constexpr int NUM_CU_D = 256;   // split-K scratch slots (one per CU)
 
+// Accumulators of one wave's (32 AI) x 64 output block, by MFMA shape MF (both with swapped operands: B fragment first).
+//   MF = 32: f32x16_t acc[AI][2], acc[i][j] = 32x32 block (32-row block i, 32-column block j) of v_mfma_f32_32x32x16_bf16;
+//            lane l holds row l & 31, columns 8 q + 4 (l >> 5) + 0..3 in registers 4 q .. 4 q + 3.
+//   MF = 16: f32x4_t acc[2 AI][4], acc[i][j] = 16x16 block (16-row block i, 16-column block j) of v_mfma_f32_16x16x32_bf16;
+//            lane l holds row l & 15, columns 4 (l >> 4) + 0..3.
+// The helpers below take the layout as a template parameter; the 32x32 staging code is spelled out in them (MF == 32), the
+// 16x16 layout brings its own:
+// unit(u) / add(u): the lane's 16-byte unit u (0 .. 8 AI - 1) in a fixed order (its split-K slots);
+// stage16(s): rows 16 s .. 16 s + 15 into a 16 x 64 fp32 slab, 16-byte unit c of row r at c ^ r (conflict-free both ways);
+// stage64(s): rows 64 s .. 64 s + 63 into a 64-row slab with rows of RP bytes.
+template <int AI, int MF> struct AccL;
+template <int AI> struct AccL<AI, 32> { typedef f32x16_t T[AI][2]; };
+template <int AI> struct AccL<AI, 16> {
+  typedef f32x4_t T[2 * AI][4];
+  static __device__ __forceinline__ f32x4_t unit(const T& a, int u) { return a[u >> 2][u & 3]; }
+  static __device__ __forceinline__ void add(T& a, int u, const f32x4_t& v) { a[u >> 2][u & 3] += v; }
+  static __device__ __forceinline__ void stage16(const T& a, int s, char* slab, int lane) {
+    const int r16 = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const f32x4_t x = a[s][j];
+      *reinterpret_cast<float4*>(slab + r16 * 256 + (((j * 4 + g) ^ r16) << 4)) = make_float4(x[0], x[1], x[2], x[3]);
+    }
+  }
+  template <int RP>
+  static __device__ __forceinline__ void stage64(const T& a, int s, char* slab, int lane) {
+    const int r16 = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int i = 4 * s + ii;
+        if (i >= 2 * AI) continue;
+        const f32x4_t x = a[i][j];
+        *reinterpret_cast<float4*>(slab + (ii * 16 + r16) * RP + (j * 16 + 4 * g) * 4) = make_float4(x[0], x[1], x[2], x[3]);
+      }
+  }
+};
+
 // Split-K hand-off of a tail tile: every piece but the last stores its fp32 partial (lane-linear slots, sc1 write-through)
 // and bumps the tile's arrival counter; the last piece waits for them and adds them in slice order.  Returns false for a
 // workgroup that is done (it only contributed a partial).
-template <int AI>
-__device__ __forceinline__ bool tile_split_exchange(const GemmP& p, f32x16_t (&acc)[AI][2], int tid, int split_j, int split_s,
+template <int AI, int MF = 32>
+__device__ __forceinline__ bool tile_split_exchange(const GemmP& p, typename AccL<AI, MF>::T& acc, int tid, int split_j, int split_s,
                                                     int tail_i) {
 #if defined(__HIP_DEVICE_COMPILE__)
+  typedef AccL<AI, MF> L;
   // ---- split-K tail: partial accumulators travel through a lane-linear fp32 slot (8 KiB per wave store).
   // sc1 (agent scope) stores write through the XCD-private L2 and sc1 loads miss in it, so no cache-wide
   // write-back / invalidate is needed; 16-byte accesses keep the gatherer off the instruction-issue limit.
@@ -137,15 +177,21 @@ __device__ __forceinline__ bool tile_split_exchange(const GemmP& p, f32x16_t (&a
     const uint32_t slot0 = (uint32_t)tail_i * (uint32_t)(split_s - 1) * SLOT + (uint32_t)tid * 16u;
     if (split_j < split_s - 1) {
       const uint32_t dst = slot0 + (uint32_t)split_j * SLOT;
+      if constexpr (MF == 32) {
 #pragma unroll
-      for (int i = 0; i < AI; ++i)
+        for (int i = 0; i < AI; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+          for (int j = 0; j < 2; ++j)
 #pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const f32x4_t v = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), rW, dst + ((i * 2 + j) * 4 + q) * 8192, 0, SC1);
-          }
+            for (int q = 0; q < 4; ++q) {
+              const f32x4_t v = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
+              __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), rW, dst + ((i * 2 + j) * 4 + q) * 8192, 0, SC1);
+            }
+      } else {
+#pragma unroll
+        for (int u = 0; u < 8 * AI; ++u)
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, L::unit(acc, u)), rW, dst + u * 8192, 0, SC1);
+      }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       if (tid == 0) __hip_atomic_fetch_add(p.flags + tail_i, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -160,17 +206,25 @@ __device__ __forceinline__ bool tile_split_exchange(const GemmP& p, f32x16_t (&a
     __syncthreads();
     for (int sj = 0; sj < split_s - 1; ++sj) {
       const uint32_t src = slot0 + (uint32_t)sj * SLOT;
+      if constexpr (MF == 32) {
 #pragma unroll
-      for (int i = 0; i < AI; ++i) {
+        for (int i = 0; i < AI; ++i) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+          for (int j = 0; j < 2; ++j)
 #pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const f32x4_t v = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rW, src + ((i * 2 + j) * 4 + q) * 8192, 0, SC1));
+            for (int q = 0; q < 4; ++q) {
+              const f32x4_t v = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rW, src + ((i * 2 + j) * 4 + q) * 8192, 0, SC1));
 #pragma unroll
-            for (int c = 0; c < 4; ++c) acc[i][j][4 * q + c] += v[c];
-          }
-        if (AI == 4 && i == 1) __builtin_amdgcn_sched_barrier(0);   // at most 16 loads (64 VGPRs) in flight
+              for (int c = 0; c < 4; ++c) acc[i][j][4 * q + c] += v[c];
+            }
+          if (AI == 4 && i == 1) __builtin_amdgcn_sched_barrier(0);   // at most 16 loads (64 VGPRs) in flight
+        }
+      } else {
+#pragma unroll
+        for (int u = 0; u < 8 * AI; ++u) {
+          L::add(acc, u, __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rW, src + u * 8192, 0, SC1)));
+          if (AI == 4 && u == 15) __builtin_amdgcn_sched_barrier(0);   // at most 16 loads (64 VGPRs) in flight
+        }
       }
     }
   }
@@ -186,18 +240,19 @@ __device__ __forceinline__ bool tile_split_exchange(const GemmP& p, f32x16_t (&a
 }
 
 // Everything after the K loop of the 256-column-tile bf16 NT kernels (ring and ping-pong main loops share it): the
-// split-K hand-off of tail tiles and the fused epilogue.  acc[i][j] = 32x32 block (32-row block i of the wave's rows,
-// 32-column block j of its 64 columns) in the v_mfma_f32_32x32x16 accumulator layout with swapped operands.
+// split-K hand-off of tail tiles and the fused epilogue.  acc: the wave's (32 AI) x 64 block in the accumulator layout
+// AccL<AI, MF>.
 // SMALL = false: 17 KiB staging slab per wave at the start of LDS (the K-loop buffers are dead by then).
 // SMALL = true : 4 KiB per wave above the 128 KiB of K-loop buffers (persistent ping-pong kernel: the next tile's
 //                LDS-DMA pieces are already landing in those buffers while this epilogue runs).
-template <typename TO, int AI, typename TE, bool SMALL = false>
-__device__ __forceinline__ void tile_finish(const GemmP& p, f32x16_t (&acc)[AI][2], char* smem, int tid, int lane, int wave,
+template <typename TO, int AI, typename TE, bool SMALL = false, int MF = 32>
+__device__ __forceinline__ void tile_finish(const GemmP& p, typename AccL<AI, MF>::T& acc, char* smem, int tid, int lane, int wave,
                                             int wm, int wn, int l32, int lh, int64_t m0, int64_t n0, int split_j,
                                             int split_s, int tail_i) {
 #if defined(__HIP_DEVICE_COMPILE__)
+  typedef AccL<AI, MF> L;
   constexpr int BMR = AI * 64;
-  if (!tile_split_exchange<AI>(p, acc, tid, split_j, split_s, tail_i)) return;
+  if (!tile_split_exchange<AI, MF>(p, acc, tid, split_j, split_s, tail_i)) return;
 
   TO* C = reinterpret_cast<TO*>(p.C);
   TO* AUX = p.aux ? reinterpret_cast<TO*>(p.aux) : nullptr;
@@ -214,17 +269,21 @@ __device__ __forceinline__ void tile_finish(const GemmP& p, f32x16_t (&acc)[AI][
     char* slab = smem + wave * (64 * ROWP);
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
+      if constexpr (MF == 32) {
 #pragma unroll
-      for (int ii = 0; ii < 2; ++ii)
+        for (int ii = 0; ii < 2; ++ii)
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+          for (int j = 0; j < 2; ++j)
 #pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int i = 2 * pass + ii;
-            if (i >= AI) continue;
-            float4 v = make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
-            *reinterpret_cast<float4*>(slab + (ii * 32 + l32) * ROWP + (j * 32 + 8 * q + 4 * lh) * 4) = v;
-          }
+            for (int q = 0; q < 4; ++q) {
+              const int i = 2 * pass + ii;
+              if (i >= AI) continue;
+              float4 v = make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
+              *reinterpret_cast<float4*>(slab + (ii * 32 + l32) * ROWP + (j * 32 + 8 * q + 4 * lh) * 4) = v;
+            }
+      } else {
+        L::template stage64<ROWP>(acc, pass, slab, lane);
+      }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
 #pragma unroll 4
@@ -245,19 +304,23 @@ __device__ __forceinline__ void tile_finish(const GemmP& p, f32x16_t (&acc)[AI][
     // u ^ r: the 8-lane groups of the ds_write_b128 (8 consecutive rows, one unit) and the 16-lane groups of the
     // ds_read_b128 (one row, 16 units / two rows, 8 + 8 units) each touch every bank once.
     char* slab = smem + 131072 + wave * 4096;
-    const int r16 = l32 & 15;
+    [[maybe_unused]] const int r16 = l32 & 15;
 #pragma unroll
     for (int i = 0; i < AI; ++i)
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh) {
-        if ((l32 >> 4) == hh) {
+        if constexpr (MF == 32) {
+          if ((l32 >> 4) == hh) {
 #pragma unroll
-          for (int j = 0; j < 2; ++j)
+            for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              float4 v = make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
-              *reinterpret_cast<float4*>(slab + r16 * 256 + (((j * 8 + 2 * q + lh) ^ r16) << 4)) = v;
-            }
+              for (int q = 0; q < 4; ++q) {
+                float4 v = make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
+                *reinterpret_cast<float4*>(slab + r16 * 256 + (((j * 8 + 2 * q + lh) ^ r16) << 4)) = v;
+              }
+          }
+        } else {
+          L::stage16(acc, 2 * i + hh, slab, lane);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -335,15 +398,15 @@ template <> struct SkIO<bf16_t> {
 // whose epilogue carries the whole menu.
 // sk_epilogue_rows: the 128 x 64 block of one wave (rows m0 + 128 wm + ..., columns n0 + 64 wn + ...); returns the lane's share of
 // the sum of squares of what it stored.  sk_epilogue: the 8-wave (2 x 4) kernels' tile = one such block per wave + the fold.
-template <typename TO, typename TE, int AI = 4>
-__device__ __forceinline__ float sk_epilogue_rows(const GemmP& p, f32x16_t (&acc)[AI][2], char* slab, int lane, int wm, int wn,
+template <typename TO, typename TE, int AI = 4, int MF = 32>
+__device__ __forceinline__ float sk_epilogue_rows(const GemmP& p, typename AccL<AI, MF>::T& acc, char* slab, int lane, int wm, int wn,
                                                   int m0, int n0) {
   float ssq = 0.f;                                   // sum of squares of the values this lane stores (p.sumsq)
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int CPL = 16 / (int)sizeof(TO);        // columns per lane: 16 bytes of output
   constexpr int LPR = 64 / CPL;                    // lanes per 64-column row (8 | 16)
   constexpr int RPI = 64 / LPR;                    // rows per wave instruction (8 | 4)
-  const int l32 = lane & 31, lh = lane >> 5, r16 = l32 & 15;
+  [[maybe_unused]] const int l32 = lane & 31, lh = lane >> 5, r16 = l32 & 15;
   const int lr = lane / LPR, lc = (lane % LPR) * CPL;
   const int n = n0 + wn * 64 + lc;
   const int rowb = m0 + wm * (32 * AI) + lr;       // + 32 i + 16 hh + RPI it   (AI = 3: the 192-row tile's 96 x 64 block)
@@ -371,14 +434,18 @@ __device__ __forceinline__ float sk_epilogue_rows(const GemmP& p, f32x16_t (&acc
   for (int i = 0; i < AI; ++i)
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh) {
-      if ((l32 >> 4) == hh) {
+      if constexpr (MF == 32) {
+        if ((l32 >> 4) == hh) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+          for (int j = 0; j < 2; ++j)
 #pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            float4 v = make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
-            *reinterpret_cast<float4*>(slab + r16 * 256 + (((j * 8 + 2 * q + lh) ^ r16) << 4)) = v;
-          }
+            for (int q = 0; q < 4; ++q) {
+              float4 v = make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
+              *reinterpret_cast<float4*>(slab + r16 * 256 + (((j * 8 + 2 * q + lh) ^ r16) << 4)) = v;
+            }
+        }
+      } else {
+        AccL<AI, MF>::stage16(acc, 2 * i + hh, slab, lane);
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -439,11 +506,11 @@ __device__ __forceinline__ float sk_epilogue_rows(const GemmP& p, f32x16_t (&acc
 // (16-byte units lq and 8 + lq of its row), rounds both to bf16 — the pre-activations as dxa_gemm would have stored them —
 // and stores out = bf16(bf16(silu(g)) * u) (elementwise.hip swiglu_fwd_k, bit for bit) plus, if asked, the two pre-activation
 // pieces: 8-byte stores, 8 lanes = one 64-byte row segment.
-template <int AI = 4>
-__device__ __forceinline__ void sk_epilogue_swiglu(const GemmP& p, f32x16_t (&acc)[AI][2], char* slab, int lane, int wm, int wn,
+template <int AI = 4, int MF = 32>
+__device__ __forceinline__ void sk_epilogue_swiglu(const GemmP& p, typename AccL<AI, MF>::T& acc, char* slab, int lane, int wm, int wn,
                                                    int m0, int n0) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  const int l32 = lane & 31, lh = lane >> 5, r16 = l32 & 15;
+  [[maybe_unused]] const int l32 = lane & 31, lh = lane >> 5, r16 = l32 & 15;
   const int lr = lane >> 3, lq = lane & 7;                 // row of the 8-row instruction, 4-output group
   const int F = (int)(p.N >> 1);
   const int nout = (n0 >> 1) + wn * 32 + lq * 4;           // first of the lane's 4 outputs
@@ -463,14 +530,18 @@ __device__ __forceinline__ void sk_epilogue_swiglu(const GemmP& p, f32x16_t (&ac
   for (int i = 0; i < AI; ++i)
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh) {
-      if ((l32 >> 4) == hh) {
+      if constexpr (MF == 32) {
+        if ((l32 >> 4) == hh) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+          for (int j = 0; j < 2; ++j)
 #pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            float4 v = make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
-            *reinterpret_cast<float4*>(slab + r16 * 256 + (((j * 8 + 2 * q + lh) ^ r16) << 4)) = v;
-          }
+            for (int q = 0; q < 4; ++q) {
+              float4 v = make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
+              *reinterpret_cast<float4*>(slab + r16 * 256 + (((j * 8 + 2 * q + lh) ^ r16) << 4)) = v;
+            }
+        }
+      } else {
+        AccL<AI, MF>::stage16(acc, 2 * i + hh, slab, lane);
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -506,11 +577,11 @@ __device__ __forceinline__ void sk_epilogue_swiglu(const GemmP& p, f32x16_t (&ac
     }
 #endif
 }
-template <typename TO, typename TE, int AI = 4>
-__device__ __forceinline__ void sk_epilogue(const GemmP& p, f32x16_t (&acc)[AI][2], char* slab, int lane, int wm, int wn,
+template <typename TO, typename TE, int AI = 4, int MF = 32>
+__device__ __forceinline__ void sk_epilogue(const GemmP& p, typename AccL<AI, MF>::T& acc, char* slab, int lane, int wm, int wn,
                                             int m0, int n0, float* red, int tile) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  float ssq = sk_epilogue_rows<TO, TE, AI>(p, acc, slab, lane, wm, wn, m0, n0);
+  float ssq = sk_epilogue_rows<TO, TE, AI, MF>(p, acc, slab, lane, wm, wn, m0, n0);
   {
     // global-norm clip: this tile's share of sum(g^2), folded lane -> wave -> workgroup in a fixed order and written to
     // the tile's own slot (the host adds the slots in index order): the separate 30 GB pass over the gradient arena that
