@@ -47,6 +47,21 @@ class GemmDesc(C.Structure):
     ]
 
 
+class GemmStepInfo(C.Structure):
+    _fields_ = [
+        ("kernel", C.c_char_p), ("grid", _i32 * 3), ("block", _i32), ("lds", _i32),
+        ("K", _i64), ("K2", _i64), ("a_off", _i64), ("b_off", _i64), ("seg2", _i32),
+        ("accumulate", _i32), ("bias", _i32), ("residual", _i32),
+        ("tm", _i32), ("tn", _i32), ("full", _i32), ("tail_r", _i32), ("split_s", _i32), ("group_m", _i32),
+        ("vecA", _i32), ("vecB", _i32), ("vecC", _i32), ("vecR", _i32), ("vecG", _i32), ("vecBias", _i32),
+        ("ksplit", _i32), ("kper", _i32), ("split_ws", _i32), ("mirror", _i32), ("sumsq", _i32),
+    ]
+
+
+class GemmPlanInfo(C.Structure):
+    _fields_ = [("nsteps", _i32), ("mirror_pass", _i32), ("sumsq_pass", _i32), ("step", GemmStepInfo * 2)]
+
+
 class Split3Op(C.Structure):
     _fields_ = [("src", _vp), ("ld", _i64), ("dst", _vp), ("rows", _i64), ("cols", _i64), ("pad", _i64), ("side", _i32), ("transposed", _i32)]
 
@@ -103,6 +118,8 @@ SIGNATURES = {
     "dxa_last_error": (C.c_char_p, []),
     "dxa_version": (_int, []),
     "dxa_gemm": (_int, [C.POINTER(GemmDesc), _vp]),
+    "dxa_gemm_plan": (_int, [C.POINTER(GemmDesc), C.POINTER(GemmPlanInfo)]),
+    "dxa_gemm_kernel_name": (C.c_char_p, [_int]),
     "dxa_split3": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _vp]),
     "dxa_split3_t": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _int, _vp]),
     "dxa_split3_pair": (_int, [C.POINTER(Split3Op), C.POINTER(Split3Op), _vp]),

@@ -20,6 +20,7 @@
 #include "gemm_common.h"
 
 #include <algorithm>
+#include <cassert>
 
 namespace {
 
@@ -474,8 +475,6 @@ __global__ __launch_bounds__(256 + 64 * WS) void gemm_nt_t128_kernel(const GemmP
     }
 #endif
 }
-template __global__ void gemm_nt_t128_kernel<bf16_t, 4, 4>(const GemmP);
-template __global__ void gemm_nt_t128_kernel<float, 4, 4>(const GemmP);
 
 // =====================================================================================================
 // Few-row NN product (M <= 8): out[M, N] = A[M, K] W[K, N] with W as it lies — the dX of a linear layer applied to a handful
@@ -943,12 +942,6 @@ __global__ __launch_bounds__(512) void gemm_nt_ring_kernel(const GemmP p) {
   tile_finish<TO, AI, TE>(p, acc, smem, tid, lane, wave, wm, wn, l32, lh, m0, n0, split_j, split_s, tail_i);
 #endif  // __HIP_DEVICE_COMPILE__
 }
-template __global__ void gemm_nt_ring_kernel<bf16_t, 4, bf16_t>(const GemmP);
-template __global__ void gemm_nt_ring_kernel<float, 4, bf16_t>(const GemmP);
-template __global__ void gemm_nt_ring_kernel<bf16_t, 3, bf16_t>(const GemmP);
-template __global__ void gemm_nt_ring_kernel<float, 3, bf16_t>(const GemmP);
-template __global__ void gemm_nt_ring_kernel<float, 4, float>(const GemmP);   // fp32 epilogue operands (bf16x3 products)
-template __global__ void gemm_nt_ring_kernel<float, 3, float>(const GemmP);
 
 // =====================================================================================================
 // Fast path 2: bf16 NT "ping-pong" kernel — 256x256 tile, K tile 64 (whole 128-byte lines), 8 waves as
@@ -1310,18 +1303,6 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
 #endif  // __HIP_DEVICE_COMPILE__
 }
 // NT: every forward linear, dX against an explicit W^T (fp32 head through bf16x3); NN: dX = dY W; TN: dW = dY^T X
-template __global__ void gemm_pp_kernel<bf16_t, bf16_t, true, false, false>(const GemmP);
-template __global__ void gemm_pp_kernel<float, bf16_t, true, false, false>(const GemmP);
-template __global__ void gemm_pp_kernel<float, float, true, false, false>(const GemmP);
-template __global__ void gemm_pp_kernel<bf16_t, bf16_t, false, false, false>(const GemmP);
-template __global__ void gemm_pp_kernel<float, bf16_t, false, false, false>(const GemmP);
-template __global__ void gemm_pp_kernel<float, float, false, false, false>(const GemmP);
-template __global__ void gemm_pp_kernel<bf16_t, bf16_t, true, false, true>(const GemmP);
-template __global__ void gemm_pp_kernel<bf16_t, bf16_t, false, false, true>(const GemmP);
-template __global__ void gemm_pp_kernel<float, bf16_t, true, false, true>(const GemmP);
-template __global__ void gemm_pp_kernel<float, bf16_t, true, true, true>(const GemmP);
-template __global__ void gemm_pp_kernel<bf16_t, bf16_t, true, true, true>(const GemmP);
-template __global__ void gemm_pp_kernel<bf16_t, bf16_t, true, false, false, 1>(const GemmP);     // gate / up + SiLU * up
 
 // =====================================================================================================
 // Fast path 2b (round 4): the ping-pong schedule on a 192-row tile — bf16 NT, K % 64 == 0, both operands K-contiguous.
@@ -1525,77 +1506,6 @@ __global__ __launch_bounds__(512) void gemm_pp3_kernel(const GemmP p) {
 #endif  // __HIP_DEVICE_COMPILE__
 }
 #undef P3_STAMP
-template __global__ void gemm_pp3_kernel<bf16_t, bf16_t, true>(const GemmP);
-template __global__ void gemm_pp3_kernel<float, bf16_t, true>(const GemmP);
-template __global__ void gemm_pp3_kernel<bf16_t, bf16_t, false>(const GemmP);
-template __global__ void gemm_pp3_kernel<float, bf16_t, false>(const GemmP);
-template __global__ void gemm_pp3_kernel<float, float, true>(const GemmP);      // fp32 epilogue operands (bf16x3 products of the fp32 head)
-template __global__ void gemm_pp3_kernel<float, float, false>(const GemmP);
-template __global__ void gemm_pp3_kernel<bf16_t, bf16_t, true, 1>(const GemmP);                  // gate / up + SiLU * up
-
-// x = hi + lo (two bf16): dst[r] = [hi | hi | lo] (side 0) or [hi | lo | hi] (side 1), 4 elements per thread
-__global__ __launch_bounds__(256) void split3_k(const float* __restrict__ src, int64_t ld, bf16_t* __restrict__ dst,
-                                                int64_t rows, int64_t cols, int side) {
-  const int64_t c4 = cols >> 2;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < rows * c4; i += (int64_t)gridDim.x * 256) {
-    const int64_t r = i / c4, c = (i - r * c4) * 4;
-    float x[4];
-    Vec<float, 4>::ld(x, src + r * ld + c);
-    float hi[4], lo[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      hi[e] = bf2f(f2bf(x[e]));
-      lo[e] = x[e] - hi[e];
-    }
-    bf16_t* d = dst + r * 3 * cols + c;
-    Vec<bf16_t, 4>::st(d, hi);
-    Vec<bf16_t, 4>::st(d + cols, side == 0 ? hi : lo);
-    Vec<bf16_t, 4>::st(d + 2 * cols, side == 0 ? lo : hi);
-  }
-}
-
-template <typename TI, typename TO, int TM>
-int launch(const GemmP& p, int layout, dim3 grid, hipStream_t st) {
-  constexpr size_t LDS = 4 * (32 * TM) * ROWB;
-  switch (layout) {
-    case DXA_NT: hipLaunchKernelGGL((gemm_kernel<TI, TO, false, false, TM>), grid, dim3(256), LDS, st, p); break;
-    case DXA_NN: hipLaunchKernelGGL((gemm_kernel<TI, TO, false, true, TM>), grid, dim3(256), LDS, st, p); break;
-    case DXA_TN: hipLaunchKernelGGL((gemm_kernel<TI, TO, true, true, TM>), grid, dim3(256), LDS, st, p); break;
-    default: return DXA_ERR_BAD_ARG;
-  }
-  return DXA_OK;
-}
-
-// Split-K scratch of the ring kernel: < 256 slots of 256 KiB + 256 counters per (device, stream), allocated on
-// first use (so the first dxa_gemm on a stream must not run under stream capture) and kept for the process.
-constexpr int NUM_CU = 256;
-static_assert(NUM_CU == NUM_CU_D, "split-K scratch sizing");
-constexpr size_t SPLIT_WS_BYTES = (size_t)NUM_CU * 256 * 256 * 4;
-struct SplitWs { float* ws; int* flags; };
-int get_split_ws(hipStream_t st, SplitWs* out) {
-  static StreamBlock blocks(SPLIT_WS_BYTES + NUM_CU * sizeof(int));
-  char* base = nullptr;
-  if (int rc = blocks.get(st, &base)) return rc;
-  DXA_CHECK_ARG(base != nullptr, "dxa_gemm: first split-K product on a stream allocates its scratch and cannot happen under stream "
-                "capture: run the request once eagerly on this stream first");
-  *out = SplitWs{(float*)base, (int*)(base + SPLIT_WS_BYTES)};
-  return DXA_OK;
-}
-
-// the ring / ping-pong kernels: 512 threads, max(4 x 32 KiB ring, 8 waves x 64 x 272 B epilogue slabs) of LDS
-constexpr int RING_LDS = 139264;
-template <auto kernel>
-int launch_ring(dim3 grid, hipStream_t st, const GemmP& p) {
-  return dxa_launch_lds<kernel>(RING_LDS, grid, dim3(512), RING_LDS, st, p);
-}
-
-inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-inline bool strides_mult(const int64_t s[3], int64_t m) { return s[0] % m == 0 && s[1] % m == 0 && s[2] % m == 0; }
-
-}  // namespace
-
-namespace {
-int gemm_dispatch(const dxa_gemm_desc* d, dxa_stream_t stream, bool* mirrored, bool* summed);
 
 // sum of squares of C [M, N] (fp32, leading dimension ldc) into `slots` per-"tile" partials for products whose kernel has no
 // sum-of-squares epilogue: workgroup b folds rows b, b + slots, ... in a fixed order, so every slot is written
@@ -1614,72 +1524,124 @@ __global__ __launch_bounds__(256) void sumsq_rows_k(const T* __restrict__ C, int
   __syncthreads();
   if (threadIdx.x == 0) out[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
-}
-extern "C" int64_t dxa_gemm_sumsq_slots(int64_t M, int64_t N) {
-  if (M <= 0 || N <= 0) return 0;
-  return ((M + 255) / 256) * ((N + 255) / 256);
-}
-extern "C" int dxa_gemm(const dxa_gemm_desc* d, dxa_stream_t stream) {
-  bool mirrored = false, summed = false;
-  if (int rc = gemm_dispatch(d, stream, &mirrored, &summed)) return rc;
-  if (d->mirror && !mirrored && d->M > 0 && d->N > 0) {   // kernels without the mirror epilogue: one narrow copy pass
-    if (int rc = dxa_copy2d(d->C, d->ldc, d->mirror, d->ldc, d->M, d->N, d->N, DXA_F32, DXA_BF16, stream)) return rc;
-  }
-  if (d->sumsq && !summed && d->M > 0 && d->N > 0) {      // ... and without the sum-of-squares epilogue: one read of C
-    const dim3 sgrid((unsigned)dxa_gemm_sumsq_slots(d->M, d->N));
-    if (d->out_dtype == DXA_F32)
-      hipLaunchKernelGGL(sumsq_rows_k<float>, sgrid, dim3(256), 0, (hipStream_t)stream, (const float*)d->C, d->ldc, d->M, d->N, d->sumsq);
-    else
-      hipLaunchKernelGGL(sumsq_rows_k<bf16_t>, sgrid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)d->C, d->ldc, d->M, d->N, d->sumsq);
-    DXA_CHECK_LAUNCH();
-  }
+
+// ---- Host side of dxa_gemm in three pieces: gemm_plan decides (pure arithmetic on the descriptor: it never dereferences a
+// pointer, allocates or touches HIP, so dxa_gemm_plan answers on a machine without a GPU), gemm_run_step does (GemmP from
+// the descriptor and a step, the split scratch, the launch through KERNELS), dxa_gemm = plan + steps + post-passes.
+
+// Split-K scratch of the ring kernel: < 256 slots of 256 KiB + 256 counters per (device, stream), allocated on
+// first use (so the first dxa_gemm on a stream must not run under stream capture) and kept for the process.
+constexpr int NUM_CU = 256;
+static_assert(NUM_CU == NUM_CU_D, "split-K scratch sizing");
+constexpr size_t SPLIT_WS_BYTES = (size_t)NUM_CU * 256 * 256 * 4;
+int get_split_ws(hipStream_t st, char** ws) {
+  static StreamBlock blocks(SPLIT_WS_BYTES + NUM_CU * sizeof(int));
+  char* base = nullptr;
+  if (int rc = blocks.get(st, &base)) return rc;
+  DXA_CHECK_ARG(base != nullptr, "dxa_gemm: first split-K product on a stream allocates its scratch and cannot happen under stream "
+                "capture: run the request once eagerly on this stream first");
+  *ws = base;
   return DXA_OK;
 }
-namespace {
-int gemm_dispatch(const dxa_gemm_desc* d, dxa_stream_t stream, bool* mirrored, bool* summed) {
-  DXA_CHECK_ARG(d != nullptr, "dxa_gemm: null desc");
-  DXA_CHECK_ARG(d->M >= 0 && d->N >= 0 && d->K >= 0, "dxa_gemm: negative dims");
-  DXA_CHECK_ARG(d->layout >= DXA_NT && d->layout <= DXA_TN, "dxa_gemm: bad layout %d", d->layout);
-  DXA_CHECK_ARG(d->in_dtype == DXA_F32 || d->in_dtype == DXA_BF16, "dxa_gemm: bad in_dtype %d", d->in_dtype);
-  DXA_CHECK_ARG(d->out_dtype == d->in_dtype || d->out_dtype == DXA_F32,
-                "dxa_gemm: out_dtype must equal in_dtype or be fp32");
-  DXA_CHECK_ARG(d->nb[0] >= 1 && d->nb[1] >= 1 && d->nb[2] >= 1, "dxa_gemm: batch extents must be >= 1");
-  if (d->M == 0 || d->N == 0) return DXA_OK;
-  DXA_CHECK_ARG(d->A && d->B && d->C, "dxa_gemm: null operand");
-  const int64_t nbatch = (int64_t)d->nb[0] * d->nb[1] * d->nb[2];
-  DXA_CHECK_ARG(nbatch <= 65535, "dxa_gemm: too many batches (%lld)", (long long)nbatch);
 
+// ---- the launcher table: one row per kernel instantiation the planner can select, grouped by family and indexed by what tells
+//      the family's members apart.  The name is what dxa_gemm_plan reports and what tests/golden/gemm_plan_parent.json.gz
+//      records; a family's rows and names come from one line each.
+enum GemmArgs { ARGS_P, ARGS_GEMV1, ARGS_GEMV2 };   // kernel parameters: (GemmP) | few-row NN stage 1 | stage 2
+struct GemmKernel {
+  const char* name;
+  const void* fn;
+  int block, lds;       // threads per workgroup, dynamic LDS bytes
+  int (*raise)(int);    // kernels above the default LDS ceiling raise theirs before the first launch (dxa_raise_lds), else null
+  GemmArgs args;
+};
+template <auto kernel>
+GemmKernel row(const char* name, int block, int lds = 0, GemmArgs args = ARGS_P) {
+  return {name, reinterpret_cast<const void*>(kernel), block, lds, lds > 65536 ? &dxa_raise_lds<kernel> : nullptr, args};
+}
+constexpr int GEN_LDS2 = 4 * (32 * 2) * ROWB, GEN_LDS4 = 4 * (32 * 4) * ROWB;   // generic kernel, 64 / 128-row tiles
+// four stages (a CU gets one workgroup: the tile count is <= NUM_CU), four dedicated loader waves
+constexpr int T128_LDS = 4 * 32768;
+// the ring / ping-pong kernels: 512 threads, max(4 x 32 KiB ring, 8 waves x 64 x 272 B epilogue slabs) of LDS
+constexpr int RING_LDS = 139264;
+// TY: <bf16, bf16> | <fp32, bf16> | <fp32, fp32> = <output, epilogue operands> of the 256-column-tile kernels
+#define KROW_TY3(X, ...) {X(bf16_t, bf16_t, "bf16,bf16", __VA_ARGS__), X(float, bf16_t, "f32,bf16", __VA_ARGS__), X(float, float, "f32,f32", __VA_ARGS__)}
+#define KROW_GENERIC(TI, TO, n, A_KS, B_KS, l) {row<gemm_kernel<TI, TO, A_KS, B_KS, 2>>("generic<" n "," l ",64>", 256, GEN_LDS2), \
+                                           row<gemm_kernel<TI, TO, A_KS, B_KS, 4>>("generic<" n "," l ",128>", 256, GEN_LDS4)}
+#define KROW_GENERIC3(TI, TO, n) {KROW_GENERIC(TI, TO, n, false, false, "nt"), KROW_GENERIC(TI, TO, n, false, true, "nn"), KROW_GENERIC(TI, TO, n, true, true, "tn")}
+#define KROW_GEMV1(M) row<gemv_nn_stage1_k<M>>("gemv_nn_stage1<" #M ">", 256, 0, ARGS_GEMV1)
+#define KROW_SKINNY_F32(MB) row<gemm_skinny_f32_kernel<MB>>("skinny_f32<" #MB ">", 512)
+#define KROW_SKINNY_BF16(MB, U) {row<gemm_skinny_bf16_kernel<MB, bf16_t, U>>("skinny_bf16<" #MB ",bf16>", 512), row<gemm_skinny_bf16_kernel<MB, float, U>>("skinny_bf16<" #MB ",f32>", 512)}
+#define KROW_RING(TO, TE, n, AI, rows) row<gemm_nt_ring_kernel<TO, AI, TE>>("ring<" n "," rows ">", 512, RING_LDS)
+#define KROW_PP(TO, TE, n, LEAN, A_KS, B_KS, FUSE, l) row<gemm_pp_kernel<TO, TE, LEAN, A_KS, B_KS, FUSE>>("pp<" n "," l ">", 512, RING_LDS)
+#define KROW_PP3(TO, TE, n, LEAN, FUSE, l) row<gemm_pp3_kernel<TO, TE, LEAN, FUSE>>("pp3<" n "," l ">", 512, RING_LDS)
+const struct GemmKernels {
+  GemmKernel generic[3][3][2];      // [<in, out>: <bf16, bf16> | <bf16, fp32> | <fp32, fp32>][layout][128-row tiles]: any layout, dtype, batching, alignment
+  GemmKernel t128[2];               // [fp32 out]: few-row NT products on 128x128 tiles
+  GemmKernel gemv1[4], gemv2[2];    // few-row NN: [log2(rows held)] the stream over W, then [fp32 out] the fold of its partials
+  GemmKernel skinny_f32[4];         // [16-row blocks - 1]: skinny (M <= 64) NT products
+  GemmKernel skinny_bf16[4][2];     // [16-row blocks - 1][fp32 out]
+  GemmKernel ring[2][3];            // [192-row tiles][TY]: ring kernel (NT, K % 64 == 32)
+  GemmKernel pp_nt[2][3];           // [full epilogue][TY]: ping-pong kernel, 256-row tiles
+  GemmKernel pp_nn[3];              // dX = dY W: bf16 out (lean, or with the activation-gradient epilogue), fp32 out lean
+  GemmKernel pp_tn[2];              // [fp32 out]: dW = dY^T X: fp32 (accumulating) or bf16 out, plain epilogue
+  GemmKernel pp_swiglu;             // gate / up + SiLU * up
+  GemmKernel pp3[2][3], pp3_swiglu; // [full epilogue][TY]: 192-row tiles on the ping-pong schedule (round 4): K % 64 == 0
+} KERNELS = {
+    {KROW_GENERIC3(bf16_t, bf16_t, "bf16,bf16"), KROW_GENERIC3(bf16_t, float, "bf16,f32"), KROW_GENERIC3(float, float, "f32,f32")},
+    {row<gemm_nt_t128_kernel<bf16_t, 4, 4>>("t128<bf16>", 512, T128_LDS), row<gemm_nt_t128_kernel<float, 4, 4>>("t128<f32>", 512, T128_LDS)},
+    {KROW_GEMV1(1), KROW_GEMV1(2), KROW_GEMV1(4), KROW_GEMV1(8)},
+    {row<gemv_nn_stage2_k<bf16_t>>("gemv_nn_stage2<bf16>", 256, 0, ARGS_GEMV2), row<gemv_nn_stage2_k<float>>("gemv_nn_stage2<f32>", 256, 0, ARGS_GEMV2)},
+    {KROW_SKINNY_F32(1), KROW_SKINNY_F32(2), KROW_SKINNY_F32(3), KROW_SKINNY_F32(4)},
+    // one row (the decode step): 4 blocks of 64 k in flight per wave, 2 for more rows
+    {KROW_SKINNY_BF16(1, 4), KROW_SKINNY_BF16(2, 2), KROW_SKINNY_BF16(3, 2), KROW_SKINNY_BF16(4, 2)},
+    {KROW_TY3(KROW_RING, 4, "256"), KROW_TY3(KROW_RING, 3, "192")},
+    {KROW_TY3(KROW_PP, true, false, false, 0, "lean,nt"), KROW_TY3(KROW_PP, false, false, false, 0, "full,nt")},
+    {KROW_PP(bf16_t, bf16_t, "bf16,bf16", true, false, true, 0, "lean,nn"), KROW_PP(bf16_t, bf16_t, "bf16,bf16", false, false, true, 0, "full,nn"),
+     KROW_PP(float, bf16_t, "f32,bf16", true, false, true, 0, "lean,nn")},
+    {KROW_PP(bf16_t, bf16_t, "bf16,bf16", true, true, true, 0, "lean,tn"), KROW_PP(float, bf16_t, "f32,bf16", true, true, true, 0, "lean,tn")},
+    KROW_PP(bf16_t, bf16_t, "bf16,bf16", true, false, false, 1, "swiglu,nt"),
+    {KROW_TY3(KROW_PP3, true, 0, "lean"), KROW_TY3(KROW_PP3, false, 0, "full")},
+    KROW_PP3(bf16_t, bf16_t, "bf16,bf16", true, 1, "swiglu"),
+};
+constexpr int NUM_KERNELS = sizeof(GemmKernels) / sizeof(GemmKernel);   // the rows are contiguous: every member is a GemmKernel
+
+struct GemmPlan {
+  dxa_gemm_plan_info info;         // what dxa_gemm_plan reports
+  const GemmKernel* kernel[2];     // the row of each step
+};
+// appends step `s` on kernel `k` over `grid` (x, y, z)
+void plan_add(GemmPlan* plan, dxa_gemm_step_info s, const GemmKernel& k, int64_t gx, int64_t gy = 1, int64_t gz = 1) {
+  assert(plan->info.nsteps < 2);
+  s.kernel = k.name;
+  s.grid[0] = (int32_t)gx; s.grid[1] = (int32_t)gy; s.grid[2] = (int32_t)gz;
+  s.block = k.block; s.lds = k.lds;
+  plan->kernel[plan->info.nsteps] = &k;
+  plan->info.step[plan->info.nsteps++] = s;
+}
+
+inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
+inline bool strides_mult(const int64_t s[3], int64_t m) { return s[0] % m == 0 && s[1] % m == 0 && s[2] % m == 0; }
+
+// K cut of the skinny (M <= 64) kernels, bf16 and fp32 alike.
+// bf16: few column tiles (<= 128) over a deep K: K cut across workgroups (>= 8 blocks of 64 k per range), as for the fp32 twin
+// fp32: few column tiles (<= 128) over a deep K: cut K so that ~256 workgroups share the exact-fp32 MFMAs (32 cycles apiece: 64
+// workgroups walking K 4096 are MFMA-bound, DiT-L fc2 33 -> 19 us cut in four); each of a range's 8 waves keeps >= 1 block of
+// 64 k.  192+ tiles measured slower cut (15.1 vs 12.1 us)
+int skinny_split(int64_t tiles, int64_t K) {
+  if (tiles > NUM_CU / 2) return 1;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8, (K / 64) / 8), dxa_cdiv(256, tiles)));
+}
+
+// One product as `d` states it: the route checks and the step (two for the few-row NN route) appended to the plan.  A second
+// (A2, B2) segment that the ping-pong kernel cannot contract sets *seg_fallback instead and appends nothing.
+int plan_product(const dxa_gemm_desc* d, int64_t nbatch, GemmPlan* plan, bool* seg_fallback) {
   const size_t es = d->in_dtype == DXA_BF16 ? 2 : 4, os = d->out_dtype == DXA_BF16 ? 2 : 4;
   const int64_t epc = 16 / es;
-  // ---- a contraction length that is not a multiple of 64 (SigLIP-So400m's 4304-wide MLP: fc2 forward, fc1 dX) would send a
-  //      large bf16 NT / NN product to the generic kernel (3x slower): K = K0 + K1 with K0 = K - K % 64 on the MFMA fast path
-  //      (bias / residual epilogue applied there) and the < 64-deep tail accumulated on top by the generic kernel.  With a bf16
-  //      C the partial result is rounded once more than a single pass would (one extra bf16 rounding of the output).
-  if (d->in_dtype == DXA_BF16 && nbatch == 1 && d->layout != DXA_TN && d->K % 64 != 0 && d->K >= 1024 &&
-      d->M >= 256 && d->N >= 256 && d->act == DXA_ACT_NONE && !d->aux_out && !d->mulgrad && !d->sumsq && !d->mirror && !d->epi_f32) {
-    const int64_t K0 = d->K - d->K % 64;
-    dxa_gemm_desc head = *d, tail = *d;
-    head.K = K0;
-    tail.K = d->K - K0;
-    tail.accumulate = 1; tail.bias = nullptr; tail.residual = nullptr;
-    tail.A = (const char*)d->A + K0 * (int64_t)es;
-    tail.B = (const char*)d->B + (d->layout == DXA_NT ? K0 : K0 * d->ldb) * (int64_t)es;
-    bool m2 = false, s2 = false;
-    if (int rc = gemm_dispatch(&head, stream, &m2, &s2)) return rc;
-    return gemm_dispatch(&tail, stream, &m2, &s2);
-  }
-  GemmP p;
-  memset(&p, 0, sizeof(p));
-  p.M = d->M; p.N = d->N; p.K = d->K;
-  p.A = (const char*)d->A; p.lda = d->lda;
-  p.B = (const char*)d->B; p.ldb = d->ldb;
-  p.C = (char*)d->C; p.ldc = d->ldc;
-  p.bias = (const char*)d->bias;
-  p.R = (const char*)d->residual; p.ldr = d->ldr;
-  p.aux = (char*)d->aux_out;
-  p.G = (const char*)d->mulgrad; p.ldg = d->ldg;
-  p.alpha = d->alpha; p.act = d->act; p.accumulate = d->accumulate;
-  p.fuse = d->fuse; p.ldaux = d->ld_aux;
+  dxa_gemm_step_info s;
+  memset(&s, 0, sizeof(s));
+  s.K = d->K;
+  s.accumulate = d->accumulate; s.bias = d->bias != nullptr; s.residual = d->residual != nullptr;
   if (d->fuse != DXA_FUSE_NONE) {
     DXA_CHECK_ARG(d->fuse == DXA_FUSE_SWIGLU, "dxa_gemm: unknown fuse mode %d", d->fuse);
     const int64_t F_ = d->N / 2;
@@ -1695,27 +1657,22 @@ int gemm_dispatch(const dxa_gemm_desc* d, dxa_stream_t stream, bool* mirrored, b
   }
   DXA_CHECK_ARG(!d->mirror || (d->out_dtype == DXA_F32 && nbatch == 1), "dxa_gemm: mirror needs an fp32, unbatched output");
   DXA_CHECK_ARG(!d->sumsq || nbatch == 1, "dxa_gemm: sumsq needs an unbatched output");
-  p.nb1 = d->nb[1]; p.nb2 = d->nb[2];
-  for (int i = 0; i < 3; ++i) {
-    p.sA[i] = d->sA[i]; p.sB[i] = d->sB[i]; p.sC[i] = d->sC[i]; p.sR[i] = d->sR[i]; p.sG[i] = d->sG[i];
-  }
-  p.tm = dxa_cdiv(d->M, BM);
-  p.tn = dxa_cdiv(d->N, BN);
+  s.tm = dxa_cdiv(d->M, BM);
+  s.tn = dxa_cdiv(d->N, BN);
   const bool a_ks = d->layout == DXA_TN, b_ks = d->layout != DXA_NT;
   // vector path: k-contiguous needs 16-B aligned rows; k-strided loads 4 consecutive rows (4*es bytes)
-  p.vecA = a_ks ? (aligned_to(d->A, 4 * es) && d->lda % 4 == 0 && strides_mult(d->sA, 4))
+  s.vecA = a_ks ? (aligned_to(d->A, 4 * es) && d->lda % 4 == 0 && strides_mult(d->sA, 4))
                 : (aligned_to(d->A, 16) && d->lda % epc == 0 && strides_mult(d->sA, epc));
-  p.vecB = b_ks ? (aligned_to(d->B, 4 * es) && d->ldb % 4 == 0 && strides_mult(d->sB, 4))
+  s.vecB = b_ks ? (aligned_to(d->B, 4 * es) && d->ldb % 4 == 0 && strides_mult(d->sB, 4))
                 : (aligned_to(d->B, 16) && d->ldb % epc == 0 && strides_mult(d->sB, epc));
-  p.vecC = aligned_to(d->C, 4 * os) && d->ldc % 4 == 0 && strides_mult(d->sC, 4) &&
+  s.vecC = aligned_to(d->C, 4 * os) && d->ldc % 4 == 0 && strides_mult(d->sC, 4) &&
            (!d->aux_out || aligned_to(d->aux_out, 4 * os));
   const size_t ees = d->epi_f32 ? 4 : es;   // element size of bias / residual / mulgrad
   DXA_CHECK_ARG(!d->epi_f32 || (d->in_dtype == DXA_BF16 && d->out_dtype == DXA_F32), "dxa_gemm: epi_f32 needs bf16 in, fp32 out");
-  p.vecR = d->residual && aligned_to(d->residual, 4 * ees) && d->ldr % 4 == 0 && strides_mult(d->sR, 4);
-  p.vecG = d->mulgrad && aligned_to(d->mulgrad, 4 * ees) && d->ldg % 4 == 0 && strides_mult(d->sG, 4);
-  p.vecBias = d->bias && aligned_to(d->bias, 4 * ees);
+  s.vecR = d->residual && aligned_to(d->residual, 4 * ees) && d->ldr % 4 == 0 && strides_mult(d->sR, 4);
+  s.vecG = d->mulgrad && aligned_to(d->mulgrad, 4 * ees) && d->ldg % 4 == 0 && strides_mult(d->sG, 4);
+  s.vecBias = d->bias && aligned_to(d->bias, 4 * ees);
 
-  hipStream_t st = (hipStream_t)stream;
   // ---- fast paths (bf16, no batching, 16-byte aligned rows, operands < 2 GiB): NT with K % 32 == 0 (ring) / K % 64 == 0
   //      (ping-pong); NN and TN (k-strided operands staged as they lie, ping-pong kernel only): NN needs K % 64 == 0 for its
   //      k-contiguous A, TN takes any K
@@ -1723,13 +1680,14 @@ int gemm_dispatch(const dxa_gemm_desc* d, dxa_stream_t stream, bool* mirrored, b
   const int64_t bytesB = (b_ks ? (d->K - 1) * d->ldb + d->N : (d->N - 1) * d->ldb + d->K) * 2;
   const bool ks_layout = d->layout != DXA_NT;
   const int64_t cpl = 16 / (int64_t)os;
+  const bool bf = d->out_dtype == DXA_BF16;
   // the lean epilogue: C = alpha * acc + bias (+ residual) (+ C) made of whole 16-byte accesses
   const bool lean_ok = d->N % cpl == 0 && d->ldc % cpl == 0 && aligned_to(d->C, 16) &&
                        ((d->M - 1) * d->ldc + d->N) * (int64_t)os < (1ll << 31) && !d->aux_out && !d->mulgrad &&
                        d->act == DXA_ACT_NONE && (!d->bias || aligned_to(d->bias, cpl * ees)) &&
                        (!d->residual || (aligned_to(d->residual, cpl * ees) && d->ldr % cpl == 0 &&
                                          ((d->M - 1) * d->ldr + d->N) * (int64_t)ees < (1ll << 31)));
-  const bool ks_ok = (d->layout == DXA_NN ? (d->out_dtype == DXA_BF16 || lean_ok) : lean_ok) && !d->epi_f32 && ks_layout && aligned_to(d->A, 16) && aligned_to(d->B, 16) && d->lda % 8 == 0 && d->ldb % 8 == 0 &&
+  const bool ks_ok = (d->layout == DXA_NN ? (bf || lean_ok) : lean_ok) && !d->epi_f32 && ks_layout && aligned_to(d->A, 16) && aligned_to(d->B, 16) && d->lda % 8 == 0 && d->ldb % 8 == 0 &&
                      (d->layout == DXA_TN || d->K % 64 == 0) && d->K >= 64;
   // ---- few-row NT products (batch-1 prefill, ViT on a couple of images): 128x128 tiles fill the chip where 256-row tiles
   //      cannot; any epilogue of the bf16 menu
@@ -1740,31 +1698,18 @@ int gemm_dispatch(const dxa_gemm_desc* d, dxa_stream_t stream, bool* mirrored, b
   const int64_t t128_tiles = (int64_t)dxa_cdiv(d->M, 128) * dxa_cdiv(d->N, 128);
   // (the split-bf16 fp32 products of the action head, epi_f32, measured the same on these tiles: they stay on the 256-row kernels)
   if (d->fuse == DXA_FUSE_NONE && d->layout == DXA_NT && d->in_dtype == DXA_BF16 && nbatch == 1 && !d->epi_f32 &&
-      d->M >= 64 && d->M <= 1024 && d->N >= 64 && d->K >= 64 && d->K % 64 == 0 && p.vecA && p.vecB &&
+      d->M >= 64 && d->M <= 1024 && d->N >= 64 && d->K >= 64 && d->K % 64 == 0 && s.vecA && s.vecB &&
       bytesA < (1ll << 31) && bytesB < (1ll << 31) && t128_tiles >= 32 && t128_tiles <= NUM_CU && d->K <= 4096) {
-    p.tm = dxa_cdiv(d->M, 128);
-    p.tn = dxa_cdiv(d->N, 128);
+    s.tm = dxa_cdiv(d->M, 128); s.tn = dxa_cdiv(d->N, 128);
     // few tiles over a deep K: cut K so that every CU gets a workgroup (>= 8 K tiles of 64 per slice, <= 4 slices)
     int t_split = 1;
     // (120 tiles x K 1024 measured slower cut in two: 21.2 vs 18.7 us; up to half the CUs over a deep K it pays: the decoder's
     //  qkv / o_proj at 287 rows are 108 / 84 tiles of K 3584, each CU's feed rate being the bound)
     if (t128_tiles <= NUM_CU / 4 || (t128_tiles <= NUM_CU / 2 && d->K >= 2048))
       t_split = (int)std::min<int64_t>(std::min<int64_t>(4, NUM_CU / t128_tiles), (d->K / 64) / 8);
-    if (t_split >= 2) {
-      SplitWs w;
-      if (int rc = get_split_ws(st, &w)) return rc;
-      p.split_s = t_split; p.ws = w.ws; p.flags = w.flags;
-    } else {
-      p.split_s = 1;
-    }
-    dim3 tgrid((unsigned)(p.tm * p.tn * p.split_s));
-    // four stages (a CU gets one workgroup: the tile count is <= NUM_CU), four dedicated loader waves
-    constexpr int T128_LDS = 4 * 32768;
-    const int rc = d->out_dtype == DXA_BF16
-                       ? dxa_launch_lds<gemm_nt_t128_kernel<bf16_t, 4, 4>>(T128_LDS, tgrid, dim3(512), T128_LDS, st, p)
-                       : dxa_launch_lds<gemm_nt_t128_kernel<float, 4, 4>>(T128_LDS, tgrid, dim3(512), T128_LDS, st, p);
-    if (rc) return rc;
-    DXA_CHECK_LAUNCH();
+    s.split_s = std::max(t_split, 1);
+    s.split_ws = t_split >= 2;
+    plan_add(plan, s, KERNELS.t128[!bf], (int64_t)s.tm * s.tn * s.split_s);
     return DXA_OK;
   }
   // ---- a second (A2, B2) segment (TN: dW over two micro-batches in one pass over C): the ping-pong kernel contracts both;
@@ -1775,28 +1720,19 @@ int gemm_dispatch(const dxa_gemm_desc* d, dxa_stream_t stream, bool* mirrored, b
     const bool seg_fast = d->in_dtype == DXA_BF16 && ks_ok && d->M >= 64 && d->N >= 64 &&
                           (int64_t)d->M * d->N >= 128 * 128 && bytesA < (1ll << 31) && bytesB < (1ll << 31) &&
                           bytesA2 < (1ll << 31) && bytesB2 < (1ll << 31) && aligned_to(d->A2, 16) && aligned_to(d->B2, 16);
-    if (!seg_fast) {
-      dxa_gemm_desc first = *d, second = *d;
-      first.A2 = first.B2 = nullptr; first.K2 = 0; first.mirror = nullptr; first.sumsq = nullptr;
-      second.A = d->A2; second.B = d->B2; second.K = d->K2; second.A2 = second.B2 = nullptr; second.K2 = 0;
-      second.accumulate = 1; second.bias = nullptr; second.residual = nullptr;
-      bool m1 = false, s1 = false;
-      if (int rc = gemm_dispatch(&first, stream, &m1, &s1)) return rc;
-      return gemm_dispatch(&second, stream, mirrored, summed);
-    }
-    p.A2 = (const char*)d->A2; p.B2 = (const char*)d->B2; p.K2 = d->K2;
+    if (!seg_fast) { *seg_fallback = true; return DXA_OK; }
+    s.K2 = d->K2;
   }
   if (d->in_dtype == DXA_BF16 && nbatch == 1 &&
-      ((d->layout == DXA_NT && d->K >= 32 && d->K % 32 == 0 && p.vecA && p.vecB) || ks_ok) &&
+      ((d->layout == DXA_NT && d->K >= 32 && d->K % 32 == 0 && s.vecA && s.vecB) || ks_ok) &&
       d->M >= 64 && d->N >= 64 && (int64_t)d->M * d->N >= 128 * 128 && bytesA < (1ll << 31) && bytesB < (1ll << 31)) {
     // 192-row tiles when they trim the padded row count by more than 8% (they run ~6% below the 256-row tile's rate)
     const int64_t pad256 = (int64_t)dxa_cdiv(d->M, 256) * 256, pad192 = (int64_t)dxa_cdiv(d->M, 192) * 192;
     const int ai = ks_layout ? 4 : (pad192 * 27 < pad256 * 25 ? 3 : 4);
-    p.tm = dxa_cdiv(d->M, ai * 64);
-    p.tn = dxa_cdiv(d->N, 256);
-    const int nt = p.tm * p.tn, nk_tot = (int)((d->K + d->K2 + 31) / 32);
-    p.full = nt; p.tail_r = 0; p.split_s = 1;
-    p.group_m = 4;
+    s.tm = dxa_cdiv(d->M, ai * 64);
+    s.tn = dxa_cdiv(d->N, 256);
+    const int nt = s.tm * s.tn, nk_tot = (int)((d->K + s.K2 + 31) / 32);
+    s.full = nt; s.tail_r = 0; s.split_s = 1; s.group_m = 4;
     const int tail = nt % NUM_CU;
     if (tail > 0) {
       // the last round would leave NUM_CU - tail CUs idle: cut its tiles along K into <= 8 pieces of >= 32 slabs, when K has
@@ -1805,58 +1741,23 @@ int gemm_dispatch(const dxa_gemm_desc* d, dxa_stream_t stream, bool* mirrored, b
       //  into up to 6 - 7 pieces of 512-deep K; at >= 32 slabs (1024-deep pieces, <= 3 of them at K = 3584) the step is 1.8 - 2.6 ms
       //  shorter, MemVLA's 2.8 ms, the 287-row request's gate/up 126 -> 119 us: a piece's fp32 partial costs its write-through and read-back
       //  whoever adds it up (profiles/r06_split_dist.txt).  24: -1.0 ms, 48: -1.3, 64: level, no split at all: +7.5 — profiles/r06_split_knobs.txt)
-      const int s = nk_tot >= 64 ? std::min(std::min(NUM_CU / tail, 8), nk_tot / 32) : 1;
-      if (s >= 2) {
-        SplitWs w;
-        if (int rc = get_split_ws(st, &w)) return rc;
-        p.full = nt - tail; p.tail_r = tail; p.split_s = s; p.ws = w.ws; p.flags = w.flags;
-      }
+      const int split = nk_tot >= 64 ? std::min(std::min(NUM_CU / tail, 8), nk_tot / 32) : 1;
+      if (split >= 2) { s.full = nt - tail; s.tail_r = tail; s.split_s = split; s.split_ws = 1; }
     }
-    dim3 fgrid((unsigned)(p.full + p.tail_r * p.split_s));
     // ---- ping-pong main loop: 256-row tiles, K % 64 == 0; the lean epilogue when it is made of whole 16-byte accesses
     const bool pp = ks_layout || (ai == 4 && d->K % 64 == 0);
     const bool lean = pp && lean_ok;
-    const bool bf = d->out_dtype == DXA_BF16;
-    if (lean) { p.mirror = (char*)d->mirror; *mirrored = d->mirror != nullptr; }
-    if (lean) { p.sumsq = d->sumsq; *summed = d->sumsq != nullptr; }
-    int rc;
-    if (d->layout == DXA_NN) {          // dX = dY W: bf16 out (lean, or with the activation-gradient epilogue), fp32 out lean
-      if (bf) rc = lean ? launch_ring<gemm_pp_kernel<bf16_t, bf16_t, true, false, true>>(fgrid, st, p)
-                        : launch_ring<gemm_pp_kernel<bf16_t, bf16_t, false, false, true>>(fgrid, st, p);
-      else rc = launch_ring<gemm_pp_kernel<float, bf16_t, true, false, true>>(fgrid, st, p);
-    } else if (d->layout == DXA_TN) {   // dW = dY^T X: fp32 (accumulating) or bf16 out, plain epilogue
-      rc = bf ? launch_ring<gemm_pp_kernel<bf16_t, bf16_t, true, true, true>>(fgrid, st, p)
-              : launch_ring<gemm_pp_kernel<float, bf16_t, true, true, true>>(fgrid, st, p);
-    } else if (d->fuse == DXA_FUSE_SWIGLU && ai == 4) {
-      rc = launch_ring<gemm_pp_kernel<bf16_t, bf16_t, true, false, false, 1>>(fgrid, st, p);
-    } else if (d->fuse == DXA_FUSE_SWIGLU) {                   // 192-row tiles
-      rc = launch_ring<gemm_pp3_kernel<bf16_t, bf16_t, true, 1>>(fgrid, st, p);
-    } else if (pp && lean) {
-      if (d->epi_f32) rc = launch_ring<gemm_pp_kernel<float, float, true, false, false>>(fgrid, st, p);
-      else if (bf) rc = launch_ring<gemm_pp_kernel<bf16_t, bf16_t, true, false, false>>(fgrid, st, p);
-      else rc = launch_ring<gemm_pp_kernel<float, bf16_t, true, false, false>>(fgrid, st, p);
-    } else if (pp) {
-      if (d->epi_f32) rc = launch_ring<gemm_pp_kernel<float, float, false, false, false>>(fgrid, st, p);
-      else if (bf) rc = launch_ring<gemm_pp_kernel<bf16_t, bf16_t, false, false, false>>(fgrid, st, p);
-      else rc = launch_ring<gemm_pp_kernel<float, bf16_t, false, false, false>>(fgrid, st, p);
-    }
-    // ---- 192-row tiles on the ping-pong schedule (round 4): K % 64 == 0
-    else if (ai == 3 && d->K % 64 == 0 && d->layout == DXA_NT) {
-      if (d->epi_f32) rc = lean_ok ? launch_ring<gemm_pp3_kernel<float, float, true>>(fgrid, st, p)
-                                   : launch_ring<gemm_pp3_kernel<float, float, false>>(fgrid, st, p);
-      else if (lean_ok) rc = bf ? launch_ring<gemm_pp3_kernel<bf16_t, bf16_t, true>>(fgrid, st, p)
-                                : launch_ring<gemm_pp3_kernel<float, bf16_t, true>>(fgrid, st, p);
-      else rc = bf ? launch_ring<gemm_pp3_kernel<bf16_t, bf16_t, false>>(fgrid, st, p)
-                   : launch_ring<gemm_pp3_kernel<float, bf16_t, false>>(fgrid, st, p);
-    }
-    else if (d->epi_f32) rc = ai == 3 ? launch_ring<gemm_nt_ring_kernel<float, 3, float>>(fgrid, st, p)
-                                      : launch_ring<gemm_nt_ring_kernel<float, 4, float>>(fgrid, st, p);
-    else if (ai == 3) rc = bf ? launch_ring<gemm_nt_ring_kernel<bf16_t, 3, bf16_t>>(fgrid, st, p)
-                              : launch_ring<gemm_nt_ring_kernel<float, 3, bf16_t>>(fgrid, st, p);
-    else rc = bf ? launch_ring<gemm_nt_ring_kernel<bf16_t, 4, bf16_t>>(fgrid, st, p)
-                 : launch_ring<gemm_nt_ring_kernel<float, 4, bf16_t>>(fgrid, st, p);
-    if (rc) return rc;
-    DXA_CHECK_LAUNCH();
+    s.mirror = lean && d->mirror;
+    s.sumsq = lean && d->sumsq;
+    const int ty = d->epi_f32 ? 2 : !bf;   // TY
+    const GemmKernel* k;
+    if (d->layout == DXA_NN) k = &KERNELS.pp_nn[bf ? !lean : 2];
+    else if (d->layout == DXA_TN) k = &KERNELS.pp_tn[!bf];
+    else if (d->fuse == DXA_FUSE_SWIGLU) k = ai == 4 ? &KERNELS.pp_swiglu : &KERNELS.pp3_swiglu;
+    else if (pp) k = &KERNELS.pp_nt[!lean][ty];
+    else if (ai == 3 && d->K % 64 == 0) k = &KERNELS.pp3[!lean_ok][ty];
+    else k = &KERNELS.ring[ai == 3][ty];
+    plan_add(plan, s, *k, s.full + s.tail_r * s.split_s);
     return DXA_OK;
   }
   DXA_CHECK_ARG(d->fuse == DXA_FUSE_NONE, "dxa_gemm: fuse is only implemented on the bf16 NT MFMA fast path (K %% 32 == 0, M, N >= 64, 16-byte aligned rows, no batching)");
@@ -1871,142 +1772,171 @@ int gemm_dispatch(const dxa_gemm_desc* d, dxa_stream_t stream, bool* mirrored, b
     if (ksplit < 1) ksplit = 1;
     int kper = dxa_cdiv(d->K, ksplit);
     if (kper > 512) { kper = 512; ksplit = dxa_cdiv(d->K, kper); }
-    if ((size_t)ksplit * d->M * d->N * sizeof(float) <= (size_t)NUM_CU * 256 * 256 * 4) {
-      SplitWs w;
-      if (int rc = get_split_ws(st, &w)) return rc;
-      dim3 g1((unsigned)nbn, (unsigned)ksplit);
-      const bf16_t* A_ = (const bf16_t*)d->A;
-      const bf16_t* W_ = (const bf16_t*)d->B;
-#define LAUNCH_GV(M_) hipLaunchKernelGGL((gemv_nn_stage1_k<M_>), g1, dim3(256), 0, st, A_, d->lda, W_, d->ldb, w.ws, (int)d->M, d->N, d->K, kper)
-      if (d->M <= 1) LAUNCH_GV(1); else if (d->M <= 2) LAUNCH_GV(2); else if (d->M <= 4) LAUNCH_GV(4); else LAUNCH_GV(8);
-#undef LAUNCH_GV
-      dim3 g2((unsigned)dxa_cdiv(d->M * d->N, 256));
-      if (d->out_dtype == DXA_BF16)
-        hipLaunchKernelGGL(gemv_nn_stage2_k<bf16_t>, g2, dim3(256), 0, st, w.ws, (bf16_t*)d->C, d->ldc, (int)d->M, d->N, ksplit, d->alpha);
-      else
-        hipLaunchKernelGGL(gemv_nn_stage2_k<float>, g2, dim3(256), 0, st, w.ws, (float*)d->C, d->ldc, (int)d->M, d->N, ksplit, d->alpha);
-      DXA_CHECK_LAUNCH();
+    if ((size_t)ksplit * d->M * d->N * sizeof(float) <= SPLIT_WS_BYTES) {
+      s.ksplit = ksplit; s.kper = kper; s.split_ws = 1;
+      plan_add(plan, s, KERNELS.gemv1[d->M <= 1 ? 0 : d->M <= 2 ? 1 : d->M <= 4 ? 2 : 3], nbn, ksplit);
+      plan_add(plan, s, KERNELS.gemv2[!bf], dxa_cdiv(d->M * d->N, 256));
       return DXA_OK;
     }
   }
-  // ---- skinny bf16 path: M <= 64 (KV-cached decode, few-row products): a stream over the weights
-  if (d->layout == DXA_NT && d->in_dtype == DXA_BF16 && nbatch == 1 && d->M <= 64 && d->K >= 64 &&
-      d->K % 64 == 0 && p.vecA && p.vecB) {
-    // few column tiles (<= 128) over a deep K: K cut across workgroups (>= 8 blocks of 64 k per range), as for the fp32 twin
-    const int64_t skb_tiles = dxa_cdiv(d->N, 16);
-    int skb_split = 1;
-    if (skb_tiles <= NUM_CU / 2)
-      skb_split = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8, (d->K / 64) / 8), dxa_cdiv(256, skb_tiles)));
-    p.split_s = 1;
-    if (skb_split >= 2) {
-      SplitWs w;
-      if (int rc = get_split_ws(st, &w)) return rc;
-      p.split_s = skb_split; p.ws = w.ws; p.flags = w.flags;
-    }
-    dim3 sgrid((unsigned)(skb_tiles * p.split_s));
-    const int mb = dxa_cdiv(d->M, 16);
-    // one row (the decode step): 4 blocks of 64 k in flight per wave, 2 for more rows
-#define LAUNCH_SK(MB_, U_)                                                                                          \
-  do {                                                                                                              \
-    if (d->out_dtype == DXA_BF16) hipLaunchKernelGGL((gemm_skinny_bf16_kernel<MB_, bf16_t, U_>), sgrid, dim3(512), 0, st, p); \
-    else hipLaunchKernelGGL((gemm_skinny_bf16_kernel<MB_, float, U_>), sgrid, dim3(512), 0, st, p);               \
-  } while (0)
-    if (mb == 1) LAUNCH_SK(1, 4); else if (mb == 2) LAUNCH_SK(2, 2); else if (mb == 3) LAUNCH_SK(3, 2); else LAUNCH_SK(4, 2);
-#undef LAUNCH_SK
-    DXA_CHECK_LAUNCH();
-    return DXA_OK;
-  }
-  // ---- skinny fp32 path: M <= 64 (DiT head at inference), weights streamed by N/16 workgroups of 8 K-splitting waves
-  if (d->layout == DXA_NT && d->in_dtype == DXA_F32 && d->out_dtype == DXA_F32 && nbatch == 1 &&
-      d->M <= 64 && d->K >= 64 && d->K % 64 == 0 && p.vecA && p.vecB) {
-    // few column tiles (<= 128) over a deep K: cut K so that ~256 workgroups share the exact-fp32 MFMAs (32 cycles apiece: 64
-    // workgroups walking K 4096 are MFMA-bound, DiT-L fc2 33 -> 19 us cut in four); each of a range's 8 waves keeps >= 1 block of
-    // 64 k.  192+ tiles measured slower cut (15.1 vs 12.1 us)
+  // ---- skinny paths: M <= 64, a stream over the weights.  bf16 in (KV-cached decode, few-row products); fp32 (DiT head at
+  //      inference), weights streamed by N/16 workgroups of 8 K-splitting waves
+  if (d->layout == DXA_NT && nbatch == 1 && d->M <= 64 && d->K >= 64 && d->K % 64 == 0 && s.vecA && s.vecB) {
     const int64_t sk_tiles = dxa_cdiv(d->N, 16);
-    int sk_split = 1;
-    if (sk_tiles <= NUM_CU / 2)
-      sk_split = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8, (d->K / 64) / 8), dxa_cdiv(256, sk_tiles)));
-    p.split_s = 1;
-    if (sk_split >= 2) {
-      SplitWs w;
-      if (int rc = get_split_ws(st, &w)) return rc;
-      p.split_s = sk_split; p.ws = w.ws; p.flags = w.flags;
-    }
-    dim3 sgrid((unsigned)(sk_tiles * p.split_s));
-    switch (dxa_cdiv(d->M, 16)) {
-      case 1: hipLaunchKernelGGL((gemm_skinny_f32_kernel<1>), sgrid, dim3(512), 0, st, p); break;
-      case 2: hipLaunchKernelGGL((gemm_skinny_f32_kernel<2>), sgrid, dim3(512), 0, st, p); break;
-      case 3: hipLaunchKernelGGL((gemm_skinny_f32_kernel<3>), sgrid, dim3(512), 0, st, p); break;
-      default: hipLaunchKernelGGL((gemm_skinny_f32_kernel<4>), sgrid, dim3(512), 0, st, p); break;
-    }
-    DXA_CHECK_LAUNCH();
+    const int mb = dxa_cdiv(d->M, 16);
+    s.split_s = skinny_split(sk_tiles, d->K);
+    s.split_ws = s.split_s >= 2;
+    plan_add(plan, s, d->in_dtype == DXA_BF16 ? KERNELS.skinny_bf16[mb - 1][!bf] : KERNELS.skinny_f32[mb - 1], sk_tiles * s.split_s);
     return DXA_OK;
   }
   // generic kernel: 128x128 tiles, or 64x64 when 128-tiles would occupy less than ~one wave of the 256 CUs
-  const bool small = (int64_t)p.tm * p.tn * nbatch < 192;
-  if (small) {
-    p.tm = dxa_cdiv(d->M, 64);
-    p.tn = dxa_cdiv(d->N, 64);
+  const bool small = (int64_t)s.tm * s.tn * nbatch < 192;
+  if (small) { s.tm = dxa_cdiv(d->M, 64); s.tn = dxa_cdiv(d->N, 64); }
+  plan_add(plan, s, KERNELS.generic[d->in_dtype == DXA_F32 ? 2 : !bf][d->layout][!small], (int64_t)s.tm * s.tn, 1, nbatch);
+  return DXA_OK;
+}
+
+// The argument checks of dxa_gemm and the plan of its launches: one step, or two where the product is cut in two.
+int gemm_plan(const dxa_gemm_desc* d, GemmPlan* plan) {
+  memset(plan, 0, sizeof(*plan));
+  DXA_CHECK_ARG(d != nullptr, "dxa_gemm: null desc");
+  DXA_CHECK_ARG(d->M >= 0 && d->N >= 0 && d->K >= 0, "dxa_gemm: negative dims");
+  DXA_CHECK_ARG(d->layout >= DXA_NT && d->layout <= DXA_TN, "dxa_gemm: bad layout %d", d->layout);
+  DXA_CHECK_ARG(d->in_dtype == DXA_F32 || d->in_dtype == DXA_BF16, "dxa_gemm: bad in_dtype %d", d->in_dtype);
+  DXA_CHECK_ARG(d->out_dtype == d->in_dtype || d->out_dtype == DXA_F32,
+                "dxa_gemm: out_dtype must equal in_dtype or be fp32");
+  DXA_CHECK_ARG(d->nb[0] >= 1 && d->nb[1] >= 1 && d->nb[2] >= 1, "dxa_gemm: batch extents must be >= 1");
+  if (d->M == 0 || d->N == 0) return DXA_OK;
+  DXA_CHECK_ARG(d->A && d->B && d->C, "dxa_gemm: null operand");
+  const int64_t nbatch = (int64_t)d->nb[0] * d->nb[1] * d->nb[2];
+  DXA_CHECK_ARG(nbatch <= 65535, "dxa_gemm: too many batches (%lld)", (long long)nbatch);
+
+  dxa_gemm_desc a = *d, b = *d;   // a product cut in two: b's operands lie at A + a_off, B + b_off (seg2: at A2, B2)
+  int64_t a_off = 0, b_off = 0;
+  bool two = false, seg2 = false;
+  const int64_t es = d->in_dtype == DXA_BF16 ? 2 : 4;
+  // ---- a contraction length that is not a multiple of 64 (SigLIP-So400m's 4304-wide MLP: fc2 forward, fc1 dX) would send a
+  //      large bf16 NT / NN product to the generic kernel (3x slower): K = K0 + K1 with K0 = K - K % 64 on the MFMA fast path
+  //      (bias / residual epilogue applied there) and the < 64-deep tail accumulated on top by the generic kernel.  With a bf16
+  //      C the partial result is rounded once more than a single pass would (one extra bf16 rounding of the output).
+  if (d->in_dtype == DXA_BF16 && nbatch == 1 && d->layout != DXA_TN && d->K % 64 != 0 && d->K >= 1024 &&
+      d->M >= 256 && d->N >= 256 && d->act == DXA_ACT_NONE && !d->aux_out && !d->mulgrad && !d->sumsq && !d->mirror && !d->epi_f32) {
+    a.K = d->K - d->K % 64; b.K = d->K - a.K;
+    b.accumulate = 1; b.bias = nullptr; b.residual = nullptr;
+    a_off = a.K * es;
+    b_off = (d->layout == DXA_NT ? a.K : a.K * d->ldb) * es;
+    b.A = (const char*)d->A + a_off; b.B = (const char*)d->B + b_off;
+    two = true;
   }
-  dim3 grid((unsigned)(p.tm * p.tn), 1, (unsigned)nbatch);
-  int rc;
-  if (d->in_dtype == DXA_BF16) {
-    if (small) rc = d->out_dtype == DXA_BF16 ? launch<bf16_t, bf16_t, 2>(p, d->layout, grid, st) : launch<bf16_t, float, 2>(p, d->layout, grid, st);
-    else rc = d->out_dtype == DXA_BF16 ? launch<bf16_t, bf16_t, 4>(p, d->layout, grid, st) : launch<bf16_t, float, 4>(p, d->layout, grid, st);
-  } else {
-    rc = small ? launch<float, float, 2>(p, d->layout, grid, st) : launch<float, float, 4>(p, d->layout, grid, st);
+  if (int rc = plan_product(&a, nbatch, plan, &seg2)) return rc;
+  if (seg2) {
+    assert(!two && d->layout == DXA_TN);   // the cuts cannot nest: a K tail is cut off NT / NN products, a second segment needs TN
+    a.A2 = a.B2 = nullptr; a.K2 = 0; a.mirror = nullptr; a.sumsq = nullptr;
+    b.A = d->A2; b.B = d->B2; b.K = d->K2; b.A2 = b.B2 = nullptr; b.K2 = 0;
+    b.accumulate = 1; b.bias = nullptr; b.residual = nullptr;
+    two = true;
+    if (int rc = plan_product(&a, nbatch, plan, &seg2)) return rc;
   }
-  if (rc != DXA_OK) return rc;
+  const int n0 = plan->info.nsteps;
+  if (two)
+    if (int rc = plan_product(&b, nbatch, plan, &seg2)) return rc;
+  for (int i = n0; i < plan->info.nsteps; ++i) {
+    dxa_gemm_step_info& s = plan->info.step[i];
+    s.seg2 = seg2; s.a_off = a_off; s.b_off = b_off;
+  }
+  const dxa_gemm_step_info& last = plan->info.step[plan->info.nsteps - 1];
+  plan->info.mirror_pass = d->mirror && !last.mirror;   // kernels without the mirror epilogue: one narrow copy pass
+  plan->info.sumsq_pass = d->sumsq && !last.sumsq;      // ... and without the sum-of-squares epilogue: one read of C
+  return DXA_OK;
+}
+
+// One step of a plan: GemmP from the descriptor and the step, the split scratch if the step takes it (*ws: fetched by the
+// first step of a product that does), the launch.
+int gemm_run_step(const dxa_gemm_desc* d, const dxa_gemm_step_info& s, const GemmKernel& k, hipStream_t st, char** ws) {
+  GemmP p;
+  memset(&p, 0, sizeof(p));
+  p.M = d->M; p.N = d->N; p.K = s.K;
+  p.A = (const char*)(s.seg2 ? d->A2 : d->A) + s.a_off; p.lda = d->lda;
+  p.B = (const char*)(s.seg2 ? d->B2 : d->B) + s.b_off; p.ldb = d->ldb;
+  p.C = (char*)d->C; p.ldc = d->ldc;
+  p.bias = s.bias ? (const char*)d->bias : nullptr;
+  p.R = s.residual ? (const char*)d->residual : nullptr; p.ldr = d->ldr;
+  p.aux = (char*)d->aux_out;
+  p.G = (const char*)d->mulgrad; p.ldg = d->ldg;
+  p.alpha = d->alpha; p.act = d->act; p.accumulate = s.accumulate;
+  p.fuse = d->fuse; p.ldaux = d->ld_aux;
+  p.nb1 = d->nb[1]; p.nb2 = d->nb[2];
+  for (int i = 0; i < 3; ++i) {
+    p.sA[i] = d->sA[i]; p.sB[i] = d->sB[i]; p.sC[i] = d->sC[i]; p.sR[i] = d->sR[i]; p.sG[i] = d->sG[i];
+  }
+  p.tm = s.tm; p.tn = s.tn;
+  p.vecA = s.vecA; p.vecB = s.vecB; p.vecC = s.vecC; p.vecR = s.vecR; p.vecG = s.vecG; p.vecBias = s.vecBias;
+  p.full = s.full; p.tail_r = s.tail_r; p.split_s = s.split_s; p.group_m = s.group_m;
+  if (s.mirror) p.mirror = (char*)d->mirror;
+  if (s.sumsq) p.sumsq = d->sumsq;
+  if (s.K2 > 0) { p.A2 = (const char*)d->A2; p.B2 = (const char*)d->B2; p.K2 = s.K2; }
+  if (s.split_ws) {
+    if (*ws == nullptr)
+      if (int rc = get_split_ws(st, ws)) return rc;
+    p.ws = (float*)*ws; p.flags = (int*)(*ws + SPLIT_WS_BYTES);
+  }
+  if (int rc = k.raise ? k.raise(k.lds) : DXA_OK) return rc;
+  // the parameters as each kernel declares them
+  int M = (int)d->M, ksplit = s.ksplit, kper = s.kper;
+  void* args_p[] = {&p};
+  void* args_gemv1[] = {&p.A, &p.lda, &p.B, &p.ldb, &p.ws, &M, &p.N, &p.K, &kper};
+  void* args_gemv2[] = {&p.ws, &p.C, &p.ldc, &M, &p.N, &ksplit, &p.alpha};
+  void** args = k.args == ARGS_P ? args_p : k.args == ARGS_GEMV1 ? args_gemv1 : args_gemv2;
+  (void)hipLaunchKernel(k.fn, dim3(s.grid[0], s.grid[1], s.grid[2]), dim3(k.block), args, k.lds, st);
   DXA_CHECK_LAUNCH();
   return DXA_OK;
 }
+
 }  // namespace
 
-namespace {
-// split3 of the TRANSPOSE in one pass: src [R, C] fp32 -> dst [C, 3 Rp] bf16, dst[c, j Rp + r] = part j of src[r, c] (r < R; the
-// padding columns R .. Rp - 1 are zero).  What transpose_k + split3_k did in two launches through an fp32 intermediate for the
-// dX = dY W and dW = dY^T X products of the fp32 heads (they run as NT products of the transposed operands).  32 x 32 tiles
-// through LDS (33-float rows: no bank conflicts), 256 threads = 32 x 8.
-__global__ __launch_bounds__(256) void split3_t_k(const float* __restrict__ src, int64_t ld, bf16_t* __restrict__ dst, int64_t R,
-                                                  int64_t C, int64_t Rp, int side) {
-  __shared__ float tile[32][33];
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const int64_t r0 = (int64_t)blockIdx.y * 32, c0 = (int64_t)blockIdx.x * 32;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int64_t r = r0 + ty + 8 * i, c = c0 + tx;
-    tile[ty + 8 * i][tx] = (r < R && c < C) ? src[r * ld + c] : 0.f;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int64_t c = c0 + ty + 8 * i, r = r0 + tx;
-    if (c < C && r < Rp) {
-      const float x = tile[tx][ty + 8 * i];
-      const bf16_t hb = f2bf(x);
-      const bf16_t lb = f2bf(x - bf2f(hb));
-      bf16_t* d = dst + c * 3 * Rp + r;
-      d[0] = hb;
-      d[Rp] = side == 0 ? hb : lb;
-      d[2 * Rp] = side == 0 ? lb : hb;
-    }
-  }
+extern "C" int64_t dxa_gemm_sumsq_slots(int64_t M, int64_t N) {
+  if (M <= 0 || N <= 0) return 0;
+  return ((M + 255) / 256) * ((N + 255) / 256);
 }
-}  // namespace
-extern "C" int dxa_split3_t(const float* src, int64_t ld, void* dst, int64_t R, int64_t C, int64_t Rp, int side,
-                            dxa_stream_t stream) {
-  DXA_CHECK_ARG(R >= 0 && C >= 0 && Rp >= R && ld >= C && (side == 0 || side == 1), "dxa_split3_t: bad arguments");
-  if (Rp == 0 || C == 0) return DXA_OK;
-  DXA_CHECK_ARG(src && dst, "dxa_split3_t: null buffer");
-  const dim3 grid((unsigned)((C + 31) / 32), (unsigned)((Rp + 31) / 32));
-  DXA_CHECK_ARG(grid.y <= 65535, "dxa_split3_t: too many rows");
-  hipLaunchKernelGGL(split3_t_k, grid, dim3(256), 0, (hipStream_t)stream, src, ld, (bf16_t*)dst, R, C, Rp, side);
-  DXA_CHECK_LAUNCH();
+extern "C" const char* dxa_gemm_kernel_name(int i) {
+  return i >= 0 && i < NUM_KERNELS ? reinterpret_cast<const GemmKernel*>(&KERNELS)[i].name : nullptr;
+}
+extern "C" int dxa_gemm_plan(const dxa_gemm_desc* d, dxa_gemm_plan_info* out) {
+  DXA_CHECK_ARG(out != nullptr, "dxa_gemm_plan: null output");
+  GemmPlan plan;
+  const int rc = gemm_plan(d, &plan);
+  *out = plan.info;
+  return rc;
+}
+extern "C" int dxa_gemm(const dxa_gemm_desc* d, dxa_stream_t stream) {
+  GemmPlan plan;
+  if (int rc = gemm_plan(d, &plan)) return rc;
+  char* ws = nullptr;
+  for (int i = 0; i < plan.info.nsteps; ++i) {
+    if (int rc = gemm_run_step(d, plan.info.step[i], *plan.kernel[i], (hipStream_t)stream, &ws)) return rc;
+  }
+  if (plan.info.mirror_pass) {
+    if (int rc = dxa_copy2d(d->C, d->ldc, d->mirror, d->ldc, d->M, d->N, d->N, DXA_F32, DXA_BF16, stream)) return rc;
+  }
+  if (plan.info.sumsq_pass) {
+    const dim3 sgrid((unsigned)dxa_gemm_sumsq_slots(d->M, d->N));
+    if (d->out_dtype == DXA_F32)
+      hipLaunchKernelGGL(sumsq_rows_k<float>, sgrid, dim3(256), 0, (hipStream_t)stream, (const float*)d->C, d->ldc, d->M, d->N, d->sumsq);
+    else
+      hipLaunchKernelGGL(sumsq_rows_k<bf16_t>, sgrid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)d->C, d->ldc, d->M, d->N, d->sumsq);
+    DXA_CHECK_LAUNCH();
+  }
   return DXA_OK;
 }
+
 namespace {
-// both operand splits of one bf16x3 product in one launch: blocks [0, a.nblocks) write operand a, the rest operand b, each with the
-// body of split3_k (grid-stride over its own blocks) or of split3_t_k (its 32 x 32 tiles flattened)
+// Both operand splits of one bf16x3 product in one launch: blocks [0, a.nblocks) write operand a, the rest operand b.
+// x = hi + lo (two bf16).  Plain operand: dst[r] = [hi | hi | lo] (side 0) or [hi | lo | hi] (side 1), 4 elements per thread,
+// grid-stride over the operand's own blocks.  Transposed operand: src [R, C] fp32 -> dst [C, 3 Rp] bf16, dst[c, j Rp + r] = part j
+// of src[r, c] (r < R; the padding columns R .. Rp - 1 are zero), what a transpose and a plain split did in two launches through
+// an fp32 intermediate for the dX = dY W and dW = dY^T X products of the fp32 heads (they run as NT products of the transposed
+// operands): 32 x 32 tiles through LDS (33-float rows: no bank conflicts), 256 threads = 32 x 8, the tiles flattened into the
+// operand's block range.
 struct S3Op { const float* src; int64_t ld; bf16_t* dst; int64_t rows, cols, pad; int side, transposed; unsigned nblocks, tiles_x; };
 __global__ __launch_bounds__(256) void split3_pair_k(const S3Op a, const S3Op b) {
   __shared__ float tile[32][33];
@@ -2059,7 +1989,7 @@ int s3_fill(const dxa_split3_op* u, S3Op* o) {
   DXA_CHECK_ARG(u && u->rows >= 0 && u->cols >= 0 && (u->side == 0 || u->side == 1) && u->ld >= u->cols, "dxa_split3_pair: bad operand");
   o->src = u->src; o->ld = u->ld; o->dst = (bf16_t*)u->dst; o->rows = u->rows; o->cols = u->cols; o->pad = u->pad; o->side = u->side;
   o->transposed = u->transposed != 0; o->nblocks = 0; o->tiles_x = 1;
-  if (u->rows == 0 || u->cols == 0) return DXA_OK;
+  if ((o->transposed ? std::max(u->rows, u->pad) : u->rows) == 0 || u->cols == 0) return DXA_OK;   // (a transposed operand without rows still has its zero padding)
   DXA_CHECK_ARG(u->src && u->dst, "dxa_split3_pair: null buffer");
   if (o->transposed) {
     DXA_CHECK_ARG(u->pad >= u->rows, "dxa_split3_pair: pad < rows");
@@ -2092,10 +2022,16 @@ extern "C" int dxa_split3(const float* src, int64_t ld, void* dst, int64_t rows,
   DXA_CHECK_ARG(cols % 4 == 0 && ld % 4 == 0 && (reinterpret_cast<uintptr_t>(src) % 16) == 0 &&
                     (reinterpret_cast<uintptr_t>(dst) % 8) == 0,
                 "dxa_split3: cols and ld must be multiples of 4 and the buffers 16-byte aligned");
-  hipLaunchKernelGGL(split3_k, dim3(dxa_grid1d(rows * (cols / 4), 256)), dim3(256), 0, (hipStream_t)stream, src, ld,
-                     (bf16_t*)dst, rows, cols, side);
-  DXA_CHECK_LAUNCH();
-  return DXA_OK;
+  const dxa_split3_op a = {src, ld, dst, rows, cols, 0, side, 0}, none = {};
+  return dxa_split3_pair(&a, &none, stream);
+}
+extern "C" int dxa_split3_t(const float* src, int64_t ld, void* dst, int64_t R, int64_t C, int64_t Rp, int side,
+                            dxa_stream_t stream) {
+  DXA_CHECK_ARG(R >= 0 && C >= 0 && Rp >= R && ld >= C && (side == 0 || side == 1), "dxa_split3_t: bad arguments");
+  if (Rp == 0 || C == 0) return DXA_OK;
+  DXA_CHECK_ARG(src && dst, "dxa_split3_t: null buffer");
+  const dxa_split3_op a = {src, ld, dst, R, C, Rp, side, 1}, none = {};
+  return dxa_split3_pair(&a, &none, stream);
 }
 
 #if defined(DXA_PP3_STAMPS)

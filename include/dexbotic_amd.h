@@ -115,19 +115,47 @@ typedef struct dxa_gemm_desc {
 } dxa_gemm_desc;
 int dxa_gemm(const dxa_gemm_desc* d, dxa_stream_t stream);
 int64_t dxa_gemm_sumsq_slots(int64_t M, int64_t N);
+/* What dxa_gemm would do with a descriptor, without doing it: its argument checks (same status, same dxa_last_error text) and
+ * the launches it would make.  Host arithmetic only: no pointer is dereferenced (operand pointers count by their alignment
+ * alone), nothing is allocated and no GPU is needed.  A product is one step; two where it is cut in two (a K tail after the
+ * MFMA-deep part, a second (A2, B2) segment the kernel cannot contract itself, the two stages of the few-row NN route);
+ * none when M or N is 0. */
+typedef struct dxa_gemm_step_info {
+  const char* kernel;        /* the kernel instantiation, e.g. "pp<bf16,bf16,lean,nn>" (static storage) */
+  int32_t grid[3], block, lds; /* workgroups, threads per workgroup, dynamic LDS bytes */
+  int64_t K, K2;             /* contraction lengths of this step (K2: the second segment, contracted by the same kernel) */
+  int64_t a_off, b_off;      /* byte offsets of this step's operands into A and B (seg2: into A2 and B2) */
+  int32_t seg2;
+  int32_t accumulate, bias, residual; /* the step adds to C / applies the bias / the residual */
+  int32_t tm, tn, full, tail_r, split_s, group_m; /* tile counts; whole tiles, tail tiles cut along K, pieces per cut tile */
+  int32_t vecA, vecB, vecC, vecR, vecG, vecBias;  /* 16-byte (vector) access per operand */
+  int32_t ksplit, kper;      /* few-row NN route: K slices, k per slice */
+  int32_t split_ws;          /* the step takes the per-stream split-K scratch */
+  int32_t mirror, sumsq;     /* the kernel's own epilogue writes dxa_gemm_desc.mirror / .sumsq */
+} dxa_gemm_step_info;
+typedef struct dxa_gemm_plan_info {
+  int32_t nsteps;
+  int32_t mirror_pass, sumsq_pass; /* dxa_gemm runs the separate mirror copy / sum-of-squares pass after the steps */
+  dxa_gemm_step_info step[2];
+} dxa_gemm_plan_info;
+int dxa_gemm_plan(const dxa_gemm_desc* d, dxa_gemm_plan_info* out);
+/* name of row i of the launcher table dxa_gemm_step_info.kernel points into, NULL past its end */
+const char* dxa_gemm_kernel_name(int i);
 
 /* fp32 product on the bf16 MFMA path ("bf16x3", the counterpart of the TF32 matmuls the reference's trainer enables
  * with tf32=True, dexbotic/exp/base_exp.py:254, for the fp32 action head under autocast(float32),
  * dexbotic/model/cogact/cogact_arch.py:133): x = hi + lo with hi = bf16(x), lo = bf16(x - hi) (16 mantissa bits), and
  *   A B^T ~= A_hi B_hi^T + A_hi B_lo^T + A_lo B_hi^T = [A_hi | A_hi | A_lo] [B_hi | B_lo | B_hi]^T,
  * i.e. ONE bf16 NT product with K' = 3K accumulated in fp32 inside the MFMA.  dxa_split3 writes that operand:
- * dst[r, 0:K | K:2K | 2K:3K] = (hi, hi, lo) for side 0 (A) and (hi, lo, hi) for side 1 (B); dst is bf16 [rows, 3*cols]. */
+ * dst[r, 0:K | K:2K | 2K:3K] = (hi, hi, lo) for side 0 (A) and (hi, lo, hi) for side 1 (B); dst is bf16 [rows, 3*cols].
+ * (dxa_split3_pair with this one operand; cols and ld multiples of 4, ld >= cols, src 16-byte and dst 8-byte aligned.) */
 int dxa_split3(const float* src, int64_t ld, void* dst, int64_t rows, int64_t cols, int side, dxa_stream_t stream);
 /* the same operand of the TRANSPOSE in one pass: src [R, C] fp32 -> dst [C, 3 Rp] bf16 (columns R..Rp-1 of every part zero):
  * the dX = dY W and dW = dY^T X products of the fp32 heads run as NT products of transposed operands (the backward of the
- * reference's autocast(float32) head, cogact_arch.py:133 / dit.py) */
+ * reference's autocast(float32) head, cogact_arch.py:133 / dit.py).  dxa_split3_pair with this one transposed operand (its size
+ * limit: fewer than 2^30 tiles of 32 x 32). */
 int dxa_split3_t(const float* src, int64_t ld, void* dst, int64_t R, int64_t C, int64_t Rp, int side, dxa_stream_t stream);
-/* BOTH operands of one such product in ONE launch (each as dxa_split3 or dxa_split3_t would write it): a product of the fp32 heads is
+/* BOTH operands of one such product in ONE launch (dxa_split3 and dxa_split3_t are this call with an empty second operand): a product of the fp32 heads is
  * two operand splits + the MFMA launch, and at 1088 rows a split is a few microseconds of work behind a launch's fixed cost — 1,014 of
  * MemVLA's and 288 of DB-CogACT's launches per step were operand splits.  transposed == 0: rows x cols of src -> dst [rows, 3 cols]
  * (pad unused); transposed != 0: src [rows, cols] -> dst [cols, 3 pad], pad >= rows (dxa_split3_t's R, C, Rp). */

@@ -216,6 +216,19 @@ def test_gemm_ring_192_row_tiles(shape, f32out):
             assert_close(out, ref + bias.double() + res.double(), 2 * rtol, 2 * atol, f"192-row bf16 rep {rep}")
 
 
+def split3_ref(x, side, transposed=False, pad_to=1, dims=None):
+    """the bf16x3 operand in torch: x = hi + lo with hi = bf16(x), lo = bf16(x - hi), laid out [hi | hi | lo] (side 0) or
+    [hi | lo | hi] (side 1); ``transposed``: of x^T, its columns zero-padded to a multiple of ``pad_to``; ``dims`` = (rows, cols)"""
+    if dims is not None:
+        x = x[:dims[0], :dims[1]]
+    hi = x.to(torch.bfloat16)
+    lo = (x - hi.float()).to(torch.bfloat16)
+    if transposed:
+        pad = -x.shape[0] % pad_to
+        hi, lo = F.pad(hi.t(), (0, pad)), F.pad(lo.t(), (0, pad))
+    return torch.cat([hi, hi, lo] if side == 0 else [hi, lo, hi], dim=1)
+
+
 @pytest.mark.parametrize("shape", [(576, 2304, 768), (1088, 3072, 1024), (130, 140, 64), (2176, 1024, 4096)])
 def test_gemm_f32_bf16x3(shape):
     """fp32 NT product as ONE bf16 ring-kernel product over [hi|hi|lo] x [hi|lo|hi] (dxa_split3 + epi_f32): 16 mantissa
@@ -241,7 +254,9 @@ def test_gemm_f32_bf16x3(shape):
     assert float((exact.double() - ref).abs().max()) < 2e-5 * scale
     assert torch.equal(small, K.mm_nt(a[:64], w))
     # the split itself: hi + lo reproduces x to 2^-17 relative
-    s3 = K.split3(a, M, Kd, Kd, 0).float()
+    s3 = K.split3(a, M, Kd, Kd, 0)
+    assert torch.equal(s3, split3_ref(a, 0))
+    s3 = s3.float()
     assert torch.equal(s3[:, :Kd], s3[:, Kd:2 * Kd])
     assert float(((s3[:, :Kd] + s3[:, 2 * Kd:]) - a).abs().max()) <= float(a.abs().max()) * 2.0 ** -16
 
@@ -1395,23 +1410,29 @@ def test_attention_small_f32_backward_one_launch(Sq, Sk, monkeypatch):
 
 def test_split3_pair_writes_what_the_single_launches_write():
     """dxa_split3_pair: both operand splits of a bf16x3 product in one launch — plain / transposed in every combination, ragged
-    extents, a padded transposed operand, an explicit leading dimension — bit for bit what dxa_split3 / dxa_split3_t write"""
+    extents, a padded transposed operand, an explicit leading dimension — and dxa_split3 / dxa_split3_t (the same launch with one
+    operand): bit for bit the split built in torch"""
     a = rnd(1088, 768, dtype=torch.float32, seed=70)
     w = rnd(2304, 768, dtype=torch.float32, seed=71)
     dy = rnd(1088, 2304, dtype=torch.float32, seed=72)
     wide = rnd(300, 520, dtype=torch.float32, seed=73)
+    a_ref, w_ref = split3_ref(a, 0), split3_ref(w, 1)
     a3, w3 = K.split3_pair(a, False, w, False)
-    assert torch.equal(a3, K.split3(a, 1088, 768, 768, 0)) and torch.equal(w3, K.split3(w, 2304, 768, 768, 1))
+    assert torch.equal(a3, a_ref) and torch.equal(w3, w_ref)
+    assert torch.equal(K.split3(a, 1088, 768, 768, 0), a_ref) and torch.equal(K.split3(w, 2304, 768, 768, 1), w_ref)
     d3, wt3 = K.split3_pair(dy, False, w, True)                                    # dX = dY W as an NT product against W^T
-    assert torch.equal(d3, K.split3(dy, 1088, 2304, 2304, 0)) and torch.equal(wt3, K.split3_t(w, 1, 1))
+    assert torch.equal(d3, split3_ref(dy, 0)) and torch.equal(wt3, split3_ref(w, 1, transposed=True))
+    assert torch.equal(K.split3(dy, 1088, 2304, 2304, 0), split3_ref(dy, 0)) and torch.equal(K.split3_t(w, 1, 1), split3_ref(w, 1, transposed=True))
     dt3, at3 = K.split3_pair(dy, True, a, True, pad_to=32)                        # dW = dY^T X
-    assert torch.equal(dt3, K.split3_t(dy, 32, 0)) and torch.equal(at3, K.split3_t(a, 32, 1))
+    assert torch.equal(dt3, split3_ref(dy, 0, transposed=True, pad_to=32)) and torch.equal(at3, split3_ref(a, 1, transposed=True, pad_to=32))
+    assert torch.equal(K.split3_t(dy, 32, 0), dt3) and torch.equal(K.split3_t(a, 32, 1), at3)
     assert dt3.shape == (2304, 3 * 1088)
     r3, s3 = K.split3_pair(wide, True, wide, False, pad_to=32, b_dims=(200, 256, 520))
-    assert r3.shape == (520, 3 * 320) and torch.equal(r3, K.split3_t(wide, 32, 0))
-    assert torch.equal(s3, K.split3(wide, 200, 256, 520, 1))
+    assert r3.shape == (520, 3 * 320) and torch.equal(r3, split3_ref(wide, 0, transposed=True, pad_to=32))
+    assert torch.equal(K.split3_t(wide, 32, 0), r3)
+    assert torch.equal(s3, split3_ref(wide, 1, dims=(200, 256))) and torch.equal(K.split3(wide, 200, 256, 520, 1), s3)
     e3, f3 = K.split3_pair(a[:0], False, w, False)                                 # an empty operand is skipped, the other one written
-    assert e3.numel() == 0 and torch.equal(f3, w3)
+    assert e3.numel() == 0 and torch.equal(f3, w_ref)
 
 
 @pytest.mark.parametrize("Sq,Sk,D", [(68, 256, 32), (40, 100, 48), (96, 129, 64)])
