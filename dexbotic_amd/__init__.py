@@ -31,11 +31,13 @@ def model_registry():
     from .model.cogact.cogact_arch import CogActConfig, CogACTForCausalLM
     from .model.dexbotic_arch import DexboticConfig, DexboticForCausalLM
     from .model.memvla.memvla_arch import MemVLAConfig, MemVLAForCausalLM
+    from .model.navila.navila_arch import NaVILAConfig, NaVILAForCausalLM
     from .model.pi0.pi0_arch import Pi0Config, Pi0ForCausalLM
     return {"dexbotic": (DexboticConfig, DexboticForCausalLM),
             "dexbotic_cogact": (CogActConfig, CogACTForCausalLM),
             "dexbotic_pi0": (Pi0Config, Pi0ForCausalLM),
-            "dexbotic_memvla": (MemVLAConfig, MemVLAForCausalLM)}
+            "dexbotic_memvla": (MemVLAConfig, MemVLAForCausalLM),
+            "dexbotic_navila": (NaVILAConfig, NaVILAForCausalLM)}
 
 
 def hybrid_cogact():

@@ -974,3 +974,264 @@ extern "C" int dxa_colsum(const void* x, int64_t ld, float* out, int64_t rows, i
   DXA_CHECK_LAUNCH();
   return DXA_OK;
 }
+
+// ------------------------------------------------------------------------ 2x2 token merge + LayerNorm
+// The `mlp_downsample` projector's DownSampleBlock + nn.LayerNorm(4C) (see include/dexbotic_amd.h): one wavefront owns one
+// OUTPUT row, whose four quarters are contiguous runs of C elements of the un-merged input (or zeros, where an odd grid was
+// padded).  Structure and statistics of layernorm_fwd_k / layernorm_bwd_k; the merged tensor never exists in memory.
+namespace {
+
+template <typename TW, int VEC>
+__device__ __forceinline__ void ld_w(float (&o)[VEC], const TW* p) {
+  if constexpr (VEC == 8 && sizeof(TW) == 4) {
+    float a[4], b[4];
+    Vec<float, 4>::ld(a, reinterpret_cast<const float*>(p));
+    Vec<float, 4>::ld(b, reinterpret_cast<const float*>(p) + 4);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { o[i] = a[i]; o[4 + i] = b[i]; }
+  } else {
+    Vec<TW, VEC>::ld(o, p);
+  }
+}
+
+// offset (elements) of quarter q of output row `row` in the un-merged input, or -1 where the quarter is padding
+__device__ __forceinline__ int64_t ds_quarter(int64_t row, int q, int G, int h, int C) {
+  const int64_t n = row / ((int64_t)h * h);
+  const int o = (int)(row - n * h * h);
+  const int j = o / h, i = o - j * h;                    // o = j * h + i: column pair major
+  const int r = 2 * i + (q >> 1), c = 2 * j + (q & 1);
+  return (r < G && c < G) ? ((n * G + r) * G + c) * (int64_t)C : -1;
+}
+
+template <typename T, typename TW, int VEC>
+__global__ __launch_bounds__(256) void ds_layernorm_fwd_k(const T* __restrict__ x, const TW* __restrict__ w,
+                                                          const TW* __restrict__ b, T* __restrict__ y,
+                                                          float* __restrict__ mean_out, float* __restrict__ rstd_out,
+                                                          int64_t rows, int G, int h, int C, float eps) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int64_t cols = 4 * (int64_t)C;
+  int64_t off[4];
+  int npad = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) { off[q] = ds_quarter(row, q, G, h, C); npad += off[q] < 0; }
+  float s = 0.f;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    if (off[q] < 0) continue;
+    const T* xq = x + off[q];
+    for (int k = lane * VEC; k < C; k += 64 * VEC) {
+      float v[VEC];
+      Vec<T, VEC>::ld(v, xq + k);
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) s += v[i];
+    }
+  }
+  const float mean = wave_sum(s) / (float)cols;
+  float ss = 0.f;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    if (off[q] < 0) continue;
+    const T* xq = x + off[q];
+    for (int k = lane * VEC; k < C; k += 64 * VEC) {
+      float v[VEC];
+      Vec<T, VEC>::ld(v, xq + k);
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) { const float d = v[i] - mean; ss += d * d; }
+    }
+  }
+  // the padded quarters are zeros: C elements at distance `mean` each
+  const float rstd = rsqrtf((wave_sum(ss) + (float)npad * (float)C * mean * mean) / (float)cols + eps);
+  if (lane == 0) {
+    if (mean_out) mean_out[row] = mean;
+    if (rstd_out) rstd_out[row] = rstd;
+  }
+  T* yr = y + row * cols;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const T* xq = off[q] < 0 ? nullptr : x + off[q];
+    for (int k = lane * VEC; k < C; k += 64 * VEC) {
+      float v[VEC], g[VEC], bb[VEC];
+      if (xq) {
+        Vec<T, VEC>::ld(v, xq + k);
+      } else {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) v[i] = 0.f;
+      }
+      if (w) ld_w<TW, VEC>(g, w + q * C + k);
+      if (b) ld_w<TW, VEC>(bb, b + q * C + k);
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) v[i] = (v[i] - mean) * rstd * (w ? g[i] : 1.f) + (b ? bb[i] : 0.f);
+      Vec<T, VEC>::st(yr + q * C + k, v);
+    }
+  }
+}
+
+// partial: [gridDim.x][2*cols] = (dw | db), cols = 4C.  A wave computes the row statistics and dx of its output row; then the
+// 256 threads of the workgroup, each owning fixed columns, add the (up to) four rows of the pass to the workgroup's partial sums
+// in row order: deterministic, no atomics, no wave waits for another.  The sums live in LDS (`use_lds`: 2*cols floats of dynamic
+// LDS) and are written out once at the end, or directly in the workgroup's slab of `partial` for rows too wide for LDS.
+template <typename T, typename TW, int VEC>
+__global__ __launch_bounds__(256) void ds_layernorm_bwd_k(const T* __restrict__ dy, const T* __restrict__ x,
+                                                          const TW* __restrict__ w, const float* __restrict__ mean,
+                                                          const float* __restrict__ rstd, T* __restrict__ dx,
+                                                          float* __restrict__ partial, int64_t rows, int G, int h, int C,
+                                                          int use_lds) {
+  extern __shared__ float ds_sums[];
+  __shared__ float st_mu[4], st_rs[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t cols = 4 * (int64_t)C;
+  float* slab = partial ? partial + (int64_t)blockIdx.x * 2 * cols : nullptr;
+  float* acc = slab ? (use_lds ? ds_sums : slab) : nullptr;
+  if (acc) {
+    for (int64_t c = threadIdx.x; c < 2 * cols; c += 256) acc[c] = 0.f;
+    __syncthreads();
+  }
+  for (int64_t base = (int64_t)blockIdx.x * 4; base < rows; base += (int64_t)gridDim.x * 4) {
+    const int64_t row = base + wave;
+    float rs = 0.f, mu = 0.f;
+    if (row < rows) {
+      rs = rstd[row];
+      mu = mean[row];
+      int64_t off[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) off[q] = ds_quarter(row, q, G, h, C);
+      const T* gr = dy + row * cols;
+      float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const T* xq = off[q] < 0 ? nullptr : x + off[q];
+        for (int k = lane * VEC; k < C; k += 64 * VEC) {
+          float xv[VEC], gv[VEC], wv[VEC];
+          if (xq) {
+            Vec<T, VEC>::ld(xv, xq + k);
+          } else {
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) xv[i] = 0.f;
+          }
+          Vec<T, VEC>::ld(gv, gr + q * C + k);
+          if (w) ld_w<TW, VEC>(wv, w + q * C + k);
+#pragma unroll
+          for (int i = 0; i < VEC; ++i) {
+            const float g = gv[i] * (w ? wv[i] : 1.f);
+            s1 += g;
+            s2 += g * ((xv[i] - mu) * rs);
+          }
+        }
+      }
+      const float c1 = wave_sum(s1) / (float)cols, c2 = wave_sum(s2) / (float)cols;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (off[q] < 0) continue;                          // padding has no input element to receive a gradient
+        const T* xq = x + off[q];
+        T* dxq = dx + off[q];
+        for (int k = lane * VEC; k < C; k += 64 * VEC) {
+          float xv[VEC], gv[VEC], wv[VEC], o[VEC];
+          Vec<T, VEC>::ld(xv, xq + k);
+          Vec<T, VEC>::ld(gv, gr + q * C + k);
+          if (w) ld_w<TW, VEC>(wv, w + q * C + k);
+#pragma unroll
+          for (int i = 0; i < VEC; ++i) {
+            const float g = gv[i] * (w ? wv[i] : 1.f);
+            o[i] = rs * (g - c1 - (xv[i] - mu) * rs * c2);
+          }
+          Vec<T, VEC>::st(dxq + k, o);
+        }
+      }
+    }
+    if (acc) {
+      if (lane == 0) { st_mu[wave] = mu; st_rs[wave] = rs; }
+      __syncthreads();
+      const int nslot = (int)min((int64_t)4, rows - base);
+      for (int64_t c = (int64_t)threadIdx.x * VEC; c < cols; c += 256 * VEC) {
+        const int q = (int)(c / C), k = (int)(c - (int64_t)q * C);      // C % VEC == 0: a chunk never straddles two quarters
+        float aw[VEC], ab[VEC];
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) { aw[i] = acc[c + i]; ab[i] = acc[cols + c + i]; }
+        for (int sl = 0; sl < nslot; ++sl) {
+          const int64_t r2 = base + sl;
+          const int64_t o2 = ds_quarter(r2, q, G, h, C);
+          const float mu2 = st_mu[sl], rs2 = st_rs[sl];
+          float xv[VEC], gv[VEC];
+          if (o2 >= 0) {
+            Vec<T, VEC>::ld(xv, x + o2 + k);
+          } else {
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) xv[i] = 0.f;
+          }
+          Vec<T, VEC>::ld(gv, dy + r2 * cols + c);
+#pragma unroll
+          for (int i = 0; i < VEC; ++i) {
+            aw[i] += gv[i] * ((xv[i] - mu2) * rs2);
+            ab[i] += gv[i];
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) { acc[c + i] = aw[i]; acc[cols + c + i] = ab[i]; }
+      }
+      __syncthreads();
+    }
+  }
+  if (acc && use_lds)
+    for (int64_t c = threadIdx.x; c < 2 * cols; c += 256) slab[c] = ds_sums[c];
+}
+
+constexpr size_t DS_LN_MAX_LDS = 60 * 1024;      // partial sums of rows up to 7680 columns stay in LDS (default 64 KB ceiling)
+
+int check_downsample_args(const char* who, int64_t N, int64_t G, int64_t C) {
+  DXA_CHECK_ARG(N >= 0 && G > 0 && C > 0 && G <= 4096 && C <= (1 << 20) && N <= (1ll << 31),
+                "%s: bad sizes N=%lld G=%lld C=%lld", who, (long long)N, (long long)G, (long long)C);
+  return DXA_OK;
+}
+
+}  // namespace
+
+extern "C" int dxa_downsample_layernorm_fwd(const void* x, const void* w, const void* b, void* y, float* mean, float* rstd,
+                                            int64_t N, int64_t G, int64_t C, float eps, int dtype, int w_dtype,
+                                            dxa_stream_t stream) {
+  if (int rc = check_norm_dtypes(dtype, w_dtype, "dxa_downsample_layernorm_fwd")) return rc;
+  DXA_CHECK_ARG(x && y, "dxa_downsample_layernorm_fwd: null x / y");
+  if (int rc = check_downsample_args("dxa_downsample_layernorm_fwd", N, G, C)) return rc;
+  const int h = (int)((G + 1) / 2);
+  const int64_t rows = N * h * h;
+  if (rows == 0) return DXA_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int vec = dtype == DXA_BF16 ? 8 : 4;              // 16 bytes per access
+  const bool vec_ok = al16(x) && al16(y) && (!w || al16(w)) && (!b || al16(b)) && C % vec == 0;
+  dim3 grid((unsigned)((rows + 3) / 4));
+#define DS_FWD(T_, TW_, V_) hipLaunchKernelGGL((ds_layernorm_fwd_k<T_, TW_, V_>), grid, dim3(256), 0, st, (const T_*)x, (const TW_*)w, (const TW_*)b, (T_*)y, mean, rstd, rows, (int)G, h, (int)C, eps)
+  if (dtype == DXA_BF16 && w_dtype == DXA_BF16) { if (vec_ok) DS_FWD(bf16_t, bf16_t, 8); else DS_FWD(bf16_t, bf16_t, 1); }
+  else if (dtype == DXA_BF16) { if (vec_ok) DS_FWD(bf16_t, float, 8); else DS_FWD(bf16_t, float, 1); }
+  else { if (vec_ok) DS_FWD(float, float, 4); else DS_FWD(float, float, 1); }
+#undef DS_FWD
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
+}
+
+extern "C" int dxa_downsample_layernorm_bwd(const void* dy, const void* x, const void* w, const float* mean,
+                                            const float* rstd, void* dx, float* partial_dwdb, int64_t N, int64_t G,
+                                            int64_t C, int dtype, int w_dtype, dxa_stream_t stream) {
+  if (int rc = check_norm_dtypes(dtype, w_dtype, "dxa_downsample_layernorm_bwd")) return rc;
+  DXA_CHECK_ARG(dy && x && mean && rstd && dx, "dxa_downsample_layernorm_bwd: null dy / x / mean / rstd / dx");
+  DXA_CHECK_ARG(!w || partial_dwdb, "dxa_downsample_layernorm_bwd: partial_dwdb required when w is given");
+  if (int rc = check_downsample_args("dxa_downsample_layernorm_bwd", N, G, C)) return rc;
+  const int h = (int)((G + 1) / 2);
+  const int64_t rows = N * h * h;
+  if (rows == 0) return DXA_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int vec = dtype == DXA_BF16 ? 8 : 4;
+  const bool vec_ok = al16(x) && al16(dy) && al16(dx) && (!w || al16(w)) && C % vec == 0;
+  float* part = w ? partial_dwdb : nullptr;
+  const size_t sums = part ? (size_t)8 * C * sizeof(float) : 0;
+  const int use_lds = sums > 0 && sums <= DS_LN_MAX_LDS;
+  const size_t lds = use_lds ? sums : 0;
+  dim3 grid((unsigned)dxa_norm_bwd_blocks(rows));
+#define DS_BWD(T_, TW_, V_) hipLaunchKernelGGL((ds_layernorm_bwd_k<T_, TW_, V_>), grid, dim3(256), lds, st, (const T_*)dy, (const T_*)x, (const TW_*)w, mean, rstd, (T_*)dx, part, rows, (int)G, h, (int)C, use_lds)
+  if (dtype == DXA_BF16 && w_dtype == DXA_BF16) { if (vec_ok) DS_BWD(bf16_t, bf16_t, 8); else DS_BWD(bf16_t, bf16_t, 1); }
+  else if (dtype == DXA_BF16) { if (vec_ok) DS_BWD(bf16_t, float, 8); else DS_BWD(bf16_t, float, 1); }
+  else { if (vec_ok) DS_BWD(float, float, 4); else DS_BWD(float, float, 1); }
+#undef DS_BWD
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
+}

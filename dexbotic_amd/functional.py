@@ -678,6 +678,38 @@ class NormFn(_StoreFn):
         return dx, None, None, None, None, None, None
 
 
+class DownsampleNormFn(_StoreFn):
+    """DownSampleBlock + nn.LayerNorm(4C) of the `mlp_downsample` projector (mm_projector/builder.py:9-33,62-69): x [N, G*G, C] ->
+    [N, ceil(G/2)^2, 4C], 2x2 neighbouring tokens side by side (column-pair major order, odd grids zero padded), normalised.  One
+    launch per direction; only the un-merged input and the row statistics are kept, so there is nothing to recompute under
+    ``ParamStore.recompute``."""
+
+    @staticmethod
+    def forward(ctx, x, anchor, st: ParamStore, wn: str, bn: str, eps: float):
+        x = x.contiguous()
+        y, mean, rstd = K.downsample_layernorm_fwd(x, st.w(wn), st.w(bn), eps)
+        ctx.st, ctx.wn, ctx.bn = st, wn, bn
+        _use(ctx, st, wn, bn)
+        ctx.save_for_backward(x, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        st, wn, bn = ctx.st, ctx.wn, ctx.bn
+        x, mean, rstd = ctx.saved_tensors
+        dx, part = K.downsample_layernorm_bwd(dy.contiguous(), x, st.w(wn), mean, rstd)
+        if st.trainable(wn):
+            cols = part.shape[1] // 2
+            dw, db, acc = st.g(wn), st.g(bn), st.accum_flag(wn)
+            if db.data_ptr() == dw.data_ptr() + 4 * cols:      # weight and bias slots lie back to back: one column sum
+                K.colsum(part, out=torch.as_strided(dw, (2 * cols,), (1,)), accumulate=acc)
+            else:
+                K.colsum(part[:, :cols], out=dw, accumulate=acc)
+                K.colsum(part[:, cols:], out=db, accumulate=acc)
+            st.mark_written(wn, bn)
+        return dx, None, None, None, None, None
+
+
 class VitEmbedFn(_StoreFn):
     """CLS + position embeddings (HF:clip/modeling_clip.py:206-217)."""
 
@@ -837,41 +869,70 @@ class LmHeadLossFn(_StoreFn):
 
     @staticmethod
     def forward(ctx, hidden, anchor, st: ParamStore, wn: str, labels_shifted: torch.Tensor, n_valid: int):
-        h2 = hidden.reshape(-1, hidden.shape[-1]).contiguous()
-        W = st.w(wn)
-        logits = K.mm_nt(h2, W)
-        row_loss, lse = K.cross_entropy_fwd(logits, labels_shifted)
-        loss = K.colsum(row_loss.view(-1, 1))
-        if n_valid > 0:
-            K.scale_(loss, 1.0 / n_valid)
-        else:
-            loss = loss * float("nan")                          # F.cross_entropy(mean) over zero targets
-        ctx.st, ctx.wn, ctx.n_valid, ctx.hshape = st, wn, n_valid, hidden.shape
-        _use(ctx, st, wn)
-        ctx.save_for_backward(h2, logits, lse, labels_shifted)
-        ctx.mark_non_differentiable(logits)
-        return loss.view(()), logits.view(*hidden.shape[:-1], W.shape[0])
+        return _lm_head_loss_fwd(ctx, hidden, st, wn, labels_shifted, n_valid, None)
 
     @staticmethod
     def backward(ctx, g, _g_logits):
-        st, wn = ctx.st, ctx.wn
-        h2, logits, lse, labels = ctx.saved_tensors
-        W = st.w(wn)
-        dz = K.cross_entropy_bwd(logits, labels, lse, g.reshape(1).float().contiguous(), 1.0 / max(ctx.n_valid, 1))
-        if st.trainable(wn):
-            # the fp32 dW of the full vocabulary (152064 x 3584 x 4 B = 2.18 GB) is past the 2 GiB the MFMA fast path addresses
-            # in one output: written in row slabs of < 2 GiB (column slices of dZ), each on the fast path
-            g, acc, mir = st.g(wn), st.accum_flag(wn), st.mirror_out(wn)
-            V, d_ = g.shape
-            slab = max(256, min(V, LMHEAD_SLAB_BYTES // (4 * d_) // 256 * 256))
-            for lo in range(0, V, slab):
-                hi = min(V, lo + slab)
-                K.mm_tn(dz[:, lo:hi], h2, out=g[lo:hi], accumulate=acc, mirror=None if mir is None else mir[lo:hi])
-            st.mark_written(wn)
-        dh = None
-        if ctx.needs_input_grad[0]:
-            dh = K.mm_nn(dz, W).view(ctx.hshape)
-        return dh, None, None, None, None, None
+        return (_lm_head_loss_bwd(ctx, g),) + (None,) * 5
+
+
+class LmHeadSoftLossFn(_StoreFn):
+    """LmHeadLossFn with the NaVILA soft targets (dexbotic/model/navila/loss.py soft_cross_entropy): rows labelled with one of
+    ``soft``'s "time" token ids are scored against a Gaussian over those ids, the others against their label; the sum is divided
+    by the number of non-ignored rows (``targets.size(0)``), and a batch without any is 0.0, not NaN."""
+
+    @staticmethod
+    def forward(ctx, hidden, anchor, st: ParamStore, wn: str, labels_shifted: torch.Tensor, n_valid: int, soft: "K.SoftTokens"):
+        return _lm_head_loss_fwd(ctx, hidden, st, wn, labels_shifted, n_valid, soft)
+
+    @staticmethod
+    def backward(ctx, g, _g_logits):
+        return (_lm_head_loss_bwd(ctx, g),) + (None,) * 6
+
+
+def _lm_head_loss_fwd(ctx, hidden, st: ParamStore, wn: str, labels_shifted: torch.Tensor, n_valid: int, soft):
+    h2 = hidden.reshape(-1, hidden.shape[-1]).contiguous()
+    W = st.w(wn)
+    logits = K.mm_nt(h2, W)
+    if soft is None:
+        row_loss, lse = K.cross_entropy_fwd(logits, labels_shifted)
+    else:
+        row_loss, lse = K.soft_cross_entropy_fwd(logits, labels_shifted, soft)
+    loss = K.colsum(row_loss.view(-1, 1))
+    if n_valid > 0:
+        K.scale_(loss, 1.0 / n_valid)
+    elif soft is None:
+        loss = loss * float("nan")                          # F.cross_entropy(mean) over zero targets
+    ctx.st, ctx.wn, ctx.n_valid, ctx.hshape, ctx.soft = st, wn, n_valid, hidden.shape, soft
+    _use(ctx, st, wn)
+    ctx.save_for_backward(h2, logits, lse, labels_shifted)
+    ctx.mark_non_differentiable(logits)
+    return loss.view(()), logits.view(*hidden.shape[:-1], W.shape[0])
+
+
+def _lm_head_loss_bwd(ctx, g):
+    st, wn = ctx.st, ctx.wn
+    h2, logits, lse, labels = ctx.saved_tensors
+    W = st.w(wn)
+    gs, scale = g.reshape(1).float().contiguous(), 1.0 / max(ctx.n_valid, 1)
+    if ctx.soft is None:
+        dz = K.cross_entropy_bwd(logits, labels, lse, gs, scale)
+    else:
+        dz = K.soft_cross_entropy_bwd(logits, labels, lse, gs, scale, ctx.soft)
+    if st.trainable(wn):
+        # the fp32 dW of the full vocabulary (152064 x 3584 x 4 B = 2.18 GB) is past the 2 GiB the MFMA fast path addresses
+        # in one output: written in row slabs of < 2 GiB (column slices of dZ), each on the fast path
+        g, acc, mir = st.g(wn), st.accum_flag(wn), st.mirror_out(wn)
+        V, d_ = g.shape
+        slab = max(256, min(V, LMHEAD_SLAB_BYTES // (4 * d_) // 256 * 256))
+        for lo in range(0, V, slab):
+            hi = min(V, lo + slab)
+            K.mm_tn(dz[:, lo:hi], h2, out=g[lo:hi], accumulate=acc, mirror=None if mir is None else mir[lo:hi])
+        st.mark_written(wn)
+    dh = None
+    if ctx.needs_input_grad[0]:
+        dh = K.mm_nn(dz, W).view(ctx.hshape)
+    return dh
 
 
 class AddPosFn(_StoreFn):

@@ -498,6 +498,46 @@ def layernorm_bwd(dy, x, w, mean, rstd, dw_out=None, db_out=None, accumulate: bo
     return dx.view(x.shape), s[:cols], s[cols:]
 
 
+def downsample_grid(n_tokens: int) -> Tuple[int, int]:
+    """(G, h) of the 2x2 token merge: n_tokens = G*G input tokens per image, h*h = ceil(G/2)^2 merged tokens"""
+    G = int(round(n_tokens ** 0.5))
+    if G * G != n_tokens or G < 1:
+        raise L.DxaError(f"downsample: {n_tokens} tokens per image are not a square grid")
+    return G, (G + 1) // 2
+
+
+def downsample_layernorm_fwd(x, w, b, eps):
+    """x [N, G*G, C] -> (y [N, h*h, 4C], mean [N*h*h], rstd [N*h*h]): 2x2 token merge (column-pair major, odd grids zero padded)
+    + LayerNorm over the 4C merged columns in one launch"""
+    assert x.dim() == 3 and x.is_contiguous()
+    N, T, C_ = x.shape
+    G, h = downsample_grid(T)
+    y = torch.empty((N, h * h, 4 * C_), device=x.device, dtype=x.dtype)
+    mean = torch.empty(N * h * h, device=x.device, dtype=torch.float32)
+    rstd = torch.empty_like(mean)
+    L.check(lib.dxa_downsample_layernorm_fwd(_ptr(x), _ptr(w), _ptr(b), _ptr(y), _ptr(mean), _ptr(rstd), N, G, C_, eps, dt(x),
+                                             dt(w) if w is not None else dt(x), _stream()), "dxa_downsample_layernorm_fwd")
+    return y, mean, rstd
+
+
+def downsample_layernorm_bwd(dy, x, w, mean, rstd, out: Optional[torch.Tensor] = None):
+    """-> (dx [N, G*G, C] in the un-merged layout, partial sums [blocks, dw | db] fp32 or None without w); the caller folds the
+    partials (colsum).  ``out``: destination for dx (every element is written)"""
+    assert x.dim() == 3 and x.is_contiguous()
+    N, T, C_ = x.shape
+    G, h = downsample_grid(T)
+    dy2 = dy.reshape(N * h * h, 4 * C_)
+    assert dy2.is_contiguous() and dy2.dtype == x.dtype
+    dx = torch.empty_like(x) if out is None else out
+    assert dx.shape == x.shape and dx.dtype == x.dtype and dx.is_contiguous()
+    part = None
+    if w is not None:
+        part = torch.empty((norm_bwd_blocks(N * h * h), 8 * C_), device=x.device, dtype=torch.float32)
+    L.check(lib.dxa_downsample_layernorm_bwd(_ptr(dy2), _ptr(x), _ptr(w), _ptr(mean), _ptr(rstd), _ptr(dx), _ptr(part), N, G, C_,
+                                             dt(x), dt(w) if w is not None else dt(x), _stream()), "dxa_downsample_layernorm_bwd")
+    return dx, part
+
+
 def colsum(x: torch.Tensor, out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
     """out[c] (+)= sum_r x[r, c]  (fp32 result)"""
     ld = _row_major(x, "x")
@@ -963,6 +1003,49 @@ def cross_entropy_bwd(logits: torch.Tensor, labels: torch.Tensor, lse: torch.Ten
     L.check(lib.dxa_cross_entropy_bwd(_ptr(logits), logits.stride(0), _ptr(labels), _ptr(lse), _ptr(gscale), float(scale),
                                       _ptr(out), out.stride(0), rows, V, ignore_index, dt(logits), _stream()),
             "dxa_cross_entropy_bwd")
+    return out
+
+
+class SoftTokens:
+    """the K soft ("time") token ids of the soft-target cross-entropy, on the host (checked by every call) and on the device, with
+    1 / (2 std^2).  Duplicate ids are refused: the reference's result for them is an accident of write order."""
+
+    def __init__(self, ids: Sequence[int], std: float, device):
+        ids = [int(i) for i in ids]
+        if len(set(ids)) != len(ids):
+            raise ValueError(f"soft token ids must be distinct, got {ids}")
+        if not float(std) > 0.0:
+            raise ValueError(f"soft-target std must be positive, got {std}")
+        self.K = len(ids)
+        self.host = (C.c_int64 * max(self.K, 1))(*ids)
+        self.dev = torch.tensor(ids, dtype=torch.int64, device=device) if self.K else None
+        self.inv2s2 = 1.0 / (2.0 * float(std) ** 2)
+
+
+def soft_cross_entropy_fwd(logits: torch.Tensor, labels: torch.Tensor, soft: SoftTokens, ignore_index: int = -100):
+    """cross_entropy_fwd with Gaussian soft targets over ``soft``'s ids for the rows labelled with one of them"""
+    rows, V = logits.shape
+    assert logits.stride(1) == 1 and labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == rows
+    row_loss = torch.empty(rows, device=logits.device, dtype=torch.float32)
+    lse = torch.empty(rows, device=logits.device, dtype=torch.float32)
+    L.check(lib.dxa_soft_cross_entropy_fwd(_ptr(logits), logits.stride(0), _ptr(labels), _ptr(row_loss), _ptr(lse), rows, V,
+                                           ignore_index, _ptr(soft.dev), C.cast(soft.host, C.c_void_p) if soft.K else None,
+                                           soft.K, soft.inv2s2, dt(logits), _stream()), "dxa_soft_cross_entropy_fwd")
+    return row_loss, lse
+
+
+def soft_cross_entropy_bwd(logits: torch.Tensor, labels: torch.Tensor, lse: torch.Tensor, gscale: Optional[torch.Tensor],
+                           scale: float, soft: SoftTokens, out: Optional[torch.Tensor] = None,
+                           ignore_index: int = -100) -> torch.Tensor:
+    """dlogits = (softmax - target) * gscale[0] * scale, target = one-hot or the soft row; ``out`` may be ``logits`` itself"""
+    rows, V = logits.shape
+    if out is None:
+        out = torch.empty_like(logits)
+    assert out.shape == logits.shape and out.dtype == logits.dtype and out.stride(1) == 1
+    L.check(lib.dxa_soft_cross_entropy_bwd(_ptr(logits), logits.stride(0), _ptr(labels), _ptr(lse), _ptr(gscale), float(scale),
+                                           _ptr(out), out.stride(0), rows, V, ignore_index, _ptr(soft.dev),
+                                           C.cast(soft.host, C.c_void_p) if soft.K else None, soft.K, soft.inv2s2,
+                                           dt(logits), _stream()), "dxa_soft_cross_entropy_bwd")
     return out
 
 

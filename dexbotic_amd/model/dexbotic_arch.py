@@ -233,6 +233,12 @@ class DexboticVLMModel(nn.Module):
         views = images.shape[1] if images.ndim == 5 else 1
         return views * self.mm_vision_module.num_patches
 
+    def _splice_plan(self, input_ids, attention_mask, labels, images) -> SplicePlan:
+        """the (cached) integer plan of this batch; a subclass with another placeholder rule overrides it (NaVILAModel)"""
+        return self._plans.get(input_ids, attention_mask, labels, self.num_image_tokens(images),
+                               getattr(self.config, "tokenizer_model_max_length", None),
+                               getattr(self.config, "tokenizer_padding_side", "right"))
+
     def _prepare_inputs_labels_for_multimodal(self, input_ids, position_ids, attention_mask, past_key_values, labels,
                                               cache_position, images) -> tuple:
         """Same contract as the reference (returns input_ids=None and the spliced inputs_embeds); the plan
@@ -241,9 +247,7 @@ class DexboticVLMModel(nn.Module):
             raise NotImplementedError("text-only forward is outside the VLA path")
         # the integer plan first (host arithmetic on a few KB; ids handed over as host tensors — the collator's own
         # output — or a batch object seen before cost no device sync), THEN the vision tower is enqueued
-        plan = self._plans.get(input_ids, attention_mask, labels, self.num_image_tokens(images),
-                               getattr(self.config, "tokenizer_model_max_length", None),
-                               getattr(self.config, "tokenizer_padding_side", "right"))
+        plan = self._splice_plan(input_ids, attention_mask, labels, images)
         self._last_plan = plan
         image_features = self._extract_vision_features(images)                          # [B, V*N_v, d]
         dev = image_features.device
@@ -475,6 +479,13 @@ class DexboticForCausalLM(NativePreTrainedMixin, nn.Module):
         """parameters that get no gradient from the LM loss (the CLIP layer after hidden_states[-2], post_layernorm)"""
         return self.model.mm_vision_tower.unused_parameter_names()
 
+    def _generation_plan(self, input_ids: np.ndarray, attention_mask: Optional[np.ndarray], feats: torch.Tensor) -> SplicePlan:
+        """splice plan of generate()'s prompt(s) over the image features [B, rows, d]; a subclass with another placeholder rule
+        overrides it (NaVILAForCausalLM)"""
+        return build_splice_plan(input_ids, attention_mask, None, feats.shape[1],
+                                 getattr(self.config, "tokenizer_model_max_length", None),
+                                 getattr(self.config, "tokenizer_padding_side", "right"))
+
     @torch.no_grad()
     def generate(self, input_ids, images=None, max_new_tokens: int = 64, do_sample: bool = False,
                  temperature: float = 1.0, eos_token_id: Optional[int] = None, stopping_criteria=None,
@@ -487,11 +498,9 @@ class DexboticForCausalLM(NativePreTrainedMixin, nn.Module):
         dev = self.store.device
         imgs = images.to(device=dev, dtype=self.store.compute_dtype)
         feats = self.model._extract_vision_features(imgs)
-        plan = build_splice_plan(input_ids.detach().cpu().numpy(),
-                                 None if attention_mask is None else attention_mask.detach().cpu().numpy().astype(bool),
-                                 None, feats.shape[1],
-                                 getattr(self.config, "tokenizer_model_max_length", None),
-                                 getattr(self.config, "tokenizer_padding_side", "right"))
+        plan = self._generation_plan(input_ids.detach().cpu().numpy(),
+                                     None if attention_mask is None else attention_mask.detach().cpu().numpy().astype(bool),
+                                     feats)
         B, S = plan.plan.shape
         pad = None
         if not plan.attention_mask.all():

@@ -57,6 +57,32 @@ class LinearProjector(nn.Module):
                                  L.ACT_NONE, None)
 
 
+class DownsampleProjector(nn.Module):
+    """`mlp_downsample` (the NaVILA family): DownSampleBlock -> LayerNorm(4C) -> Linear(4C, d) -> GELU(erf) -> Linear(d, d);
+    state_dict names of the reference's nn.Sequential: `1.*` (LayerNorm), `2.*`, `4.*` (the block and the GELU hold nothing)"""
+
+    def __init__(self, store: ParamStore, prefix: str, in_dim: int, out_dim: int, eps: float = 1e-5):
+        super().__init__()
+        self.store, self.p, self.eps = store, prefix, eps
+        store.new_bucket()
+        store.register([(prefix + "1.weight", (4 * in_dim,)), (prefix + "1.bias", (4 * in_dim,))], layernorm=True)
+        store.register([(prefix + "2.weight", (out_dim, 4 * in_dim)), (prefix + "2.bias", (out_dim,))])
+        store.register([(prefix + "4.weight", (out_dim, out_dim)), (prefix + "4.bias", (out_dim,))])
+
+    @staticmethod
+    def num_tokens(n_patches: int) -> int:
+        """tokens per image after the 2x2 merge of a G x G patch grid (odd G padded)"""
+        G = int(round(n_patches ** 0.5))
+        return ((G + 1) // 2) ** 2
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """[N, G*G, C] -> [N, ceil(G/2)^2, d]"""
+        st, p = self.store, self.p
+        anchor = st.params[p + "2.weight"]
+        y = Fn.DownsampleNormFn.apply(x, anchor, st, p + "1.weight", p + "1.bias", self.eps)
+        return Fn.MlpFn.apply(y, anchor, st, p + "2.weight", p + "2.bias", p + "4.weight", p + "4.bias", L.ACT_GELU_ERF)
+
+
 def build_vision_projector(config, store: Optional[ParamStore] = None, prefix: str = "model.mm_projector."):
     """reference signature ``build_vision_projector(config)``; the arena comes from the enclosing build context"""
     store = current_store(store)
@@ -74,6 +100,5 @@ def build_vision_projector(config, store: Optional[ParamStore] = None, prefix: s
         return LinearProjector(store, prefix, config.mm_hidden_size * int(m.group(1)), config.hidden_size,
                                bias=bool(getattr(config, "projector_bias", False)))
     if projector_type == "mlp_downsample":
-        raise NotImplementedError("projector 'mlp_downsample' (2x2 token merge + LayerNorm, used by the NaVILA family) is not on "
-                                  "the CogACT / pi0 / MemVLA paths")
+        return DownsampleProjector(store, prefix, config.mm_hidden_size, config.hidden_size)
     raise ValueError(f"Unknown projector type: {projector_type}")

@@ -60,8 +60,9 @@ class SiglipVisionTower(nn.Module):
     def __init__(self, vision_tower_config, store: ParamStore, prefix: str = "model.mm_vision_tower.",
                  processor_config=None, delay_load=False, select_layer=None):
         super().__init__()
-        if select_layer is not None:
-            raise NotImplementedError("native SigLIP tower: last_hidden_state (select_layer=None), the pi0 setting")
+        if select_layer not in (None, -2):
+            raise NotImplementedError("native SigLIP tower: last_hidden_state (select_layer=None, the pi0 setting) or "
+                                      "hidden_states[-2] (select_layer=-2, the NaVILA setting)")
         self.is_loaded = True
         self.select_layer = select_layer
         self.processor_config = processor_config
@@ -111,7 +112,10 @@ class SiglipVisionTower(nn.Module):
         store.register([(h + "mlp.fc2.weight", (C_, I)), (h + "mlp.fc2.bias", (C_,))])
 
     def unused_parameter_names(self):
-        return [n for n in self.store.slots if n.startswith(self.p + "head.")]
+        dead = [self.p + "head."]
+        if self.select_layer == -2:            # hidden_states[-2]: the last layer and post_layernorm never run
+            dead += [f"{self.p}encoder.layers.{self.cfg.num_hidden_layers - 1}.", self.p + "post_layernorm."]
+        return [n for n in self.store.slots if any(n.startswith(d) for d in dead)]
 
     def load_model(self):
         return
@@ -129,7 +133,8 @@ class SiglipVisionTower(nn.Module):
         return self._image_processor
 
     def forward(self, images: torch.Tensor) -> torch.Tensor:
-        """images [N,3,H,W] -> [N, N_patches, C] = post_layernorm(encoder(embeddings)) in the compute dtype"""
+        """images [N,3,H,W] -> [N, N_patches, C] in the compute dtype: post_layernorm(encoder(embeddings)), or with
+        ``select_layer=-2`` the hidden state after the last layer but one, without post_layernorm"""
         if isinstance(images, list):
             images = torch.stack(images, 0)
         st, c, p = self.store, self.cfg, self.p
@@ -142,6 +147,11 @@ class SiglipVisionTower(nn.Module):
         patch = Fn.LinearFn.apply(rows, anchor, st, p + "embeddings.patch_embedding.weight",
                                   p + "embeddings.patch_embedding.bias", L.ACT_NONE, (C_, 3 * P * P))
         x = Fn.AddPosFn.apply(patch.view(N, self.np_, C_), anchor, st, p + "embeddings.position_embedding.weight")
+        if self.select_layer == -2:
+            for sp in self.layer_specs[:-1]:
+                sp.N, sp.T = N, self.np_
+                x = Fn.VitBlockFn.apply(x, st.params[sp.fc2_w], st, sp)
+            return x.view(N, self.np_, C_)
         for sp in self.layer_specs:
             sp.N, sp.T = N, self.np_
             x = Fn.VitBlockFn.apply(x, st.params[sp.fc2_w], st, sp)

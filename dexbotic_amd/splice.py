@@ -121,6 +121,62 @@ def build_splice_plan(input_ids: np.ndarray, attention_mask: Optional[np.ndarray
     return SplicePlan(plan, new_mask, new_labels, lengths, kv_start, kv_end, last)
 
 
+def build_navila_splice_plan(input_ids: np.ndarray, attention_mask: Optional[np.ndarray], labels: Optional[np.ndarray],
+                             n_sample_rows: int, n_feature_samples: Optional[int] = None, max_length: Optional[int] = None,
+                             padding_side: str = "right") -> SplicePlan:
+    """NaVILA's per-sample rule (dexbotic/model/navila/navila_arch.py:41-214, ``_insert_multimodal_embeds_per_batch``): sample b
+    owns the feature rows [b R, (b + 1) R), R = ``n_sample_rows`` = frames x tokens per frame (b clamped to the last feature
+    sample, :161).  With n placeholders in the sample, placeholder i expands to rows i (R // n) ... (i + 1) (R // n) of that
+    block; a single placeholder expands to all R rows; a sample without a placeholder uses none.  Truncation, padding side,
+    labels, mask, key ranges and last index as in ``build_splice_plan``; same plan encoding, same kernel."""
+    input_ids = np.asarray(input_ids, dtype=np.int64)
+    B, Lt = input_ids.shape
+    mask = np.ones((B, Lt), dtype=bool) if attention_mask is None else np.asarray(attention_mask).astype(bool)
+    lab = np.full((B, Lt), IGNORE_INDEX, dtype=np.int64) if labels is None else np.asarray(labels, dtype=np.int64)
+    n_feat = B if n_feature_samples is None else int(n_feature_samples)
+    R = int(n_sample_rows)
+    rows, row_labels = [], []
+    for b in range(B):
+        ids, lb = input_ids[b][mask[b]], lab[b][mask[b]]
+        where = np.flatnonzero(ids == IMAGE_TOKEN_INDEX)
+        n = where.size
+        if n == 0:
+            rows.append(ids)
+            row_labels.append(lb)
+            continue
+        per = R if n == 1 else R // n
+        first = min(b, n_feat - 1) * R
+        pieces, lpieces, prev = [], [], 0
+        for i, pos in enumerate(where):
+            pieces += [ids[prev:pos], -1 - (first + i * per + np.arange(per, dtype=np.int64))]
+            lpieces += [lb[prev:pos], np.full(per, IGNORE_INDEX, dtype=np.int64)]
+            prev = pos + 1
+        pieces.append(ids[prev:])
+        lpieces.append(lb[prev:])
+        rows.append(np.concatenate(pieces))
+        row_labels.append(np.concatenate(lpieces))
+    if max_length is not None:
+        rows = [r[:max_length] for r in rows]
+        row_labels = [r[:max_length] for r in row_labels]
+    lengths = np.array([len(r) for r in rows], dtype=np.int64)
+    S = int(lengths.max()) if B else 0
+    plan = np.full((B, S), PLAN_PAD, dtype=np.int64)
+    new_mask = np.zeros((B, S), dtype=bool)
+    new_labels = np.full((B, S), IGNORE_INDEX, dtype=np.int64)
+    kv_start = np.zeros(B, dtype=np.int32)
+    kv_end = np.zeros(B, dtype=np.int32)
+    for b, (r, l) in enumerate(zip(rows, row_labels)):
+        n = len(r)
+        lo = S - n if padding_side == "left" else 0
+        plan[b, lo:lo + n] = r
+        new_mask[b, lo:lo + n] = True
+        new_labels[b, lo:lo + n] = l
+        kv_start[b], kv_end[b] = lo, lo + n
+    cs = new_mask.cumsum(axis=1)
+    last = (cs == cs.max(axis=1, keepdims=True)).argmax(axis=1).astype(np.int64) if S else np.zeros(B, np.int64)
+    return SplicePlan(plan, new_mask, new_labels, lengths, kv_start, kv_end, last)
+
+
 class PlanCache:
     """Splice plans keyed by the CONTENT of the integer inputs (ids / mask / labels are a few KB), plus an identity
     shortcut for device-resident id tensors so that a batch object seen before costs no device->host copy (the
@@ -153,13 +209,22 @@ class PlanCache:
         self._by_ident[key] = (ref, arr)
         return arr
 
-    def get(self, ids, mask, labels, n_img_rows: int, max_length, padding_side: str) -> SplicePlan:
+    def get(self, ids, mask, labels, n_img_rows: int, max_length, padding_side: str, rule: str = "base",
+            n_feature_samples: Optional[int] = None) -> SplicePlan:
+        """``rule``: "base" (``build_splice_plan``: one block of ``n_img_rows`` per placeholder, counted across the batch) or
+        "navila" (``build_navila_splice_plan``: ``n_img_rows`` rows per SAMPLE, split between its placeholders).  The rule is part
+        of the key: the same ids mean different plans under the two."""
+        if rule not in ("base", "navila"):
+            raise ValueError(f"unknown splice rule {rule!r}")
         ids, mask, labels = self.host(ids), self.host(mask), self.host(labels)
         key = (ids.shape, ids.tobytes(), None if mask is None else mask.tobytes(),
-               None if labels is None else labels.tobytes(), n_img_rows, max_length, padding_side)
+               None if labels is None else labels.tobytes(), n_img_rows, max_length, padding_side, rule, n_feature_samples)
         plan = self._by_content.get(key)
         if plan is None:
-            plan = build_splice_plan(ids, mask, labels, n_img_rows, max_length, padding_side)
+            if rule == "navila":
+                plan = build_navila_splice_plan(ids, mask, labels, n_img_rows, n_feature_samples, max_length, padding_side)
+            else:
+                plan = build_splice_plan(ids, mask, labels, n_img_rows, max_length, padding_side)
             if len(self._by_content) >= self.capacity:
                 self._by_content.pop(next(iter(self._by_content)))
             self._by_content[key] = plan

@@ -189,7 +189,20 @@ int dxa_layernorm_bwd(const void* dy, const void* x, const void* w, const float*
                       void* dx, const void* residual, float* partial_dwdb, int64_t rows, int64_t cols, int dtype,
                       int w_dtype, dxa_stream_t stream);
 int dxa_norm_bwd_blocks(int64_t rows);
-/* out[c] (+)= sum_r x[r*ld + c]   (bias gradients, norm-weight gradients, pos-emb gradients).
+/* 2x2 token merge + LayerNorm(4C) in one launch per direction: the `mlp_downsample` projector's DownSampleBlock followed by
+ * nn.LayerNorm (dexbotic/model/modules/mm_projector/builder.py:9-33,62-69).  x [N, G*G, C], token t = r*G + c; an odd grid is
+ * zero padded to Gp = G + 1 on the bottom and right; h = Gp / 2.  y [N, h*h, 4C], output token o = j*h + i (j: column pair,
+ * i: row pair) = [x(2i,2j) | x(2i,2j+1) | x(2i+1,2j) | x(2i+1,2j+1)] normalised over its 4C columns (padded positions count as
+ * zeros); mean / rstd [N*h*h] as dxa_layernorm_fwd writes them.  The merged, un-normalised tensor is never written.
+ * bwd reads dy [N*h*h, 4C] and the UN-merged x, writes dx in the un-merged layout (every real token lies in exactly one quarter of
+ * one output row: each is written once, padded positions are not written) and partial dw/db as dxa_layernorm_bwd does
+ * ([dxa_norm_bwd_blocks(N*h*h), 2*4C] fp32, folded by dxa_colsum). */
+int dxa_downsample_layernorm_fwd(const void* x, const void* w, const void* b, void* y, float* mean, float* rstd,
+                                 int64_t N, int64_t G, int64_t C, float eps, int dtype, int w_dtype, dxa_stream_t stream);
+int dxa_downsample_layernorm_bwd(const void* dy, const void* x, const void* w, const float* mean, const float* rstd,
+                                 void* dx, float* partial_dwdb, int64_t N, int64_t G, int64_t C, int dtype, int w_dtype,
+                                 dxa_stream_t stream);
+/* out[c] (+)= sum_r x[r*ld + c]  (bias gradients, norm-weight gradients, pos-emb gradients).
  * Deterministic two-stage reduction; scratch >= min(64, ceil(rows/32)) * cols floats. */
 int dxa_colsum(const void* x, int64_t ld, float* out, int64_t rows, int64_t cols, int dtype,
                int accumulate, float* scratch, size_t scratch_bytes, dxa_stream_t stream);
@@ -451,6 +464,20 @@ int dxa_cross_entropy_bwd(const void* logits, int64_t ld, const int64_t* labels,
                           int64_t ignore_index, int dtype, dxa_stream_t stream);
 int dxa_argmax_rows(const void* x, int64_t ld, int64_t* out, int64_t rows, int64_t cols, int dtype,
                     dxa_stream_t stream);
+/* Soft-target cross-entropy (dexbotic/model/navila/loss.py soft_cross_entropy): dxa_cross_entropy_fwd/bwd with Gaussian soft
+ * targets for the rows whose label is one of the K `soft_ids` (DEVICE array, int64, distinct, any order, each in [0, V)):
+ *   p_k = exp(-(label - soft_ids[k])^2 * inv2s2) / sum_k exp(...)   (inv2s2 = 1 / (2 std^2); fp32 from the integer difference)
+ *   fwd: row_loss = lse - sum_k p_k logits[soft_ids[k]];  bwd: dlogits = (softmax - p) * g at the soft ids, softmax * g elsewhere.
+ * Every other row, ignored rows included, is treated exactly as by dxa_cross_entropy_fwd/bwd; with K = 0 (soft_ids may be NULL)
+ * the results are bit-identical to them.  K <= 64.  soft_ids_host: the same K ids in HOST memory (required when K > 0): the call
+ * checks them against V and for duplicates without a device round trip. */
+int dxa_soft_cross_entropy_fwd(const void* logits, int64_t ld, const int64_t* labels, float* row_loss, float* lse,
+                               int64_t rows, int64_t V, int64_t ignore_index, const int64_t* soft_ids,
+                               const int64_t* soft_ids_host, int K, float inv2s2, int dtype, dxa_stream_t stream);
+int dxa_soft_cross_entropy_bwd(const void* logits, int64_t ld, const int64_t* labels, const float* lse,
+                               const float* gscale, float scale, void* dlogits, int64_t ldd, int64_t rows, int64_t V,
+                               int64_t ignore_index, const int64_t* soft_ids, const int64_t* soft_ids_host, int K,
+                               float inv2s2, int dtype, dxa_stream_t stream);
 
 /* ---- device-side image preprocessing ------------------------------------------------
  * Replaces, for uint8 RGB frames already on the device, what the reference does per frame on the host with
