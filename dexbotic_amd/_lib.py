@@ -186,7 +186,8 @@ SIGNATURES = {
     "dxa_soft_cross_entropy_bwd": (_int, [_vp, _i64, _vp, _vp, _vp, _f32, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _int, _f32,
                                           _int, _vp]),
     "dxa_argmax_rows": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _vp]),
-    "dxa_resample_ksize": (_int, [_int, _int]),
+    "dxa_sample_rows": (_int, [_vp, _i64, _i64, _i64, _int, _f32, _i64, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dxa_resample_ksize":(_int, [_int, _int]),
     "dxa_resample_coeffs": (_int, [_int, _int, _int, _vp, _vp]),
     "dxa_image_preprocess": (_int, [C.POINTER(ImageDesc), _vp]),
     "dxa_dit_blocks_workspace": (_sz, [_int, _int, _int]),

@@ -4,7 +4,9 @@
 //                               non-ignored (already shifted) labels.
 //   dxa_argmax_rows           : torch.argmax over the vocabulary (first index among equal maxima), the greedy
 //                               choice of GenerationMixin.generate(do_sample=False) (discrete_vla_arch.py:33-41).
-// All three are one 256-thread workgroup per row streaming the row once (HBM-bound: 152 k logits = 304 KB bf16):
+//   dxa_sample_rows           : the sampled choice of generate(do_sample=True): temperature, top-k, top-p, softmax and the draw in
+//                               one launch (its own section at the end of this file).
+// The first three are one 256-thread workgroup per row streaming the row once (HBM-bound: 152 k logits = 304 KB bf16):
 // online (max, sum-exp) pairs per thread folded across the block — no second pass for the maximum.
 #include "common.h"
 
@@ -398,6 +400,297 @@ extern "C" int dxa_soft_cross_entropy_bwd(const void* logits, int64_t ld, const 
   if (dtype == DXA_BF16) { if (vec) SOFT_BWD(bf16_t, 4); else SOFT_BWD(bf16_t, 1); }
   else { if (vec) SOFT_BWD(float, 4); else SOFT_BWD(float, 1); }
 #undef SOFT_BWD
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
+}
+
+// ------------------------------------------------------------------------------------ sampled token choice
+// dxa_sample_rows: GenerationMixin.generate(do_sample=True) on one [rows, V] logits matrix — temperature, top-k, top-p, softmax and
+// the draw (semantics, tie rule and argument checks: include/dexbotic_amd.h).  One 1024-thread workgroup per row; the row (304 KB of
+// bf16 at V = 152,064) is read several times, from L2 after the first:
+//   1. extremes       largest / smallest key and number of the row's valid entries (neither NaN nor -inf)
+//   2. top-k          radix select, 8 bits per pass from the top of the order-preserving integer key of x (bf16: 2 passes, fp32: 4),
+//                     counting entries per digit.  For top_k <= 1024 the top_k-th largest of the 1024 per-thread maxima, found the
+//                     same way from registers, is a lower bound of the threshold: only the few entries at or above it are counted.
+//   3. top-p          one pass for the mass of the top-k set, then the same select with an entry's mass e as its weight
+//   4. draw           wave w sums the kept mass of the w-th sixteenth of the index range; the sixteenth that holds u * Z is cut into
+//                     sixteen again until it fits one element group per thread, which a workgroup-wide scan resolves
+// Mass is kept in fixed point: q = (uint64) (e * 2^40), e = exp(z - max z) in [0, 1].  Sums of integers do not depend on their order,
+// so every threshold and the draw are the same bits on every run although the digit histograms are filled with LDS atomics, and the
+// partial sums of the draw agree exactly between its steps.  An entry with e < 2^-40 weighs nothing (it is never drawn); the sum of
+// what the truncation drops is below V * 2^-40 of the largest entry's weight.
+namespace {
+
+typedef unsigned long long u64;
+
+constexpr int SMP_THREADS = 1024;
+constexpr int SMP_COPIES = 16;                       // copies of a digit's counter, one per lane & 15: a wave's adds spread over the banks
+constexpr float SMP_ONE = 1099511627776.f;           // 2^40
+
+// order-preserving key of a float: a > b <=> key(a) > key(b); -0 = +0; NaN -> 0, below -inf
+__device__ __forceinline__ uint32_t f32_key(float x) {
+  uint32_t b = __float_as_uint(x);
+  if ((b & 0x7fffffffu) > 0x7f800000u) return 0u;
+  if (b == 0x80000000u) b = 0u;
+  return (b >> 31) ? ~b : (b | 0x80000000u);
+}
+template <typename T> struct SampleKey;
+template <> struct SampleKey<float> { static constexpr int BITS = 32; };
+template <> struct SampleKey<bf16_t> { static constexpr int BITS = 16; };   // the low 16 bits of a bf16's fp32 key depend on its sign only
+template <typename T> __device__ __forceinline__ uint32_t sample_key(float x) { return f32_key(x) >> (32 - SampleKey<T>::BITS); }
+template <typename T> __device__ __forceinline__ float sample_unkey(uint32_t k) {
+  k <<= (32 - SampleKey<T>::BITS);
+  const uint32_t b = (k >> 31) ? (k & 0x7fffffffu) : ~k;
+  return __uint_as_float(b & ~((1u << (32 - SampleKey<T>::BITS)) - 1u));
+}
+
+struct SampleShared {
+  u64 hist[256 * SMP_COPIES];
+  u64 suffix[256];
+  u64 wsum[16];
+  uint32_t wa[16], wb[16], wc[16], wd[16];
+};
+
+__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// inclusive prefix sum over the lanes of a wave
+__device__ __forceinline__ u64 wave_scan_u64(u64 v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const u64 t = __shfl_up(v, o, 64);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
+
+template <typename T, int VEC>
+__global__ __launch_bounds__(SMP_THREADS) void sample_rows_k(const T* __restrict__ logits, int64_t ld, int64_t V, float inv_t,
+                                                             int64_t top_k, float top_p, const float* __restrict__ u,
+                                                             int64_t* __restrict__ token, int32_t* __restrict__ kept_out,
+                                                             float* __restrict__ thresh_out, float* __restrict__ prob_out) {
+  __shared__ SampleShared sh;
+  constexpr int BITS = SampleKey<T>::BITS;
+  constexpr uint32_t KEY_NINF = 0x007fffffu >> (32 - BITS);          // key of -inf: a valid entry's key is larger
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int64_t r = blockIdx.x;
+  const T* x = logits + r * ld;
+
+  // every element of the row once, a wave reading consecutive addresses: f(key, value)
+  auto sweep = [&](auto&& f) {
+    for (int64_t i = (int64_t)tid * VEC; i < V; i += (int64_t)SMP_THREADS * VEC) {      // VEC > 1: V % VEC == 0
+      float v[VEC];
+      Vec<T, VEC>::ld(v, x + i);
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) f(sample_key<T>(v[e]), v[e]);
+    }
+  };
+  auto block_sum_u64 = [&](u64 v) -> u64 {
+    v = wave_sum_u64(v);
+    if (lane == 0) sh.wsum[w] = v;
+    __syncthreads();
+    u64 t = 0;
+    for (int i = 0; i < 16; ++i) t += sh.wsum[i];
+    __syncthreads();
+    return t;
+  };
+
+  // 1. extremes of the valid entries
+  uint32_t kmax = 0u, kmin = 0xffffffffu, cnt = 0u;
+  sweep([&](uint32_t k, float) {
+    if (k > KEY_NINF) { kmax = max(kmax, k); kmin = min(kmin, k); ++cnt; }
+  });
+  const uint32_t own_max = kmax;                                    // of this thread's entries, 0 without a valid one
+  uint32_t nthr = cnt ? 1u : 0u;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    kmax = max(kmax, (uint32_t)__shfl_xor(kmax, o, 64));
+    kmin = min(kmin, (uint32_t)__shfl_xor(kmin, o, 64));
+    cnt += __shfl_xor(cnt, o, 64);
+    nthr += __shfl_xor(nthr, o, 64);
+  }
+  if (lane == 0) { sh.wa[w] = kmax; sh.wb[w] = kmin; sh.wc[w] = cnt; sh.wd[w] = nthr; }
+  __syncthreads();
+  kmax = 0u; kmin = 0xffffffffu; cnt = 0u; nthr = 0u;
+  for (int i = 0; i < 16; ++i) { kmax = max(kmax, sh.wa[i]); kmin = min(kmin, sh.wb[i]); cnt += sh.wc[i]; nthr += sh.wd[i]; }
+  __syncthreads();
+  if (cnt == 0u) {                                                  // no finite logit: index 0, as dxa_argmax_rows
+    if (tid == 0) {
+      token[r] = 0;
+      if (kept_out) kept_out[r] = 0;
+      if (thresh_out) thresh_out[r] = INFINITY;
+      if (prob_out) prob_out[r] = 0.f;
+    }
+    return;
+  }
+
+  const float zmax = sample_unkey<T>(kmax) * inv_t;
+  auto weight = [&](float v) -> u64 {                               // e = exp(z - max z) in fixed point; the maximum weighs exactly 2^40
+    const float z = v * inv_t;
+    const float e = (z == zmax) ? 1.f : expf(z - zmax);
+    return (u64)(e * SMP_ONE);
+  };
+
+  // Radix select over the entries `sw` visits whose key is >= floor: the largest key t with weight{key >= t} >= target, weight = 1
+  // (count) or the entry's mass.  The caller guarantees 1 <= target <= weight{key >= floor}.
+  auto select = [&](auto&& sw, uint32_t floor, bool mass, u64 target) -> uint32_t {
+    uint32_t prefix = 0u;
+    u64 above = 0;                                                  // weight of the keys whose leading digits are larger than prefix
+    for (int lvl = 0; lvl < BITS / 8; ++lvl) {
+      const int shift = BITS - 8 * (lvl + 1);
+      for (int i = tid; i < 256 * SMP_COPIES; i += SMP_THREADS) sh.hist[i] = 0;
+      __syncthreads();
+      sw([&](uint32_t k, float v) {
+        if (k >= floor && (lvl == 0 || (k >> (shift + 8)) == prefix))
+          atomicAdd(&sh.hist[((k >> shift) & 255u) * SMP_COPIES + (lane & (SMP_COPIES - 1))], mass ? weight(v) : (u64)1);
+      });
+      __syncthreads();
+      u64 s = 0;
+      if (tid < 256) {                                              // thread t owns digit 255 - t: a prefix sum over t is a suffix sum over digits
+        const int d = 255 - tid;
+        for (int c = 0; c < SMP_COPIES; ++c) s += sh.hist[d * SMP_COPIES + ((c + tid) & (SMP_COPIES - 1))];
+        s = wave_scan_u64(s, lane);
+        if (lane == 63) sh.wsum[w] = s;
+      }
+      __syncthreads();
+      if (tid < 256) {
+        for (int i = 0; i < w; ++i) s += sh.wsum[i];
+        sh.suffix[tid] = s;                                         // weight of the digits >= 255 - t
+        const u64 short_of = __ballot(above + s < target);
+        if (lane == 0) sh.wa[w] = (uint32_t)__popcll(short_of);
+      }
+      __syncthreads();
+      int t = (int)(sh.wa[0] + sh.wa[1] + sh.wa[2] + sh.wa[3]);     // digits 255 .. 256 - t together stay short of the target
+      if (t > 255) t = 255;
+      if (t > 0) above += sh.suffix[t - 1];
+      prefix = (prefix << 8) | (uint32_t)(255 - t);
+      __syncthreads();
+    }
+    return prefix;
+  };
+
+  uint32_t tkey = kmin;                                             // smallest kept key
+
+  // 2. top-k: the top_k-th largest key, ties with it kept
+  if (top_k > 0 && top_k < V && (u64)top_k < (u64)cnt) {
+    uint32_t floor = KEY_NINF + 1u;
+    if ((u64)top_k <= (u64)nthr)
+      floor = select([&](auto&& f) { if (own_max > KEY_NINF) f(own_max, 0.f); }, floor, false, (u64)top_k);
+    tkey = select(sweep, floor, false, (u64)top_k);
+  }
+
+  // 3. top-p over what top-k kept: an entry stays iff the mass of the strictly larger entries is < top_p * Z
+  if (top_p < 1.f) {
+    u64 z = 0;
+    sweep([&](uint32_t k, float v) { if (k >= tkey) z += weight(v); });
+    z = block_sum_u64(z);
+    const double want = ceil((double)top_p * (double)z);
+    u64 target = want >= (double)z ? z : (u64)want;
+    if (target < 1) target = 1;
+    tkey = select(sweep, tkey, true, target);
+  }
+
+  // 4. draw: first index, in ascending order, whose running kept mass exceeds u * Z
+  int64_t lo = 0, hi = V;
+  u64 target = 0, zq = 0;
+  uint32_t kept = 0u;
+  for (bool first = true;; first = false) {
+    const int64_t len = hi - lo;
+    if (!first && len <= (int64_t)SMP_THREADS * VEC) break;
+    const int64_t span = ((len + 15) / 16 + 64 * VEC - 1) / (64 * VEC) * (64 * VEC);   // of one wave
+    const int64_t a = lo + (int64_t)w * span, b = min(hi, a + span);
+    u64 s = 0;
+    uint32_t c = 0u;
+    for (int64_t i = a + (int64_t)lane * VEC; i < b; i += 64 * VEC) {
+      float v[VEC];
+      Vec<T, VEC>::ld(v, x + i);
+#pragma unroll
+      for (int e = 0; e < VEC; ++e)
+        if (sample_key<T>(v[e]) >= tkey) { s += weight(v[e]); ++c; }
+    }
+    s = wave_sum_u64(s);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if (lane == 0) { sh.wsum[w] = s; sh.wa[w] = c; }
+    __syncthreads();
+    if (first) {
+      for (int i = 0; i < 16; ++i) { zq += sh.wsum[i]; kept += sh.wa[i]; }
+      double t = (double)u[r] * (double)zq;
+      if (!(t >= 0.0)) t = 0.0;
+      target = t >= (double)zq ? zq - 1 : (u64)t;                   // u >= 1 or rounding: the last kept entry that weighs something
+    }
+    int ws = 0;
+    u64 before = 0;
+    for (; ws < 15; ++ws) {
+      if (before + sh.wsum[ws] > target) break;
+      before += sh.wsum[ws];
+    }
+    target -= before;
+    lo += (int64_t)ws * span;
+    hi = min(hi, lo + span);
+    __syncthreads();
+  }
+  {
+    const int64_t i = lo + (int64_t)tid * VEC;
+    u64 q[VEC];
+    u64 s = 0;
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) q[e] = 0;
+    if (i < hi) {
+      float v[VEC];
+      Vec<T, VEC>::ld(v, x + i);
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        if (sample_key<T>(v[e]) >= tkey) q[e] = weight(v[e]);
+        s += q[e];
+      }
+    }
+    u64 inc = wave_scan_u64(s, lane);
+    if (lane == 63) sh.wsum[w] = inc;
+    __syncthreads();
+    for (int k = 0; k < w; ++k) inc += sh.wsum[k];
+    u64 run = inc - s;
+    if (run <= target && target < inc) {                            // exactly one thread: target < the mass of [lo, hi)
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        const bool was_short = run <= target;
+        run += q[e];
+        if (was_short && run > target) {
+          token[r] = i + e;
+          if (prob_out) prob_out[r] = (float)q[e] / (float)zq;
+        }
+      }
+    }
+    if (tid == 0) {
+      if (kept_out) kept_out[r] = (int32_t)kept;
+      if (thresh_out) thresh_out[r] = sample_unkey<T>(tkey);
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int dxa_sample_rows(const void* logits, int64_t ld, int64_t rows, int64_t V, int dtype, float temperature,
+                               int64_t top_k, float top_p, const float* u, int64_t* token, int32_t* kept, float* thresh,
+                               float* prob, dxa_stream_t stream) {
+  DXA_CHECK_ARG(logits && u && token, "dxa_sample_rows: null pointer (logits, u and token are required)");
+  DXA_CHECK_ARG(dtype == DXA_F32 || dtype == DXA_BF16, "dxa_sample_rows: dtype %d (DXA_F32 or DXA_BF16)", dtype);
+  DXA_CHECK_ARG(rows >= 0 && rows <= INT_MAX && V > 0 && V < (1ll << 31) && ld >= V,
+                "dxa_sample_rows: bad shape (rows %lld, V %lld, ld %lld: rows >= 0, 0 < V < 2^31, ld >= V)", (long long)rows,
+                (long long)V, (long long)ld);
+  DXA_CHECK_ARG(temperature > 0.f && temperature < INFINITY, "dxa_sample_rows: temperature %g (must be positive and finite)",
+                (double)temperature);
+  DXA_CHECK_ARG(top_p > 0.f && top_p <= 1.f, "dxa_sample_rows: top_p %g outside (0, 1]", (double)top_p);
+  if (rows == 0) return DXA_OK;
+  const bool vec = V % 8 == 0 && ld % 8 == 0 && al(logits, 16);     // every row starts on a 16-byte boundary
+  const float inv_t = 1.f / temperature;
+  dim3 grid((unsigned)rows);
+#define SAMPLE(T_, V_) hipLaunchKernelGGL((sample_rows_k<T_, V_>), grid, dim3(SMP_THREADS), 0, ST, (const T_*)logits, ld, V, inv_t, top_k, top_p, u, token, kept, thresh, prob)
+  if (dtype == DXA_BF16) { if (vec) SAMPLE(bf16_t, 8); else SAMPLE(bf16_t, 1); }
+  else { if (vec) SAMPLE(float, 4); else SAMPLE(float, 1); }
+#undef SAMPLE
   DXA_CHECK_LAUNCH();
   return DXA_OK;
 }

@@ -1058,6 +1058,29 @@ def argmax_rows(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def sample_rows(logits: torch.Tensor, u: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                return_info: bool = False):
+    """one token per row drawn from softmax(logits / temperature) after HF's top-k (0 = off) and top-p (1 = off) warpers, with the
+    uniform ``u[r]`` in [0, 1) deciding row r's draw -> int64 [rows]; ``return_info``: (token, kept int32 = size of the kept
+    set, thresh fp32 = its smallest logit, prob fp32 = probability of the token).  Semantics: include/dexbotic_amd.h"""
+    if not temperature > 0:
+        raise ValueError(f"sample_rows: temperature {temperature!r} must be positive")
+    if not 0 < top_p <= 1:
+        raise ValueError(f"sample_rows: top_p {top_p!r} outside (0, 1]")
+    rows, V = logits.shape
+    assert logits.stride(1) == 1
+    assert u.dtype == torch.float32 and u.is_contiguous() and u.numel() == rows and u.device == logits.device
+    token = torch.empty(rows, device=logits.device, dtype=torch.int64)
+    kept = thresh = prob = None
+    if return_info:
+        kept = torch.empty(rows, device=logits.device, dtype=torch.int32)
+        thresh = torch.empty(rows, device=logits.device, dtype=torch.float32)
+        prob = torch.empty(rows, device=logits.device, dtype=torch.float32)
+    L.check(lib.dxa_sample_rows(_ptr(logits), logits.stride(0), rows, V, dt(logits), float(temperature), int(top_k), float(top_p),
+                                _ptr(u), _ptr(token), _ptr(kept), _ptr(thresh), _ptr(prob), _stream()), "dxa_sample_rows")
+    return (token, kept, thresh, prob) if return_info else token
+
+
 # ------------------------------------------------------------------------------------------------ image preprocessing
 _RESAMPLE_TABLES: dict = {}
 

@@ -490,11 +490,17 @@ class DexboticForCausalLM(NativePreTrainedMixin, nn.Module):
     def generate(self, input_ids, images=None, max_new_tokens: int = 64, do_sample: bool = False,
                  temperature: float = 1.0, eos_token_id: Optional[int] = None, stopping_criteria=None,
                  return_dict_in_generate: bool = False, generator: Optional[torch.Generator] = None,
-                 attention_mask=None, **kwargs):
+                 attention_mask=None, top_k: Optional[int] = None, top_p: Optional[float] = None, **kwargs):
         """Token-by-token continuation over a KV cache — the subset of GenerationMixin.generate the reference uses
         (discrete_vla_arch.py:33-41: batch 1, greedy or temperature sampling, stopping criteria on the decoded tail).
         Prefill = vision tower + splice + decoder with the cache filled; each step = one cached decoder pass on the
-        new token, lm_head on its hidden state, argmax (first maximal index) or a multinomial draw."""
+        new token, lm_head on its hidden state, argmax (first maximal index) or a draw by K.sample_rows.
+
+        Sampling (``do_sample=True``): HF's warpers in HF's order — temperature, ``top_k`` (None or 0 = off), ``top_p`` (None or
+        1.0 = off) — then the softmax and the draw, all in dxa_sample_rows.  The uniforms of the whole call are drawn once, before
+        the first token: ``torch.rand(max_new_tokens, B, dtype=torch.float32, generator=generator, device=<the generator's
+        device, or the model's when generator is None>)``, moved to the model's device; step t uses row t.  With the same
+        generator state the same tokens come out."""
         dev = self.store.device
         imgs = images.to(device=dev, dtype=self.store.compute_dtype)
         feats = self.model._extract_vision_features(imgs)
@@ -524,11 +530,13 @@ class DexboticForCausalLM(NativePreTrainedMixin, nn.Module):
         last = llm.forward_cached(x, cache, pad)[:, -1].contiguous()
         seq = input_ids.to(dev)
         new_tokens, step_logits = [], []
+        if do_sample:
+            u = torch.rand(max_new_tokens, B, dtype=torch.float32, generator=generator,
+                           device=generator.device if generator is not None else dev).to(dev)
         logits = K.mm_nt(last, W_lm)                                           # [B, V]
         for t in range(max_new_tokens):
             if do_sample:
-                probs = torch.softmax(logits.float() / max(temperature, 1e-6), dim=-1)
-                nxt = torch.multinomial(probs, 1, generator=generator).view(-1)
+                nxt = K.sample_rows(logits, u[t], max(temperature, 1e-6), top_k or 0, top_p or 1.0)
             else:
                 nxt = K.argmax_rows(logits)
             new_tokens.append(nxt)

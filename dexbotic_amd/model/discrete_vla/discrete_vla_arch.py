@@ -57,6 +57,11 @@ class DiscreteVLAForCausalLM(DexboticForCausalLM, ActionOutputForCausalLM):
                 print(f"Attempt {attempt} failed: {e}")
 
     def _real_inference_action(self, input_ids, image_tensor, inference_args={}, **kwargs):
+        """discrete_vla_arch.py:24-50.  The reference's ``generate(do_sample=True, temperature=0.7, ...)`` passes no ``top_k`` /
+        ``top_p``, so transformers' generation defaults hold there: ``top_k = 50``, ``top_p = 1.0``
+        (transformers/generation/configuration_utils.py, ``_get_default_generation_params``) — every digit is drawn from the 50
+        most likely tokens.  A checkpoint's ``generation_config.json`` can override them in the reference; here
+        ``inference_args["top_k"]`` / ``inference_args["top_p"]`` are the override."""
         conv = inference_args.get("conv")
         tokenizer = inference_args.get("tokenizer")
         vocab_size = inference_args.get("vocab_size")
@@ -68,6 +73,7 @@ class DiscreteVLAForCausalLM(DexboticForCausalLM, ActionOutputForCausalLM):
                             max_new_tokens=inference_args.get("max_new_tokens", 1024),
                             do_sample=inference_args.get("do_sample", True),
                             temperature=inference_args.get("temperature", 0.7),
+                            top_k=inference_args.get("top_k", 50), top_p=inference_args.get("top_p", 1.0),
                             return_dict_in_generate=True, stopping_criteria=[criteria],
                             generator=kwargs.get("generator"))
         new = out.sequences[0, input_ids.shape[1]:]

@@ -464,6 +464,27 @@ int dxa_cross_entropy_bwd(const void* logits, int64_t ld, const int64_t* labels,
                           int64_t ignore_index, int dtype, dxa_stream_t stream);
 int dxa_argmax_rows(const void* x, int64_t ld, int64_t* out, int64_t rows, int64_t cols, int dtype,
                     dxa_stream_t stream);
+/* dxa_sample_rows: token[r] = one draw from row r of logits [rows, V] (fp32 or bf16, row stride ld elements, any alignment,
+ *   V < 2^31) — the token choice of GenerationMixin.generate(do_sample=True) as DiscreteVLAForCausalLM calls it
+ *   (dexbotic/model/discrete_vla/discrete_vla_arch.py:35-41), in HF's order of logits warpers.  x = the row read as fp32:
+ *     temperature  z_i = x_i * (1 / temperature)                                       (TemperatureLogitsWarper)
+ *     top-k        active when 0 < top_k < V: tau = the top_k-th largest x counted with multiplicity, keep x_i >= tau — ties at
+ *                  the threshold are all kept, as TopKLogitsWarper keeps them
+ *     top-p        active when top_p < 1: softmax over the entries still kept; entry i stays iff the probability of the kept
+ *                  entries with x_j > x_i is < top_p.  Without ties this is TopPLogitsWarper (ascending cumulative sum
+ *                  <= 1 - top_p removed, at least one kept).  DEVIATION: entries equal to the boundary entry are all kept; HF
+ *                  cuts through a run of equal values wherever its sort put them.
+ *     draw         e_i = exp(z_i - max z) over the kept entries, Z = sum e_i; the first index j in ascending order whose running
+ *                  sum exceeds u[r] * Z (the last kept index with e > 0 if rounding leaves none); prob[r] = e_j / Z
+ *   The largest entry is always kept.  NaN and -inf have probability 0; a row without a finite entry gives token 0 like
+ *   dxa_argmax_rows (kept 0, thresh +inf, prob 0).  u: device, [rows], each in [0, 1).  Optional outputs (NULL to skip):
+ *   kept[r] = number of kept entries, thresh[r] = the smallest kept logit in input units ({i : x_i >= thresh} is the kept set),
+ *   prob[r].  Sums are taken in 2^-40 fixed point (e < 2^-40 counts as 0), so equal inputs and equal u give equal outputs bit for
+ *   bit on every run.  No device allocation, no sort.  Refused with DXA_ERR_BAD_ARG: null logits / u / token, ld < V, V <= 0,
+ *   rows < 0, temperature <= 0, top_p outside (0, 1], a dtype other than DXA_F32 / DXA_BF16. */
+int dxa_sample_rows(const void* logits, int64_t ld, int64_t rows, int64_t V, int dtype, float temperature, int64_t top_k,
+                    float top_p, const float* u, int64_t* token, int32_t* kept, float* thresh, float* prob,
+                    dxa_stream_t stream);
 /* Soft-target cross-entropy (dexbotic/model/navila/loss.py soft_cross_entropy): dxa_cross_entropy_fwd/bwd with Gaussian soft
  * targets for the rows whose label is one of the K `soft_ids` (DEVICE array, int64, distinct, any order, each in [0, V)):
  *   p_k = exp(-(label - soft_ids[k])^2 * inv2s2) / sum_k exp(...)   (inv2s2 = 1 / (2 std^2); fp32 from the integer difference)
