@@ -78,6 +78,180 @@ __global__ __launch_bounds__(TPB) void rope_k(const T* __restrict__ tok, T* __re
   }
 }
 
+// ---------------------------------------------------------------------- per-head RMSNorm + RoPE (Qwen3)
+// HF:qwen3/modeling_qwen3.py: q = rope(q_norm(q_proj(h).view(.., H, D))), the same for k, one RMSNorm(D) weight shared by all heads.
+// Same work item as rope_k, always at 16 bytes per access (VEC = 4 fp32 / 8 bf16): a lane holds VEC dims of the first half of a head
+// and their rotation partners in the second half, so the qn = D / (2 VEC) lanes of a head are ADJACENT lanes of one wavefront
+// (qn is a power of two <= 32 and divides the grid stride) and the per-head sums are a butterfly over them: no LDS round trip.
+// Every lane of a workgroup makes the same number of trips; a lane past the end re-reads item 0 and stores nothing.
+constexpr int QKN_MAX_BLOCKS = 1024;      // workgroups (= rows of weight-gradient partial sums) of the backward
+
+__device__ __forceinline__ float group_sum(float v, int n) {      // sum over the n adjacent lanes (n = 2^j) this lane belongs to
+  for (int o = n >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+template <int VEC>
+__device__ __forceinline__ void rope_row(float (&c)[VEC], float (&sn)[VEC], const float* cos_t, const float* sin_t, int64_t off) {
+#pragma unroll
+  for (int u = 0; u < VEC / 4; ++u) {
+    float c4[4], s4[4];
+    Vec<float, 4>::ld(c4, cos_t + off + 4 * u);
+    Vec<float, 4>::ld(s4, sin_t + off + 4 * u);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { c[4 * u + i] = c4[i]; sn[4 * u + i] = s4[i]; }
+  }
+}
+
+template <typename T, int VEC>
+__global__ __launch_bounds__(TPB) void qknorm_rope_split_k(const T* __restrict__ tok, T* __restrict__ q, T* __restrict__ k,
+                                                           T* __restrict__ v, const T* __restrict__ wq, const T* __restrict__ wk,
+                                                           float eps, float* __restrict__ rstd_out, const float* __restrict__ cos_t,
+                                                           const float* __restrict__ sin_t, const int32_t* __restrict__ pos, int B,
+                                                           int S, int Hq, int Hkv, int D) {
+  const int HS = Hq + 2 * Hkv, HN = Hq + Hkv, half = D / 2, qn = half / VEC;
+  const int64_t total = (int64_t)B * S * HS * qn;
+  const int64_t ld = (int64_t)HS * D;
+  for (int64_t base = (int64_t)blockIdx.x * TPB; base < total; base += (int64_t)gridDim.x * TPB) {
+    const bool ok = base + threadIdx.x < total;
+    const int64_t it = ok ? base + threadIdx.x : 0;
+    const int qd = (int)(it % qn);
+    const int hs = (int)((it / qn) % HS);
+    const int64_t t = it / ((int64_t)qn * HS);
+    const int b = (int)(t / S), s = (int)(t % S);
+    const int d0 = qd * VEC;
+    T* hm;
+    const T* w = nullptr;
+    if (hs < Hq) { hm = q + (((int64_t)b * Hq + hs) * S + s) * D; w = wq; }
+    else if (hs < HN) { hm = k + (((int64_t)b * Hkv + (hs - Hq)) * S + s) * D; w = wk; }
+    else hm = v + (((int64_t)b * Hkv + (hs - HN)) * S + s) * D;
+    const int64_t toff = t * ld + (int64_t)hs * D;
+    float x1[VEC], x2[VEC];
+    Vec<T, VEC>::ld(x1, tok + toff + d0);
+    Vec<T, VEC>::ld(x2, tok + toff + d0 + half);
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) ss += x1[i] * x1[i] + x2[i] * x2[i];
+    ss = group_sum(ss, qn);
+    if (w) {
+      const float rs = rsqrtf(ss / (float)D + eps);
+      if (ok && qd == 0 && rstd_out) rstd_out[t * HN + hs] = rs;
+      float w1[VEC], w2[VEC], c[VEC], sn[VEC];
+      Vec<T, VEC>::ld(w1, w + d0);
+      Vec<T, VEC>::ld(w2, w + d0 + half);
+      rope_row<VEC>(c, sn, cos_t, sin_t, (int64_t)(pos ? pos[t] : s) * half + d0);
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) {
+        // Qwen3RMSNorm: normalised in fp32, cast to the input dtype, THEN times the weight; the rotation as rope_k does it
+        const float y1 = rnd<T>(w1[i] * rnd<T>(x1[i] * rs)), y2 = rnd<T>(w2[i] * rnd<T>(x2[i] * rs));
+        const float cc = rnd<T>(c[i]), sv = rnd<T>(sn[i]);
+        x1[i] = rnd<T>(y1 * cc) + rnd<T>(-y2 * sv);
+        x2[i] = rnd<T>(y2 * cc) + rnd<T>(y1 * sv);
+      }
+    }
+    if (ok) {
+      Vec<T, VEC>::st(hm + d0, x1);
+      Vec<T, VEC>::st(hm + d0 + half, x2);
+    }
+  }
+}
+
+// Backward in one pass: un-rotate dq / dk (rope_k<MERGE>), RMSNorm backward per head from the saved pre-norm qkv and rstd,
+// dqkv token-major, dv passed through.  Weight gradients: every lane keeps the sums of dy * x_hat of its 2 VEC dims in registers,
+// apart for q and k, over all its trips (its dims never change: the grid stride is a multiple of qn); at the end the lanes of a
+// wavefront that hold the same dims fold by butterfly, the four wavefronts through LDS in fixed order, and the workgroup writes ONE
+// row [dw_q (D) | dw_k (D)] of `partial` — the layout of the norm backward kernels, folded by dxa_colsum.  No atomics.
+template <typename T, int VEC>
+__global__ __launch_bounds__(TPB) void qknorm_rope_merge_k(const T* __restrict__ dq, const T* __restrict__ dk,
+                                                           const T* __restrict__ dv, const T* __restrict__ tok,
+                                                           const float* __restrict__ rstd, const T* __restrict__ wq,
+                                                           const T* __restrict__ wk, T* __restrict__ dtok,
+                                                           float* __restrict__ partial, const float* __restrict__ cos_t,
+                                                           const float* __restrict__ sin_t, const int32_t* __restrict__ pos, int B,
+                                                           int S, int Hq, int Hkv, int D) {
+  __shared__ float red[TPB / 64][2 * 256];
+  const int HS = Hq + 2 * Hkv, HN = Hq + Hkv, half = D / 2, qn = half / VEC;
+  const int64_t total = (int64_t)B * S * HS * qn;
+  const int64_t ld = (int64_t)HS * D;
+  float aq[2 * VEC], ak[2 * VEC];
+#pragma unroll
+  for (int i = 0; i < 2 * VEC; ++i) aq[i] = ak[i] = 0.f;
+  for (int64_t base = (int64_t)blockIdx.x * TPB; base < total; base += (int64_t)gridDim.x * TPB) {
+    const bool ok = base + threadIdx.x < total;
+    const int64_t it = ok ? base + threadIdx.x : 0;
+    const int qd = (int)(it % qn);
+    const int hs = (int)((it / qn) % HS);
+    const int64_t t = it / ((int64_t)qn * HS);
+    const int b = (int)(t / S), s = (int)(t % S);
+    const int d0 = qd * VEC;
+    const T* hm;
+    const T* w = nullptr;
+    if (hs < Hq) { hm = dq + (((int64_t)b * Hq + hs) * S + s) * D; w = wq; }
+    else if (hs < HN) { hm = dk + (((int64_t)b * Hkv + (hs - Hq)) * S + s) * D; w = wk; }
+    else hm = dv + (((int64_t)b * Hkv + (hs - HN)) * S + s) * D;
+    const int64_t toff = t * ld + (int64_t)hs * D;
+    float g1[VEC], g2[VEC], x1[VEC], x2[VEC], w1[VEC], w2[VEC];
+    Vec<T, VEC>::ld(g1, hm + d0);
+    Vec<T, VEC>::ld(g2, hm + d0 + half);
+    float rs = 0.f, dot = 0.f;
+    if (w) {
+      float c[VEC], sn[VEC];
+      rope_row<VEC>(c, sn, cos_t, sin_t, (int64_t)(pos ? pos[t] : s) * half + d0);
+      Vec<T, VEC>::ld(x1, tok + toff + d0);
+      Vec<T, VEC>::ld(x2, tok + toff + d0 + half);
+      Vec<T, VEC>::ld(w1, w + d0);
+      Vec<T, VEC>::ld(w2, w + d0 + half);
+      rs = rstd[t * HN + hs];
+      const float live = ok ? 1.f : 0.f;
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) {
+        const float cc = rnd<T>(c[i]), sv = rnd<T>(sn[i]);
+        const float dy1 = g1[i] * cc + g2[i] * sv, dy2 = g2[i] * cc - g1[i] * sv;      // gradient of the normalised, weighted head
+        x1[i] *= rs;
+        x2[i] *= rs;
+        const float a1 = live * dy1 * rnd<T>(x1[i]), a2 = live * dy2 * rnd<T>(x2[i]);
+        if (hs < Hq) { aq[i] += a1; aq[VEC + i] += a2; }
+        else { ak[i] += a1; ak[VEC + i] += a2; }
+        g1[i] = dy1 * w1[i];
+        g2[i] = dy2 * w2[i];
+        dot += g1[i] * x1[i] + g2[i] * x2[i];
+      }
+    }
+    dot = group_sum(dot, qn) / (float)D;
+    if (w) {
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) {
+        g1[i] = rs * (g1[i] - x1[i] * dot);
+        g2[i] = rs * (g2[i] - x2[i] * dot);
+      }
+    }
+    if (ok) {
+      Vec<T, VEC>::st(dtok + toff + d0, g1);
+      Vec<T, VEC>::st(dtok + toff + d0 + half, g2);
+    }
+  }
+  if (!partial) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int o = qn; o < 64; o <<= 1) {
+#pragma unroll
+    for (int i = 0; i < 2 * VEC; ++i) {
+      aq[i] += __shfl_xor(aq[i], o, 64);
+      ak[i] += __shfl_xor(ak[i], o, 64);
+    }
+  }
+  if (lane < qn) {      // lane == its qd: the grid stride and the wavefront's first item are multiples of qn
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) {
+      red[wave][lane * VEC + i] = aq[i];
+      red[wave][half + lane * VEC + i] = aq[VEC + i];
+      red[wave][D + lane * VEC + i] = ak[i];
+      red[wave][D + half + lane * VEC + i] = ak[VEC + i];
+    }
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < 2 * D; c += TPB)
+    partial[(int64_t)blockIdx.x * 2 * D + c] = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
+}
+
 // ---------------------------------------------------------------------------------------------- SwiGLU
 template <typename T, int VEC>
 __global__ __launch_bounds__(TPB) void swiglu_fwd_k(const T* __restrict__ gu, T* __restrict__ out, int64_t rows, int64_t F) {
@@ -524,6 +698,58 @@ extern "C" int dxa_rope_merge(const void* dq, const void* dk, const void* dv, vo
                               const float* sin_t, const int32_t* pos, int B, int S, int Hq, int Hkv, int D, int dtype,
                               dxa_stream_t stream) {
   return dxa_rope_merge_at(dq, dk, dv, dqkv, cos_t, sin_t, pos, B, S, Hq, Hkv, D, S, 0, dtype, stream);
+}
+
+namespace {
+inline bool qkn_head_dim(int D) { return D == 32 || D == 64 || D == 128 || D == 256; }
+// 16-byte work items of one pass over [tokens, (Hq + 2 Hkv) * D]
+inline int64_t qkn_items(int64_t tokens, int Hq, int Hkv, int D, int dtype) {
+  return tokens * (Hq + 2 * Hkv) * (D / 2 / (dtype == DXA_BF16 ? 8 : 4));
+}
+}  // namespace
+
+extern "C" int dxa_qknorm_rope_split(const void* qkv, void* q, void* k, void* v, const void* q_norm_w, const void* k_norm_w,
+                                     float eps, float* rstd, const float* cos_t, const float* sin_t, const int32_t* pos, int B,
+                                     int S, int Hq, int Hkv, int D, int dtype, dxa_stream_t stream) {
+  DXA_CHECK_ARG(qkv && q && k && v && q_norm_w && k_norm_w && cos_t && sin_t && ok_dtype(dtype), "dxa_qknorm_rope_split: bad args");
+  DXA_CHECK_ARG(qkn_head_dim(D), "dxa_qknorm_rope_split: head_dim must be 32, 64, 128 or 256 (got %d)", D);
+  DXA_CHECK_ARG(B >= 0 && S >= 0 && Hq > 0 && Hkv > 0, "dxa_qknorm_rope_split: bad shape B %d S %d Hq %d Hkv %d", B, S, Hq, Hkv);
+  DXA_CHECK_ARG(al(qkv, 16) && al(q, 16) && al(k, 16) && al(v, 16) && al(q_norm_w, 16) && al(k_norm_w, 16) && al(cos_t, 16) && al(sin_t, 16),
+                "dxa_qknorm_rope_split: every tensor must be 16-byte aligned");
+  const int64_t total = qkn_items((int64_t)B * S, Hq, Hkv, D, dtype);
+  if (total == 0) return DXA_OK;
+  dim3 grid(dxa_grid1d(total, TPB));
+  if (dtype == DXA_BF16)
+    hipLaunchKernelGGL((qknorm_rope_split_k<bf16_t, 8>), grid, dim3(TPB), 0, ST, (const bf16_t*)qkv, (bf16_t*)q, (bf16_t*)k, (bf16_t*)v, (const bf16_t*)q_norm_w, (const bf16_t*)k_norm_w, eps, rstd, cos_t, sin_t, pos, B, S, Hq, Hkv, D);
+  else
+    hipLaunchKernelGGL((qknorm_rope_split_k<float, 4>), grid, dim3(TPB), 0, ST, (const float*)qkv, (float*)q, (float*)k, (float*)v, (const float*)q_norm_w, (const float*)k_norm_w, eps, rstd, cos_t, sin_t, pos, B, S, Hq, Hkv, D);
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
+}
+extern "C" int dxa_qknorm_rope_merge_blocks(int64_t tokens, int Hq, int Hkv, int D, int dtype) {
+  DXA_CHECK_ARG(tokens >= 0 && Hq > 0 && Hkv > 0 && qkn_head_dim(D) && ok_dtype(dtype), "dxa_qknorm_rope_merge_blocks: bad args");
+  return dxa_grid1d(qkn_items(tokens, Hq, Hkv, D, dtype), TPB, QKN_MAX_BLOCKS);
+}
+extern "C" int dxa_qknorm_rope_merge(const void* dq, const void* dk, const void* dv, const void* qkv, const float* rstd,
+                                     const void* q_norm_w, const void* k_norm_w, void* dqkv, float* partial_dw, const float* cos_t,
+                                     const float* sin_t, const int32_t* pos, int B, int S, int Hq, int Hkv, int D, int dtype,
+                                     dxa_stream_t stream) {
+  DXA_CHECK_ARG(dq && dk && dv && qkv && rstd && q_norm_w && k_norm_w && dqkv && cos_t && sin_t && ok_dtype(dtype),
+                "dxa_qknorm_rope_merge: bad args");
+  DXA_CHECK_ARG(qkn_head_dim(D), "dxa_qknorm_rope_merge: head_dim must be 32, 64, 128 or 256 (got %d)", D);
+  DXA_CHECK_ARG(B >= 0 && S >= 0 && Hq > 0 && Hkv > 0, "dxa_qknorm_rope_merge: bad shape B %d S %d Hq %d Hkv %d", B, S, Hq, Hkv);
+  DXA_CHECK_ARG(al(dq, 16) && al(dk, 16) && al(dv, 16) && al(qkv, 16) && al(dqkv, 16) && al(q_norm_w, 16) && al(k_norm_w, 16) &&
+                    al(cos_t, 16) && al(sin_t, 16),
+                "dxa_qknorm_rope_merge: every tensor must be 16-byte aligned");
+  const int64_t total = qkn_items((int64_t)B * S, Hq, Hkv, D, dtype);
+  if (total == 0) return DXA_OK;
+  dim3 grid(dxa_grid1d(total, TPB, QKN_MAX_BLOCKS));      // = dxa_qknorm_rope_merge_blocks: the rows of partial_dw
+  if (dtype == DXA_BF16)
+    hipLaunchKernelGGL((qknorm_rope_merge_k<bf16_t, 8>), grid, dim3(TPB), 0, ST, (const bf16_t*)dq, (const bf16_t*)dk, (const bf16_t*)dv, (const bf16_t*)qkv, rstd, (const bf16_t*)q_norm_w, (const bf16_t*)k_norm_w, (bf16_t*)dqkv, partial_dw, cos_t, sin_t, pos, B, S, Hq, Hkv, D);
+  else
+    hipLaunchKernelGGL((qknorm_rope_merge_k<float, 4>), grid, dim3(TPB), 0, ST, (const float*)dq, (const float*)dk, (const float*)dv, (const float*)qkv, rstd, (const float*)q_norm_w, (const float*)k_norm_w, (float*)dqkv, partial_dw, cos_t, sin_t, pos, B, S, Hq, Hkv, D);
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
 }
 
 extern "C" int dxa_swiglu_fwd(const void* gu, void* out, int64_t rows, int64_t F, int dtype, dxa_stream_t stream) {

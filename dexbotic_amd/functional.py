@@ -257,7 +257,7 @@ def _vgrad(st: ParamStore, name: str, val: torch.Tensor) -> None:
 class Qwen2LayerSpec:
     ln1: str
     qkv_w: Tuple[str, str, str]
-    qkv_b: Tuple[str, str, str]
+    qkv_b: Optional[Tuple[str, str, str]]      # None: projections without bias (Qwen3, attention_bias=False)
     o_w: str
     ln2: str
     gu_w: Tuple[str, str]
@@ -271,11 +271,16 @@ class Qwen2LayerSpec:
     F: int = 0
     eps: float = 1e-6
     grad_mode: bool = True     # grad mode of the caller of the current forward (Qwen2Backbone.forward records it)
+    # Qwen3: names of self_attn.q_norm.weight / k_norm.weight [D], adjacent in the arena — the per-head RMSNorm of q and k between the
+    # projection and RoPE (HF:qwen3/modeling_qwen3.py), run inside the RoPE / split pass (dxa_qknorm_rope_split / _merge)
+    qk_norm: Optional[Tuple[str, str]] = None
 
 
 class Qwen2LayerFn(_StoreFn):
     """HF Qwen2DecoderLayer (HF:qwen2/modeling_qwen2.py:258-300) called from cogact_arch.py:97-106:
-    x + o_proj(attn(rope(qkv(rmsnorm(x))))) ; then + down(silu(gate)*up) of rmsnorm."""
+    x + o_proj(attn(rope(qkv(rmsnorm(x))))) ; then + down(silu(gate)*up) of rmsnorm.
+    With ``sp.qk_norm`` the layer is HF Qwen3DecoderLayer: rope(q_norm(q)), rope(k_norm(k)) per head, no projection bias; the
+    backward then also reads the pre-norm qkv and the per-head rstd (kept, or re-run under recompute like everything else)."""
 
     @staticmethod
     def _run(st: ParamStore, sp: Qwen2LayerSpec, x, cos_t, sin_t, kv_start, kv_end, keep: bool = True):
@@ -285,8 +290,14 @@ class Qwen2LayerFn(_StoreFn):
         M = B * S
         nq = (Hq + 2 * Hkv) * D
         h1, rstd1 = K.rmsnorm_fwd(x, st.w(sp.ln1), sp.eps)
-        qkv = K.mm_nt(h1, st.w(*sp.qkv_w, shape=(nq, d)), bias=st.w(*sp.qkv_b, shape=(nq,)))
-        q, k, v = K.rope_split(qkv, cos_t, sin_t, None, B, S, Hq, Hkv, D)
+        qkv = K.mm_nt(h1, st.w(*sp.qkv_w, shape=(nq, d)), bias=st.w(*sp.qkv_b, shape=(nq,)) if sp.qkv_b is not None else None)
+        extra = ()
+        if sp.qk_norm is None:
+            q, k, v = K.rope_split(qkv, cos_t, sin_t, None, B, S, Hq, Hkv, D)
+        else:
+            q, k, v, rstd_qk = K.qknorm_rope_split(qkv, st.w(sp.qk_norm[0]), st.w(sp.qk_norm[1]), sp.eps, cos_t, sin_t, None,
+                                                   B, S, Hq, Hkv, D, want_rstd=keep)
+            extra = (qkv, rstd_qk)
         del qkv
         o = torch.empty((B, S, Hq, D), device=x.device, dtype=x.dtype)
         lse = K.attn_fwd(q, k, v, o.permute(0, 2, 1, 3), causal=True, scale=D ** -0.5, kv_start=kv_start, kv_end=kv_end)
@@ -299,7 +310,7 @@ class Qwen2LayerFn(_StoreFn):
             gu = K.mm_nt(h2, w_gu)
             a = K.swiglu_fwd(gu)
         y = K.mm_nt(a, st.w(sp.down_w), residual=x2)
-        return y, (rstd1, h1, q, k, v, o, lse, x2, rstd2, h2, gu, a)
+        return y, (rstd1, h1, q, k, v, o, lse, x2, rstd2, h2, gu, a) + extra
 
     @staticmethod
     def forward(ctx, x, anchor, st: ParamStore, sp: Qwen2LayerSpec, cos_t, sin_t, kv_start, kv_end):
@@ -310,7 +321,7 @@ class Qwen2LayerFn(_StoreFn):
         if not need:
             return y
         ctx.st, ctx.sp = st, sp
-        _use(ctx, st, sp.ln1, sp.qkv_w, sp.qkv_b, sp.o_w, sp.ln2, sp.gu_w, sp.down_w)
+        _use(ctx, st, sp.ln1, sp.qkv_w, sp.qkv_b, sp.qk_norm, sp.o_w, sp.ln2, sp.gu_w, sp.down_w)
         ctx.aux = (cos_t, sin_t, kv_start, kv_end)
         ctx.recompute = _recompute(ctx, st)
         if ctx.recompute:
@@ -325,9 +336,9 @@ class Qwen2LayerFn(_StoreFn):
         cos_t, sin_t, kv_start, kv_end = ctx.aux
         if ctx.recompute:
             (x,) = ctx.saved_tensors
-            rstd1, h1, q, k, v, o, lse, x2, rstd2, h2, gu, a = Qwen2LayerFn._run(st, sp, x, cos_t, sin_t, kv_start, kv_end)[1]
+            rstd1, h1, q, k, v, o, lse, x2, rstd2, h2, gu, a, *extra = Qwen2LayerFn._run(st, sp, x, cos_t, sin_t, kv_start, kv_end)[1]
         else:
-            x, rstd1, h1, q, k, v, o, lse, x2, rstd2, h2, gu, a = ctx.saved_tensors
+            x, rstd1, h1, q, k, v, o, lse, x2, rstd2, h2, gu, a, *extra = ctx.saved_tensors
         B, S, Hq, Hkv, D, d, F_ = sp.B, sp.S, sp.Hq, sp.Hkv, sp.D, sp.d, sp.F
         M = B * S
         nq = (Hq + 2 * Hkv) * D
@@ -359,11 +370,21 @@ class Qwen2LayerFn(_StoreFn):
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         K.attn_bwd(q, k, v, o.permute(0, 2, 1, 3), lse, do, dq, dk, dv, causal=True, scale=D ** -0.5,
                    kv_start=kv_start, kv_end=kv_end)
-        dqkv = K.rope_merge(dq, dk, dv, cos_t, sin_t, None, B, S, Hq, Hkv, D)
+        if sp.qk_norm is None:
+            dqkv = K.rope_merge(dq, dk, dv, cos_t, sin_t, None, B, S, Hq, Hkv, D)
+        else:
+            qkv, rstd_qk = extra
+            tr_qk = all(st.trainable(n) for n in sp.qk_norm)
+            dqkv, part = K.qknorm_rope_merge(dq, dk, dv, qkv, rstd_qk, st.w(sp.qk_norm[0]), st.w(sp.qk_norm[1]), cos_t, sin_t, None,
+                                             B, S, Hq, Hkv, D, want_dw=tr_qk)
+            if tr_qk:
+                _bgrad(st, sp.qk_norm, part)       # rows of (dw_q | dw_k) partial sums: the column sum that folds the bias gradients
+            del qkv, extra
         del dq, dk, dv, do
         dh1 = _dx(st, sp.qkv_w, (nq, d), dqkv)
         _wgrad(st, sp.qkv_w, dqkv, h1, (nq, d))
-        _bgrad(st, sp.qkv_b, dqkv)
+        if sp.qkv_b is not None:
+            _bgrad(st, sp.qkv_b, dqkv)
         del dqkv
         tr1 = st.trainable(sp.ln1)
         dx, _ = K.rmsnorm_bwd(dh1, x, st.w(sp.ln1), rstd1, dw_out=st.g(sp.ln1) if tr1 else None,

@@ -593,6 +593,46 @@ def rope_merge(dq, dk, dv, cos_t, sin_t, pos, B, S, Hq, Hkv, D):
     return dqkv
 
 
+QKNORM_HEAD_DIMS = (32, 64, 128, 256)      # csrc/elementwise.hip qknorm_rope_*_k
+
+
+def qknorm_rope_split(qkv: torch.Tensor, q_norm_w: torch.Tensor, k_norm_w: torch.Tensor, eps: float, cos_t, sin_t, pos, B, S, Hq, Hkv,
+                      D, want_rstd: bool = True):
+    """rope_split with Qwen3's per-head RMSNorm of q and k (weights [D] in qkv's dtype) in the same pass
+    -> (q, k, v, rstd [B*S, Hq+Hkv] fp32 or None): what qknorm_rope_merge needs besides qkv itself"""
+    assert qkv.is_contiguous() and qkv.shape == (B * S, (Hq + 2 * Hkv) * D)
+    assert q_norm_w.dtype == qkv.dtype == k_norm_w.dtype and q_norm_w.numel() == D == k_norm_w.numel()
+    q = torch.empty((B, Hq, S, D), device=qkv.device, dtype=qkv.dtype)
+    k = torch.empty((B, Hkv, S, D), device=qkv.device, dtype=qkv.dtype)
+    v = torch.empty((B, Hkv, S, D), device=qkv.device, dtype=qkv.dtype)
+    rstd = torch.empty((B * S, Hq + Hkv), device=qkv.device, dtype=torch.float32) if want_rstd else None
+    L.check(lib.dxa_qknorm_rope_split(_ptr(qkv), _ptr(q), _ptr(k), _ptr(v), _ptr(q_norm_w), _ptr(k_norm_w), float(eps), _ptr(rstd),
+                                      _ptr(cos_t), _ptr(sin_t), _ptr(pos), B, S, Hq, Hkv, D, dt(qkv), _stream()),
+            "dxa_qknorm_rope_split")
+    return q, k, v, rstd
+
+
+def qknorm_rope_merge(dq, dk, dv, qkv: torch.Tensor, rstd: torch.Tensor, q_norm_w, k_norm_w, cos_t, sin_t, pos, B, S, Hq, Hkv, D,
+                      want_dw: bool = True):
+    """-> (dqkv [B*S, (Hq+2Hkv)*D] token-major, partial sums [blocks, dw_q | dw_k] fp32 or None): rope_merge followed by the
+    per-head RMSNorm backward, one launch; the caller folds the partials (colsum)"""
+    assert dq.is_contiguous() and dk.is_contiguous() and dv.is_contiguous() and qkv.is_contiguous() and rstd.is_contiguous()
+    assert qkv.shape == (B * S, (Hq + 2 * Hkv) * D) and dq.shape == (B, Hq, S, D) and dk.shape == (B, Hkv, S, D) == dv.shape
+    assert dq.dtype == dk.dtype == dv.dtype == qkv.dtype == q_norm_w.dtype == k_norm_w.dtype
+    assert rstd.shape == (B * S, Hq + Hkv) and rstd.dtype == torch.float32
+    dqkv = torch.empty_like(qkv)
+    part = None
+    if want_dw:
+        nblk = int(lib.dxa_qknorm_rope_merge_blocks(B * S, Hq, Hkv, D, dt(qkv)))
+        if nblk < 0:
+            L.check(nblk, "dxa_qknorm_rope_merge_blocks")
+        part = torch.empty((nblk, 2 * D), device=qkv.device, dtype=torch.float32)
+    L.check(lib.dxa_qknorm_rope_merge(_ptr(dq), _ptr(dk), _ptr(dv), _ptr(qkv), _ptr(rstd), _ptr(q_norm_w), _ptr(k_norm_w), _ptr(dqkv),
+                                      _ptr(part), _ptr(cos_t), _ptr(sin_t), _ptr(pos), B, S, Hq, Hkv, D, dt(qkv), _stream()),
+            "dxa_qknorm_rope_merge")
+    return dqkv, part
+
+
 # ------------------------------------------------------------------------------------------- attention
 def _bhsd_strides(t: torch.Tensor) -> Tuple[int, int, int]:
     """t is a [B,H,S,D] VIEW (any memory order) with D contiguous -> (sb, sh, ss)"""

@@ -25,7 +25,7 @@ from .. import kernels as K
 from ..constants import IGNORE_INDEX
 from ..engine import ParamStore, attach_parameters, building
 from ..splice import PlanCache, SplicePlan, build_splice_plan
-from .llm.qwen2 import Qwen2Backbone, Qwen2Config
+from .llm.qwen3 import build_llm_backbone, llm_config_from_any
 from .modules.mm_projector.builder import build_vision_projector
 from .modules.mm_vision.builder import build_vision_tower
 
@@ -41,8 +41,8 @@ def _hf_config_base():
 class DexboticConfig(_hf_config_base()):
     """``transformers.PretrainedConfig`` subclass like the reference's (dexbotic_arch.py:17-23), registered with
     ``AutoConfig`` under the same ``model_type`` string, so ``AutoConfig.from_pretrained(ckpt)`` / ``config.json`` written
-    by either implementation resolve to it.  ``llm_config`` may be a Qwen2Config, a dict, an HF config object or a
-    directory with config.json; its keys are merged in (``_merge_llm``, dexbotic_arch.py:79-85) so ``hidden_size`` /
+    by either implementation resolve to it.  ``llm_config`` may be a Qwen2Config / Qwen3Config, a dict, an HF config object or a
+    directory with config.json (``model_type`` "qwen2", the default, or "qwen3" picks the decoder); its keys are merged in (``_merge_llm``, dexbotic_arch.py:79-85) so ``hidden_size`` /
     ``vocab_size`` are top-level."""
     model_type = "dexbotic"
 
@@ -52,7 +52,7 @@ class DexboticConfig(_hf_config_base()):
         if isinstance(llm_config, str):
             with open(os.path.join(llm_config, "config.json")) as f:
                 llm_config = json.load(f)
-        self.llm_config = Qwen2Config.from_any(llm_config if llm_config is not None else {})
+        self.llm_config = llm_config_from_any(llm_config if llm_config is not None else {})
         self.mm_projector_type = mm_projector_type
         self.mm_vision_tower = mm_vision_tower
         self.chat_template = chat_template
@@ -169,7 +169,7 @@ class DexboticVLMModel(nn.Module):
         if getattr(config, "mm_vision_tower", None) is not None:
             self.mm_vision_tower = self._build_mm_vision_module(config.mm_vision_tower)
             self.mm_projector = self._build_mm_projector_module(config)
-        self.llm = Qwen2Backbone(store, "model.llm.", config.llm_config)
+        self.llm = build_llm_backbone(store, "model.llm.", config.llm_config)
         self._last_plan: Optional[SplicePlan] = None
         self._plans = PlanCache()
 

@@ -49,13 +49,22 @@ class Qwen2Config:
         keys = {f for f in cls.__dataclass_fields__}
         kw = {k: v for k, v in d.items() if k in keys and v is not None}
         kw["rope_theta"] = theta
-        if kw.get("model_type", "qwen2") != "qwen2":
-            raise NotImplementedError(f"llm_config.model_type={kw['model_type']!r}: only the Qwen2 backbone of "
-                                      "DB-CogACT is implemented natively")
+        if kw.get("model_type", cls.model_type) != cls.model_type:
+            raise NotImplementedError(f"llm_config.model_type={kw['model_type']!r} is not {cls.model_type!r}: the decoder backbones "
+                                      "implemented natively are 'qwen2' (Qwen2Backbone) and 'qwen3' (Qwen3Backbone, "
+                                      "model/llm/qwen3.py: llm_config_from_any picks the class by model_type)")
+        cls._check_supported(d)
         return cls(**kw)
+
+    @classmethod
+    def _check_supported(cls, d: dict) -> None:
+        """refuse what the native layer does not compute (nothing for Qwen2; Qwen3Config overrides it)"""
 
 
 class Qwen2Backbone(nn.Module):
+    attention_bias = True       # q / k / v projections carry a bias (Qwen2); Qwen3Backbone: none
+    qk_norm = False             # per-head RMSNorm of q and k before RoPE (Qwen3Backbone)
+
     def __init__(self, store: ParamStore, prefix: str, config: Qwen2Config):
         super().__init__()
         self.store, self.p, self.config = store, prefix, config
@@ -69,10 +78,14 @@ class Qwen2Backbone(nn.Module):
             lp = f"{prefix}layers.{i}."
             store.new_bucket()
             qkv_w = tuple(lp + f"self_attn.{n}_proj.weight" for n in "qkv")
-            qkv_b = tuple(lp + f"self_attn.{n}_proj.bias" for n in "qkv")
+            qkv_b = tuple(lp + f"self_attn.{n}_proj.bias" for n in "qkv") if self.attention_bias else None
+            qk_norm = (lp + "self_attn.q_norm.weight", lp + "self_attn.k_norm.weight") if self.qk_norm else None
             store.register([(lp + "input_layernorm.weight", (d,))])
             store.register([(qkv_w[0], (Hq * hd, d)), (qkv_w[1], (Hkv * hd, d)), (qkv_w[2], (Hkv * hd, d))])
-            store.register([(qkv_b[0], (Hq * hd,)), (qkv_b[1], (Hkv * hd,)), (qkv_b[2], (Hkv * hd,))])
+            if qkv_b is not None:
+                store.register([(qkv_b[0], (Hq * hd,)), (qkv_b[1], (Hkv * hd,)), (qkv_b[2], (Hkv * hd,))])
+            if qk_norm is not None:
+                store.register([(qk_norm[0], (hd,)), (qk_norm[1], (hd,))])
             store.register([(lp + "self_attn.o_proj.weight", (d, Hq * hd))])
             store.register([(lp + "post_attention_layernorm.weight", (d,))])
             gu = (lp + "mlp.gate_proj.weight", lp + "mlp.up_proj.weight")
@@ -81,7 +94,7 @@ class Qwen2Backbone(nn.Module):
             self.layer_specs.append(Fn.Qwen2LayerSpec(
                 ln1=lp + "input_layernorm.weight", qkv_w=qkv_w, qkv_b=qkv_b, o_w=lp + "self_attn.o_proj.weight",
                 ln2=lp + "post_attention_layernorm.weight", gu_w=gu, down_w=lp + "mlp.down_proj.weight",
-                Hq=Hq, Hkv=Hkv, D=hd, d=d, F=f, eps=c.rms_norm_eps))
+                Hq=Hq, Hkv=Hkv, D=hd, d=d, F=f, eps=c.rms_norm_eps, qk_norm=qk_norm))
         store.new_bucket()
         store.register([(prefix + "norm.weight", (d,))])
         self._rope = {}
@@ -171,8 +184,12 @@ class Qwen2Backbone(nn.Module):
             Hq, Hkv, D, F_ = sp.Hq, sp.Hkv, sp.D, sp.F
             nq = (Hq + 2 * Hkv) * D
             h1, _ = K.rmsnorm_fwd(x, st.w(sp.ln1), sp.eps)
-            qkv = K.mm_nt(h1, st.w(*sp.qkv_w, shape=(nq, d)), bias=st.w(*sp.qkv_b, shape=(nq,)))
-            q, k, v = K.rope_split(qkv, cos_t, sin_t, pos, B, S, Hq, Hkv, D)
+            qkv = K.mm_nt(h1, st.w(*sp.qkv_w, shape=(nq, d)), bias=st.w(*sp.qkv_b, shape=(nq,)) if sp.qkv_b is not None else None)
+            if sp.qk_norm is None:
+                q, k, v = K.rope_split(qkv, cos_t, sin_t, pos, B, S, Hq, Hkv, D)
+            else:
+                q, k, v, _ = K.qknorm_rope_split(qkv, st.w(sp.qk_norm[0]), st.w(sp.qk_norm[1]), sp.eps, cos_t, sin_t, pos,
+                                                 B, S, Hq, Hkv, D, want_rstd=False)
             cache.k[i][:, :, past:total].copy_(k)
             cache.v[i][:, :, past:total].copy_(v)
             o = torch.empty((B, S, Hq, D), device=x.device, dtype=x.dtype)

@@ -227,6 +227,25 @@ int dxa_rope_split_at(const void* qkv, void* q, void* k, void* v, const float* c
                       int S, int Hq, int Hkv, int D, int S_cap, int s0, int dtype, dxa_stream_t stream);
 int dxa_rope_merge_at(const void* dq, const void* dk, const void* dv, void* dqkv, const float* cos_t, const float* sin_t,
                       const int32_t* pos, int B, int S, int Hq, int Hkv, int D, int S_cap, int s0, int dtype, dxa_stream_t stream);
+/* Qwen3's per-head RMSNorm of q and k (HF:qwen3/modeling_qwen3.py: q = rope(q_norm(q_proj(h).view(.., H, D))), likewise k; the
+ * weights q_norm_w / k_norm_w [D], in the tensors' dtype, are shared by all heads; v is not normalised) inside the same pass:
+ * y = w * round_to_dtype(x * rsqrt(mean_D(x^2) + eps)) per (token, head), statistics in fp32, then the rotation of dxa_rope_split.
+ * D in {32, 64, 128, 256}; every tensor 16-byte aligned; fp32 and bf16.
+ * dxa_qknorm_rope_split : qkv token-major -> q, k, v head-major as dxa_rope_split; rstd [B*S, Hq+Hkv] fp32 (q heads, then k heads)
+ *                         is written for the backward (NULL: not written).
+ * dxa_qknorm_rope_merge : dq, dk, dv head-major + the saved pre-norm qkv and rstd -> dqkv token-major in one launch: inverse
+ *                         rotation, then dx = rstd * (w*dy - x_hat * mean_D(w*dy*x_hat)) per head; dv is passed through.
+ *                         partial_dw (NULL: weight gradients not wanted): [dxa_qknorm_rope_merge_blocks(B*S, ..), 2*D] fp32 rows
+ *                         of (dw_q | dw_k) partial sums over tokens and heads, every row written; reduce them with dxa_colsum.
+ *                         No atomics: the same inputs give the same bits. */
+int dxa_qknorm_rope_split(const void* qkv, void* q, void* k, void* v, const void* q_norm_w, const void* k_norm_w, float eps,
+                          float* rstd, const float* cos_t, const float* sin_t, const int32_t* pos, int B, int S, int Hq, int Hkv,
+                          int D, int dtype, dxa_stream_t stream);
+int dxa_qknorm_rope_merge(const void* dq, const void* dk, const void* dv, const void* qkv, const float* rstd,
+                          const void* q_norm_w, const void* k_norm_w, void* dqkv, float* partial_dw, const float* cos_t,
+                          const float* sin_t, const int32_t* pos, int B, int S, int Hq, int Hkv, int D, int dtype,
+                          dxa_stream_t stream);
+int dxa_qknorm_rope_merge_blocks(int64_t tokens, int Hq, int Hkv, int D, int dtype);
 
 /* ------------------------------------------------------------------------------------------------
  * Attention.  Replaces torch SDPA at HF:qwen2/modeling_qwen2.py:143-235 (causal + key padding, GQA),
