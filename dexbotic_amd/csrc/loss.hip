@@ -13,75 +13,6 @@
 namespace {
 
 template <typename T, int VEC>
-__global__ __launch_bounds__(256) void ce_fwd_k(const T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
-                                                float* __restrict__ row_loss, float* __restrict__ lse_out, int64_t V,
-                                                int64_t ignore_index) {
-  __shared__ float red_m[4], red_s[4];
-  const int64_t r = blockIdx.x;
-  const T* x = logits + r * ld;
-  float m = -INFINITY, s = 0.f;
-  for (int64_t i = (int64_t)threadIdx.x * VEC; i < V; i += 256 * VEC) {
-    float v[VEC];
-    Vec<T, VEC>::ld(v, x + i);
-    float vm = v[0];
-#pragma unroll
-    for (int e = 1; e < VEC; ++e) vm = fmaxf(vm, v[e]);
-    const float mn = fmaxf(m, vm);
-    float acc = s * expf(m - mn);          // m = -inf on the first visit: s = 0, exp(-inf) = 0
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) acc += expf(v[e] - mn);
-    m = mn; s = acc;
-  }
-  // fold (m, s) pairs: wave shuffle, then the 4 waves through LDS
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-    const float mn = fmaxf(m, m2);
-    s = (mn == -INFINITY) ? 0.f : s * expf(m - mn) + s2 * expf(m2 - mn);
-    m = mn;
-  }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) { red_m[w] = m; red_s[w] = s; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float M = red_m[0], S = red_s[0];
-    for (int i = 1; i < 4; ++i) {
-      const float mn = fmaxf(M, red_m[i]);
-      S = (mn == -INFINITY) ? 0.f : S * expf(M - mn) + red_s[i] * expf(red_m[i] - mn);
-      M = mn;
-    }
-    const float lse = M + logf(S);
-    lse_out[r] = lse;
-    const int64_t lab = labels[r];
-    row_loss[r] = (lab == ignore_index || lab < 0 || lab >= V) ? 0.f : lse - ldf<T>(x + lab);
-  }
-}
-
-// dlogits = (softmax(x) - onehot(label)) * g ; g = gscale[0] * scale ; ignored rows -> 0.  May run in place.
-template <typename T, int VEC>
-__global__ __launch_bounds__(256) void ce_bwd_k(const T* logits, int64_t ld, const int64_t* __restrict__ labels,
-                                                const float* __restrict__ lse, const float* __restrict__ gscale, float scale,
-                                                T* dlogits, int64_t ldd, int64_t V, int64_t ignore_index) {
-  const int64_t r = blockIdx.x;
-  const T* x = logits + r * ld;
-  T* d = dlogits + r * ldd;
-  const int64_t lab = labels[r];
-  const bool ign = (lab == ignore_index || lab < 0 || lab >= V);
-  const float g = ign ? 0.f : (gscale ? gscale[0] : 1.f) * scale;
-  const float l = lse[r];
-  for (int64_t i = (int64_t)threadIdx.x * VEC; i < V; i += 256 * VEC) {
-    float v[VEC];
-    Vec<T, VEC>::ld(v, x + i);
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-      const float p = ign ? 0.f : expf(v[e] - l);
-      v[e] = (p - ((i + e) == lab ? 1.f : 0.f)) * g;
-    }
-    Vec<T, VEC>::st(d + i, v);
-  }
-}
-
-template <typename T, int VEC>
 __global__ __launch_bounds__(256) void argmax_rows_k(const T* __restrict__ xin, int64_t ld, int64_t* __restrict__ out,
                                                      int64_t cols) {
   __shared__ float red_v[4];
@@ -162,45 +93,6 @@ inline bool al(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p)
 
 #define ST ((hipStream_t)stream)
 
-extern "C" int dxa_cross_entropy_fwd(const void* logits, int64_t ld, const int64_t* labels, float* row_loss, float* lse,
-                                     int64_t rows, int64_t V, int64_t ignore_index, int dtype, dxa_stream_t stream) {
-  DXA_CHECK_ARG(logits && labels && row_loss && lse && rows >= 0 && V > 0 && ld >= V &&
-                (dtype == DXA_F32 || dtype == DXA_BF16), "dxa_cross_entropy_fwd: bad args");
-  if (rows == 0) return DXA_OK;
-  const size_t es = dtype == DXA_BF16 ? 2 : 4;
-  const bool vec = V % 4 == 0 && ld % 4 == 0 && al(logits, 4 * es);
-  dim3 grid((unsigned)rows);
-  if (dtype == DXA_BF16) {
-    if (vec) hipLaunchKernelGGL((ce_fwd_k<bf16_t, 4>), grid, dim3(256), 0, ST, (const bf16_t*)logits, ld, labels, row_loss, lse, V, ignore_index);
-    else hipLaunchKernelGGL((ce_fwd_k<bf16_t, 1>), grid, dim3(256), 0, ST, (const bf16_t*)logits, ld, labels, row_loss, lse, V, ignore_index);
-  } else {
-    if (vec) hipLaunchKernelGGL((ce_fwd_k<float, 4>), grid, dim3(256), 0, ST, (const float*)logits, ld, labels, row_loss, lse, V, ignore_index);
-    else hipLaunchKernelGGL((ce_fwd_k<float, 1>), grid, dim3(256), 0, ST, (const float*)logits, ld, labels, row_loss, lse, V, ignore_index);
-  }
-  DXA_CHECK_LAUNCH();
-  return DXA_OK;
-}
-
-extern "C" int dxa_cross_entropy_bwd(const void* logits, int64_t ld, const int64_t* labels, const float* lse,
-                                     const float* gscale, float scale, void* dlogits, int64_t ldd, int64_t rows, int64_t V,
-                                     int64_t ignore_index, int dtype, dxa_stream_t stream) {
-  DXA_CHECK_ARG(logits && labels && lse && dlogits && rows >= 0 && V > 0 && ld >= V && ldd >= V &&
-                (dtype == DXA_F32 || dtype == DXA_BF16), "dxa_cross_entropy_bwd: bad args");
-  if (rows == 0) return DXA_OK;
-  const size_t es = dtype == DXA_BF16 ? 2 : 4;
-  const bool vec = V % 4 == 0 && ld % 4 == 0 && ldd % 4 == 0 && al(logits, 4 * es) && al(dlogits, 4 * es);
-  dim3 grid((unsigned)rows);
-  if (dtype == DXA_BF16) {
-    if (vec) hipLaunchKernelGGL((ce_bwd_k<bf16_t, 4>), grid, dim3(256), 0, ST, (const bf16_t*)logits, ld, labels, lse, gscale, scale, (bf16_t*)dlogits, ldd, V, ignore_index);
-    else hipLaunchKernelGGL((ce_bwd_k<bf16_t, 1>), grid, dim3(256), 0, ST, (const bf16_t*)logits, ld, labels, lse, gscale, scale, (bf16_t*)dlogits, ldd, V, ignore_index);
-  } else {
-    if (vec) hipLaunchKernelGGL((ce_bwd_k<float, 4>), grid, dim3(256), 0, ST, (const float*)logits, ld, labels, lse, gscale, scale, (float*)dlogits, ldd, V, ignore_index);
-    else hipLaunchKernelGGL((ce_bwd_k<float, 1>), grid, dim3(256), 0, ST, (const float*)logits, ld, labels, lse, gscale, scale, (float*)dlogits, ldd, V, ignore_index);
-  }
-  DXA_CHECK_LAUNCH();
-  return DXA_OK;
-}
-
 extern "C" int dxa_argmax_rows(const void* x, int64_t ld, int64_t* out, int64_t rows, int64_t cols, int dtype,
                                dxa_stream_t stream) {
   DXA_CHECK_ARG(x && out && rows >= 0 && cols > 0 && ld >= cols && (dtype == DXA_F32 || dtype == DXA_BF16),
@@ -225,10 +117,10 @@ extern "C" int dxa_argmax_rows(const void* x, int64_t ld, int64_t* out, int64_t 
   return DXA_OK;
 }
 
-// ------------------------------------------------------------------------------- soft-target cross-entropy
-// dexbotic/model/navila/loss.py soft_cross_entropy: a row whose label is one of the K soft ("time") token ids is scored against a
-// Gaussian over those ids centred on the label; every other row is ce_fwd_k / ce_bwd_k, instruction for instruction (K = 0 gives
-// their bits).  The kernels above are left as they are.
+// ------------------------------------------------------------------------- cross-entropy, hard and soft targets
+// One kernel pair serves dxa_cross_entropy_* and dxa_soft_cross_entropy_*.  dexbotic/model/navila/loss.py soft_cross_entropy: a row
+// whose label is one of the K soft ("time") token ids is scored against a Gaussian over those ids centred on the label; every other
+// row is the plain cross-entropy.  dxa_cross_entropy_* launches the pair with K = 0 (no soft ids: every row is a plain one).
 namespace {
 
 constexpr int SOFT_CE_MAX_K = 64;
@@ -261,11 +153,12 @@ __global__ __launch_bounds__(256) void soft_ce_fwd_k(const T* __restrict__ logit
 #pragma unroll
     for (int e = 1; e < VEC; ++e) vm = fmaxf(vm, v[e]);
     const float mn = fmaxf(m, vm);
-    float acc = s * expf(m - mn);
+    float acc = s * expf(m - mn);          // m = -inf on the first visit: s = 0, exp(-inf) = 0
 #pragma unroll
     for (int e = 0; e < VEC; ++e) acc += expf(v[e] - mn);
     m = mn; s = acc;
   }
+  // fold (m, s) pairs: wave shuffle, then the 4 waves through LDS
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
@@ -303,9 +196,12 @@ __global__ __launch_bounds__(256) void soft_ce_fwd_k(const T* __restrict__ logit
   }
 }
 
-// as ce_bwd_k; a soft row first keeps z[s_k] of its K soft ids (dlogits may alias logits), writes softmax * g everywhere, and then
-// the K soft columns once more as (softmax - p_k) * g: one rounding per element, no search per element
-template <typename T, int VEC>
+// dlogits = (softmax(x) - onehot(label)) * g ; g = gscale[0] * scale ; ignored rows -> 0.  May run in place.
+// A soft row first keeps z[s_k] of its K soft ids (dlogits may alias logits), writes softmax * g everywhere, and then
+// the K soft columns once more as (softmax - p_k) * g: one rounding per element, no search per element.  SOFT = false (launched
+// for K = 0) compiles the soft rows' LDS and branches away: with them the K = 0 launch measured 2 - 6 us over 120 - 126 us at
+// [512, 152064] bf16 (profiles/ce_merge.txt)
+template <typename T, int VEC, bool SOFT>
 __global__ __launch_bounds__(256) void soft_ce_bwd_k(const T* logits, int64_t ld, const int64_t* __restrict__ labels,
                                                      const float* __restrict__ lse, const float* __restrict__ gscale, float scale,
                                                      T* dlogits, int64_t ldd, int64_t V, int64_t ignore_index,
@@ -318,7 +214,7 @@ __global__ __launch_bounds__(256) void soft_ce_bwd_k(const T* logits, int64_t ld
   const bool ign = (lab == ignore_index || lab < 0 || lab >= V);
   const float g = ign ? 0.f : (gscale ? gscale[0] : 1.f) * scale;
   const float l = lse[r];
-  const bool soft = !ign && soft_find(soft_ids, K, lab) >= 0;          // uniform over the workgroup
+  const bool soft = SOFT && !ign && soft_find(soft_ids, K, lab) >= 0;  // uniform over the workgroup
   if (soft) {
     if ((int)threadIdx.x < K) {
       const int64_t sk = soft_ids[threadIdx.x];
@@ -365,43 +261,73 @@ int check_soft_ids(const char* who, const int64_t* soft_ids, const int64_t* host
   return DXA_OK;
 }
 
-}  // namespace
-
-extern "C" int dxa_soft_cross_entropy_fwd(const void* logits, int64_t ld, const int64_t* labels, float* row_loss, float* lse,
-                                          int64_t rows, int64_t V, int64_t ignore_index, const int64_t* soft_ids,
-                                          const int64_t* soft_ids_host, int K, float inv2s2, int dtype, dxa_stream_t stream) {
+// argument checks and launch of both forward entry points; `who` names the caller in the error text
+int ce_fwd_launch(const char* who, const void* logits, int64_t ld, const int64_t* labels, float* row_loss, float* lse, int64_t rows,
+                  int64_t V, int64_t ignore_index, const int64_t* soft_ids, const int64_t* soft_ids_host, int K, float inv2s2,
+                  int dtype, dxa_stream_t stream) {
   DXA_CHECK_ARG(logits && labels && row_loss && lse && rows >= 0 && V > 0 && ld >= V &&
-                (dtype == DXA_F32 || dtype == DXA_BF16), "dxa_soft_cross_entropy_fwd: bad args");
-  if (int rc = check_soft_ids("dxa_soft_cross_entropy_fwd", soft_ids, soft_ids_host, K, V)) return rc;
+                (dtype == DXA_F32 || dtype == DXA_BF16), "%s: bad args", who);
+  if (int rc = check_soft_ids(who, soft_ids, soft_ids_host, K, V)) return rc;
   if (rows == 0) return DXA_OK;
   const size_t es = dtype == DXA_BF16 ? 2 : 4;
   const bool vec = V % 4 == 0 && ld % 4 == 0 && al(logits, 4 * es);
   dim3 grid((unsigned)rows);
-#define SOFT_FWD(T_, V_) hipLaunchKernelGGL((soft_ce_fwd_k<T_, V_>), grid, dim3(256), 0, ST, (const T_*)logits, ld, labels, row_loss, lse, V, ignore_index, soft_ids, K, inv2s2)
-  if (dtype == DXA_BF16) { if (vec) SOFT_FWD(bf16_t, 4); else SOFT_FWD(bf16_t, 1); }
-  else { if (vec) SOFT_FWD(float, 4); else SOFT_FWD(float, 1); }
-#undef SOFT_FWD
+#define CE_FWD(T_, V_) hipLaunchKernelGGL((soft_ce_fwd_k<T_, V_>), grid, dim3(256), 0, ST, (const T_*)logits, ld, labels, row_loss, lse, V, ignore_index, soft_ids, K, inv2s2)
+  if (dtype == DXA_BF16) { if (vec) CE_FWD(bf16_t, 4); else CE_FWD(bf16_t, 1); }
+  else { if (vec) CE_FWD(float, 4); else CE_FWD(float, 1); }
+#undef CE_FWD
   DXA_CHECK_LAUNCH();
   return DXA_OK;
+}
+
+int ce_bwd_launch(const char* who, const void* logits, int64_t ld, const int64_t* labels, const float* lse, const float* gscale,
+                  float scale, void* dlogits, int64_t ldd, int64_t rows, int64_t V, int64_t ignore_index, const int64_t* soft_ids,
+                  const int64_t* soft_ids_host, int K, float inv2s2, int dtype, dxa_stream_t stream) {
+  DXA_CHECK_ARG(logits && labels && lse && dlogits && rows >= 0 && V > 0 && ld >= V && ldd >= V &&
+                (dtype == DXA_F32 || dtype == DXA_BF16), "%s: bad args", who);
+  if (int rc = check_soft_ids(who, soft_ids, soft_ids_host, K, V)) return rc;
+  if (rows == 0) return DXA_OK;
+  const size_t es = dtype == DXA_BF16 ? 2 : 4;
+  const bool vec = V % 4 == 0 && ld % 4 == 0 && ldd % 4 == 0 && al(logits, 4 * es) && al(dlogits, 4 * es);
+  dim3 grid((unsigned)rows);
+#define CE_BWD_S(T_, V_, S_) hipLaunchKernelGGL((soft_ce_bwd_k<T_, V_, S_>), grid, dim3(256), 0, ST, (const T_*)logits, ld, labels, lse, gscale, scale, (T_*)dlogits, ldd, V, ignore_index, soft_ids, K, inv2s2)
+#define CE_BWD(T_, V_) do { if (K > 0) CE_BWD_S(T_, V_, true); else CE_BWD_S(T_, V_, false); } while (0)
+  if (dtype == DXA_BF16) { if (vec) CE_BWD(bf16_t, 4); else CE_BWD(bf16_t, 1); }
+  else { if (vec) CE_BWD(float, 4); else CE_BWD(float, 1); }
+#undef CE_BWD
+#undef CE_BWD_S
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
+}
+
+}  // namespace
+
+extern "C" int dxa_cross_entropy_fwd(const void* logits, int64_t ld, const int64_t* labels, float* row_loss, float* lse,
+                                     int64_t rows, int64_t V, int64_t ignore_index, int dtype, dxa_stream_t stream) {
+  return ce_fwd_launch("dxa_cross_entropy_fwd", logits, ld, labels, row_loss, lse, rows, V, ignore_index, nullptr, nullptr, 0, 0.f,
+                       dtype, stream);
+}
+
+extern "C" int dxa_cross_entropy_bwd(const void* logits, int64_t ld, const int64_t* labels, const float* lse,
+                                     const float* gscale, float scale, void* dlogits, int64_t ldd, int64_t rows, int64_t V,
+                                     int64_t ignore_index, int dtype, dxa_stream_t stream) {
+  return ce_bwd_launch("dxa_cross_entropy_bwd", logits, ld, labels, lse, gscale, scale, dlogits, ldd, rows, V, ignore_index, nullptr,
+                       nullptr, 0, 0.f, dtype, stream);
+}
+
+extern "C" int dxa_soft_cross_entropy_fwd(const void* logits, int64_t ld, const int64_t* labels, float* row_loss, float* lse,
+                                          int64_t rows, int64_t V, int64_t ignore_index, const int64_t* soft_ids,
+                                          const int64_t* soft_ids_host, int K, float inv2s2, int dtype, dxa_stream_t stream) {
+  return ce_fwd_launch("dxa_soft_cross_entropy_fwd", logits, ld, labels, row_loss, lse, rows, V, ignore_index, soft_ids, soft_ids_host,
+                       K, inv2s2, dtype, stream);
 }
 
 extern "C" int dxa_soft_cross_entropy_bwd(const void* logits, int64_t ld, const int64_t* labels, const float* lse,
                                           const float* gscale, float scale, void* dlogits, int64_t ldd, int64_t rows, int64_t V,
                                           int64_t ignore_index, const int64_t* soft_ids, const int64_t* soft_ids_host, int K,
                                           float inv2s2, int dtype, dxa_stream_t stream) {
-  DXA_CHECK_ARG(logits && labels && lse && dlogits && rows >= 0 && V > 0 && ld >= V && ldd >= V &&
-                (dtype == DXA_F32 || dtype == DXA_BF16), "dxa_soft_cross_entropy_bwd: bad args");
-  if (int rc = check_soft_ids("dxa_soft_cross_entropy_bwd", soft_ids, soft_ids_host, K, V)) return rc;
-  if (rows == 0) return DXA_OK;
-  const size_t es = dtype == DXA_BF16 ? 2 : 4;
-  const bool vec = V % 4 == 0 && ld % 4 == 0 && ldd % 4 == 0 && al(logits, 4 * es) && al(dlogits, 4 * es);
-  dim3 grid((unsigned)rows);
-#define SOFT_BWD(T_, V_) hipLaunchKernelGGL((soft_ce_bwd_k<T_, V_>), grid, dim3(256), 0, ST, (const T_*)logits, ld, labels, lse, gscale, scale, (T_*)dlogits, ldd, V, ignore_index, soft_ids, K, inv2s2)
-  if (dtype == DXA_BF16) { if (vec) SOFT_BWD(bf16_t, 4); else SOFT_BWD(bf16_t, 1); }
-  else { if (vec) SOFT_BWD(float, 4); else SOFT_BWD(float, 1); }
-#undef SOFT_BWD
-  DXA_CHECK_LAUNCH();
-  return DXA_OK;
+  return ce_bwd_launch("dxa_soft_cross_entropy_bwd", logits, ld, labels, lse, gscale, scale, dlogits, ldd, rows, V, ignore_index,
+                       soft_ids, soft_ids_host, K, inv2s2, dtype, stream);
 }
 
 // ------------------------------------------------------------------------------------ sampled token choice

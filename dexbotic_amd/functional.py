@@ -283,22 +283,33 @@ class Qwen2LayerFn(_StoreFn):
     backward then also reads the pre-norm qkv and the per-head rstd (kept, or re-run under recompute like everything else)."""
 
     @staticmethod
-    def _run(st: ParamStore, sp: Qwen2LayerSpec, x, cos_t, sin_t, kv_start, kv_end, keep: bool = True):
-        """the layer's forward launches -> (y, what the backward reads besides x).  ``keep`` = False (no gradient will be asked
-        for: serving): the gated MLP's pre-activations are not stored and SiLU * up runs in the gate / up product's epilogue"""
-        B, S, Hq, Hkv, D, d, F_ = sp.B, sp.S, sp.Hq, sp.Hkv, sp.D, sp.d, sp.F
+    def _run(st: ParamStore, sp: Qwen2LayerSpec, B: int, S: int, x, cos_t, sin_t, kv_start, kv_end, keep: bool = True, pos=None,
+             cache=None):
+        """the layer's forward launches on x [B*S, d] -> (y, what the backward reads besides x): training, serving and the
+        key/value-cached path (Qwen2Backbone.forward_cached) all run this one sequence.  ``keep`` = False (no gradient will be asked
+        for: serving): the gated MLP's pre-activations are not stored and SiLU * up runs in the gate / up product's epilogue.
+        ``pos``: int32 rows of the rotary tables per token (None: token s of a sequence reads row s).  ``cache`` (with ``keep`` =
+        False only) = (k cache [B, Hkv, max_len, D], v cache, past): the new keys / values are appended at [past, past + S) and
+        attention reads the cache's first past + S positions."""
+        assert cache is None or not keep, "a backward must not read keys / values out of a cache that the next step overwrites"
+        Hq, Hkv, D, d, F_ = sp.Hq, sp.Hkv, sp.D, sp.d, sp.F
         M = B * S
         nq = (Hq + 2 * Hkv) * D
         h1, rstd1 = K.rmsnorm_fwd(x, st.w(sp.ln1), sp.eps)
         qkv = K.mm_nt(h1, st.w(*sp.qkv_w, shape=(nq, d)), bias=st.w(*sp.qkv_b, shape=(nq,)) if sp.qkv_b is not None else None)
         extra = ()
         if sp.qk_norm is None:
-            q, k, v = K.rope_split(qkv, cos_t, sin_t, None, B, S, Hq, Hkv, D)
+            q, k, v = K.rope_split(qkv, cos_t, sin_t, pos, B, S, Hq, Hkv, D)
         else:
-            q, k, v, rstd_qk = K.qknorm_rope_split(qkv, st.w(sp.qk_norm[0]), st.w(sp.qk_norm[1]), sp.eps, cos_t, sin_t, None,
+            q, k, v, rstd_qk = K.qknorm_rope_split(qkv, st.w(sp.qk_norm[0]), st.w(sp.qk_norm[1]), sp.eps, cos_t, sin_t, pos,
                                                    B, S, Hq, Hkv, D, want_rstd=keep)
             extra = (qkv, rstd_qk)
         del qkv
+        if cache is not None:
+            k_cache, v_cache, past = cache
+            k_cache[:, :, past:past + S].copy_(k)
+            v_cache[:, :, past:past + S].copy_(v)
+            k, v = k_cache[:, :, :past + S], v_cache[:, :, :past + S]
         o = torch.empty((B, S, Hq, D), device=x.device, dtype=x.dtype)
         lse = K.attn_fwd(q, k, v, o.permute(0, 2, 1, 3), causal=True, scale=D ** -0.5, kv_start=kv_start, kv_end=kv_end)
         x2 = K.mm_nt(o.view(M, Hq * D), st.w(sp.o_w), residual=x)
@@ -317,7 +328,7 @@ class Qwen2LayerFn(_StoreFn):
         # will a backward come?  (needs_input_grad reports requires_grad of the inputs whatever the grad mode of the caller: a served
         #  model keeps its parameters trainable, so the caller's grad mode — recorded by Qwen2Backbone.forward — decides too)
         need = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) and getattr(sp, "grad_mode", True)
-        y, saved = Qwen2LayerFn._run(st, sp, x, cos_t, sin_t, kv_start, kv_end, keep=need)
+        y, saved = Qwen2LayerFn._run(st, sp, sp.B, sp.S, x, cos_t, sin_t, kv_start, kv_end, keep=need)
         if not need:
             return y
         ctx.st, ctx.sp = st, sp
@@ -336,7 +347,8 @@ class Qwen2LayerFn(_StoreFn):
         cos_t, sin_t, kv_start, kv_end = ctx.aux
         if ctx.recompute:
             (x,) = ctx.saved_tensors
-            rstd1, h1, q, k, v, o, lse, x2, rstd2, h2, gu, a, *extra = Qwen2LayerFn._run(st, sp, x, cos_t, sin_t, kv_start, kv_end)[1]
+            rstd1, h1, q, k, v, o, lse, x2, rstd2, h2, gu, a, *extra = \
+                Qwen2LayerFn._run(st, sp, sp.B, sp.S, x, cos_t, sin_t, kv_start, kv_end)[1]
         else:
             x, rstd1, h1, q, k, v, o, lse, x2, rstd2, h2, gu, a, *extra = ctx.saved_tensors
         B, S, Hq, Hkv, D, d, F_ = sp.B, sp.S, sp.Hq, sp.Hkv, sp.D, sp.d, sp.F
@@ -673,7 +685,7 @@ class NormFn(_StoreFn):
             y, rstd = K.rmsnorm_fwd(x.contiguous(), st.w(wn), eps)
             mean = rstd.new_empty(0)
         elif kind == "rms1p":                       # GemmaRMSNorm: scale by (1 + weight) in fp32
-            y, rstd = K.rmsnorm_fwd(x.contiguous(), st.w(wn).float() + 1.0, eps)
+            y, rstd = K.rmsnorm_fwd(x.contiguous(), gemma_norm_w(st, wn), eps)
             mean = rstd.new_empty(0)
         else:
             y, mean, rstd = K.layernorm_fwd(x.contiguous(), st.w(wn) if wn else None, st.w(bn) if bn else None, eps)
@@ -689,7 +701,7 @@ class NormFn(_StoreFn):
         dy = dy.contiguous()
         if ctx.kind in ("rms", "rms1p"):
             tr = st.trainable(ctx.wn)
-            w = st.w(ctx.wn) if ctx.kind == "rms" else st.w(ctx.wn).float() + 1.0      # d(1+w) = dw
+            w = st.w(ctx.wn) if ctx.kind == "rms" else gemma_norm_w(st, ctx.wn)      # d(1+w) = dw
             dx, _ = K.rmsnorm_bwd(dy, x.contiguous(), w, rstd, dw_out=st.g(ctx.wn) if tr else None,
                                   accumulate=st.accum_flag(ctx.wn), want_dw=tr)
             if tr:
@@ -1028,18 +1040,45 @@ class GemmaLayerSpec:
     eps: float
 
 
-def _gemma_norm_w(st: ParamStore, name: str) -> torch.Tensor:
-    """fp32 (1 + w) of a GemmaRMSNorm weight, computed once per state of the weights (forward and backward of a step share it; the
-    two aten launches per use were 290 launches of a pi0 step)"""
+def gemma_norm_w(st: ParamStore, name: str) -> torch.Tensor:
+    """fp32 (1 + w) of a GemmaRMSNorm weight (HF multiplies the normalised fp32 activations by 1 + w.float()): the one place that
+    forms it.  One tensor per name, allocated once and re-formed IN PLACE when the weights have moved since that name was last
+    formed (ParamStore.weights_key): forward and backward of a step share it (the two aten launches per use were 290 launches of a
+    pi0 step), and its address never changes, so nothing a captured graph holds is ever freed under it.  The refresh itself is host
+    code: whoever replays a captured graph that reads these tensors calls ``gemma_norm_refresh`` first (Pi0ForCausalLM.inference_action
+    does), or the replay normalises with the 1 + w of the capture."""
     key = st.weights_key()
     cache = st.__dict__.setdefault("_gemma_norm_cache", {})
-    if cache.get("key") != key:
-        cache.clear()
-        cache["key"] = key
-    w = cache.get(name)
-    if w is None:
-        w = cache[name] = st.w(name).float() + 1.0
-    return w
+    ent = cache.get(name)
+    if ent is None:
+        ent = cache[name] = [None, torch.empty(st.slots[name].shape, device=st.device, dtype=torch.float32)]
+    if ent[0] != key:
+        torch.add(st.w(name).float(), 1.0, out=ent[1])
+        ent[0] = key
+    return ent[1]
+
+
+def gemma_norm_refresh(st: ParamStore) -> None:
+    """bring every (1 + w) formed so far up to date: before the replay of a captured graph, which runs no host code of its own"""
+    for name in st.__dict__.get("_gemma_norm_cache", ()):
+        gemma_norm_w(st, name)
+
+
+def gemma_pre_attention(st: ParamStore, sp: GemmaLayerSpec, x, nq: int):
+    """first half of one expert's Gemma layer on x [M, d]: input GemmaRMSNorm, then the fused q/k/v product
+    -> (h, rstd, qkv [M, nq = (Hq + 2 Hkv) * D])"""
+    h, rstd = K.rmsnorm_fwd(x, gemma_norm_w(st, sp.ln1), sp.eps)
+    return h, rstd, K.mm_nt(h, st.w(*sp.qkv, shape=(nq, sp.d)))
+
+
+def gemma_post_attention(st: ParamStore, sp: GemmaLayerSpec, x, a):
+    """second half, a [M, Hq * D] = this expert's rows of the attention output: x + o_proj(a); then + down(gelu_tanh(gate) * up) of
+    the post-attention GemmaRMSNorm -> (y, what the backward reads besides a: r, rstd2, h2, gu, act)"""
+    r = K.mm_nt(a, st.w(sp.o), residual=x)
+    h2, rstd2 = K.rmsnorm_fwd(r, gemma_norm_w(st, sp.ln2), sp.eps)
+    gu = K.mm_nt(h2, st.w(*sp.gu, shape=(2 * sp.F, sp.d)))
+    act = K.glu_fwd(gu, L.ACT_GELU_TANH)
+    return K.mm_nt(act, st.w(sp.down), residual=r), (r, rstd2, h2, gu, act)
 
 
 class Pi0MotLayerFn(_StoreFn):
@@ -1062,8 +1101,9 @@ class Pi0MotLayerFn(_StoreFn):
         v = torch.empty((B, Hkv, S0 + S1, D), device=x0.device, dtype=x0.dtype)
         off = 0
         for x, sp, S, pos in zip(xs, sps, Ss, poss):
-            h, r = K.rmsnorm_fwd(x, _gemma_norm_w(st, sp.ln1), sp.eps)
-            K.rope_split_into(K.mm_nt(h, st.w(*sp.qkv, shape=(nq, sp.d))), q, k, v, off, cos_t, sin_t, pos, B, S, Hq, Hkv, D)
+            h, r, qkv = gemma_pre_attention(st, sp, x, nq)
+            K.rope_split_into(qkv, q, k, v, off, cos_t, sin_t, pos, B, S, Hq, Hkv, D)
+            del qkv
             off += S
             h1.append(h); rstd1.append(r)
         o = torch.empty((B, S0 + S1, Hq, D), device=x0.device, dtype=x0.dtype)
@@ -1077,12 +1117,9 @@ class Pi0MotLayerFn(_StoreFn):
                 ys.append(x.new_zeros((0,)))                   # placeholder, never read downstream
                 saved += [a, a.new_empty(0), a.new_empty(0), a.new_empty(0), a.new_empty(0), a.new_empty(0)]
                 continue
-            r = K.mm_nt(a, st.w(sp.o), residual=x)
-            h2, rs2 = K.rmsnorm_fwd(r, _gemma_norm_w(st, sp.ln2), sp.eps)
-            gu = K.mm_nt(h2, st.w(*sp.gu, shape=(2 * sp.F, sp.d)))
-            act = K.glu_fwd(gu, L.ACT_GELU_TANH)
-            ys.append(K.mm_nt(act, st.w(sp.down), residual=r))
-            saved += [a, r, rs2, h2, gu, act]
+            y, kept = gemma_post_attention(st, sp, x, a)
+            ys.append(y)
+            saved += [a, *kept]
         return (ys[0], ys[1]), (h1[0], h1[1], rstd1[0], rstd1[1], q, k, v, o, lse, *saved)
 
     @staticmethod
@@ -1134,7 +1171,7 @@ class Pi0MotLayerFn(_StoreFn):
             dh2 = _dx(st, sp.gu, (2 * sp.F, sp.d), dgu)
             _wgrad(st, sp.gu, dgu, h2, (2 * sp.F, sp.d))
             tr = st.trainable(sp.ln2)
-            dr, _ = K.rmsnorm_bwd(dh2, r, _gemma_norm_w(st, sp.ln2), rs2, dw_out=st.g(sp.ln2) if tr else None,
+            dr, _ = K.rmsnorm_bwd(dh2, r, gemma_norm_w(st, sp.ln2), rs2, dw_out=st.g(sp.ln2) if tr else None,
                                   accumulate=st.accum_flag(sp.ln2), want_dw=tr, residual=dy)
             if tr:
                 st.mark_written(sp.ln2)
@@ -1155,7 +1192,7 @@ class Pi0MotLayerFn(_StoreFn):
             dh = _dx(st, sp.qkv, (nq, sp.d), dqkv)
             _wgrad(st, sp.qkv, dqkv, h1[i], (nq, sp.d))
             tr = st.trainable(sp.ln1)
-            dxn, _ = K.rmsnorm_bwd(dh, xs[i], _gemma_norm_w(st, sp.ln1), rstd1[i], dw_out=st.g(sp.ln1) if tr else None,
+            dxn, _ = K.rmsnorm_bwd(dh, xs[i], gemma_norm_w(st, sp.ln1), rstd1[i], dw_out=st.g(sp.ln1) if tr else None,
                                    accumulate=st.accum_flag(sp.ln1), want_dw=tr, residual=drs[i])
             if tr:
                 st.mark_written(sp.ln1)

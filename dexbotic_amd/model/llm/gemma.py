@@ -3,9 +3,10 @@
 Stands in for the HF ``GemmaModel`` objects the reference builds through ``AutoModel.from_config`` (pi0_arch.py:
 86-91) and walks layer by layer in ``_inner_forward_mot`` (:116-216).  Arithmetic per HF gemma/modeling_gemma.py:
 GemmaRMSNorm (fp32 normalise, scale by 1 + weight), bias-free q/k/v/o, rotate-half RoPE, GeGLU MLP
-(gelu_pytorch_tanh(gate) * up), final norm.  Parameter names are HF's.  A layer is split in the two halves the
-mixture needs: ``pre_attention`` (norm + fused QKV) and ``post_attention`` (o_proj + residual + norm + MLP +
-residual); the attention itself runs once over BOTH experts' tokens (pi0_arch.py:161-191).
+(gelu_pytorch_tanh(gate) * up), final norm.  Parameter names are HF's.  This module registers the parameters and
+names them per layer (``layer_specs``); the layer's launches are the two halves the mixture needs,
+``functional.gemma_pre_attention`` (norm + fused QKV) and ``functional.gemma_post_attention`` (o_proj + residual +
+norm + MLP + residual), around ONE attention over BOTH experts' tokens (pi0_arch.py:161-191).
 """
 from __future__ import annotations
 
@@ -15,9 +16,7 @@ from typing import Dict, Tuple
 import torch
 import torch.nn as nn
 
-from ... import _lib as L
 from ... import functional as Fn
-from ... import kernels as K
 from ...engine import ParamStore
 
 
@@ -61,7 +60,6 @@ class GemmaExpert(nn.Module):
         d, f, hd, Hq, Hkv = c.hidden_size, c.intermediate_size, c.head_dim, c.num_attention_heads, c.num_key_value_heads
         store.new_bucket()
         store.register([(prefix + "embed_tokens.weight", (c.vocab_size, d))])
-        self.layer_names = []
         self.layer_specs = []
         for i in range(c.num_hidden_layers):
             lp = f"{prefix}layers.{i}."
@@ -74,32 +72,16 @@ class GemmaExpert(nn.Module):
             store.register([(lp + "post_attention_layernorm.weight", (d,))])
             store.register([(gu[0], (f, d)), (gu[1], (f, d))])
             store.register([(lp + "mlp.down_proj.weight", (d, f))])
-            self.layer_names.append(dict(ln1=lp + "input_layernorm.weight", qkv=qkv, o=lp + "self_attn.o_proj.weight",
-                                    ln2=lp + "post_attention_layernorm.weight", gu=gu, down=lp + "mlp.down_proj.weight"))
-            self.layer_specs.append(Fn.GemmaLayerSpec(d=d, F=f, eps=c.rms_norm_eps, **self.layer_names[-1]))
+            self.layer_specs.append(Fn.GemmaLayerSpec(
+                ln1=lp + "input_layernorm.weight", qkv=qkv, o=lp + "self_attn.o_proj.weight",
+                ln2=lp + "post_attention_layernorm.weight", gu=gu, down=lp + "mlp.down_proj.weight", d=d, F=f, eps=c.rms_norm_eps))
         store.new_bucket()
         store.register([(prefix + "norm.weight", (d,))])
         self._rope: Dict = {}
-        self._w1: Dict[str, torch.Tensor] = {}
 
     @property
     def embed_name(self) -> str:
         return self.p + "embed_tokens.weight"
-
-    # ---- pieces -------------------------------------------------------------------------------------
-    def norm_weight(self, name: str) -> torch.Tensor:
-        """1 + weight in fp32 (GemmaRMSNorm multiplies the normalised fp32 activations by (1 + w.float()));
-        cached while the module is in eval mode, rebuilt every call in training (the weights move)."""
-        if not self.training and name in self._w1:
-            return self._w1[name]
-        w1 = self.store.w(name).float() + 1.0
-        if not self.training:
-            self._w1[name] = w1
-        return w1
-
-    def train(self, mode: bool = True):
-        self._w1.clear()
-        return super().train(mode)
 
     def rope_tables(self, n_pos: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
         """cos/sin [n_pos, head_dim/2] fp32 (GemmaRotaryEmbedding: inv_freq = theta^(-2i/hd), angles in fp32)"""
@@ -123,22 +105,3 @@ class GemmaExpert(nn.Module):
         rows = Fn.SpliceFn.apply(dummy, st.params[self.embed_name], st, self.embed_name,
                                  input_ids.reshape(-1).to(device=st.device, dtype=torch.int64).contiguous())
         return Fn.ScaleFn.apply(rows, float(d) ** 0.5).view(*input_ids.shape, d)
-
-    def pre_attention(self, x2d: torch.Tensor, li: int) -> torch.Tensor:
-        """[M, d] -> fused qkv [M, (Hq + 2 Hkv) * hd] of layer li (input_layernorm + q/k/v projections)"""
-        c, ly, st = self.config, self.layer_names[li], self.store
-        nq = (c.num_attention_heads + 2 * c.num_key_value_heads) * c.head_dim
-        h, _ = K.rmsnorm_fwd(x2d, self.norm_weight(ly["ln1"]), c.rms_norm_eps)
-        return K.mm_nt(h, st.w(*ly["qkv"], shape=(nq, c.hidden_size)))
-
-    def post_attention(self, x2d: torch.Tensor, attn2d: torch.Tensor, li: int) -> torch.Tensor:
-        """x + o_proj(attn); then + down(gelu_tanh(gate) * up) of the post-attention norm"""
-        c, ly, st = self.config, self.layer_names[li], self.store
-        r = K.mm_nt(attn2d, st.w(ly["o"]), residual=x2d)
-        h, _ = K.rmsnorm_fwd(r, self.norm_weight(ly["ln2"]), c.rms_norm_eps)
-        gu = K.mm_nt(h, st.w(*ly["gu"], shape=(2 * c.intermediate_size, c.hidden_size)))
-        return K.mm_nt(K.glu_fwd(gu, L.ACT_GELU_TANH), st.w(ly["down"]), residual=r)
-
-    def final_norm(self, x2d: torch.Tensor) -> torch.Tensor:
-        y, _ = K.rmsnorm_fwd(x2d, self.norm_weight(self.p + "norm.weight"), self.config.rms_norm_eps)
-        return y

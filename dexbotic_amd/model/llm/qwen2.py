@@ -180,29 +180,9 @@ class Qwen2Backbone(nn.Module):
             kv_end = torch.full((B,), total, dtype=torch.int32, device=dev)
         st = self.store
         x = inputs_embeds.reshape(B * S, d).contiguous()
-        for i, sp in enumerate(self.layer_specs):
-            Hq, Hkv, D, F_ = sp.Hq, sp.Hkv, sp.D, sp.F
-            nq = (Hq + 2 * Hkv) * D
-            h1, _ = K.rmsnorm_fwd(x, st.w(sp.ln1), sp.eps)
-            qkv = K.mm_nt(h1, st.w(*sp.qkv_w, shape=(nq, d)), bias=st.w(*sp.qkv_b, shape=(nq,)) if sp.qkv_b is not None else None)
-            if sp.qk_norm is None:
-                q, k, v = K.rope_split(qkv, cos_t, sin_t, pos, B, S, Hq, Hkv, D)
-            else:
-                q, k, v, _ = K.qknorm_rope_split(qkv, st.w(sp.qk_norm[0]), st.w(sp.qk_norm[1]), sp.eps, cos_t, sin_t, pos,
-                                                 B, S, Hq, Hkv, D, want_rstd=False)
-            cache.k[i][:, :, past:total].copy_(k)
-            cache.v[i][:, :, past:total].copy_(v)
-            o = torch.empty((B, S, Hq, D), device=x.device, dtype=x.dtype)
-            K.attn_fwd(q, cache.k[i][:, :, :total], cache.v[i][:, :, :total], o.permute(0, 2, 1, 3), causal=True,
-                       scale=D ** -0.5, kv_start=kv_start, kv_end=kv_end)
-            x2 = K.mm_nt(o.view(B * S, Hq * D), st.w(sp.o_w), residual=x)
-            h2, _ = K.rmsnorm_fwd(x2, st.w(sp.ln2), sp.eps)
-            w_gu = st.w(*sp.gu_w, shape=(2 * F_, d))
-            if K.swiglu_gemm_supported(h2, w_gu):
-                a, _ = K.mm_nt_swiglu(h2, w_gu, keep_pre=False)
-            else:
-                a = K.swiglu_fwd(K.mm_nt(h2, w_gu))
-            x = K.mm_nt(a, st.w(sp.down_w), residual=x2)
+        for i, sp in enumerate(self.layer_specs):          # the layer's launches: functional.Qwen2LayerFn._run, as forward() runs them
+            x = Fn.Qwen2LayerFn._run(st, sp, B, S, x, cos_t, sin_t, kv_start, kv_end, keep=False, pos=pos,
+                                     cache=(cache.k[i], cache.v[i], past))[0]
         x, _ = K.rmsnorm_fwd(x, st.w(self.p + "norm.weight"), self.config.rms_norm_eps)
         cache.length = total
         return x.view(B, S, d)

@@ -8,7 +8,8 @@ Stands in for the HF ``Qwen3Model`` that ``AutoModel.from_config(llm_config)`` g
 * a per-head ``RMSNorm(head_dim)`` on q (``self_attn.q_norm.weight``) and on k (``self_attn.k_norm.weight``) sits between the
   projection and RoPE.  It runs inside the RoPE / split pass (``dxa_qknorm_rope_split`` forward, ``dxa_qknorm_rope_merge`` backward).
 
-Everything else — registration, forward, the cached path — is ``Qwen2Backbone``'s code, switched by two class attributes.
+Everything else is shared: registration and the two forward drivers are ``Qwen2Backbone``'s, switched by two class attributes, and the
+layer itself — with or without a key/value cache — is the one launch sequence of ``functional.Qwen2LayerFn._run``.
 Parameter names are HF's.
 
 Known gap: the persistent one-launch decode step (csrc/decode_fused.hip) has no q/k norm, so ``_decode_state`` returns None and every

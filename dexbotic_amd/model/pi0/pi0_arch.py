@@ -250,6 +250,8 @@ class Pi0ForCausalLM(NativePreTrainedMixin, nn.Module, ActionOutputForCausalLM):
         experts = [self.model.llm, self.model.action_expert]
         c = self.config.llm_config
         Hq, Hkv, D = c.num_attention_heads, c.num_key_value_heads, c.head_dim
+        nq = (Hq + 2 * Hkv) * D
+        st = self.store
         live = [(e, x) for e, x in zip(experts, xs) if x is not None]
         B = live[0][1].shape[0]
         lens = [x.shape[1] for _, x in live]
@@ -270,11 +272,13 @@ class Pi0ForCausalLM(NativePreTrainedMixin, nn.Module, ActionOutputForCausalLM):
             inplace = (past is not None and past_len is not None and len(live) == 1 and B == 1 and Hkv == 1
                        and kf.shape[2] == past_len + lens[0])
             for (e, _), h, n, pp in zip(live, hs, lens, pos_parts):
+                _, _, qkv = Fn.gemma_pre_attention(st, e.layer_specs[li], h, nq)
                 if inplace:
-                    q, k, v = K.rope_split(e.pre_attention(h, li), cos_t, sin_t, pp, B, n, Hq, Hkv, D,
+                    q, k, v = K.rope_split(qkv, cos_t, sin_t, pp, B, n, Hq, Hkv, D,
                                            k_out=kf[:, :, past_len:], v_out=vf[:, :, past_len:])
                 else:
-                    q, k, v = K.rope_split(e.pre_attention(h, li), cos_t, sin_t, pp, B, n, Hq, Hkv, D)
+                    q, k, v = K.rope_split(qkv, cos_t, sin_t, pp, B, n, Hq, Hkv, D)
+                del qkv
                 qs.append(q); ks.append(k); vs.append(v)
             q = qs[0] if len(qs) == 1 else torch.cat(qs, dim=2)
             k = ks[0] if len(ks) == 1 else torch.cat(ks, dim=2)
@@ -291,7 +295,8 @@ class Pi0ForCausalLM(NativePreTrainedMixin, nn.Module, ActionOutputForCausalLM):
             nxt = []
             for i, ((e, _), h, n) in enumerate(zip(live, hs, lens)):
                 a2 = o[:, offs[i]:offs[i + 1]].reshape(B * n, Hq * D)
-                nxt.append(e.post_attention(h, a2.contiguous(), li))
+                y, _ = Fn.gemma_post_attention(st, e.layer_specs[li], h, a2.contiguous())
+                nxt.append(y)
             hs = nxt
         outs, it = [], iter(zip(live, hs, lens))
         for x in xs:
@@ -299,7 +304,8 @@ class Pi0ForCausalLM(NativePreTrainedMixin, nn.Module, ActionOutputForCausalLM):
                 outs.append(None)
             else:
                 (e, _), h, n = next(it)
-                outs.append(e.final_norm(h).view(B, n, -1))
+                y, _ = K.rmsnorm_fwd(h, Fn.gemma_norm_w(st, e.p + "norm.weight"), e.config.rms_norm_eps)
+                outs.append(y.view(B, n, -1))
         return outs, cache
 
     def _mot_train(self, ptok, stok, positions, q_limit, key_valid) -> torch.Tensor:
@@ -427,6 +433,7 @@ class Pi0ForCausalLM(NativePreTrainedMixin, nn.Module, ActionOutputForCausalLM):
         from ... import graphs
         if dev.type == "cuda" and kwargs.get("use_graph", graphs.enabled()):
             gc_ = self.__dict__.setdefault("_sampler_graphs", graphs.GraphCache(dev))
+            Fn.gemma_norm_refresh(st)      # the graph holds the action expert's (1 + w) tensors; only host code notices a weight change
             return gc_.run(("euler", int(diffusion_steps), int(fpos.max()), rope[0].data_ptr()), euler, inputs).clone()
         return euler(**inputs)
 

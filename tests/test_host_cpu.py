@@ -475,3 +475,27 @@ def test_host_thread_pool_is_held_inside_the_cgroup_cpu_quota(tmp_path, monkeypa
         assert H.limit_host_threads() == 3                               # 0 = leave torch alone
     finally:
         torch.set_num_threads(before)
+
+
+def test_gemma_norm_weight_is_one_tensor_per_name_refreshed_in_place():
+    """functional.gemma_norm_w: fp32 (1 + w), the same tensor at the same address for the life of the store (a captured graph may
+    hold it), re-formed in place when the masters moved — by a torch-side write or by a native update (native_epoch)"""
+    from dexbotic_amd import functional as Fn
+    from dexbotic_amd.engine import ParamStore
+    st = ParamStore("cpu", torch.float32)
+    st.register([("norm.weight", (8,))])
+    st.finalize(train=False)
+    master = st.w32("norm.weight")
+    master.copy_(torch.arange(8, dtype=torch.float32) * 0.25)
+    w1 = Fn.gemma_norm_w(st, "norm.weight")
+    assert w1.dtype == torch.float32 and torch.equal(w1, master + 1)
+    assert Fn.gemma_norm_w(st, "norm.weight") is w1
+    ptr = w1.data_ptr()
+    master.add_(0.5)                                     # torch-side write: the arena's version counter moves
+    w2 = Fn.gemma_norm_w(st, "norm.weight")
+    assert w2.data_ptr() == ptr and torch.equal(w2, master + 1) and torch.equal(w1, master + 1)
+    master.data.mul_(-2.0)                               # a write the version counter does not see, as the native optimizer's
+    st.native_epoch += 1
+    w3 = Fn.gemma_norm_w(st, "norm.weight")
+    assert w3.data_ptr() == ptr and torch.equal(w3, master + 1)
+    assert float(w3[1]) == -2.0 * 0.75 + 1.0

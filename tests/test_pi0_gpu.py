@@ -72,6 +72,25 @@ def test_pi0_sampler_graph_replay_equals_eager_launches(golden_dir):
             assert rel_err(acts.cpu().numpy(), g["infer_actions"]) < FP32_TOL
 
 
+def test_pi0_sampler_graph_follows_a_weight_change(golden_dir):
+    """a replayed graph runs no host code: the fp32 (1 + w) tensors of the action expert it holds (functional.gemma_norm_w) are
+    brought up to date before the replay, so a served model whose weights are replaced samples with the new ones"""
+    for dtype in ("float32", "bfloat16"):
+        g, m = build(golden_dir, dtype)
+        kw = dict(input_ids=T(g["input_ids"]), attention_mask=T(g["attention_mask"]), states=T(g["states"]),
+                  images=T(g["images"]), image_masks=T(g["image_masks"]), diffusion_steps=10, noise=T(g["init_noise"]))
+        for _ in range(3):                                    # eager, capture, replay
+            before = m.inference_action(use_graph=True, **kw).clone()
+        assert any(e["graph"] is not None for e in m._sampler_graphs.entries.values())
+        for name in m.store.slots:
+            if name.startswith("model.action_expert.") and name.endswith("norm.weight"):
+                m.store.w32(name).add_(0.25)
+        got = m.inference_action(use_graph=True, **kw).clone()                 # the replay first: nothing eager has touched the expert yet
+        want = m.inference_action(use_graph=False, **kw)
+        assert torch.equal(got, want), dtype
+        assert not torch.equal(got, before), dtype
+
+
 def test_fp32_pi0_forward_loss_matches_reference(golden_dir):
     g, m = build(golden_dir, "float32")
     with torch.no_grad():
@@ -80,6 +99,24 @@ def test_fp32_pi0_forward_loss_matches_reference(golden_dir):
                 time=g["time"])
     assert rel_err(out.logits.cpu().numpy(), g["v_t"]) < FP32_TOL
     assert abs(out.loss.item() - float(g["loss"])) < FP32_TOL * abs(float(g["loss"]))
+
+
+@pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
+def test_pi0_forward_without_and_with_autograd_is_one_arithmetic(golden_dir, dtype):
+    """the loss under torch.no_grad() (_mot_forward, both experts live) and with gradients enabled (_mot_train, Pi0MotLayerFn) in
+    the same module mode: both callers run functional.gemma_pre_attention / gemma_post_attention around the same attention launch,
+    so the losses are the same bits"""
+    g, m = build(golden_dir, dtype, train=True)
+    m.store.set_expected(m.unused_parameter_names())
+    m.store.begin_step()
+    kw = dict(input_ids=T(g["input_ids"]), attention_mask=T(g["attention_mask"]), images=T(g["images"]),
+              image_masks=T(g["image_masks"]), states=T(g["states"]), actions=T(g["actions"]), noise=T(g["noise"]), time=g["time"])
+    with torch.no_grad():
+        plain = m(**kw).loss
+    with torch.enable_grad():
+        tracked = m(**kw).loss
+    assert tracked.requires_grad and not plain.requires_grad
+    assert torch.isfinite(plain).all() and torch.equal(plain, tracked.detach())
 
 
 def test_fp32_pi0_training_step_grads_match_reference(golden_dir):
