@@ -53,6 +53,13 @@ def discrete_vla():
     return DiscreteVLAForCausalLM
 
 
+def muvla():
+    """MUVLAForCausalLM shares model_type "dexbotic" with the base class in the reference (muvla_arch.py:17-18); exps pick it by
+    class, so it is exported by name here."""
+    from .model.muvla.muvla_arch import MUVLAForCausalLM
+    return MUVLAForCausalLM
+
+
 def from_pretrained(path: str, **kw):
     """load any registered policy from a reference-format checkpoint directory"""
     import json

@@ -128,6 +128,8 @@ SIGNATURES = {
     "dxa_layernorm_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _int, _int, _vp]),
     "dxa_layernorm_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _vp]),
     "dxa_norm_bwd_blocks": (_int, [_i64]),
+    "dxa_add_layernorm_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _int, _int, _vp]),
+    "dxa_add_layernorm_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _vp]),
     "dxa_downsample_layernorm_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _int, _int, _vp]),
     "dxa_downsample_layernorm_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _int, _vp]),
     "dxa_colsum": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _int, _vp, _sz, _vp]),
@@ -177,6 +179,7 @@ SIGNATURES = {
     "dxa_token_sum": (_int, [_vp, _vp, _i64, _i64, _i64, _f32, _int, _vp]),
     "dxa_mse_loss": (_int, [_vp, _vp, _vp, _vp, _i64, _f32, _vp]),
     "dxa_mse_loss_rows": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _vp]),
+    "dxa_expectile_loss": (_int, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _vp]),
     "dxa_ddim_step": (_int, [_vp, _vp, _i64, _i64, _int, _f32, _f32, _f32, _f32, _vp]),
     "dxa_adamw": (_int, [C.POINTER(AdamWDesc), _vp]),
     "dxa_sumsq": (_int, [_vp, _i64, _int, _vp, _vp, _int, _vp]),
@@ -185,6 +188,8 @@ SIGNATURES = {
     "dxa_gemm_sumsq_slots": (_i64, [_i64, _i64]),
     "dxa_cross_entropy_fwd": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp]),
     "dxa_cross_entropy_bwd": (_int, [_vp, _i64, _vp, _vp, _vp, _f32, _vp, _i64, _i64, _i64, _i64, _int, _vp]),
+    "dxa_cross_entropy_rows_bwd": (_int, [_vp, _i64, _vp, _vp, _vp, _f32, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp]),
+    "dxa_ce_sample_reduce": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
     "dxa_soft_cross_entropy_fwd": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _int, _f32, _int, _vp]),
     "dxa_soft_cross_entropy_bwd": (_int, [_vp, _i64, _vp, _vp, _vp, _f32, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _int, _f32,
                                           _int, _vp]),

@@ -4,9 +4,11 @@
 //                               non-ignored (already shifted) labels.
 //   dxa_argmax_rows           : torch.argmax over the vocabulary (first index among equal maxima), the greedy
 //                               choice of GenerationMixin.generate(do_sample=False) (discrete_vla_arch.py:33-41).
+//   dxa_cross_entropy_rows_bwd, dxa_ce_sample_reduce, dxa_expectile_loss : MuVLA's per-sample normalised, reward-weighted loss and its
+//                               reward head's expectile regression (dexbotic/model/muvla/muvla_arch.py:559-592).
 //   dxa_sample_rows           : the sampled choice of generate(do_sample=True): temperature, top-k, top-p, softmax and the draw in
 //                               one launch (its own section at the end of this file).
-// The first three are one 256-thread workgroup per row streaming the row once (HBM-bound: 152 k logits = 304 KB bf16):
+// The cross-entropy and argmax kernels are one 256-thread workgroup per row streaming the row once (HBM-bound: 152 k logits = 304 KB bf16):
 // online (max, sum-exp) pairs per thread folded across the block — no second pass for the maximum.
 #include "common.h"
 
@@ -200,19 +202,24 @@ __global__ __launch_bounds__(256) void soft_ce_fwd_k(const T* __restrict__ logit
 // A soft row first keeps z[s_k] of its K soft ids (dlogits may alias logits), writes softmax * g everywhere, and then
 // the K soft columns once more as (softmax - p_k) * g: one rounding per element, no search per element.  SOFT = false (launched
 // for K = 0) compiles the soft rows' LDS and branches away: with them the K = 0 launch measured 2 - 6 us over 120 - 126 us at
-// [512, 152064] bf16 (profiles/ce_merge.txt)
-template <typename T, int VEC, bool SOFT>
+// [512, 152064] bf16 (profiles/ce_merge.txt).  ROWW (dxa_cross_entropy_rows_bwd with a row_w): one more factor of g per row, read
+// once per workgroup; a compile-time flag for the same reason, so the other entry points launch the code they always did.
+template <typename T, int VEC, bool SOFT, bool ROWW>
 __global__ __launch_bounds__(256) void soft_ce_bwd_k(const T* logits, int64_t ld, const int64_t* __restrict__ labels,
                                                      const float* __restrict__ lse, const float* __restrict__ gscale, float scale,
                                                      T* dlogits, int64_t ldd, int64_t V, int64_t ignore_index,
-                                                     const int64_t* __restrict__ soft_ids, int K, float inv2s2) {
+                                                     const int64_t* __restrict__ soft_ids, int K, float inv2s2,
+                                                     const float* __restrict__ row_w) {
   __shared__ float sz[SOFT_CE_MAX_K], se[SOFT_CE_MAX_K];
   const int64_t r = blockIdx.x;
   const T* x = logits + r * ld;
   T* d = dlogits + r * ldd;
   int64_t lab = labels[r];
   const bool ign = (lab == ignore_index || lab < 0 || lab >= V);
-  const float g = ign ? 0.f : (gscale ? gscale[0] : 1.f) * scale;
+  float g = ign ? 0.f : (gscale ? gscale[0] : 1.f) * scale;
+  if constexpr (ROWW) {
+    if (!ign) g *= row_w[r];
+  }
   const float l = lse[r];
   const bool soft = SOFT && !ign && soft_find(soft_ids, K, lab) >= 0;  // uniform over the workgroup
   if (soft) {
@@ -282,7 +289,7 @@ int ce_fwd_launch(const char* who, const void* logits, int64_t ld, const int64_t
 
 int ce_bwd_launch(const char* who, const void* logits, int64_t ld, const int64_t* labels, const float* lse, const float* gscale,
                   float scale, void* dlogits, int64_t ldd, int64_t rows, int64_t V, int64_t ignore_index, const int64_t* soft_ids,
-                  const int64_t* soft_ids_host, int K, float inv2s2, int dtype, dxa_stream_t stream) {
+                  const int64_t* soft_ids_host, int K, float inv2s2, const float* row_w, int dtype, dxa_stream_t stream) {
   DXA_CHECK_ARG(logits && labels && lse && dlogits && rows >= 0 && V > 0 && ld >= V && ldd >= V &&
                 (dtype == DXA_F32 || dtype == DXA_BF16), "%s: bad args", who);
   if (int rc = check_soft_ids(who, soft_ids, soft_ids_host, K, V)) return rc;
@@ -290,8 +297,8 @@ int ce_bwd_launch(const char* who, const void* logits, int64_t ld, const int64_t
   const size_t es = dtype == DXA_BF16 ? 2 : 4;
   const bool vec = V % 4 == 0 && ld % 4 == 0 && ldd % 4 == 0 && al(logits, 4 * es) && al(dlogits, 4 * es);
   dim3 grid((unsigned)rows);
-#define CE_BWD_S(T_, V_, S_) hipLaunchKernelGGL((soft_ce_bwd_k<T_, V_, S_>), grid, dim3(256), 0, ST, (const T_*)logits, ld, labels, lse, gscale, scale, (T_*)dlogits, ldd, V, ignore_index, soft_ids, K, inv2s2)
-#define CE_BWD(T_, V_) do { if (K > 0) CE_BWD_S(T_, V_, true); else CE_BWD_S(T_, V_, false); } while (0)
+#define CE_BWD_S(T_, V_, S_, W_) hipLaunchKernelGGL((soft_ce_bwd_k<T_, V_, S_, W_>), grid, dim3(256), 0, ST, (const T_*)logits, ld, labels, lse, gscale, scale, (T_*)dlogits, ldd, V, ignore_index, soft_ids, K, inv2s2, row_w)
+#define CE_BWD(T_, V_) do { if (K > 0) CE_BWD_S(T_, V_, true, false); else if (row_w) CE_BWD_S(T_, V_, false, true); /* (no entry point passes row_w with soft ids) */ else CE_BWD_S(T_, V_, false, false); } while (0)
   if (dtype == DXA_BF16) { if (vec) CE_BWD(bf16_t, 4); else CE_BWD(bf16_t, 1); }
   else { if (vec) CE_BWD(float, 4); else CE_BWD(float, 1); }
 #undef CE_BWD
@@ -312,7 +319,14 @@ extern "C" int dxa_cross_entropy_bwd(const void* logits, int64_t ld, const int64
                                      const float* gscale, float scale, void* dlogits, int64_t ldd, int64_t rows, int64_t V,
                                      int64_t ignore_index, int dtype, dxa_stream_t stream) {
   return ce_bwd_launch("dxa_cross_entropy_bwd", logits, ld, labels, lse, gscale, scale, dlogits, ldd, rows, V, ignore_index, nullptr,
-                       nullptr, 0, 0.f, dtype, stream);
+                       nullptr, 0, 0.f, nullptr, dtype, stream);
+}
+
+extern "C" int dxa_cross_entropy_rows_bwd(const void* logits, int64_t ld, const int64_t* labels, const float* lse,
+                                          const float* gscale, float scale, const float* row_w, void* dlogits, int64_t ldd,
+                                          int64_t rows, int64_t V, int64_t ignore_index, int dtype, dxa_stream_t stream) {
+  return ce_bwd_launch("dxa_cross_entropy_rows_bwd", logits, ld, labels, lse, gscale, scale, dlogits, ldd, rows, V, ignore_index,
+                       nullptr, nullptr, 0, 0.f, row_w, dtype, stream);
 }
 
 extern "C" int dxa_soft_cross_entropy_fwd(const void* logits, int64_t ld, const int64_t* labels, float* row_loss, float* lse,
@@ -327,7 +341,82 @@ extern "C" int dxa_soft_cross_entropy_bwd(const void* logits, int64_t ld, const 
                                           int64_t ignore_index, const int64_t* soft_ids, const int64_t* soft_ids_host, int K,
                                           float inv2s2, int dtype, dxa_stream_t stream) {
   return ce_bwd_launch("dxa_soft_cross_entropy_bwd", logits, ld, labels, lse, gscale, scale, dlogits, ldd, rows, V, ignore_index,
-                       soft_ids, soft_ids_host, K, inv2s2, dtype, stream);
+                       soft_ids, soft_ids_host, K, inv2s2, nullptr, dtype, stream);
+}
+
+// ------------------------------------------------------------------- per-sample reduction and expectile loss (MuVLA)
+// dexbotic/model/muvla/muvla_arch.py:559-592.  The language loss is the mean over the samples of w_b * (sum of the sample's row
+// losses) / max(n_b, 1), w_b = 1 + sigmoid(reward_b); the reward head is trained with an expectile-weighted squared error.
+namespace {
+
+// one workgroup, sample after sample in order; a sample's rows are summed in double through a fixed LDS tree (sum_f32_k's)
+__global__ __launch_bounds__(1024) void ce_sample_reduce_k(const float* __restrict__ row_loss, const int64_t* __restrict__ labels,
+                                                           const float* __restrict__ reward, float* __restrict__ row_w,
+                                                           float* __restrict__ loss, int64_t B, int64_t L, int64_t V,
+                                                           int64_t ignore_index) {
+  __shared__ double red_s[1024];
+  __shared__ int red_n[1024];
+  double total = 0.0;                                      // thread 0's only
+  for (int64_t b = 0; b < B; ++b) {
+    double s = 0.0;
+    int n = 0;
+    for (int64_t t = threadIdx.x; t < L; t += 1024) {
+      const int64_t lab = labels[b * L + t];
+      if (!(lab == ignore_index || lab < 0 || lab >= V)) { s += (double)row_loss[b * L + t]; ++n; }   // the forward's own rule
+    }
+    red_s[threadIdx.x] = s;
+    red_n[threadIdx.x] = n;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+      if ((int)threadIdx.x < o) { red_s[threadIdx.x] += red_s[threadIdx.x + o]; red_n[threadIdx.x] += red_n[threadIdx.x + o]; }
+      __syncthreads();
+    }
+    const double w = reward ? 1.0 + (double)(1.f / (1.f + expf(-reward[b]))) : 1.0;
+    const double den = (double)(red_n[0] > 1 ? red_n[0] : 1) * (double)B;
+    const float rw = (float)(w / den);
+    for (int64_t t = threadIdx.x; t < L; t += 1024) row_w[b * L + t] = rw;
+    if (threadIdx.x == 0) total += w * red_s[0] / den;
+    __syncthreads();                                       // red_* are rewritten by the next sample
+  }
+  if (threadIdx.x == 0) loss[0] = (float)total;
+}
+
+__global__ __launch_bounds__(1024) void expectile_loss_k(const float* __restrict__ pred, const float* __restrict__ target,
+                                                         float* __restrict__ loss, float* __restrict__ dpred, int64_t n, float tau,
+                                                         float gscale) {
+  __shared__ float red[16];
+  float s = 0.f;
+  const float k = 2.f / (float)n * gscale;
+  for (int64_t i = threadIdx.x; i < n; i += 1024) {
+    const float d = pred[i] - target[i];
+    const float w = d < 0.f ? tau : 1.f - tau;
+    s += w * d * d;
+    if (dpred) dpred[i] = k * w * d;
+  }
+  const float tot = block_sum(s, red);
+  if (threadIdx.x == 0) loss[0] = tot / (float)n;
+}
+
+}  // namespace
+
+extern "C" int dxa_ce_sample_reduce(const float* row_loss, const int64_t* labels, const float* reward, float* row_w, float* loss,
+                                    int64_t B, int64_t L, int64_t V, int64_t ignore_index, dxa_stream_t stream) {
+  DXA_CHECK_ARG(row_loss && labels && row_w && loss, "dxa_ce_sample_reduce: null pointer (row_loss, labels, row_w and loss are required)");
+  DXA_CHECK_ARG(B > 0 && L > 0 && V > 0, "dxa_ce_sample_reduce: bad sizes (B %lld, L %lld, V %lld: all must be positive)",
+                (long long)B, (long long)L, (long long)V);
+  hipLaunchKernelGGL(ce_sample_reduce_k, dim3(1), dim3(1024), 0, ST, row_loss, labels, reward, row_w, loss, B, L, V, ignore_index);
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
+}
+
+extern "C" int dxa_expectile_loss(const float* pred, const float* target, float* loss, float* dpred, int64_t n, float tau,
+                                  float gscale, dxa_stream_t stream) {
+  DXA_CHECK_ARG(pred && target && loss, "dxa_expectile_loss: null pointer (pred, target and loss are required)");
+  DXA_CHECK_ARG(n > 0, "dxa_expectile_loss: n = %lld (must be positive)", (long long)n);
+  DXA_CHECK_ARG(tau > 0.f && tau < 1.f, "dxa_expectile_loss: tau %g outside (0, 1)", (double)tau);
+  hipLaunchKernelGGL(expectile_loss_k, dim3(1), dim3(1024), 0, ST, pred, target, loss, dpred, n, tau, gscale);
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
 }
 
 // ------------------------------------------------------------------------------------ sampled token choice

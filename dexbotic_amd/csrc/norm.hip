@@ -116,19 +116,33 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_k(const T* __restrict__ dy, c
 }
 
 // ----------------------------------------------------------------------------------------- LayerNorm
-template <typename T, typename TW, int VEC>
+// ADD (dxa_add_layernorm_fwd/bwd): the normalised row is x + x2, formed in fp32 from the two inputs wherever the row is read and
+// never rounded or written; compiled away otherwise
+template <typename T, int VEC, bool ADD>
+__device__ __forceinline__ void ld_row(float (&v)[VEC], const T* xr, const T* x2r, int64_t c) {
+  Vec<T, VEC>::ld(v, xr + c);
+  if constexpr (ADD) {
+    float a[VEC];
+    Vec<T, VEC>::ld(a, x2r + c);
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) v[i] += a[i];
+  }
+}
+
+template <typename T, typename TW, int VEC, bool ADD = false>
 __global__ __launch_bounds__(256) void layernorm_fwd_k(const T* __restrict__ x, const TW* __restrict__ w,
                                                        const TW* __restrict__ b, T* __restrict__ y,
                                                        float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                       int64_t rows, int64_t cols, float eps) {
+                                                       int64_t rows, int64_t cols, float eps, const T* __restrict__ x2 = nullptr) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const T* xr = x + row * cols;
+  const T* x2r = ADD ? x2 + row * cols : nullptr;
   float s = 0.f;
   for (int64_t c = (int64_t)lane * VEC; c < cols; c += 64 * VEC) {
     float v[VEC];
-    Vec<T, VEC>::ld(v, xr + c);
+    ld_row<T, VEC, ADD>(v, xr, x2r, c);
 #pragma unroll
     for (int i = 0; i < VEC; ++i) s += v[i];
   }
@@ -136,7 +150,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_k(const T* __restrict__ x, 
   float ss = 0.f;
   for (int64_t c = (int64_t)lane * VEC; c < cols; c += 64 * VEC) {
     float v[VEC];
-    Vec<T, VEC>::ld(v, xr + c);
+    ld_row<T, VEC, ADD>(v, xr, x2r, c);
 #pragma unroll
     for (int i = 0; i < VEC; ++i) { const float d = v[i] - mean; ss += d * d; }
   }
@@ -148,7 +162,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_k(const T* __restrict__ x, 
   T* yr = y + row * cols;
   for (int64_t c = (int64_t)lane * VEC; c < cols; c += 64 * VEC) {
     float v[VEC], g[VEC], bb[VEC];
-    Vec<T, VEC>::ld(v, xr + c);
+    ld_row<T, VEC, ADD>(v, xr, x2r, c);
     if (w) Vec<TW, VEC>::ld(g, w + c);
     if (b) Vec<TW, VEC>::ld(bb, b + c);
 #pragma unroll
@@ -158,12 +172,12 @@ __global__ __launch_bounds__(256) void layernorm_fwd_k(const T* __restrict__ x, 
 }
 
 // partial: [gridDim.x][2*cols] = (dw | db)
-template <typename T, typename TW, int VEC>
+template <typename T, typename TW, int VEC, bool ADD = false>
 __global__ __launch_bounds__(256) void layernorm_bwd_k(const T* __restrict__ dy, const T* __restrict__ x,
                                                        const TW* __restrict__ w, const float* __restrict__ mean,
                                                        const float* __restrict__ rstd, T* __restrict__ dx,
                                                        const T* __restrict__ res, float* __restrict__ partial,
-                                                       int64_t rows, int64_t cols) {
+                                                       int64_t rows, int64_t cols, const T* __restrict__ x2 = nullptr) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float* slab = partial ? partial + (int64_t)blockIdx.x * 2 * cols : nullptr;
   if (slab) {
@@ -178,11 +192,12 @@ __global__ __launch_bounds__(256) void layernorm_bwd_k(const T* __restrict__ dy,
       rs = rstd[row];
       mu = mean[row];
       const T* xr = x + row * cols;
+      const T* x2r = ADD ? x2 + row * cols : nullptr;
       const T* gr = dy + row * cols;
       float s1 = 0.f, s2 = 0.f;
       for (int64_t c = (int64_t)lane * VEC; c < cols; c += 64 * VEC) {
         float xv[VEC], gv[VEC], wv[VEC];
-        Vec<T, VEC>::ld(xv, xr + c);
+        ld_row<T, VEC, ADD>(xv, xr, x2r, c);
         Vec<T, VEC>::ld(gv, gr + c);
         if (w) Vec<TW, VEC>::ld(wv, w + c);
 #pragma unroll
@@ -196,7 +211,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_k(const T* __restrict__ dy,
       T* dxr = dx + row * cols;
       for (int64_t c = (int64_t)lane * VEC; c < cols; c += 64 * VEC) {
         float xv[VEC], gv[VEC], wv[VEC], o[VEC];
-        Vec<T, VEC>::ld(xv, xr + c);
+        ld_row<T, VEC, ADD>(xv, xr, x2r, c);
         Vec<T, VEC>::ld(gv, gr + c);
         if (w) Vec<TW, VEC>::ld(wv, w + c);
 #pragma unroll
@@ -217,10 +232,11 @@ __global__ __launch_bounds__(256) void layernorm_bwd_k(const T* __restrict__ dy,
       for (int turn = 0; turn < 4; ++turn) {
         if (turn == wave && ok) {
           const T* xr = x + row * cols;
+          const T* x2r = ADD ? x2 + row * cols : nullptr;
           const T* gr = dy + row * cols;
           for (int64_t c = (int64_t)lane * VEC; c < cols; c += 64 * VEC) {
             float xv[VEC], gv[VEC];
-            Vec<T, VEC>::ld(xv, xr + c);
+            ld_row<T, VEC, ADD>(xv, xr, x2r, c);
             Vec<T, VEC>::ld(gv, gr + c);
 #pragma unroll
             for (int i = 0; i < VEC; ++i) {
@@ -918,6 +934,48 @@ extern "C" int dxa_layernorm_bwd(const void* dy, const void* x, const void* w, c
     if (vec_ok && cols % 4 == 0) hipLaunchKernelGGL((layernorm_bwd_k<float, float, 4>), grid, dim3(256), 0, st, (const float*)dy, (const float*)x, (const float*)w, mean, rstd, (float*)dx, (const float*)residual, part, rows, cols);
     else hipLaunchKernelGGL((layernorm_bwd_k<float, float, 1>), grid, dim3(256), 0, st, (const float*)dy, (const float*)x, (const float*)w, mean, rstd, (float*)dx, (const float*)residual, part, rows, cols);
   }
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
+}
+
+// y = LayerNorm(x + res): layernorm_fwd_k / layernorm_bwd_k with the second addend read beside the first (ADD); the sum exists in
+// registers only.  The backward's dx is the gradient of both addends.
+extern "C" int dxa_add_layernorm_fwd(const void* x, const void* res, const void* w, const void* b, void* y, float* mean,
+                                     float* rstd, int64_t rows, int64_t cols, float eps, int dtype, int w_dtype,
+                                     dxa_stream_t stream) {
+  if (int rc = check_norm_dtypes(dtype, w_dtype, "dxa_add_layernorm_fwd")) return rc;
+  DXA_CHECK_ARG(x && res && y, "dxa_add_layernorm_fwd: null x / res / y");
+  DXA_CHECK_ARG(rows >= 0 && cols > 0, "dxa_add_layernorm_fwd: bad sizes (rows %lld, cols %lld)", (long long)rows, (long long)cols);
+  if (rows == 0) return DXA_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const bool vec = al16(x) && al16(res) && al16(y) && (!w || al16(w)) && (!b || al16(b)) && cols % 4 == 0;
+  dim3 grid((unsigned)((rows + 3) / 4));
+#define ADD_LN_FWD(T_, TW_, V_) hipLaunchKernelGGL((layernorm_fwd_k<T_, TW_, V_, true>), grid, dim3(256), 0, st, (const T_*)x, (const TW_*)w, (const TW_*)b, (T_*)y, mean, rstd, rows, cols, eps, (const T_*)res)
+  if (dtype == DXA_BF16 && w_dtype == DXA_BF16) { if (vec) ADD_LN_FWD(bf16_t, bf16_t, 4); else ADD_LN_FWD(bf16_t, bf16_t, 1); }
+  else if (dtype == DXA_BF16) { if (vec) ADD_LN_FWD(bf16_t, float, 4); else ADD_LN_FWD(bf16_t, float, 1); }
+  else { if (vec) ADD_LN_FWD(float, float, 4); else ADD_LN_FWD(float, float, 1); }
+#undef ADD_LN_FWD
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
+}
+
+extern "C" int dxa_add_layernorm_bwd(const void* dy, const void* x, const void* res, const void* w, const float* mean,
+                                     const float* rstd, void* dx, float* partial_dwdb, int64_t rows, int64_t cols, int dtype,
+                                     int w_dtype, dxa_stream_t stream) {
+  if (int rc = check_norm_dtypes(dtype, w_dtype, "dxa_add_layernorm_bwd")) return rc;
+  DXA_CHECK_ARG(dy && x && res && mean && rstd && dx, "dxa_add_layernorm_bwd: null dy / x / res / mean / rstd / dx");
+  DXA_CHECK_ARG(rows >= 0 && cols > 0, "dxa_add_layernorm_bwd: bad sizes (rows %lld, cols %lld)", (long long)rows, (long long)cols);
+  DXA_CHECK_ARG(!w || partial_dwdb, "dxa_add_layernorm_bwd: partial_dwdb required when w is given");
+  if (rows == 0) return DXA_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const bool vec = al16(x) && al16(res) && al16(dy) && al16(dx) && (!w || al16(w)) && cols % 4 == 0;
+  dim3 grid((unsigned)dxa_norm_bwd_blocks(rows));
+  float* part = w ? partial_dwdb : nullptr;
+#define ADD_LN_BWD(T_, TW_, V_) hipLaunchKernelGGL((layernorm_bwd_k<T_, TW_, V_, true>), grid, dim3(256), 0, st, (const T_*)dy, (const T_*)x, (const TW_*)w, mean, rstd, (T_*)dx, (const T_*)nullptr, part, rows, cols, (const T_*)res)
+  if (dtype == DXA_BF16 && w_dtype == DXA_BF16) { if (vec) ADD_LN_BWD(bf16_t, bf16_t, 4); else ADD_LN_BWD(bf16_t, bf16_t, 1); }
+  else if (dtype == DXA_BF16) { if (vec) ADD_LN_BWD(bf16_t, float, 4); else ADD_LN_BWD(bf16_t, float, 1); }
+  else { if (vec) ADD_LN_BWD(float, float, 4); else ADD_LN_BWD(float, float, 1); }
+#undef ADD_LN_BWD
   DXA_CHECK_LAUNCH();
   return DXA_OK;
 }

@@ -711,6 +711,18 @@ class NormFn(_StoreFn):
         return dx, None, None, None, None, None, None
 
 
+def _fold_ln_partials(st: ParamStore, wn: str, bn: str, part: torch.Tensor) -> None:
+    """a LayerNorm backward's per-workgroup partial sums [blocks, dw | db] into the gradient slots of its weight and bias"""
+    cols = part.shape[1] // 2
+    dw, db, acc = st.g(wn), st.g(bn), st.accum_flag(wn)
+    if db.data_ptr() == dw.data_ptr() + 4 * cols:      # weight and bias slots lie back to back: one column sum
+        K.colsum(part, out=torch.as_strided(dw, (2 * cols,), (1,)), accumulate=acc)
+    else:
+        K.colsum(part[:, :cols], out=dw, accumulate=acc)
+        K.colsum(part[:, cols:], out=db, accumulate=acc)
+    st.mark_written(wn, bn)
+
+
 class DownsampleNormFn(_StoreFn):
     """DownSampleBlock + nn.LayerNorm(4C) of the `mlp_downsample` projector (mm_projector/builder.py:9-33,62-69): x [N, G*G, C] ->
     [N, ceil(G/2)^2, 4C], 2x2 neighbouring tokens side by side (column-pair major order, odd grids zero padded), normalised.  One
@@ -732,15 +744,31 @@ class DownsampleNormFn(_StoreFn):
         x, mean, rstd = ctx.saved_tensors
         dx, part = K.downsample_layernorm_bwd(dy.contiguous(), x, st.w(wn), mean, rstd)
         if st.trainable(wn):
-            cols = part.shape[1] // 2
-            dw, db, acc = st.g(wn), st.g(bn), st.accum_flag(wn)
-            if db.data_ptr() == dw.data_ptr() + 4 * cols:      # weight and bias slots lie back to back: one column sum
-                K.colsum(part, out=torch.as_strided(dw, (2 * cols,), (1,)), accumulate=acc)
-            else:
-                K.colsum(part[:, :cols], out=dw, accumulate=acc)
-                K.colsum(part[:, cols:], out=db, accumulate=acc)
-            st.mark_written(wn, bn)
+            _fold_ln_partials(st, wn, bn, part)
         return dx, None, None, None, None, None
+
+
+class AddNormFn(_StoreFn):
+    """LayerNorm(x + res) in one launch per direction (the MuVLA fuser, dexbotic/model/muvla/muvla_arch.py:46-47): the sum is
+    never written; the one dx of the backward is the gradient of both addends."""
+
+    @staticmethod
+    def forward(ctx, x, res, anchor, st: ParamStore, wn: str, bn: str, eps: float):
+        x, res = x.contiguous(), res.contiguous()
+        y, mean, rstd = K.add_layernorm_fwd(x, res, st.w(wn), st.w(bn), eps)
+        ctx.st, ctx.wn, ctx.bn = st, wn, bn
+        _use(ctx, st, wn, bn)
+        ctx.save_for_backward(x, res, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        st, wn, bn = ctx.st, ctx.wn, ctx.bn
+        x, res, mean, rstd = ctx.saved_tensors
+        dx, part = K.add_layernorm_bwd(dy.contiguous(), x, res, st.w(wn), mean, rstd)
+        if st.trainable(wn):
+            _fold_ln_partials(st, wn, bn, part)
+        return dx, dx, None, None, None, None, None
 
 
 class VitEmbedFn(_StoreFn):
@@ -890,6 +918,22 @@ class MseLossFn(Function):
         return K.scale_dev_(dpred.clone(), g.reshape(1).float().contiguous()), None
 
 
+class ExpectileLossFn(Function):
+    """mean(w d^2), d = pred - target, w = tau where d < 0 and 1 - tau elsewhere: the reward head's loss
+    (dexbotic/model/muvla/muvla_arch.py:584-587, expectile 0.9)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, tau: float):
+        loss, dpred = K.expectile_loss(pred.contiguous(), target.contiguous(), tau, 1.0, want_grad=True)
+        ctx.save_for_backward(dpred)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (dpred,) = ctx.saved_tensors
+        return K.scale_dev_(dpred.clone(), g.reshape(1).float().contiguous()), None, None
+
+
 LMHEAD_SLAB_BYTES = (1 << 31) - 4096        # largest output one launch of the MFMA fast path addresses (tests shrink it)
 
 
@@ -923,7 +967,24 @@ class LmHeadSoftLossFn(_StoreFn):
         return (_lm_head_loss_bwd(ctx, g),) + (None,) * 6
 
 
-def _lm_head_loss_fwd(ctx, hidden, st: ParamStore, wn: str, labels_shifted: torch.Tensor, n_valid: int, soft):
+class LmHeadSampleLossFn(_StoreFn):
+    """LmHeadLossFn with MuVLA's reduction (dexbotic/model/muvla/muvla_arch.py:559-576): every sample's row losses are divided by
+    that sample's own number of non-ignored rows (at least 1), weighted by 1 + sigmoid(reward_b) when ``reward`` ([B] fp32, on the
+    device) is given, and the B results are averaged.  The per-row factor w_b / (max(n_b, 1) B) goes into the cross-entropy
+    backward kernel itself (dxa_cross_entropy_rows_bwd): no second pass over the [rows, V] gradient."""
+
+    @staticmethod
+    def forward(ctx, hidden, anchor, st: ParamStore, wn: str, labels_shifted: torch.Tensor, B: int, reward):
+        return _lm_head_loss_fwd(ctx, hidden, st, wn, labels_shifted, 0, None, samples=(B, reward))
+
+    @staticmethod
+    def backward(ctx, g, _g_logits):
+        return (_lm_head_loss_bwd(ctx, g),) + (None,) * 6
+
+
+def _lm_head_loss_fwd(ctx, hidden, st: ParamStore, wn: str, labels_shifted: torch.Tensor, n_valid: int, soft, samples=None):
+    """``samples`` = (B, reward [B] fp32 on the device or None): the per-sample normalised, reward-weighted mean of
+    LmHeadSampleLossFn instead of the mean over the non-ignored rows (``n_valid`` is then unused)"""
     h2 = hidden.reshape(-1, hidden.shape[-1]).contiguous()
     W = st.w(wn)
     logits = K.mm_nt(h2, W)
@@ -931,24 +992,30 @@ def _lm_head_loss_fwd(ctx, hidden, st: ParamStore, wn: str, labels_shifted: torc
         row_loss, lse = K.cross_entropy_fwd(logits, labels_shifted)
     else:
         row_loss, lse = K.soft_cross_entropy_fwd(logits, labels_shifted, soft)
-    loss = K.colsum(row_loss.view(-1, 1))
-    if n_valid > 0:
-        K.scale_(loss, 1.0 / n_valid)
-    elif soft is None:
-        loss = loss * float("nan")                          # F.cross_entropy(mean) over zero targets
-    ctx.st, ctx.wn, ctx.n_valid, ctx.hshape, ctx.soft = st, wn, n_valid, hidden.shape, soft
+    row_w = None
+    if samples is not None:
+        loss, row_w = K.ce_sample_reduce(row_loss, labels_shifted, samples[1], samples[0], W.shape[0])
+    else:
+        loss = K.colsum(row_loss.view(-1, 1))
+        if n_valid > 0:
+            K.scale_(loss, 1.0 / n_valid)
+        elif soft is None:
+            loss = loss * float("nan")                          # F.cross_entropy(mean) over zero targets
+    ctx.st, ctx.wn, ctx.n_valid, ctx.hshape, ctx.soft, ctx.weighted = st, wn, n_valid, hidden.shape, soft, row_w is not None
     _use(ctx, st, wn)
-    ctx.save_for_backward(h2, logits, lse, labels_shifted)
+    ctx.save_for_backward(h2, logits, lse, labels_shifted, *(() if row_w is None else (row_w,)))
     ctx.mark_non_differentiable(logits)
     return loss.view(()), logits.view(*hidden.shape[:-1], W.shape[0])
 
 
 def _lm_head_loss_bwd(ctx, g):
     st, wn = ctx.st, ctx.wn
-    h2, logits, lse, labels = ctx.saved_tensors
+    h2, logits, lse, labels, *row_w = ctx.saved_tensors
     W = st.w(wn)
     gs, scale = g.reshape(1).float().contiguous(), 1.0 / max(ctx.n_valid, 1)
-    if ctx.soft is None:
+    if ctx.weighted:
+        dz = K.cross_entropy_rows_bwd(logits, labels, lse, gs, 1.0, row_w[0])     # each row's 1 / (n_b B) is inside its weight
+    elif ctx.soft is None:
         dz = K.cross_entropy_bwd(logits, labels, lse, gs, scale)
     else:
         dz = K.soft_cross_entropy_bwd(logits, labels, lse, gs, scale, ctx.soft)
@@ -1441,3 +1508,61 @@ class RowGateFn(Function):
         dy = dy.contiguous()
         B = x.shape[0]
         return K.mul_rows(dy, g), K.token_sum(K.mul(dy, x))
+
+
+
+class ParamFn(_StoreFn):
+    """a parameter used as an ACTIVATION (the Q-former's learned queries, dexbotic/model/muvla/muvla_arch.py:53,61): its
+    compute-dtype value going in, its gradient written to the arena coming back"""
+
+    @staticmethod
+    def forward(ctx, anchor, st: ParamStore, name: str):
+        ctx.st, ctx.name = st, name
+        _use(ctx, st, name)
+        w = st.w(name)
+        return w.view(w.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = dy.contiguous()
+        _vgrad(ctx.st, ctx.name, dy if dy.dtype == torch.float32 else K.cast(dy, torch.float32))
+        return None, None, None
+
+
+class BroadcastBatchFn(Function):
+    """x [S, ...] -> a stride-0 view [B, S, ...] (one projection of the shared queries serves every sample); the backward sums the B
+    gradients with the library's token sum, in batch order"""
+
+    @staticmethod
+    def forward(ctx, x, B: int):
+        ctx.B = B
+        return x.unsqueeze(0).expand(B, *x.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        B = ctx.B
+        dy = dy.contiguous()
+        if B == 1:
+            return dy[0], None
+        return K.token_sum(dy.view(1, B, -1)).view(dy.shape[1:]), None
+
+
+class SplitRowsFn(Function):
+    """[R, ...] -> ([n, ...], [R - n, ...]) views; the backward writes the two gradients side by side with library copies"""
+
+    @staticmethod
+    def forward(ctx, x, n: int):
+        ctx.shape, ctx.dt, ctx.n = tuple(x.shape), x.dtype, n
+        x = x.contiguous()
+        return x[:n], x[n:]
+
+    @staticmethod
+    def backward(ctx, ga, gb):
+        n = ctx.n
+        out = torch.empty(ctx.shape, device=(ga if ga is not None else gb).device, dtype=ctx.dt)
+        for g, dst in ((ga, out[:n]), (gb, out[n:])):
+            if g is None:
+                dst.zero_()
+            else:
+                K.cast(g.contiguous(), ctx.dt, out=dst)
+        return out, None

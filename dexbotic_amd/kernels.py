@@ -498,6 +498,37 @@ def layernorm_bwd(dy, x, w, mean, rstd, dw_out=None, db_out=None, accumulate: bo
     return dx.view(x.shape), s[:cols], s[cols:]
 
 
+def add_layernorm_fwd(x, res, w, b, eps):
+    """y = LayerNorm(x + res) in one launch; the sum is never written -> (y, mean [rows], rstd [rows])"""
+    x2 = x.reshape(-1, x.shape[-1])
+    r2 = res.reshape(-1, x.shape[-1])
+    assert x2.is_contiguous() and r2.is_contiguous() and r2.shape == x2.shape and r2.dtype == x2.dtype
+    y = torch.empty_like(x2)
+    mean = torch.empty(x2.shape[0], device=x.device, dtype=torch.float32)
+    rstd = torch.empty_like(mean)
+    L.check(lib.dxa_add_layernorm_fwd(_ptr(x2), _ptr(r2), _ptr(w), _ptr(b), _ptr(y), _ptr(mean), _ptr(rstd), x2.shape[0],
+                                      x2.shape[1], eps, dt(x2), dt(w) if w is not None else dt(x2), _stream()),
+            "dxa_add_layernorm_fwd")
+    return y.view(x.shape), mean, rstd
+
+
+def add_layernorm_bwd(dy, x, res, w, mean, rstd):
+    """-> (dx, the gradient of BOTH addends; partial sums [blocks, dw | db] fp32 or None without w): the caller folds the partials"""
+    x2 = x.reshape(-1, x.shape[-1])
+    r2 = res.reshape(-1, x.shape[-1])
+    dy2 = dy.reshape(-1, x.shape[-1])
+    assert x2.is_contiguous() and r2.is_contiguous() and dy2.is_contiguous() and r2.shape == x2.shape == dy2.shape
+    assert r2.dtype == x2.dtype == dy2.dtype
+    rows, cols = x2.shape
+    dx = torch.empty_like(x2)
+    part = None
+    if w is not None:
+        part = torch.empty((norm_bwd_blocks(rows), 2 * cols), device=x.device, dtype=torch.float32)
+    L.check(lib.dxa_add_layernorm_bwd(_ptr(dy2), _ptr(x2), _ptr(r2), _ptr(w), _ptr(mean), _ptr(rstd), _ptr(dx), _ptr(part), rows,
+                                      cols, dt(x2), dt(w) if w is not None else dt(x2), _stream()), "dxa_add_layernorm_bwd")
+    return dx.view(x.shape), part
+
+
 def downsample_grid(n_tokens: int) -> Tuple[int, int]:
     """(G, h) of the 2x2 token merge: n_tokens = G*G input tokens per image, h*h = ceil(G/2)^2 merged tokens"""
     G = int(round(n_tokens ** 0.5))
@@ -941,6 +972,17 @@ def mse_loss_rows(pred, target, row_w, gscale: float = 1.0, want_grad: bool = Tr
     return loss, dpred
 
 
+def expectile_loss(pred, target, tau: float, gscale: float = 1.0, want_grad: bool = True):
+    """mean(w d^2), w = tau where d = pred - target < 0 and 1 - tau elsewhere -> (loss [1], dpred or None)"""
+    assert pred.is_contiguous() and target.is_contiguous() and pred.dtype == torch.float32 and target.dtype == torch.float32
+    assert pred.numel() == target.numel()
+    loss = torch.empty(1, device=pred.device, dtype=torch.float32)
+    dpred = torch.empty_like(pred) if want_grad else None
+    L.check(lib.dxa_expectile_loss(_ptr(pred), _ptr(target), _ptr(loss), _ptr(dpred), pred.numel(), float(tau), gscale,
+                                   _stream()), "dxa_expectile_loss")
+    return loss, dpred
+
+
 def ddim_step(x, model_out, B, use_cfg, cfg_scale, c_recip, c_recipm1, ab_prev):
     per = x.numel() // x.shape[0]
     L.check(lib.dxa_ddim_step(_ptr(x), _ptr(model_out), B, per, int(use_cfg), cfg_scale, c_recip, c_recipm1, ab_prev,
@@ -1044,6 +1086,38 @@ def cross_entropy_bwd(logits: torch.Tensor, labels: torch.Tensor, lse: torch.Ten
                                       _ptr(out), out.stride(0), rows, V, ignore_index, dt(logits), _stream()),
             "dxa_cross_entropy_bwd")
     return out
+
+
+def cross_entropy_rows_bwd(logits: torch.Tensor, labels: torch.Tensor, lse: torch.Tensor, gscale: Optional[torch.Tensor],
+                           scale: float, row_w: Optional[torch.Tensor], out: Optional[torch.Tensor] = None,
+                           ignore_index: int = -100) -> torch.Tensor:
+    """dlogits = (softmax - onehot) * row_w[r] * gscale[0] * scale; ``row_w`` [rows] fp32 (None: cross_entropy_bwd's result)"""
+    rows, V = logits.shape
+    if out is None:
+        out = torch.empty_like(logits)
+    assert out.shape == logits.shape and out.dtype == logits.dtype and out.stride(1) == 1
+    if row_w is not None:
+        assert row_w.dtype == torch.float32 and row_w.is_contiguous() and row_w.numel() == rows
+    L.check(lib.dxa_cross_entropy_rows_bwd(_ptr(logits), logits.stride(0), _ptr(labels), _ptr(lse), _ptr(gscale), float(scale),
+                                           _ptr(row_w), _ptr(out), out.stride(0), rows, V, ignore_index, dt(logits), _stream()),
+            "dxa_cross_entropy_rows_bwd")
+    return out
+
+
+def ce_sample_reduce(row_loss: torch.Tensor, labels: torch.Tensor, reward: Optional[torch.Tensor], B: int, V: int,
+                     ignore_index: int = -100):
+    """row_loss / labels [B*L] (cross_entropy_fwd's), reward [B] fp32 on the device or None -> (loss [1], row_w [B*L]):
+    loss = mean_b w_b sum_t row_loss[b, t] / max(n_b, 1), row_w[b, t] = w_b / (max(n_b, 1) B), w_b = 1 + sigmoid(reward_b) or 1"""
+    assert row_loss.dtype == torch.float32 and row_loss.is_contiguous() and labels.dtype == torch.int64 and labels.is_contiguous()
+    n = row_loss.numel()
+    assert labels.numel() == n and B > 0 and n % B == 0
+    if reward is not None:
+        assert reward.dtype == torch.float32 and reward.is_contiguous() and reward.numel() == B and reward.device == row_loss.device
+    loss = torch.empty(1, device=row_loss.device, dtype=torch.float32)
+    row_w = torch.empty(n, device=row_loss.device, dtype=torch.float32)
+    L.check(lib.dxa_ce_sample_reduce(_ptr(row_loss), _ptr(labels), _ptr(reward), _ptr(row_w), _ptr(loss), B, n // B, V,
+                                     ignore_index, _stream()), "dxa_ce_sample_reduce")
+    return loss, row_w
 
 
 class SoftTokens:

@@ -189,6 +189,16 @@ int dxa_layernorm_bwd(const void* dy, const void* x, const void* w, const float*
                       void* dx, const void* residual, float* partial_dwdb, int64_t rows, int64_t cols, int dtype,
                       int w_dtype, dxa_stream_t stream);
 int dxa_norm_bwd_blocks(int64_t rows);
+/* y = LayerNorm(x + res) in one launch per direction (the fuser of dexbotic/model/muvla/muvla_arch.py:44-48: ln(attn + obs)).
+ * x and res are [rows, cols] of `dtype`; the sum is formed in fp32 wherever the row is read, never rounded to `dtype` and never
+ * written.  mean / rstd [rows] as dxa_layernorm_fwd writes them; with res == 0 every output equals dxa_layernorm_fwd's bit for bit.
+ * bwd re-forms x + res from its two inputs and writes ONE dx [rows, cols]: the same tensor is the gradient of both addends.
+ * partial dw/db as dxa_layernorm_bwd ([dxa_norm_bwd_blocks(rows), 2*cols] fp32, folded by dxa_colsum; required when w is given). */
+int dxa_add_layernorm_fwd(const void* x, const void* res, const void* w, const void* b, void* y, float* mean, float* rstd,
+                          int64_t rows, int64_t cols, float eps, int dtype, int w_dtype, dxa_stream_t stream);
+int dxa_add_layernorm_bwd(const void* dy, const void* x, const void* res, const void* w, const float* mean, const float* rstd,
+                          void* dx, float* partial_dwdb, int64_t rows, int64_t cols, int dtype, int w_dtype,
+                          dxa_stream_t stream);
 /* 2x2 token merge + LayerNorm(4C) in one launch per direction: the `mlp_downsample` projector's DownSampleBlock followed by
  * nn.LayerNorm (dexbotic/model/modules/mm_projector/builder.py:9-33,62-69).  x [N, G*G, C], token t = r*G + c; an odd grid is
  * zero padded to Gp = G + 1 on the bottom and right; h = Gp / 2.  y [N, h*h, 4C], output token o = j*h + i (j: column pair,
@@ -406,6 +416,11 @@ int dxa_mse_loss(const float* pred, const float* target, float* loss, float* dpr
  * loss = sum_r w[r] * mean_c((pred-target)[r,c]^2) / (sum_r w[r] + 1e-6); dpred = d loss / d pred * gscale */
 int dxa_mse_loss_rows(const float* pred, const float* target, const float* row_w, float* loss, float* dpred,
                       int64_t rows, int64_t cols, float gscale, dxa_stream_t stream);
+/* expectile regression of the MuVLA reward head (dexbotic/model/muvla/muvla_arch.py:584-587), one launch:
+ * diff = pred - target; w = diff < 0 ? tau : 1 - tau (diff == 0 takes 1 - tau; its gradient is 0);
+ * loss = mean(w * diff^2); dpred = 2 * w * diff / n * gscale (NULL to skip).  0 < tau < 1, n > 0. */
+int dxa_expectile_loss(const float* pred, const float* target, float* loss, float* dpred, int64_t n, float tau,
+                       float gscale, dxa_stream_t stream);
 /* One DDIM(eta=0) update with classifier-free guidance (dit.py:294-311, diffusion.py:626-673):
  * eps = eu + s (ec - eu) with ec = model_out[0:B], eu = model_out[B:2B] (cfg) or eps = model_out;
  * x0 = c_recip x - c_recipm1 eps ; eps' = (c_recip x - x0)/c_recipm1 ; x <- sqrt(ab_prev) x0 +
@@ -481,6 +496,21 @@ int dxa_cross_entropy_fwd(const void* logits, int64_t ld, const int64_t* labels,
 int dxa_cross_entropy_bwd(const void* logits, int64_t ld, const int64_t* labels, const float* lse,
                           const float* gscale, float scale, void* dlogits, int64_t ldd, int64_t rows, int64_t V,
                           int64_t ignore_index, int dtype, dxa_stream_t stream);
+/* dxa_cross_entropy_bwd with one more factor per row (the same kernel):
+ *   dlogits[r, v] = (exp(logits[r, v] - lse[r]) - [v == label]) * row_w[r] * gscale[0] * scale
+ * row_w: [rows] fp32, device.  Ignored rows are written as zeros; dlogits may alias logits.  With row_w == NULL the result is
+ * bit-identical to dxa_cross_entropy_bwd at the same scale. */
+int dxa_cross_entropy_rows_bwd(const void* logits, int64_t ld, const int64_t* labels, const float* lse,
+                               const float* gscale, float scale, const float* row_w, void* dlogits, int64_t ldd,
+                               int64_t rows, int64_t V, int64_t ignore_index, int dtype, dxa_stream_t stream);
+/* Per-sample normalised, reward-weighted language loss of MuVLA (dexbotic/model/muvla/muvla_arch.py:566-576) from the row losses
+ * of dxa_cross_entropy_fwd over [B, L] rows: n_b = number of non-ignored labels of sample b (ignore_index, or outside [0, V):
+ * the forward's own rule), w_b = 1 + sigmoid(reward[b]) (reward: [B] fp32 on the DEVICE, NULL for w_b = 1),
+ *   loss      = sum_b w_b * (sum_t row_loss[b, t]) / max(n_b, 1) / B
+ *   row_w[b,t] = w_b / (max(n_b, 1) * B)        for every t: the row weights dxa_cross_entropy_rows_bwd takes
+ * One launch of one workgroup, samples in order, double accumulation through a fixed tree: the same bits on every run. */
+int dxa_ce_sample_reduce(const float* row_loss, const int64_t* labels, const float* reward, float* row_w, float* loss,
+                         int64_t B, int64_t L, int64_t V, int64_t ignore_index, dxa_stream_t stream);
 int dxa_argmax_rows(const void* x, int64_t ld, int64_t* out, int64_t rows, int64_t cols, int dtype,
                     dxa_stream_t stream);
 /* dxa_sample_rows: token[r] = one draw from row r of logits [rows, V] (fp32 or bf16, row stride ld elements, any alignment,
