@@ -30,6 +30,7 @@ def model_registry():
     reference (dexbotic_arch.py:18, cogact_arch.py:14)."""
     from .model.cogact.cogact_arch import CogActConfig, CogACTForCausalLM
     from .model.dexbotic_arch import DexboticConfig, DexboticForCausalLM
+    from .model.dm0.dm0_arch import DM0Config, DM0ForCausalLM
     from .model.memvla.memvla_arch import MemVLAConfig, MemVLAForCausalLM
     from .model.navila.navila_arch import NaVILAConfig, NaVILAForCausalLM
     from .model.pi0.pi0_arch import Pi0Config, Pi0ForCausalLM
@@ -37,7 +38,8 @@ def model_registry():
             "dexbotic_cogact": (CogActConfig, CogACTForCausalLM),
             "dexbotic_pi0": (Pi0Config, Pi0ForCausalLM),
             "dexbotic_memvla": (MemVLAConfig, MemVLAForCausalLM),
-            "dexbotic_navila": (NaVILAConfig, NaVILAForCausalLM)}
+            "dexbotic_navila": (NaVILAConfig, NaVILAForCausalLM),
+            "dexbotic_dm0": (DM0Config, DM0ForCausalLM)}
 
 
 def hybrid_cogact():

@@ -140,6 +140,8 @@ SIGNATURES = {
     "dxa_qknorm_rope_split": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _vp]),
     "dxa_qknorm_rope_merge": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _vp]),
     "dxa_qknorm_rope_merge_blocks": (_int, [_i64, _int, _int, _int, _int]),
+    "dxa_qknorm_rope_split_at": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _int, _int, _int, _int, _vp]),
+    "dxa_qknorm_rope_merge_from": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _int, _int, _vp]),
     "dxa_attn_fwd": (_int, [C.POINTER(AttnDesc), _vp]),
     "dxa_attn_fwd_workspace": (_sz, [C.POINTER(AttnDesc)]),
     "dxa_attn_fwd_ws": (_int, [C.POINTER(AttnDesc), _vp, _sz, _vp]),

@@ -107,7 +107,9 @@ __global__ __launch_bounds__(TPB) void qknorm_rope_split_k(const T* __restrict__
                                                            T* __restrict__ v, const T* __restrict__ wq, const T* __restrict__ wk,
                                                            float eps, float* __restrict__ rstd_out, const float* __restrict__ cos_t,
                                                            const float* __restrict__ sin_t, const int32_t* __restrict__ pos, int B,
-                                                           int S, int Hq, int Hkv, int D) {
+                                                           int S, int Hq, int Hkv, int D, int Sq, int q0, int Sk, int k0) {
+  // this call's S tokens sit at positions q0 .. q0 + S - 1 of the Sq that q holds per (b, head) and at k0 .. k0 + S - 1 of the Sk of
+  // k / v, apart, as rope_k's Sc / s0: a sampler's queries are the suffix alone while its keys land behind the cached prefix
   const int HS = Hq + 2 * Hkv, HN = Hq + Hkv, half = D / 2, qn = half / VEC;
   const int64_t total = (int64_t)B * S * HS * qn;
   const int64_t ld = (int64_t)HS * D;
@@ -121,9 +123,9 @@ __global__ __launch_bounds__(TPB) void qknorm_rope_split_k(const T* __restrict__
     const int d0 = qd * VEC;
     T* hm;
     const T* w = nullptr;
-    if (hs < Hq) { hm = q + (((int64_t)b * Hq + hs) * S + s) * D; w = wq; }
-    else if (hs < HN) { hm = k + (((int64_t)b * Hkv + (hs - Hq)) * S + s) * D; w = wk; }
-    else hm = v + (((int64_t)b * Hkv + (hs - HN)) * S + s) * D;
+    if (hs < Hq) { hm = q + (((int64_t)b * Hq + hs) * Sq + q0 + s) * D; w = wq; }
+    else if (hs < HN) { hm = k + (((int64_t)b * Hkv + (hs - Hq)) * Sk + k0 + s) * D; w = wk; }
+    else hm = v + (((int64_t)b * Hkv + (hs - HN)) * Sk + k0 + s) * D;
     const int64_t toff = t * ld + (int64_t)hs * D;
     float x1[VEC], x2[VEC];
     Vec<T, VEC>::ld(x1, tok + toff + d0);
@@ -167,7 +169,7 @@ __global__ __launch_bounds__(TPB) void qknorm_rope_merge_k(const T* __restrict__
                                                            const T* __restrict__ wk, T* __restrict__ dtok,
                                                            float* __restrict__ partial, const float* __restrict__ cos_t,
                                                            const float* __restrict__ sin_t, const int32_t* __restrict__ pos, int B,
-                                                           int S, int Hq, int Hkv, int D) {
+                                                           int S, int Hq, int Hkv, int D, int Sc, int s0) {
   __shared__ float red[TPB / 64][2 * 256];
   const int HS = Hq + 2 * Hkv, HN = Hq + Hkv, half = D / 2, qn = half / VEC;
   const int64_t total = (int64_t)B * S * HS * qn;
@@ -185,9 +187,9 @@ __global__ __launch_bounds__(TPB) void qknorm_rope_merge_k(const T* __restrict__
     const int d0 = qd * VEC;
     const T* hm;
     const T* w = nullptr;
-    if (hs < Hq) { hm = dq + (((int64_t)b * Hq + hs) * S + s) * D; w = wq; }
-    else if (hs < HN) { hm = dk + (((int64_t)b * Hkv + (hs - Hq)) * S + s) * D; w = wk; }
-    else hm = dv + (((int64_t)b * Hkv + (hs - HN)) * S + s) * D;
+    if (hs < Hq) { hm = dq + (((int64_t)b * Hq + hs) * Sc + s0 + s) * D; w = wq; }
+    else if (hs < HN) { hm = dk + (((int64_t)b * Hkv + (hs - Hq)) * Sc + s0 + s) * D; w = wk; }
+    else hm = dv + (((int64_t)b * Hkv + (hs - HN)) * Sc + s0 + s) * D;
     const int64_t toff = t * ld + (int64_t)hs * D;
     float g1[VEC], g2[VEC], x1[VEC], x2[VEC], w1[VEC], w2[VEC];
     Vec<T, VEC>::ld(g1, hm + d0);
@@ -708,36 +710,45 @@ inline int64_t qkn_items(int64_t tokens, int Hq, int Hkv, int D, int dtype) {
 }
 }  // namespace
 
-extern "C" int dxa_qknorm_rope_split(const void* qkv, void* q, void* k, void* v, const void* q_norm_w, const void* k_norm_w,
-                                     float eps, float* rstd, const float* cos_t, const float* sin_t, const int32_t* pos, int B,
-                                     int S, int Hq, int Hkv, int D, int dtype, dxa_stream_t stream) {
+extern "C" int dxa_qknorm_rope_split_at(const void* qkv, void* q, void* k, void* v, const void* q_norm_w, const void* k_norm_w,
+                                        float eps, float* rstd, const float* cos_t, const float* sin_t, const int32_t* pos, int B,
+                                        int S, int Hq, int Hkv, int D, int Sq_cap, int q0, int Skv_cap, int kv0, int dtype,
+                                        dxa_stream_t stream) {
   DXA_CHECK_ARG(qkv && q && k && v && q_norm_w && k_norm_w && cos_t && sin_t && ok_dtype(dtype), "dxa_qknorm_rope_split: bad args");
   DXA_CHECK_ARG(qkn_head_dim(D), "dxa_qknorm_rope_split: head_dim must be 32, 64, 128 or 256 (got %d)", D);
   DXA_CHECK_ARG(B >= 0 && S >= 0 && Hq > 0 && Hkv > 0, "dxa_qknorm_rope_split: bad shape B %d S %d Hq %d Hkv %d", B, S, Hq, Hkv);
+  DXA_CHECK_ARG(q0 >= 0 && Sq_cap >= 0 && (int64_t)q0 + S <= Sq_cap, "dxa_qknorm_rope_split: positions %d .. %lld outside the %d q holds", q0, (long long)q0 + S, Sq_cap);
+  DXA_CHECK_ARG(kv0 >= 0 && Skv_cap >= 0 && (int64_t)kv0 + S <= Skv_cap, "dxa_qknorm_rope_split: positions %d .. %lld outside the %d k and v hold", kv0, (long long)kv0 + S, Skv_cap);
   DXA_CHECK_ARG(al(qkv, 16) && al(q, 16) && al(k, 16) && al(v, 16) && al(q_norm_w, 16) && al(k_norm_w, 16) && al(cos_t, 16) && al(sin_t, 16),
                 "dxa_qknorm_rope_split: every tensor must be 16-byte aligned");
   const int64_t total = qkn_items((int64_t)B * S, Hq, Hkv, D, dtype);
   if (total == 0) return DXA_OK;
   dim3 grid(dxa_grid1d(total, TPB));
   if (dtype == DXA_BF16)
-    hipLaunchKernelGGL((qknorm_rope_split_k<bf16_t, 8>), grid, dim3(TPB), 0, ST, (const bf16_t*)qkv, (bf16_t*)q, (bf16_t*)k, (bf16_t*)v, (const bf16_t*)q_norm_w, (const bf16_t*)k_norm_w, eps, rstd, cos_t, sin_t, pos, B, S, Hq, Hkv, D);
+    hipLaunchKernelGGL((qknorm_rope_split_k<bf16_t, 8>), grid, dim3(TPB), 0, ST, (const bf16_t*)qkv, (bf16_t*)q, (bf16_t*)k, (bf16_t*)v, (const bf16_t*)q_norm_w, (const bf16_t*)k_norm_w, eps, rstd, cos_t, sin_t, pos, B, S, Hq, Hkv, D, Sq_cap, q0, Skv_cap, kv0);
   else
-    hipLaunchKernelGGL((qknorm_rope_split_k<float, 4>), grid, dim3(TPB), 0, ST, (const float*)qkv, (float*)q, (float*)k, (float*)v, (const float*)q_norm_w, (const float*)k_norm_w, eps, rstd, cos_t, sin_t, pos, B, S, Hq, Hkv, D);
+    hipLaunchKernelGGL((qknorm_rope_split_k<float, 4>), grid, dim3(TPB), 0, ST, (const float*)qkv, (float*)q, (float*)k, (float*)v, (const float*)q_norm_w, (const float*)k_norm_w, eps, rstd, cos_t, sin_t, pos, B, S, Hq, Hkv, D, Sq_cap, q0, Skv_cap, kv0);
   DXA_CHECK_LAUNCH();
   return DXA_OK;
+}
+extern "C" int dxa_qknorm_rope_split(const void* qkv, void* q, void* k, void* v, const void* q_norm_w, const void* k_norm_w,
+                                     float eps, float* rstd, const float* cos_t, const float* sin_t, const int32_t* pos, int B,
+                                     int S, int Hq, int Hkv, int D, int dtype, dxa_stream_t stream) {
+  return dxa_qknorm_rope_split_at(qkv, q, k, v, q_norm_w, k_norm_w, eps, rstd, cos_t, sin_t, pos, B, S, Hq, Hkv, D, S, 0, S, 0, dtype, stream);
 }
 extern "C" int dxa_qknorm_rope_merge_blocks(int64_t tokens, int Hq, int Hkv, int D, int dtype) {
   DXA_CHECK_ARG(tokens >= 0 && Hq > 0 && Hkv > 0 && qkn_head_dim(D) && ok_dtype(dtype), "dxa_qknorm_rope_merge_blocks: bad args");
   return dxa_grid1d(qkn_items(tokens, Hq, Hkv, D, dtype), TPB, QKN_MAX_BLOCKS);
 }
-extern "C" int dxa_qknorm_rope_merge(const void* dq, const void* dk, const void* dv, const void* qkv, const float* rstd,
-                                     const void* q_norm_w, const void* k_norm_w, void* dqkv, float* partial_dw, const float* cos_t,
-                                     const float* sin_t, const int32_t* pos, int B, int S, int Hq, int Hkv, int D, int dtype,
-                                     dxa_stream_t stream) {
+extern "C" int dxa_qknorm_rope_merge_from(const void* dq, const void* dk, const void* dv, const void* qkv, const float* rstd,
+                                          const void* q_norm_w, const void* k_norm_w, void* dqkv, float* partial_dw,
+                                          const float* cos_t, const float* sin_t, const int32_t* pos, int B, int S, int Hq, int Hkv,
+                                          int D, int S_cap, int s0, int dtype, dxa_stream_t stream) {
   DXA_CHECK_ARG(dq && dk && dv && qkv && rstd && q_norm_w && k_norm_w && dqkv && cos_t && sin_t && ok_dtype(dtype),
                 "dxa_qknorm_rope_merge: bad args");
   DXA_CHECK_ARG(qkn_head_dim(D), "dxa_qknorm_rope_merge: head_dim must be 32, 64, 128 or 256 (got %d)", D);
   DXA_CHECK_ARG(B >= 0 && S >= 0 && Hq > 0 && Hkv > 0, "dxa_qknorm_rope_merge: bad shape B %d S %d Hq %d Hkv %d", B, S, Hq, Hkv);
+  DXA_CHECK_ARG(s0 >= 0 && S_cap >= 0 && (int64_t)s0 + S <= S_cap, "dxa_qknorm_rope_merge: positions %d .. %lld outside the %d the head-major tensors hold", s0, (long long)s0 + S, S_cap);
   DXA_CHECK_ARG(al(dq, 16) && al(dk, 16) && al(dv, 16) && al(qkv, 16) && al(dqkv, 16) && al(q_norm_w, 16) && al(k_norm_w, 16) &&
                     al(cos_t, 16) && al(sin_t, 16),
                 "dxa_qknorm_rope_merge: every tensor must be 16-byte aligned");
@@ -745,11 +756,17 @@ extern "C" int dxa_qknorm_rope_merge(const void* dq, const void* dk, const void*
   if (total == 0) return DXA_OK;
   dim3 grid(dxa_grid1d(total, TPB, QKN_MAX_BLOCKS));      // = dxa_qknorm_rope_merge_blocks: the rows of partial_dw
   if (dtype == DXA_BF16)
-    hipLaunchKernelGGL((qknorm_rope_merge_k<bf16_t, 8>), grid, dim3(TPB), 0, ST, (const bf16_t*)dq, (const bf16_t*)dk, (const bf16_t*)dv, (const bf16_t*)qkv, rstd, (const bf16_t*)q_norm_w, (const bf16_t*)k_norm_w, (bf16_t*)dqkv, partial_dw, cos_t, sin_t, pos, B, S, Hq, Hkv, D);
+    hipLaunchKernelGGL((qknorm_rope_merge_k<bf16_t, 8>), grid, dim3(TPB), 0, ST, (const bf16_t*)dq, (const bf16_t*)dk, (const bf16_t*)dv, (const bf16_t*)qkv, rstd, (const bf16_t*)q_norm_w, (const bf16_t*)k_norm_w, (bf16_t*)dqkv, partial_dw, cos_t, sin_t, pos, B, S, Hq, Hkv, D, S_cap, s0);
   else
-    hipLaunchKernelGGL((qknorm_rope_merge_k<float, 4>), grid, dim3(TPB), 0, ST, (const float*)dq, (const float*)dk, (const float*)dv, (const float*)qkv, rstd, (const float*)q_norm_w, (const float*)k_norm_w, (float*)dqkv, partial_dw, cos_t, sin_t, pos, B, S, Hq, Hkv, D);
+    hipLaunchKernelGGL((qknorm_rope_merge_k<float, 4>), grid, dim3(TPB), 0, ST, (const float*)dq, (const float*)dk, (const float*)dv, (const float*)qkv, rstd, (const float*)q_norm_w, (const float*)k_norm_w, (float*)dqkv, partial_dw, cos_t, sin_t, pos, B, S, Hq, Hkv, D, S_cap, s0);
   DXA_CHECK_LAUNCH();
   return DXA_OK;
+}
+extern "C" int dxa_qknorm_rope_merge(const void* dq, const void* dk, const void* dv, const void* qkv, const float* rstd,
+                                     const void* q_norm_w, const void* k_norm_w, void* dqkv, float* partial_dw, const float* cos_t,
+                                     const float* sin_t, const int32_t* pos, int B, int S, int Hq, int Hkv, int D, int dtype,
+                                     dxa_stream_t stream) {
+  return dxa_qknorm_rope_merge_from(dq, dk, dv, qkv, rstd, q_norm_w, k_norm_w, dqkv, partial_dw, cos_t, sin_t, pos, B, S, Hq, Hkv, D, S, 0, dtype, stream);
 }
 
 extern "C" int dxa_swiglu_fwd(const void* gu, void* out, int64_t rows, int64_t F, int dtype, dxa_stream_t stream) {

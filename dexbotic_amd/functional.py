@@ -1267,6 +1267,174 @@ class Pi0MotLayerFn(_StoreFn):
         return (dxs[0], dxs[1]) + (None,) * 12
 
 
+# ------------------------------------------------------------------------------- Qwen3 mixture layer (DM0)
+def qwen3_pre_attention(st: ParamStore, sp: Qwen2LayerSpec, x):
+    """first half of one expert's Qwen3 layer on x [M, d]: input RMSNorm (plain weight), then the fused q/k/v product without bias
+    -> (h, rstd, qkv [M, (Hq + 2 Hkv) * D]); the per-head q/k norm runs in the RoPE / split pass that follows"""
+    h, rstd = K.rmsnorm_fwd(x, st.w(sp.ln1), sp.eps)
+    return h, rstd, K.mm_nt(h, st.w(*sp.qkv_w, shape=((sp.Hq + 2 * sp.Hkv) * sp.D, sp.d)))
+
+
+def qwen3_post_attention(st: ParamStore, sp: Qwen2LayerSpec, x, a, keep: bool = True):
+    """second half, a [M, Hq * D] = this expert's rows of the attention output: x + o_proj(a); then + down(silu(gate) * up) of the
+    post-attention RMSNorm -> (y, what the backward reads besides a: r, rstd2, h2, gu, act).  ``keep`` = False (no backward will
+    come): the pre-activations gu are not stored (None) where the product's SwiGLU epilogue applies — the same bits either way
+    (kernels.mm_nt_swiglu)."""
+    r = K.mm_nt(a, st.w(sp.o_w), residual=x)
+    h2, rstd2 = K.rmsnorm_fwd(r, st.w(sp.ln2), sp.eps)
+    w_gu = st.w(*sp.gu_w, shape=(2 * sp.F, sp.d))
+    if K.swiglu_gemm_supported(h2, w_gu, keep_pre=keep):
+        act, gu = K.mm_nt_swiglu(h2, w_gu, keep_pre=keep)
+    else:
+        gu = K.mm_nt(h2, w_gu)
+        act = K.swiglu_fwd(gu)
+    return K.mm_nt(act, st.w(sp.down_w), residual=r), (r, rstd2, h2, gu, act)
+
+
+class Qwen3MotLayerFn(_StoreFn):
+    """One layer of DM0's mixture of two Qwen3 experts (dm0_arch.py:145-268), the counterpart of Pi0MotLayerFn: per expert RMSNorm ->
+    fused q/k/v -> per-head q/k RMSNorm + RoPE written by ONE launch straight into the q / k / v both experts share
+    (dxa_qknorm_rope_split_at); ONE attention over all tokens with the block mask as q_limit / key_valid; per expert o_proj +
+    residual -> RMSNorm -> SwiGLU -> residual.  The rotary tables are the llm's for both experts.  ``skip_post0``: the last layer's
+    llm half after attention feeds only prefix_out, which nothing reads — it is not computed; that layer's q_proj / q_norm still get
+    their (zero) gradient written, like the reference."""
+
+    @staticmethod
+    def _run(st: ParamStore, sps, geom, skip_post0: bool, x0, x1, cos_t, sin_t, pos0, pos1, q_limit, key_valid, keep: bool = True,
+             kv=None, kv0: int = 0):
+        """the layer's forward launches -> ((y0, y1), what the backward reads besides x0, x1): the training forward, its recompute,
+        the no-grad forward and the sampler all run this one sequence.  An expert whose x is None (its S in ``geom`` is 0) is left
+        out (the sampler: the prefix pass runs the llm alone, the Euler steps the action expert alone).  ``keep`` = False: nothing
+        is kept for a backward (no rstd of the heads, no SwiGLU pre-activations).  ``kv`` (with ``keep`` = False only) = (k, v)
+        [B, Hkv, cap, D] buffers: this call's keys / values are WRITTEN at [kv0, kv0 + S) and attention reads [0, kv0 + S) — the
+        sampler's prefix pass fills [0, P), every Euler step the slots behind it; no concatenation, no copy."""
+        assert kv is None or not keep, "a backward must not read keys / values out of a buffer that the next step overwrites"
+        B, S0, S1, Hq, Hkv, D = geom
+        S = S0 + S1
+        live = [i for i, x in enumerate((x0, x1)) if x is not None]
+        xs, Ss, poss = (x0, x1), (S0, S1), (pos0, pos1)
+        assert all(Ss[i] > 0 for i in live) and sum(Ss[i] for i in live) == S
+        dev, dtype = xs[live[0]].device, xs[live[0]].dtype
+        q = torch.empty((B, Hq, S, D), device=dev, dtype=dtype)
+        if kv is None:
+            k = torch.empty((B, Hkv, S, D), device=dev, dtype=dtype)
+            v = torch.empty((B, Hkv, S, D), device=dev, dtype=dtype)
+        else:
+            k, v = kv
+        h1, rstd1, qkvs, rstd_qk = [None, None], [None, None], [None, None], [None, None]
+        off = 0
+        for i in live:
+            sp = sps[i]
+            h1[i], rstd1[i], qkvs[i] = qwen3_pre_attention(st, sp, xs[i])
+            rstd_qk[i] = K.qknorm_rope_split_into(qkvs[i], q, k, v, off, kv0 + off, st.w(sp.qk_norm[0]), st.w(sp.qk_norm[1]), sp.eps,
+                                                  cos_t, sin_t, poss[i], B, Ss[i], Hq, Hkv, D, want_rstd=keep)
+            if not keep:
+                qkvs[i] = None
+            off += Ss[i]
+        o = torch.empty((B, S, Hq, D), device=dev, dtype=dtype)
+        ka, va = (k, v) if kv is None or k.shape[2] == kv0 + S else (k[:, :, :kv0 + S], v[:, :, :kv0 + S])
+        lse = K.attn_fwd(q, ka, va, o.permute(0, 2, 1, 3), causal=False, scale=D ** -0.5, q_limit=q_limit, key_valid=key_valid)
+        ys, saved = [None, None], []
+        off = 0
+        for i in range(2):
+            if i not in live or (i == 0 and skip_post0):
+                saved += [None] * 6
+                off += Ss[i] if i in live else 0
+                continue
+            a = o[:, off:off + Ss[i]].reshape(B * Ss[i], Hq * D).contiguous()
+            off += Ss[i]
+            ys[i], kept = qwen3_post_attention(st, sps[i], xs[i], a, keep=keep)
+            saved += [a, *kept]
+        return (ys[0], ys[1]), (*h1, *rstd1, q, k, v, o, lse, *saved, *qkvs, *rstd_qk)
+
+    @staticmethod
+    def forward(ctx, x0, x1, anchor, st: ParamStore, sp0: Qwen2LayerSpec, sp1: Qwen2LayerSpec, geom, cos_t, sin_t,
+                pos0, pos1, q_limit, key_valid, skip_post0: bool):
+        sps = (sp0, sp1)
+        ys, saved = Qwen3MotLayerFn._run(st, sps, geom, skip_post0, x0, x1, cos_t, sin_t, pos0, pos1, q_limit, key_valid)
+        ctx.st, ctx.sps, ctx.geom, ctx.skip_post0 = st, sps, geom, skip_post0
+        for i, sp in enumerate(sps):
+            _use(ctx, st, sp.ln1, sp.qkv_w, sp.qk_norm)
+            if not (i == 0 and skip_post0):
+                _use(ctx, st, sp.o_w, sp.ln2, sp.gu_w, sp.down_w)
+        ctx.aux = (cos_t, sin_t, pos0, pos1, q_limit, key_valid)
+        ctx.recompute = _recompute(ctx, st)
+        if ctx.recompute:
+            ctx.save_for_backward(x0, x1)
+        else:
+            ctx.save_for_backward(x0, x1, *saved)
+        if skip_post0:
+            return x0.new_zeros((0,)), ys[1]                   # placeholder, never read downstream
+        return ys
+
+    @staticmethod
+    def backward(ctx, dy0, dy1):
+        st, sps, skip_post0 = ctx.st, ctx.sps, ctx.skip_post0
+        B, S0, S1, Hq, Hkv, D = ctx.geom
+        cos_t, sin_t, pos0, pos1, q_limit, key_valid = ctx.aux
+        sv = ctx.saved_tensors
+        if ctx.recompute:
+            sv = tuple(sv) + tuple(Qwen3MotLayerFn._run(st, sps, ctx.geom, skip_post0, sv[0], sv[1], cos_t, sin_t, pos0, pos1,
+                                                         q_limit, key_valid)[1])
+        xs, h1, rstd1 = sv[0:2], sv[2:4], sv[4:6]
+        q, k, v, o, lse = sv[6:11]
+        per = [sv[11:17], sv[17:23]]
+        qkvs, rstd_qk = sv[23:25], sv[25:27]
+        nq = (Hq + 2 * Hkv) * D
+        Ss, poss, dys = (S0, S1), (pos0, pos1), (dy0, dy1)
+        S = S0 + S1
+        do = torch.zeros((B, S, Hq, D), device=q.device, dtype=q.dtype)
+        drs = []
+        off = 0
+        for i, (sp, Sn, dy) in enumerate(zip(sps, Ss, dys)):
+            a, r, rs2, h2, gu, act = per[i]
+            if i == 0 and skip_post0:
+                drs.append(None)
+                off += Sn
+                continue
+            dy = dy.contiguous()
+            dact = _dx(st, sp.down_w, (sp.d, sp.F), dy)
+            _wgrad(st, sp.down_w, dy, act, (sp.d, sp.F))
+            dgu = K.swiglu_bwd(gu, dact)
+            del dact
+            dh2 = _dx(st, sp.gu_w, (2 * sp.F, sp.d), dgu)
+            _wgrad(st, sp.gu_w, dgu, h2, (2 * sp.F, sp.d))
+            del dgu
+            tr = st.trainable(sp.ln2)
+            dr, _ = K.rmsnorm_bwd(dh2, r, st.w(sp.ln2), rs2, dw_out=st.g(sp.ln2) if tr else None,
+                                  accumulate=st.accum_flag(sp.ln2), want_dw=tr, residual=dy)
+            if tr:
+                st.mark_written(sp.ln2)
+            da = _dx(st, sp.o_w, (sp.d, Hq * D), dr)
+            _wgrad(st, sp.o_w, dr, a, (sp.d, Hq * D))
+            do[:, off:off + Sn].copy_(da.view(B, Sn, Hq, D))
+            off += Sn
+            drs.append(dr)
+        do_h = K.permute_bshd(do, B, S, Hq, D, True)                       # head-major dO for the GQA fold
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        K.attn_bwd(q, k, v, o.permute(0, 2, 1, 3), lse, do_h, dq, dk, dv, causal=False, scale=D ** -0.5,
+                   q_limit=q_limit, key_valid=key_valid)
+        dxs = []
+        off = 0
+        for i, (sp, Sn, pos) in enumerate(zip(sps, Ss, poss)):
+            tr_qk = all(st.trainable(n) for n in sp.qk_norm)
+            dqkv, part = K.qknorm_rope_merge_from(dq, dk, dv, off, qkvs[i], rstd_qk[i], st.w(sp.qk_norm[0]), st.w(sp.qk_norm[1]),
+                                                  cos_t, sin_t, pos, B, Sn, Hq, Hkv, D, want_dw=tr_qk)      # (no slicing copies)
+            if tr_qk:
+                _bgrad(st, sp.qk_norm, part)       # rows of (dw_q | dw_k) partial sums, folded by the column sum as Qwen2LayerFn does
+            off += Sn
+            dh = _dx(st, sp.qkv_w, (nq, sp.d), dqkv)
+            _wgrad(st, sp.qkv_w, dqkv, h1[i], (nq, sp.d))
+            del dqkv
+            tr = st.trainable(sp.ln1)
+            dxn, _ = K.rmsnorm_bwd(dh, xs[i], st.w(sp.ln1), rstd1[i], dw_out=st.g(sp.ln1) if tr else None,
+                                   accumulate=st.accum_flag(sp.ln1), want_dw=tr, residual=drs[i])
+            if tr:
+                st.mark_written(sp.ln1)
+            dxs.append(dxn)
+        return (dxs[0], dxs[1]) + (None,) * 12
+
+
 # ------------------------------------------------------------------ small differentiable pieces (MemVLA memory modules)
 class AddFn(Function):
     """a + b (same shape): residual connections outside the fused blocks"""

@@ -664,6 +664,45 @@ def qknorm_rope_merge(dq, dk, dv, qkv: torch.Tensor, rstd: torch.Tensor, q_norm_
     return dqkv, part
 
 
+def qknorm_rope_split_into(qkv: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q0: int, kv0: int, q_norm_w, k_norm_w,
+                           eps: float, cos_t, sin_t, pos, B, S, Hq, Hkv, D, want_rstd: bool = True):
+    """qknorm_rope_split writing its S tokens at positions q0 .. q0 + S - 1 of SHARED contiguous q [B, Hq, Sq_cap, D] and at
+    kv0 .. kv0 + S - 1 of k / v [B, Hkv, Skv_cap, D] (capacities and offsets of q and of k / v apart: a sampler's queries are the
+    suffix alone, its keys land behind the cached prefix) -> rstd [B*S, Hq+Hkv] fp32 or None"""
+    Sq_cap, Skv_cap = q.shape[2], k.shape[2]
+    assert qkv.is_contiguous() and qkv.shape == (B * S, (Hq + 2 * Hkv) * D)
+    assert q_norm_w.dtype == qkv.dtype == k_norm_w.dtype and q_norm_w.numel() == D == k_norm_w.numel()
+    assert q.is_contiguous() and k.is_contiguous() and v.is_contiguous() and q.shape == (B, Hq, Sq_cap, D) and \
+        k.shape == (B, Hkv, Skv_cap, D) == v.shape and q.dtype == k.dtype == v.dtype == qkv.dtype
+    rstd = torch.empty((B * S, Hq + Hkv), device=qkv.device, dtype=torch.float32) if want_rstd else None
+    L.check(lib.dxa_qknorm_rope_split_at(_ptr(qkv), _ptr(q), _ptr(k), _ptr(v), _ptr(q_norm_w), _ptr(k_norm_w), float(eps), _ptr(rstd),
+                                         _ptr(cos_t), _ptr(sin_t), _ptr(pos), B, S, Hq, Hkv, D, Sq_cap, q0, Skv_cap, kv0, dt(qkv),
+                                         _stream()), "dxa_qknorm_rope_split_at")
+    return rstd
+
+
+def qknorm_rope_merge_from(dq, dk, dv, s0: int, qkv: torch.Tensor, rstd: torch.Tensor, q_norm_w, k_norm_w, cos_t, sin_t, pos, B, S, Hq,
+                           Hkv, D, want_dw: bool = True):
+    """qknorm_rope_merge of positions s0 .. s0 + S - 1 of SHARED contiguous dq [B, Hq, S_cap, D], dk / dv [B, Hkv, S_cap, D];
+    qkv and rstd are these S tokens' own -> (dqkv, partial sums or None)"""
+    S_cap = dq.shape[2]
+    assert dq.is_contiguous() and dk.is_contiguous() and dv.is_contiguous() and qkv.is_contiguous() and rstd.is_contiguous()
+    assert qkv.shape == (B * S, (Hq + 2 * Hkv) * D) and dq.shape == (B, Hq, S_cap, D) and dk.shape == (B, Hkv, S_cap, D) == dv.shape
+    assert dq.dtype == dk.dtype == dv.dtype == qkv.dtype == q_norm_w.dtype == k_norm_w.dtype
+    assert rstd.shape == (B * S, Hq + Hkv) and rstd.dtype == torch.float32
+    dqkv = torch.empty_like(qkv)
+    part = None
+    if want_dw:
+        nblk = int(lib.dxa_qknorm_rope_merge_blocks(B * S, Hq, Hkv, D, dt(qkv)))
+        if nblk < 0:
+            L.check(nblk, "dxa_qknorm_rope_merge_blocks")
+        part = torch.empty((nblk, 2 * D), device=qkv.device, dtype=torch.float32)
+    L.check(lib.dxa_qknorm_rope_merge_from(_ptr(dq), _ptr(dk), _ptr(dv), _ptr(qkv), _ptr(rstd), _ptr(q_norm_w), _ptr(k_norm_w),
+                                           _ptr(dqkv), _ptr(part), _ptr(cos_t), _ptr(sin_t), _ptr(pos), B, S, Hq, Hkv, D, S_cap, s0,
+                                           dt(qkv), _stream()), "dxa_qknorm_rope_merge_from")
+    return dqkv, part
+
+
 # ------------------------------------------------------------------------------------------- attention
 def _bhsd_strides(t: torch.Tensor) -> Tuple[int, int, int]:
     """t is a [B,H,S,D] VIEW (any memory order) with D contiguous -> (sb, sh, ss)"""

@@ -64,6 +64,7 @@ class Qwen2Config:
 class Qwen2Backbone(nn.Module):
     attention_bias = True       # q / k / v projections carry a bias (Qwen2); Qwen3Backbone: none
     qk_norm = False             # per-head RMSNorm of q and k before RoPE (Qwen3Backbone)
+    has_embed_tokens = True     # False: a decoder that is only ever fed embeddings (Qwen3Expert, DM0's action expert)
 
     def __init__(self, store: ParamStore, prefix: str, config: Qwen2Config):
         super().__init__()
@@ -71,8 +72,9 @@ class Qwen2Backbone(nn.Module):
         c = config
         d, f, hd = c.hidden_size, c.intermediate_size, c.head_dim
         Hq, Hkv = c.num_attention_heads, c.num_key_value_heads
-        store.new_bucket()
-        store.register([(prefix + "embed_tokens.weight", (c.vocab_size, d))])
+        if self.has_embed_tokens:
+            store.new_bucket()
+            store.register([(prefix + "embed_tokens.weight", (c.vocab_size, d))])
         self.layer_specs = []
         for i in range(c.num_hidden_layers):
             lp = f"{prefix}layers.{i}."

@@ -64,6 +64,12 @@ class Qwen3Backbone(Qwen2Backbone):
         return None
 
 
+class Qwen3Expert(Qwen3Backbone):
+    """``Qwen3ForCausalLM(config).model`` with ``embed_tokens = None`` (dm0_arch.py:79-80): the action expert of DM0's mixture, which
+    is only ever fed embeddings.  The layers run through ``functional.Qwen3MotLayerFn`` together with the llm's."""
+    has_embed_tokens = False
+
+
 def llm_config_from_any(obj) -> Qwen2Config:
     """``llm_config`` (a native config, a dict, an HF config object) -> Qwen3Config for ``model_type == "qwen3"``, Qwen2Config
     otherwise (which refuses every other type)"""

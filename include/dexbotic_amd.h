@@ -256,6 +256,19 @@ int dxa_qknorm_rope_merge(const void* dq, const void* dk, const void* dv, const 
                           const float* sin_t, const int32_t* pos, int B, int S, int Hq, int Hkv, int D, int dtype,
                           dxa_stream_t stream);
 int dxa_qknorm_rope_merge_blocks(int64_t tokens, int Hq, int Hkv, int D, int dtype);
+/* The same into / from head-major tensors several calls share, as dxa_rope_split_at / dxa_rope_merge_at (the two Qwen3 experts of
+ * DM0's mixture layer, dm0_arch.py; a key / value cache).  The split takes q and k / v APART: the S tokens go to positions
+ * q0 .. q0 + S - 1 of q [B, Hq, Sq_cap, D] and to kv0 .. kv0 + S - 1 of k, v [B, Hkv, Skv_cap, D] (a sampler's queries are the
+ * suffix alone while its keys land behind the cached prefix: no concatenation, no copy).  The merge reads positions
+ * s0 .. s0 + S - 1 of dq, dk, dv that all hold S_cap; qkv, rstd, dqkv and partial_dw are this call's S tokens alone, as above.
+ * A window outside the capacity is refused before any launch. */
+int dxa_qknorm_rope_split_at(const void* qkv, void* q, void* k, void* v, const void* q_norm_w, const void* k_norm_w, float eps,
+                             float* rstd, const float* cos_t, const float* sin_t, const int32_t* pos, int B, int S, int Hq, int Hkv,
+                             int D, int Sq_cap, int q0, int Skv_cap, int kv0, int dtype, dxa_stream_t stream);
+int dxa_qknorm_rope_merge_from(const void* dq, const void* dk, const void* dv, const void* qkv, const float* rstd,
+                               const void* q_norm_w, const void* k_norm_w, void* dqkv, float* partial_dw, const float* cos_t,
+                               const float* sin_t, const int32_t* pos, int B, int S, int Hq, int Hkv, int D, int S_cap, int s0,
+                               int dtype, dxa_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Attention.  Replaces torch SDPA at HF:qwen2/modeling_qwen2.py:143-235 (causal + key padding, GQA),
