@@ -34,12 +34,21 @@ def model_registry():
     from .model.memvla.memvla_arch import MemVLAConfig, MemVLAForCausalLM
     from .model.navila.navila_arch import NaVILAConfig, NaVILAForCausalLM
     from .model.pi0.pi0_arch import Pi0Config, Pi0ForCausalLM
+    from .model.pi05.pi05_arch import Pi05Config, Pi05ForCausalLM
     return {"dexbotic": (DexboticConfig, DexboticForCausalLM),
             "dexbotic_cogact": (CogActConfig, CogACTForCausalLM),
             "dexbotic_pi0": (Pi0Config, Pi0ForCausalLM),
             "dexbotic_memvla": (MemVLAConfig, MemVLAForCausalLM),
             "dexbotic_navila": (NaVILAConfig, NaVILAForCausalLM),
-            "dexbotic_dm0": (DM0Config, DM0ForCausalLM)}
+            "dexbotic_dm0": (DM0Config, DM0ForCausalLM),
+            "dexbotic_pi05": (Pi05Config, Pi05ForCausalLM)}
+
+
+def __getattr__(name):
+    if name in ("Pi05Config", "Pi05ForCausalLM", "Pi05Model"):
+        from .model import pi05
+        return getattr(pi05, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def hybrid_cogact():

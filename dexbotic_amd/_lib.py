@@ -132,6 +132,11 @@ SIGNATURES = {
     "dxa_add_layernorm_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _vp]),
     "dxa_downsample_layernorm_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _int, _int, _vp]),
     "dxa_downsample_layernorm_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _int, _vp]),
+    "dxa_adarms_fwd": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _int, _vp]),
+    "dxa_gated_residual_fwd": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _int, _vp]),
+    "dxa_adarms_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _sz, _i64, _i64, _i64, _int, _vp]),
+    "dxa_gated_residual_bwd": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _sz, _i64, _i64, _i64, _int, _vp]),
+    "dxa_adarms_bwd_groups": (_int, [_i64]),
     "dxa_colsum": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _int, _vp, _sz, _vp]),
     "dxa_rope_split": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _vp]),
     "dxa_rope_merge": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _vp]),

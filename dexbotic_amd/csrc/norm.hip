@@ -1293,3 +1293,419 @@ extern "C" int dxa_downsample_layernorm_bwd(const void* dy, const void* x, const
   DXA_CHECK_LAUNCH();
   return DXA_OK;
 }
+
+// ------------------------------------------------------------------- adaptive RMSNorm + gated residual (pi0.5)
+// The action expert of pi0.5 (pi05_arch.py:118-250, transformers_pi05/gemma/modeling_gemma.py:38-120) has no norm gains: every
+// norm is modulated PER SAMPLE by mod [B, 3 * cols] = [scale | shift | gate] (a dense layer of the flow-time embedding), and both
+// residual adds of a layer are gated.  Sample s = row / rows_per_sample, taken per ROW: a workgroup's four rows may lie in two
+// samples.  All arithmetic fp32, every output rounded once.
+//   forward    r = x + branch * gate_prev[s]   (optional; r is written: the next add and the backward read it)
+//              y = r * rsqrt(mean(r^2) + eps) * (1 + scale[s]) + shift[s]
+//   backward   g = dy * (1 + scale[s]);  dr = rstd * (g - xh * mean(g * xh)) (+ residual);  dbranch = dr * gate_prev[s]
+//              dscale[s] = sum_rows dy * xh,  dshift[s] = sum_rows dy,  dgate_prev[s] = sum_rows dr * branch
+// The per-sample sums are deterministic: a wave adds its rows into a partial row of its own (grid = (row groups, samples), a row
+// group = 4 waves), adarms_fold_k adds a sample's partial rows in a fixed order.  No atomics.
+namespace {
+
+template <typename T, int VEC, bool GATED>
+__global__ __launch_bounds__(256) void adarms_fwd_k(const T* __restrict__ x, const T* __restrict__ branch,
+                                                    const T* __restrict__ gate, int64_t gate_ld, const T* __restrict__ mod,
+                                                    T* __restrict__ r_out, T* __restrict__ y, float* __restrict__ rstd_out,
+                                                    int64_t rows, int64_t rps, int64_t cols, float eps) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int64_t s = row / rps;
+  const T* xr = x + row * cols;
+  const T* br = GATED ? branch + row * cols : nullptr;
+  const T* gt = GATED ? gate + s * gate_ld : nullptr;
+  // the row that is normalised: x, or the gated sum rounded to the storage type (what r_out holds and the backward reads)
+  auto ld_r = [&](float (&v)[VEC], int64_t c) {
+    Vec<T, VEC>::ld(v, xr + c);
+    if constexpr (GATED) {
+      float b[VEC], g[VEC];
+      Vec<T, VEC>::ld(b, br + c);
+      Vec<T, VEC>::ld(g, gt + c);
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) v[i] = rnd<T>(__builtin_fmaf(b[i], g[i], v[i]));
+    }
+  };
+  float ss = 0.f;
+  for (int64_t c = (int64_t)lane * VEC; c < cols; c += 64 * VEC) {
+    float v[VEC];
+    ld_r(v, c);
+    if constexpr (GATED) Vec<T, VEC>::st(r_out + row * cols + c, v);
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) ss += v[i] * v[i];
+  }
+  const float rstd = rsqrtf(wave_sum(ss) / (float)cols + eps);
+  if (lane == 0 && rstd_out) rstd_out[row] = rstd;
+  const T* sc = mod + s * 3 * cols;
+  const T* sh = sc + cols;
+  T* yr = y + row * cols;
+  for (int64_t c = (int64_t)lane * VEC; c < cols; c += 64 * VEC) {
+    float v[VEC], a[VEC], b[VEC];
+    ld_r(v, c);
+    Vec<T, VEC>::ld(a, sc + c);
+    Vec<T, VEC>::ld(b, sh + c);
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) v[i] = v[i] * rstd * (1.f + a[i]) + b[i];
+    Vec<T, VEC>::st(yr + c, v);
+  }
+}
+
+// bf16 rows of up to 8192 columns (cols % 8 == 0), as rmsnorm_fwd_fast_k: the wave requests its whole row at once and keeps it in
+// registers — x and branch are read ONCE, the gated sum is formed, written and normalised from the same registers
+template <bool GATED>
+__global__ __launch_bounds__(256) void adarms_fwd_fast_k(const bf16_t* __restrict__ x, const bf16_t* __restrict__ branch,
+                                                         const bf16_t* __restrict__ gate, int64_t gate_ld,
+                                                         const bf16_t* __restrict__ mod, bf16_t* __restrict__ r_out,
+                                                         bf16_t* __restrict__ y, float* __restrict__ rstd_out, int64_t rows,
+                                                         int64_t rps, int64_t cols, float eps) {
+  constexpr int NIT = 16;
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int64_t s = row / rps;
+  const bf16_t* xr = x + row * cols;
+  auto unpack = [](const u32x4& v, float (&o)[8]) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { o[2 * e] = __uint_as_float(v[e] << 16); o[2 * e + 1] = __uint_as_float(v[e] & 0xffff0000u); }
+  };
+  u32x4 v[NIT];
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int64_t c = ((int64_t)it * 64 + lane) * 8;
+    v[it] = c < cols ? *reinterpret_cast<const u32x4*>(xr + c) : (u32x4){0u, 0u, 0u, 0u};
+  }
+  if constexpr (GATED) {
+    const bf16_t* br = branch + row * cols;
+    const bf16_t* gt = gate + s * gate_ld;
+    bf16_t* ro = r_out + row * cols;
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int64_t c = ((int64_t)it * 64 + lane) * 8;
+      if (c < cols) {
+        float xf[8], bf[8], gf[8];
+        unpack(v[it], xf);
+        Vec<bf16_t, 8>::ld(bf, br + c);
+        Vec<bf16_t, 8>::ld(gf, gt + c);
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          v[it][e] = pack_bf16x2(__builtin_fmaf(bf[2 * e], gf[2 * e], xf[2 * e]), __builtin_fmaf(bf[2 * e + 1], gf[2 * e + 1], xf[2 * e + 1]));
+        *reinterpret_cast<u32x4*>(ro + c) = v[it];
+      }
+    }
+  }
+  float ss = 0.f;
+#pragma unroll
+  for (int it = 0; it < NIT; ++it)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float a = __uint_as_float(v[it][e] << 16), b = __uint_as_float(v[it][e] & 0xffff0000u);
+      ss += a * a + b * b;
+    }
+  const float rstd = rsqrtf(wave_sum(ss) / (float)cols + eps);
+  if (lane == 0 && rstd_out) rstd_out[row] = rstd;
+  const bf16_t* sc = mod + s * 3 * cols;
+  const bf16_t* sh = sc + cols;
+  bf16_t* yr = y + row * cols;
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int64_t c = ((int64_t)it * 64 + lane) * 8;
+    if (c < cols) {
+      float rf[8], a[8], b[8];
+      unpack(v[it], rf);
+      Vec<bf16_t, 8>::ld(a, sc + c);
+      Vec<bf16_t, 8>::ld(b, sh + c);
+      u32x4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        o[e] = pack_bf16x2(rf[2 * e] * rstd * (1.f + a[2 * e]) + b[2 * e], rf[2 * e + 1] * rstd * (1.f + a[2 * e + 1]) + b[2 * e + 1]);
+      *reinterpret_cast<u32x4*>(yr + c) = o;
+    }
+  }
+}
+
+// y = x + branch * gate[s]: the add that ends a layer (the norm that follows belongs to the next layer's autograd node)
+template <typename T, int VEC>
+__global__ __launch_bounds__(256) void gated_residual_fwd_k(const T* __restrict__ x, const T* __restrict__ branch,
+                                                            const T* __restrict__ gate, int64_t gate_ld, T* __restrict__ y,
+                                                            int64_t rows, int64_t rps, int64_t cols) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const T* gt = gate + (row / rps) * gate_ld;
+  for (int64_t c = (int64_t)lane * VEC; c < cols; c += 64 * VEC) {
+    float v[VEC], b[VEC], g[VEC];
+    Vec<T, VEC>::ld(v, x + row * cols + c);
+    Vec<T, VEC>::ld(b, branch + row * cols + c);
+    Vec<T, VEC>::ld(g, gt + c);
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) v[i] = __builtin_fmaf(b[i], g[i], v[i]);
+    Vec<T, VEC>::st(y + row * cols + c, v);
+  }
+}
+
+// grid (row groups, samples).  Wave w of row group b owns rows b * 4 + w, + 4 * gridDim.x, ... of its sample and partial row
+// (sample * gridDim.x + b) * 4 + w of `partial` [..][NS * cols] = (dscale | dshift | dgate_prev): written on the wave's first row,
+// added to on the following ones (or zeroed, for a wave without a row) — every element by the one lane that owns its column.
+template <typename T, int VEC, bool GATED>
+__global__ __launch_bounds__(256) void adarms_bwd_k(const T* __restrict__ dy, const T* __restrict__ r, const T* __restrict__ mod,
+                                                    const float* __restrict__ rstd, const T* __restrict__ res, T* __restrict__ dr,
+                                                    const T* __restrict__ branch, const T* __restrict__ gate, int64_t gate_ld,
+                                                    T* __restrict__ dbranch, float* __restrict__ partial, int64_t rps,
+                                                    int64_t cols) {
+  constexpr int NS = GATED ? 3 : 2;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t s = blockIdx.y;
+  float* slab = partial + ((s * gridDim.x + blockIdx.x) * 4 + wave) * NS * cols;
+  const T* sc = mod + s * 3 * cols;
+  const T* gt = GATED ? gate + s * gate_ld : nullptr;
+  bool first = true;
+  for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < rps; i += (int64_t)gridDim.x * 4) {
+    const int64_t off = (s * rps + i) * cols;
+    const float rs = rstd[s * rps + i];
+    float s2 = 0.f;
+    for (int64_t c = (int64_t)lane * VEC; c < cols; c += 64 * VEC) {
+      float xv[VEC], gv[VEC], a[VEC];
+      Vec<T, VEC>::ld(xv, r + off + c);
+      Vec<T, VEC>::ld(gv, dy + off + c);
+      Vec<T, VEC>::ld(a, sc + c);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) s2 += gv[k] * (1.f + a[k]) * (xv[k] * rs);
+    }
+    const float c2 = wave_sum(s2) / (float)cols;
+    for (int64_t c = (int64_t)lane * VEC; c < cols; c += 64 * VEC) {
+      float xv[VEC], gv[VEC], a[VEC], o[VEC];
+      Vec<T, VEC>::ld(xv, r + off + c);
+      Vec<T, VEC>::ld(gv, dy + off + c);
+      Vec<T, VEC>::ld(a, sc + c);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) {
+        const float xh = xv[k] * rs;
+        o[k] = rs * (gv[k] * (1.f + a[k]) - xh * c2);
+        xv[k] = gv[k] * xh;                                  // this row's share of dscale
+      }
+      if (res) {
+        float rv[VEC];
+        Vec<T, VEC>::ld(rv, res + off + c);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) o[k] += rv[k];
+      }
+      Vec<T, VEC>::st(dr + off + c, o);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) {
+        slab[c + k] = first ? xv[k] : slab[c + k] + xv[k];
+        slab[cols + c + k] = first ? gv[k] : slab[cols + c + k] + gv[k];
+      }
+      if constexpr (GATED) {
+        float bv[VEC], g[VEC], ob[VEC];
+        Vec<T, VEC>::ld(bv, branch + off + c);
+        Vec<T, VEC>::ld(g, gt + c);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+          ob[k] = o[k] * g[k];
+          const float t = o[k] * bv[k];
+          slab[2 * cols + c + k] = first ? t : slab[2 * cols + c + k] + t;
+        }
+        Vec<T, VEC>::st(dbranch + off + c, ob);
+      }
+    }
+    first = false;
+  }
+  if (first)
+    for (int64_t c = lane; c < NS * cols; c += 64) slab[c] = 0.f;
+}
+
+// backward of gated_residual_fwd_k, same grid and partial rows ([..][cols] = dgate): dbranch = dy * gate[s], dgate[s] = sum dy * branch
+template <typename T, int VEC>
+__global__ __launch_bounds__(256) void gated_residual_bwd_k(const T* __restrict__ dy, const T* __restrict__ branch,
+                                                            const T* __restrict__ gate, int64_t gate_ld, T* __restrict__ dbranch,
+                                                            float* __restrict__ partial, int64_t rps, int64_t cols) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t s = blockIdx.y;
+  float* slab = partial + ((s * gridDim.x + blockIdx.x) * 4 + wave) * cols;
+  const T* gt = gate + s * gate_ld;
+  bool first = true;
+  for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < rps; i += (int64_t)gridDim.x * 4) {
+    const int64_t off = (s * rps + i) * cols;
+    for (int64_t c = (int64_t)lane * VEC; c < cols; c += 64 * VEC) {
+      float gv[VEC], bv[VEC], g[VEC], ob[VEC];
+      Vec<T, VEC>::ld(gv, dy + off + c);
+      Vec<T, VEC>::ld(bv, branch + off + c);
+      Vec<T, VEC>::ld(g, gt + c);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) {
+        ob[k] = gv[k] * g[k];
+        const float t = gv[k] * bv[k];
+        slab[c + k] = first ? t : slab[c + k] + t;
+      }
+      Vec<T, VEC>::st(dbranch + off + c, ob);
+    }
+    first = false;
+  }
+  if (first)
+    for (int64_t c = lane; c < cols; c += 64) slab[c] = 0.f;
+}
+
+// a sample's `nrow` partial rows [n] added in row order (eight loads in flight), rounded once: columns [0, n_a) go to out_a
+// (row stride ld_a), the rest to out_b (row stride ld_b) — the gate belongs to ANOTHER modulation tensor than scale and shift
+template <typename T>
+__global__ __launch_bounds__(256) void adarms_fold_k(const float* __restrict__ partial, int nrow, int64_t n, T* __restrict__ out_a,
+                                                     int64_t ld_a, int64_t n_a, T* __restrict__ out_b, int64_t ld_b) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t s = blockIdx.y;
+  if (j >= n) return;
+  const float* p = partial + s * nrow * n + j;
+  float acc = 0.f;
+  int i = 0;
+  for (; i + 8 <= nrow; i += 8) {
+    float v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = p[(int64_t)(i + u) * n];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) acc += v[u];
+  }
+  for (; i < nrow; ++i) acc += p[(int64_t)i * n];
+  if (j < n_a) stf<T>(out_a + s * ld_a + j, acc);
+  else stf<T>(out_b + s * ld_b + (j - n_a), acc);
+}
+
+constexpr int ADARMS_BWD_MAX_GROUPS = 128;
+
+// widest access every pointer and stride allows: 8 (bf16 only), 4 or 1 elements
+int adarms_vec(int dtype, int64_t cols, int64_t gate_ld, std::initializer_list<const void*> ptrs) {
+  const size_t es = dtype == DXA_BF16 ? 2 : 4;
+  int vec = dtype == DXA_BF16 ? 8 : 4;
+  for (; vec > 1; vec >>= 1) {
+    bool ok = cols % vec == 0 && gate_ld % vec == 0;
+    for (const void* p : ptrs) ok = ok && (reinterpret_cast<uintptr_t>(p) % (vec * es)) == 0;
+    if (ok) break;
+  }
+  return vec;
+}
+
+int check_adarms(const char* who, int64_t rows, int64_t rps, int64_t cols, int dtype) {
+  DXA_CHECK_ARG(dtype == DXA_F32 || dtype == DXA_BF16, "%s: unsupported dtype %d", who, dtype);
+  DXA_CHECK_ARG(cols > 0 && rows >= 0 && rps > 0, "%s: bad sizes (rows %lld, rows_per_sample %lld, cols %lld)", who, (long long)rows,
+                (long long)rps, (long long)cols);
+  DXA_CHECK_ARG(rows % rps == 0, "%s: %lld rows are not a whole number of samples of %lld rows", who, (long long)rows, (long long)rps);
+  DXA_CHECK_ARG(rows / rps <= 65535, "%s: more than 65535 samples", who);
+  return DXA_OK;
+}
+
+}  // namespace
+
+extern "C" int dxa_adarms_bwd_groups(int64_t rows_per_sample) {
+  int64_t g = (rows_per_sample + 3) / 4;
+  if (g < 1) g = 1;
+  if (g > ADARMS_BWD_MAX_GROUPS) g = ADARMS_BWD_MAX_GROUPS;
+  return (int)g;
+}
+
+extern "C" int dxa_adarms_fwd(const void* x, const void* branch, const void* gate_prev, int64_t gate_ld, const void* mod,
+                              void* r_out, void* y, float* rstd, int64_t rows, int64_t rows_per_sample, int64_t cols, float eps,
+                              int dtype, dxa_stream_t stream) {
+  if (int rc = check_adarms("dxa_adarms_fwd", rows, rows_per_sample, cols, dtype)) return rc;
+  DXA_CHECK_ARG(x && mod && y, "dxa_adarms_fwd: null x / mod / y");
+  DXA_CHECK_ARG(!branch || (gate_prev && r_out && gate_ld >= cols), "dxa_adarms_fwd: a branch needs gate_prev, r_out and gate_ld >= cols");
+  if (rows == 0) return DXA_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int vec = adarms_vec(dtype, cols, branch ? gate_ld : 0, {x, mod, y, branch, branch ? gate_prev : nullptr, branch ? r_out : nullptr});
+  dim3 grid((unsigned)((rows + 3) / 4));
+#define ADARMS_FWD(K_, ...) do { \
+    if (branch) hipLaunchKernelGGL((K_<__VA_ARGS__ true>), grid, dim3(256), 0, st, (const T_*)x, (const T_*)branch, (const T_*)gate_prev, gate_ld, (const T_*)mod, (T_*)r_out, (T_*)y, rstd, rows, rows_per_sample, cols, eps); \
+    else hipLaunchKernelGGL((K_<__VA_ARGS__ false>), grid, dim3(256), 0, st, (const T_*)x, (const T_*)nullptr, (const T_*)nullptr, (int64_t)0, (const T_*)mod, (T_*)nullptr, (T_*)y, rstd, rows, rows_per_sample, cols, eps); } while (0)
+  if (dtype == DXA_BF16) {
+    typedef bf16_t T_;
+    if (vec == 8 && cols <= 8192) ADARMS_FWD(adarms_fwd_fast_k, );
+    else if (vec == 8) ADARMS_FWD(adarms_fwd_k, bf16_t, 8,);
+    else if (vec == 4) ADARMS_FWD(adarms_fwd_k, bf16_t, 4,);
+    else ADARMS_FWD(adarms_fwd_k, bf16_t, 1,);
+  } else {
+    typedef float T_;
+    if (vec == 4) ADARMS_FWD(adarms_fwd_k, float, 4,);
+    else ADARMS_FWD(adarms_fwd_k, float, 1,);
+  }
+#undef ADARMS_FWD
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
+}
+
+extern "C" int dxa_gated_residual_fwd(const void* x, const void* branch, const void* gate, int64_t gate_ld, void* y, int64_t rows,
+                                      int64_t rows_per_sample, int64_t cols, int dtype, dxa_stream_t stream) {
+  if (int rc = check_adarms("dxa_gated_residual_fwd", rows, rows_per_sample, cols, dtype)) return rc;
+  DXA_CHECK_ARG(x && branch && gate && y && gate_ld >= cols, "dxa_gated_residual_fwd: null x / branch / gate / y, or gate_ld < cols");
+  if (rows == 0) return DXA_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int vec = adarms_vec(dtype, cols, gate_ld, {x, branch, gate, y});
+  dim3 grid((unsigned)((rows + 3) / 4));
+#define GATED_FWD(T_, V_) hipLaunchKernelGGL((gated_residual_fwd_k<T_, V_>), grid, dim3(256), 0, st, (const T_*)x, (const T_*)branch, (const T_*)gate, gate_ld, (T_*)y, rows, rows_per_sample, cols)
+  if (dtype == DXA_BF16) { if (vec == 8) GATED_FWD(bf16_t, 8); else if (vec == 4) GATED_FWD(bf16_t, 4); else GATED_FWD(bf16_t, 1); }
+  else { if (vec == 4) GATED_FWD(float, 4); else GATED_FWD(float, 1); }
+#undef GATED_FWD
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
+}
+
+extern "C" int dxa_adarms_bwd(const void* dy, const void* r, const void* mod, const float* rstd, const void* residual, void* dr,
+                              void* dmod, const void* branch, const void* gate_prev, int64_t gate_ld, void* dbranch,
+                              void* dgate_prev, int64_t dgate_ld, float* partial, size_t partial_bytes, int64_t rows,
+                              int64_t rows_per_sample, int64_t cols, int dtype, dxa_stream_t stream) {
+  if (int rc = check_adarms("dxa_adarms_bwd", rows, rows_per_sample, cols, dtype)) return rc;
+  DXA_CHECK_ARG(dy && r && mod && rstd && dr && dmod && partial, "dxa_adarms_bwd: null dy / r / mod / rstd / dr / dmod / partial");
+  DXA_CHECK_ARG(!branch || (gate_prev && dbranch && dgate_prev && gate_ld >= cols && dgate_ld >= cols),
+                "dxa_adarms_bwd: a branch needs gate_prev, dbranch, dgate_prev and gate_ld, dgate_ld >= cols");
+  if (rows == 0) return DXA_OK;
+  const int64_t B = rows / rows_per_sample;
+  const int groups = dxa_adarms_bwd_groups(rows_per_sample);
+  const int ns = branch ? 3 : 2;
+  const size_t need = (size_t)B * groups * 4 * ns * cols * sizeof(float);
+  DXA_CHECK_ARG(partial_bytes >= need, "dxa_adarms_bwd: partial too small (need %zu bytes)", need);
+  hipStream_t st = (hipStream_t)stream;
+  const int vec = adarms_vec(dtype, cols, branch ? gate_ld : 0, {dy, r, mod, dr, residual, branch, branch ? gate_prev : nullptr, branch ? dbranch : nullptr});
+  dim3 grid((unsigned)groups, (unsigned)B);
+#define ADARMS_BWD(T_, V_) do { \
+    if (branch) hipLaunchKernelGGL((adarms_bwd_k<T_, V_, true>), grid, dim3(256), 0, st, (const T_*)dy, (const T_*)r, (const T_*)mod, rstd, (const T_*)residual, (T_*)dr, (const T_*)branch, (const T_*)gate_prev, gate_ld, (T_*)dbranch, partial, rows_per_sample, cols); \
+    else hipLaunchKernelGGL((adarms_bwd_k<T_, V_, false>), grid, dim3(256), 0, st, (const T_*)dy, (const T_*)r, (const T_*)mod, rstd, (const T_*)residual, (T_*)dr, (const T_*)nullptr, (const T_*)nullptr, (int64_t)0, (T_*)nullptr, partial, rows_per_sample, cols); } while (0)
+  if (dtype == DXA_BF16) { if (vec == 8) ADARMS_BWD(bf16_t, 8); else if (vec == 4) ADARMS_BWD(bf16_t, 4); else ADARMS_BWD(bf16_t, 1); }
+  else { if (vec == 4) ADARMS_BWD(float, 4); else ADARMS_BWD(float, 1); }
+#undef ADARMS_BWD
+  const int64_t n = (int64_t)ns * cols;
+  dim3 fgrid((unsigned)((n + 255) / 256), (unsigned)B);
+  if (dtype == DXA_BF16)
+    hipLaunchKernelGGL((adarms_fold_k<bf16_t>), fgrid, dim3(256), 0, st, partial, groups * 4, n, (bf16_t*)dmod, 3 * cols, 2 * cols, (bf16_t*)dgate_prev, dgate_ld);
+  else
+    hipLaunchKernelGGL((adarms_fold_k<float>), fgrid, dim3(256), 0, st, partial, groups * 4, n, (float*)dmod, 3 * cols, 2 * cols, (float*)dgate_prev, dgate_ld);
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
+}
+
+extern "C" int dxa_gated_residual_bwd(const void* dy, const void* branch, const void* gate, int64_t gate_ld, void* dbranch,
+                                      void* dgate, int64_t dgate_ld, float* partial, size_t partial_bytes, int64_t rows,
+                                      int64_t rows_per_sample, int64_t cols, int dtype, dxa_stream_t stream) {
+  if (int rc = check_adarms("dxa_gated_residual_bwd", rows, rows_per_sample, cols, dtype)) return rc;
+  DXA_CHECK_ARG(dy && branch && gate && dbranch && dgate && partial, "dxa_gated_residual_bwd: null dy / branch / gate / dbranch / dgate / partial");
+  DXA_CHECK_ARG(gate_ld >= cols && dgate_ld >= cols, "dxa_gated_residual_bwd: gate_ld / dgate_ld < cols");
+  if (rows == 0) return DXA_OK;
+  const int64_t B = rows / rows_per_sample;
+  const int groups = dxa_adarms_bwd_groups(rows_per_sample);
+  const size_t need = (size_t)B * groups * 4 * cols * sizeof(float);
+  DXA_CHECK_ARG(partial_bytes >= need, "dxa_gated_residual_bwd: partial too small (need %zu bytes)", need);
+  hipStream_t st = (hipStream_t)stream;
+  const int vec = adarms_vec(dtype, cols, gate_ld, {dy, branch, gate, dbranch});
+  dim3 grid((unsigned)groups, (unsigned)B);
+#define GATED_BWD(T_, V_) hipLaunchKernelGGL((gated_residual_bwd_k<T_, V_>), grid, dim3(256), 0, st, (const T_*)dy, (const T_*)branch, (const T_*)gate, gate_ld, (T_*)dbranch, partial, rows_per_sample, cols)
+  if (dtype == DXA_BF16) { if (vec == 8) GATED_BWD(bf16_t, 8); else if (vec == 4) GATED_BWD(bf16_t, 4); else GATED_BWD(bf16_t, 1); }
+  else { if (vec == 4) GATED_BWD(float, 4); else GATED_BWD(float, 1); }
+#undef GATED_BWD
+  dim3 fgrid((unsigned)((cols + 255) / 256), (unsigned)B);
+  if (dtype == DXA_BF16)
+    hipLaunchKernelGGL((adarms_fold_k<bf16_t>), fgrid, dim3(256), 0, st, partial, groups * 4, cols, (bf16_t*)nullptr, (int64_t)0, (int64_t)0, (bf16_t*)dgate, dgate_ld);
+  else
+    hipLaunchKernelGGL((adarms_fold_k<float>), fgrid, dim3(256), 0, st, partial, groups * 4, cols, (float*)nullptr, (int64_t)0, (int64_t)0, (float*)dgate, dgate_ld);
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
+}

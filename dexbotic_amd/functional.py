@@ -1435,6 +1435,218 @@ class Qwen3MotLayerFn(_StoreFn):
         return (dxs[0], dxs[1]) + (None,) * 12
 
 
+# ------------------------------------------------------------------------------- pi0.5 mixture layer (adaRMS expert)
+def adarms_pre_attention(st: ParamStore, sp: GemmaLayerSpec, x, mod1, nq: int):
+    """first half of the pi0.5 action expert's layer on x [M, d]: adaptive RMSNorm with mod1 [B, 3 d] = [scale | shift | gate], then
+    the fused q/k/v product -> (h, rstd, qkv [M, nq])"""
+    h, rstd, _ = K.adarms_fwd(x, mod1, sp.eps)
+    return h, rstd, K.mm_nt(h, st.w(*sp.qkv, shape=(nq, sp.d)))
+
+
+def adarms_post_attention(st: ParamStore, sp: GemmaLayerSpec, x, a, mod1, mod2):
+    """second half: o_proj; r = x + o * gate1 and the post-attention adaptive norm of r in ONE launch; GeGLU; r + down * gate2
+    -> (y, what the backward reads besides a: ob, r, rstd2, h2, gu, act, mb)"""
+    d = sp.d
+    ob = K.mm_nt(a, st.w(sp.o))
+    h2, rstd2, r = K.adarms_fwd(x, mod2, sp.eps, branch=ob, gate_prev=mod1[:, 2 * d:])
+    gu = K.mm_nt(h2, st.w(*sp.gu, shape=(2 * sp.F, d)))
+    act = K.glu_fwd(gu, L.ACT_GELU_TANH)
+    mb = K.mm_nt(act, st.w(sp.down))
+    return K.gated_residual_fwd(r, mb, mod2[:, 2 * d:]), (ob, r, rstd2, h2, gu, act, mb)
+
+
+class Pi05MotLayerFn(_StoreFn):
+    """One layer of the pi0.5 mixture (pi05_arch.py:134-238) for its two experts at once, the counterpart of Pi0MotLayerFn: expert 0
+    (the llm) is gemma_pre_attention / gemma_post_attention unchanged; expert 1 (the action expert) has no norm gains — its two
+    norms are adaptive (``mod1`` / ``mod2`` [B, 3 d_a] = [scale | shift | gate], dense layers of the flow-time embedding evaluated
+    OUTSIDE the layer) and its two residual adds are gated.  ONE attention over both experts' tokens.  The backward returns dmod1 /
+    dmod2; the dense layers' weight / bias gradients and the gradient of the time embedding are ordinary linear-layer work upstream.
+    ``skip_post0`` as in Pi0MotLayerFn."""
+
+    @staticmethod
+    def _run(st: ParamStore, sps, geom, skip_post0: bool, x0, x1, mod1, mod2, cos_t, sin_t, pos0, pos1, q_limit, key_valid,
+             keep: bool = True, kv=None, kv0: int = 0):
+        """the layer's forward launches -> ((y0, y1), what the backward reads besides x0, x1, mod1, mod2): the training forward, its
+        recompute, the no-grad forward and the sampler all run this one sequence.  An expert whose x is None (its S in ``geom`` is 0)
+        is left out.  ``kv`` (with ``keep`` = False only) = (k, v) [B, Hkv, cap, D] buffers: this call's keys / values are WRITTEN at
+        [kv0, kv0 + S) and attention reads [0, kv0 + S) (the sampler: the prefix pass fills [0, P), every Euler step the slots
+        behind it).  dxa_rope_split_at writes q, k and v at ONE offset, so the queries then get a scratch tensor of the same
+        capacity, of which attention reads the window."""
+        assert kv is None or not keep, "a backward must not read keys / values out of a buffer that the next step overwrites"
+        B, S0, S1, Hq, Hkv, D = geom
+        S = S0 + S1
+        nq = (Hq + 2 * Hkv) * D
+        live = [i for i, x in enumerate((x0, x1)) if x is not None]
+        xs, Ss, poss = (x0, x1), (S0, S1), (pos0, pos1)
+        assert all(Ss[i] > 0 for i in live) and sum(Ss[i] for i in live) == S
+        dev, dtype = xs[live[0]].device, xs[live[0]].dtype
+        if kv is None:
+            qb = torch.empty((B, Hq, S, D), device=dev, dtype=dtype)
+            k = torch.empty((B, Hkv, S, D), device=dev, dtype=dtype)
+            v = torch.empty((B, Hkv, S, D), device=dev, dtype=dtype)
+        else:
+            k, v = kv
+            qb = torch.empty((B, Hq, k.shape[2], D), device=dev, dtype=dtype)
+        h1, rstd1 = [None, None], [None, None]
+        off = kv0
+        for i in live:
+            if i == 0:
+                h1[i], rstd1[i], qkv = gemma_pre_attention(st, sps[i], xs[i], nq)
+            else:
+                h1[i], rstd1[i], qkv = adarms_pre_attention(st, sps[i], xs[i], mod1, nq)
+            K.rope_split_into(qkv, qb, k, v, off, cos_t, sin_t, poss[i], B, Ss[i], Hq, Hkv, D)
+            del qkv
+            off += Ss[i]
+        q = qb if kv is None else qb[:, :, kv0:kv0 + S]
+        ka, va = (k, v) if k.shape[2] == kv0 + S else (k[:, :, :kv0 + S], v[:, :, :kv0 + S])
+        o = torch.empty((B, S, Hq, D), device=dev, dtype=dtype)
+        lse = K.attn_fwd(q, ka, va, o.permute(0, 2, 1, 3), causal=False, scale=D ** -0.5, q_limit=q_limit, key_valid=key_valid)
+        ys, saved0, saved1 = [None, None], [None] * 6, [None] * 8
+        off = 0
+        for i in live:
+            a = o[:, off:off + Ss[i]].reshape(B * Ss[i], Hq * D).contiguous()
+            off += Ss[i]
+            if i == 0:
+                if not skip_post0:
+                    ys[0], kept = gemma_post_attention(st, sps[0], x0, a)
+                    saved0 = [a, *kept]
+                else:
+                    saved0[0] = a
+            else:
+                ys[1], kept = adarms_post_attention(st, sps[1], x1, a, mod1, mod2)
+                saved1 = [a, *kept]
+        if not keep:
+            return (ys[0], ys[1]), None
+        return (ys[0], ys[1]), (*h1, *rstd1, q, k, v, o, lse, *saved0, *saved1)
+
+    @staticmethod
+    def forward(ctx, x0, x1, mod1, mod2, anchor, st: ParamStore, sp0: GemmaLayerSpec, sp1: GemmaLayerSpec, geom, cos_t, sin_t,
+                pos0, pos1, q_limit, key_valid, skip_post0: bool):
+        sps = (sp0, sp1)
+        ys, saved = Pi05MotLayerFn._run(st, sps, geom, skip_post0, x0, x1, mod1, mod2, cos_t, sin_t, pos0, pos1, q_limit, key_valid)
+        ctx.st, ctx.sps, ctx.geom, ctx.skip_post0 = st, sps, geom, skip_post0
+        _use(ctx, st, sp0.ln1, sp0.qkv, sp1.qkv, sp1.o, sp1.gu, sp1.down)
+        if not skip_post0:
+            _use(ctx, st, sp0.o, sp0.ln2, sp0.gu, sp0.down)
+        ctx.aux = (cos_t, sin_t, pos0, pos1, q_limit, key_valid)
+        ctx.recompute = _recompute(ctx, st)
+        if ctx.recompute:
+            ctx.save_for_backward(x0, x1, mod1, mod2)
+        else:
+            ctx.save_for_backward(x0, x1, mod1, mod2, *saved)
+        if skip_post0:
+            return x0.new_zeros((0,)), ys[1]                   # placeholder, never read downstream
+        return ys
+
+    @staticmethod
+    def backward(ctx, dy0, dy1):
+        st, (sp0, sp1), skip_post0 = ctx.st, ctx.sps, ctx.skip_post0
+        B, S0, S1, Hq, Hkv, D = ctx.geom
+        cos_t, sin_t, pos0, pos1, q_limit, key_valid = ctx.aux
+        sv = ctx.saved_tensors
+        if ctx.recompute:
+            sv = tuple(sv) + tuple(Pi05MotLayerFn._run(st, ctx.sps, ctx.geom, skip_post0, sv[0], sv[1], sv[2], sv[3], cos_t, sin_t,
+                                                        pos0, pos1, q_limit, key_valid)[1])
+        x0, x1, mod1, mod2 = sv[0:4]
+        h1, rstd1 = sv[4:6], sv[6:8]
+        q, k, v, o, lse = sv[8:13]
+        a0, r0, rs2_0, h2_0, gu0, act0 = sv[13:19]
+        a1, ob, r1, rs2_1, h2_1, gu1, act1, mb = sv[19:27]
+        nq = (Hq + 2 * Hkv) * D
+        S = S0 + S1
+        do = torch.zeros((B, S, Hq, D), device=q.device, dtype=q.dtype)
+        # ---- expert 0 (the llm), Pi0MotLayerFn's sequence
+        dr0 = None
+        if not skip_post0:
+            dy = dy0.contiguous()
+            dact = _dx(st, sp0.down, (sp0.d, sp0.F), dy)
+            _wgrad(st, sp0.down, dy, act0, (sp0.d, sp0.F))
+            dgu = K.glu_bwd(gu0, dact, L.ACT_GELU_TANH)
+            dh2 = _dx(st, sp0.gu, (2 * sp0.F, sp0.d), dgu)
+            _wgrad(st, sp0.gu, dgu, h2_0, (2 * sp0.F, sp0.d))
+            tr = st.trainable(sp0.ln2)
+            dr0, _ = K.rmsnorm_bwd(dh2, r0, gemma_norm_w(st, sp0.ln2), rs2_0, dw_out=st.g(sp0.ln2) if tr else None,
+                                   accumulate=st.accum_flag(sp0.ln2), want_dw=tr, residual=dy)
+            if tr:
+                st.mark_written(sp0.ln2)
+            da = _dx(st, sp0.o, (sp0.d, Hq * D), dr0)
+            _wgrad(st, sp0.o, dr0, a0, (sp0.d, Hq * D))
+            do[:, :S0].copy_(da.view(B, S0, Hq, D))
+        # ---- expert 1 (the action expert): gated add, GeGLU, fused adaptive norm + gated add, o_proj
+        d = sp1.d
+        dmod1, dmod2 = torch.empty_like(mod1), torch.empty_like(mod2)
+        dy = dy1.contiguous()
+        dmb = K.gated_residual_bwd(dy, mb, mod2[:, 2 * d:], dmod2[:, 2 * d:])
+        dact = _dx(st, sp1.down, (d, sp1.F), dmb)
+        _wgrad(st, sp1.down, dmb, act1, (d, sp1.F))
+        dgu = K.glu_bwd(gu1, dact, L.ACT_GELU_TANH)
+        dh2 = _dx(st, sp1.gu, (2 * sp1.F, d), dgu)
+        _wgrad(st, sp1.gu, dgu, h2_1, (2 * sp1.F, d))
+        dr1, dob = K.adarms_bwd(dh2, r1, mod2, rs2_1, dmod2, residual=dy, branch=ob, gate_prev=mod1[:, 2 * d:],
+                                dgate_prev=dmod1[:, 2 * d:])
+        da = _dx(st, sp1.o, (d, Hq * D), dob)
+        _wgrad(st, sp1.o, dob, a1, (d, Hq * D))
+        do[:, S0:].copy_(da.view(B, S1, Hq, D))
+        do_h = K.permute_bshd(do, B, S, Hq, D, True)                       # head-major dO for the GQA fold
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        K.attn_bwd(q, k, v, o.permute(0, 2, 1, 3), lse, do_h, dq, dk, dv, causal=False, scale=D ** -0.5,
+                   q_limit=q_limit, key_valid=key_valid)
+        dqkv = K.rope_merge_from(dq, dk, dv, 0, cos_t, sin_t, pos0, B, S0, Hq, Hkv, D)
+        dh = _dx(st, sp0.qkv, (nq, sp0.d), dqkv)
+        _wgrad(st, sp0.qkv, dqkv, h1[0], (nq, sp0.d))
+        tr = st.trainable(sp0.ln1)
+        dx0, _ = K.rmsnorm_bwd(dh, x0, gemma_norm_w(st, sp0.ln1), rstd1[0], dw_out=st.g(sp0.ln1) if tr else None,
+                               accumulate=st.accum_flag(sp0.ln1), want_dw=tr, residual=dr0)
+        if tr:
+            st.mark_written(sp0.ln1)
+        dqkv = K.rope_merge_from(dq, dk, dv, S0, cos_t, sin_t, pos1, B, S1, Hq, Hkv, D)
+        dh = _dx(st, sp1.qkv, (nq, d), dqkv)
+        _wgrad(st, sp1.qkv, dqkv, h1[1], (nq, d))
+        dx1, _ = K.adarms_bwd(dh, x1, mod1, rstd1[1], dmod1, residual=dr1)
+        return (dx0, dx1, dmod1, dmod2) + (None,) * 12
+
+
+class AdaRMSNormFn(Function):
+    """adaptive RMSNorm on its own (the action expert's final norm, whose gate nothing reads: that third of dmod is zero)"""
+
+    @staticmethod
+    def forward(ctx, x, mod, eps: float):
+        y, rstd, _ = K.adarms_fwd(x, mod, eps)
+        ctx.save_for_backward(x, mod, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, mod, rstd = ctx.saved_tensors
+        dmod = torch.zeros_like(mod)
+        dx, _ = K.adarms_bwd(dy.contiguous(), x, mod, rstd, dmod)
+        return dx, dmod, None
+
+
+class FusedLinearFn(_StoreFn):
+    """y = x W^T + b for W / b the fused views over ADJACENT parameters (``wn`` / ``bn``: tuples of names registered as one group
+    each): the 2 L + 1 ``dense`` layers of the pi0.5 action expert's adaptive norms as ONE product, one dW product, one column sum"""
+
+    @staticmethod
+    def forward(ctx, x, anchor, st: ParamStore, wn: Tuple[str, ...], bn: Tuple[str, ...], wshape):
+        x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        y = K.mm_nt(x2, st.w(*wn, shape=wshape), bias=st.w(*bn, shape=(wshape[0],)))
+        ctx.st, ctx.wn, ctx.bn, ctx.wshape, ctx.xshape = st, wn, bn, tuple(wshape), x.shape
+        _use(ctx, st, wn, bn)
+        ctx.save_for_backward(x2)
+        return y.view(*x.shape[:-1], wshape[0])
+
+    @staticmethod
+    def backward(ctx, dy):
+        st = ctx.st
+        x2, = ctx.saved_tensors
+        dy2 = dy.reshape(-1, ctx.wshape[0]).contiguous()
+        _wgrad(st, ctx.wn, dy2, x2, ctx.wshape)
+        _bgrad(st, ctx.bn, dy2)
+        dx = _dx(st, ctx.wn, ctx.wshape, dy2).view(ctx.xshape) if ctx.needs_input_grad[0] else None
+        return dx, None, None, None, None, None
+
+
 # ------------------------------------------------------------------ small differentiable pieces (MemVLA memory modules)
 class AddFn(Function):
     """a + b (same shape): residual connections outside the fused blocks"""

@@ -529,6 +529,97 @@ def add_layernorm_bwd(dy, x, res, w, mean, rstd):
     return dx.view(x.shape), part
 
 
+def _gate_view(gate: torch.Tensor, B: int, cols: int, like: torch.Tensor) -> int:
+    """gate [B, cols], usually the last third of a [B, 3 * cols] modulation tensor: a view with contiguous columns -> its row stride"""
+    assert gate.shape == (B, cols) and gate.dtype == like.dtype and gate.stride(1) == 1 and gate.stride(0) >= cols, \
+        (gate.shape, gate.stride(), gate.dtype)
+    return gate.stride(0)
+
+
+def _adarms_rows(x: torch.Tensor, mod: torch.Tensor):
+    x2 = x.reshape(-1, x.shape[-1])
+    rows, cols = x2.shape
+    assert x2.is_contiguous() and mod.is_contiguous() and mod.dim() == 2 and mod.shape[1] == 3 * cols and mod.dtype == x.dtype
+    B = mod.shape[0]
+    assert B > 0 and rows % B == 0, (rows, B)
+    return x2, rows, cols, B
+
+
+def adarms_fwd(x: torch.Tensor, mod: torch.Tensor, eps: float, branch: Optional[torch.Tensor] = None,
+               gate_prev: Optional[torch.Tensor] = None):
+    """adaptive RMSNorm with the per-sample modulation mod [B, 3 * cols] = [scale | shift | gate] (rows / B rows per sample).
+    With ``branch`` and ``gate_prev`` [B, cols] (a view into another modulation tensor): r = x + branch * gate_prev[sample] first,
+    in the same launch.  -> (y, rstd [rows], r or None)"""
+    x2, rows, cols, B = _adarms_rows(x, mod)
+    y = torch.empty_like(x2)
+    rstd = torch.empty(rows, device=x.device, dtype=torch.float32)
+    r, b2, gate_ld = None, None, 0
+    if branch is not None:
+        b2 = branch.reshape(-1, cols)
+        assert b2.is_contiguous() and b2.shape == x2.shape and b2.dtype == x2.dtype
+        gate_ld = _gate_view(gate_prev, B, cols, x2)
+        r = torch.empty_like(x2)
+    L.check(lib.dxa_adarms_fwd(_ptr(x2), _ptr(b2), _ptr(gate_prev) if branch is not None else None, gate_ld, _ptr(mod), _ptr(r),
+                               _ptr(y), _ptr(rstd), rows, rows // B, cols, eps, dt(x2), _stream()), "dxa_adarms_fwd")
+    return y.view(x.shape), rstd, (r.view(x.shape) if r is not None else None)
+
+
+def gated_residual_fwd(x: torch.Tensor, branch: torch.Tensor, gate: torch.Tensor) -> torch.Tensor:
+    """x + branch * gate[sample]; gate [B, cols] may be a view into a modulation tensor"""
+    x2 = x.reshape(-1, x.shape[-1])
+    b2 = branch.reshape(-1, x.shape[-1])
+    rows, cols = x2.shape
+    B = gate.shape[0]
+    assert x2.is_contiguous() and b2.is_contiguous() and b2.shape == x2.shape and b2.dtype == x2.dtype and rows % B == 0
+    y = torch.empty_like(x2)
+    L.check(lib.dxa_gated_residual_fwd(_ptr(x2), _ptr(b2), _ptr(gate), _gate_view(gate, B, cols, x2), _ptr(y), rows, rows // B, cols,
+                                       dt(x2), _stream()), "dxa_gated_residual_fwd")
+    return y.view(x.shape)
+
+
+def _adarms_partial(B: int, rows: int, n: int, cols: int, device) -> torch.Tensor:
+    return torch.empty(B * 4 * int(lib.dxa_adarms_bwd_groups(rows // B)) * n * cols, device=device, dtype=torch.float32)
+
+
+def adarms_bwd(dy, r, mod, rstd, dmod: torch.Tensor, residual=None, branch=None, gate_prev=None, dgate_prev=None):
+    """backward of adarms_fwd on the row it normalised (``r``: x, or the gated sum).  Writes the scale and shift thirds of ``dmod``
+    [B, 3 * cols]; with ``branch``: also ``dgate_prev`` [B, cols] (a view into the other modulation tensor's gradient).
+    -> (dr (+ residual), dbranch or None)"""
+    r2, rows, cols, B = _adarms_rows(r, mod)
+    dy2 = dy.reshape(-1, cols)
+    assert dy2.is_contiguous() and dy2.shape == r2.shape and dy2.dtype == r2.dtype
+    assert dmod.is_contiguous() and dmod.shape == mod.shape and dmod.dtype == mod.dtype
+    dr = torch.empty_like(r2)
+    b2 = dbranch = None
+    gate_ld = dgate_ld = 0
+    if branch is not None:
+        b2 = branch.reshape(-1, cols)
+        assert b2.is_contiguous() and b2.shape == r2.shape and b2.dtype == r2.dtype
+        gate_ld, dgate_ld = _gate_view(gate_prev, B, cols, r2), _gate_view(dgate_prev, B, cols, r2)
+        dbranch = torch.empty_like(r2)
+    part = _adarms_partial(B, rows, 3 if branch is not None else 2, cols, r.device)
+    L.check(lib.dxa_adarms_bwd(_ptr(dy2), _ptr(r2), _ptr(mod), _ptr(rstd), _ptr(_residual2d(residual, r2)), _ptr(dr), _ptr(dmod),
+                               _ptr(b2), _ptr(gate_prev) if branch is not None else None, gate_ld, _ptr(dbranch),
+                               _ptr(dgate_prev) if branch is not None else None, dgate_ld, _ptr(part), part.numel() * 4, rows,
+                               rows // B, cols, dt(r2), _stream()), "dxa_adarms_bwd")
+    return dr.view(r.shape), (dbranch.view(r.shape) if dbranch is not None else None)
+
+
+def gated_residual_bwd(dy, branch, gate, dgate: torch.Tensor) -> torch.Tensor:
+    """backward of gated_residual_fwd: -> dbranch = dy * gate[sample]; ``dgate`` [B, cols] (a view) receives sum_rows dy * branch"""
+    dy2 = dy.reshape(-1, dy.shape[-1])
+    b2 = branch.reshape(-1, dy.shape[-1])
+    rows, cols = dy2.shape
+    B = gate.shape[0]
+    assert dy2.is_contiguous() and b2.is_contiguous() and b2.shape == dy2.shape and b2.dtype == dy2.dtype and rows % B == 0
+    dbranch = torch.empty_like(dy2)
+    part = _adarms_partial(B, rows, 1, cols, dy.device)
+    L.check(lib.dxa_gated_residual_bwd(_ptr(dy2), _ptr(b2), _ptr(gate), _gate_view(gate, B, cols, dy2), _ptr(dbranch), _ptr(dgate),
+                                       _gate_view(dgate, B, cols, dy2), _ptr(part), part.numel() * 4, rows, rows // B, cols, dt(dy2),
+                                       _stream()), "dxa_gated_residual_bwd")
+    return dbranch.view(dy.shape)
+
+
 def downsample_grid(n_tokens: int) -> Tuple[int, int]:
     """(G, h) of the 2x2 token merge: n_tokens = G*G input tokens per image, h*h = ceil(G/2)^2 merged tokens"""
     G = int(round(n_tokens ** 0.5))

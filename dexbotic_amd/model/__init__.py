@@ -1,4 +1,4 @@
-"""Policy classes.  The NaVILA, MuVLA and DM0 families are exported by name (resolved on first use, so importing one policy module
+"""Policy classes.  The NaVILA, MuVLA, DM0 and pi0.5 families are exported by name (resolved on first use, so importing one policy module
 does not import the others)."""
 
 
@@ -12,8 +12,11 @@ def __getattr__(name):
     if name in ("DM0Config", "DM0ForCausalLM", "DM0Model"):
         from . import dm0
         return getattr(dm0, name)
+    if name in ("Pi05Config", "Pi05ForCausalLM", "Pi05Model"):
+        from . import pi05
+        return getattr(pi05, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 __all__ = ["NaVILAConfig", "NaVILAForCausalLM", "NaVILAModel", "MUVLAConfig", "MUVLAForCausalLM", "MUVLAModel",
-           "DM0Config", "DM0ForCausalLM", "DM0Model"]
+           "DM0Config", "DM0ForCausalLM", "DM0Model", "Pi05Config", "Pi05ForCausalLM", "Pi05Model"]

@@ -212,6 +212,34 @@ int dxa_downsample_layernorm_fwd(const void* x, const void* w, const void* b, vo
 int dxa_downsample_layernorm_bwd(const void* dy, const void* x, const void* w, const float* mean, const float* rstd,
                                  void* dx, float* partial_dwdb, int64_t N, int64_t G, int64_t C, int dtype, int w_dtype,
                                  dxa_stream_t stream);
+/* Adaptive RMSNorm and gated residual of the pi0.5 action expert (dexbotic/model/pi05/transformers_pi05/gemma/modeling_gemma.py:
+ * 38-120): no gain, a per-SAMPLE modulation mod [B, 3*cols] = [scale | shift | gate] in `dtype` (fp32 or bf16, like every row
+ * tensor here).  Row `i` of the [rows, cols] tensors belongs to sample i / rows_per_sample (rows % rows_per_sample == 0).  All
+ * arithmetic fp32, every output rounded once.
+ *   fwd:  r = x + branch * gate_prev[s] when `branch` is given (r_out receives r; gate_prev points at the gate third of ANOTHER
+ *         modulation tensor, rows gate_ld apart), r = x otherwise;  y = r * rsqrt(mean(r^2) + eps) * (1 + scale[s]) + shift[s];
+ *         rstd [rows] (may be NULL).  One launch: o_proj -> gated add -> post-attention norm reads x and branch once.
+ *   gated_residual_fwd:  y = x + branch * gate[s].
+ *   bwd (`r`: what the norm normalised, i.e. x or r_out):  g = dy * (1 + scale[s]);  dr = rstd * (g - xh * mean(g * xh)) (+ residual);
+ *         dmod [B, 3*cols]: dscale[s] = sum_rows dy * xh and dshift[s] = sum_rows dy are WRITTEN to its first two thirds (the gate
+ *         third is not touched: its gradient comes from the add the gate multiplies); with `branch`: dbranch = dr * gate_prev[s] and
+ *         dgate_prev[s] = sum_rows dr * branch (rows dgate_ld apart).
+ *   gated_residual_bwd:  dbranch = dy * gate[s], dgate[s] = sum_rows dy * branch (the gradient of x is dy itself).
+ * The per-sample sums are fp32 and deterministic (a partial row per wave, folded in a fixed order; no atomics): `partial` holds
+ * B * 4 * dxa_adarms_bwd_groups(rows_per_sample) * n * cols floats, n = 3 with a branch, 2 without, 1 for gated_residual_bwd.
+ * Refused with DXA_ERR_BAD_ARG: a null pointer, rows % rows_per_sample != 0, cols <= 0, a stride < cols, a partial too small. */
+int dxa_adarms_fwd(const void* x, const void* branch, const void* gate_prev, int64_t gate_ld, const void* mod, void* r_out, void* y,
+                   float* rstd, int64_t rows, int64_t rows_per_sample, int64_t cols, float eps, int dtype, dxa_stream_t stream);
+int dxa_gated_residual_fwd(const void* x, const void* branch, const void* gate, int64_t gate_ld, void* y, int64_t rows,
+                           int64_t rows_per_sample, int64_t cols, int dtype, dxa_stream_t stream);
+int dxa_adarms_bwd(const void* dy, const void* r, const void* mod, const float* rstd, const void* residual, void* dr, void* dmod,
+                   const void* branch, const void* gate_prev, int64_t gate_ld, void* dbranch, void* dgate_prev, int64_t dgate_ld,
+                   float* partial, size_t partial_bytes, int64_t rows, int64_t rows_per_sample, int64_t cols, int dtype,
+                   dxa_stream_t stream);
+int dxa_gated_residual_bwd(const void* dy, const void* branch, const void* gate, int64_t gate_ld, void* dbranch, void* dgate,
+                           int64_t dgate_ld, float* partial, size_t partial_bytes, int64_t rows, int64_t rows_per_sample,
+                           int64_t cols, int dtype, dxa_stream_t stream);
+int dxa_adarms_bwd_groups(int64_t rows_per_sample);
 /* out[c] (+)= sum_r x[r*ld + c]  (bias gradients, norm-weight gradients, pos-emb gradients).
  * Deterministic two-stage reduction; scratch >= min(64, ceil(rows/32)) * cols floats. */
 int dxa_colsum(const void* x, int64_t ld, float* out, int64_t rows, int64_t cols, int dtype,
