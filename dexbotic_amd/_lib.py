@@ -174,6 +174,13 @@ SIGNATURES = {
     "dxa_im2col": (_int, [_vp, _vp, _int, _int, _int, _int, _i64, _int, _int, _vp]),
     "dxa_vit_embed_fwd": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _int, _int, _vp]),
     "dxa_vit_embed_bwd": (_int, [_vp, _vp, _int, _int, _int, _int, _vp]),
+    "dxa_rope2d_fwd": (_int, [_vp, _vp, _vp, _i64, _int, _int, _int, _int, _vp]),
+    "dxa_rope2d_bwd": (_int, [_vp, _vp, _vp, _i64, _int, _int, _int, _int, _vp]),
+    "dxa_layerscale_residual_fwd": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _int, _vp]),
+    "dxa_layerscale_residual_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _sz, _i64, _i64, _int, _vp]),
+    "dxa_layerscale_bwd_rows": (_int, [_i64]),
+    "dxa_conv3x3s2_im2col": (_int, [_vp, _vp, _i64, _int, _int, _int, _vp]),
+    "dxa_conv3x3s2_col2im": (_int, [_vp, _vp, _i64, _int, _int, _int, _vp]),
     "dxa_qsample": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
     "dxa_timestep_embedding": (_int, [_vp, _vp, _vp, _i64, _int, _vp]),
     "dxa_dit_assemble_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _int, _int, _vp]),

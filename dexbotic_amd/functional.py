@@ -555,6 +555,205 @@ def _ln_bwd(st: ParamStore, dy, x, wn: Optional[str], bn: Optional[str], mean, r
     return dx
 
 
+# ------------------------------------------------------------------- Perception Encoder block and downsampler
+@dataclass
+class PeBlockSpec:
+    ln1_w: str
+    ln1_b: str
+    qkv_w: str                  # attn.in_proj_weight [3C, C]
+    qkv_b: str
+    out_w: str
+    out_b: str
+    ln2_w: str
+    ln2_b: str
+    fc1_w: str
+    fc1_b: str
+    fc2_w: str
+    fc2_b: str
+    ls1: Optional[str]          # ls_1.gamma / ls_2.gamma, None without LayerScale (ls_init_value=None)
+    ls2: Optional[str]
+    eps: float
+    N: int = 0
+    T: int = 0
+    H: int = 0
+    D: int = 0
+    I: int = 0
+    cos: Optional[torch.Tensor] = None     # fp32 [T, D] angle tables of the grid in use (kernels.rope2d_tables)
+    sin: Optional[torch.Tensor] = None
+
+
+def _fold_gamma(st: ParamStore, name: str, part: torch.Tensor) -> None:
+    """a LayerScale backward's partial sums [p, cols] into the gradient slot of its gamma"""
+    if st.trainable(name):
+        K.colsum(part, out=st.g(name), accumulate=st.accum_flag(name))
+        st.mark_written(name)
+
+
+class PeBlockFn(_StoreFn):
+    """ResidualAttentionBlock of the Perception Encoder (mm_vision/pe/pe_model.py:188-313): x + ls_1(out(attn(rope2d(qkv(LN(x)))))),
+    then + ls_2(c_proj(gelu(c_fc(LN(.))))).  2-D RoPE turns q and k in place in the packed projection; with LayerScale the two
+    adds are dxa_layerscale_residual launches (the GEMM epilogue has no per-column scale), without it the GEMMs' residual epilogue
+    as in VitBlockFn.  Recomputed under ``ParamStore.recompute``."""
+
+    @staticmethod
+    def _run(st: ParamStore, sp: PeBlockSpec, x):
+        """the block's forward launches on x [M, C] -> (y [M, C], what the backward reads besides x)"""
+        N, T, H, D, I = sp.N, sp.T, sp.H, sp.D, sp.I
+        C_ = H * D
+        M = N * T
+        none = x.new_empty(0)
+        h1, mean1, rstd1 = K.layernorm_fwd(x, st.w(sp.ln1_w), st.w(sp.ln1_b), sp.eps)
+        qkv = K.mm_nt(h1, st.w(sp.qkv_w), bias=st.w(sp.qkv_b))
+        K.rope2d_(qkv, sp.cos, sp.sin, N, T, H, D)
+        Dp = _padded_head_dim(D, x.dtype)
+        if Dp != D:     # (a head width the MFMA attention kernels do not take: zero-padded heads, as in VitBlockFn)
+            qkv = K.copy2d(qkv.view(M * 3 * H, D), torch.empty((M * 3 * H, Dp), device=x.device, dtype=x.dtype), D, Dp)
+        q5 = qkv.view(N, T, 3, H, Dp)
+        q, k, v = (q5[:, :, i].permute(0, 2, 1, 3) for i in range(3))
+        o = torch.empty((N, T, H, Dp), device=x.device, dtype=x.dtype)
+        lse = K.attn_fwd(q, k, v, o.permute(0, 2, 1, 3), causal=False, scale=D ** -0.5)
+        o_in = o if Dp == D else K.copy2d(o.view(M * H, Dp), torch.empty((M * H, D), device=x.device, dtype=x.dtype), D, D)
+        if sp.ls1 is not None:
+            att = K.mm_nt(o_in.view(M, C_), st.w(sp.out_w), bias=st.w(sp.out_b))
+            x2 = K.layerscale_residual_fwd(x, att, st.w(sp.ls1))
+        else:
+            att, x2 = none, K.mm_nt(o_in.view(M, C_), st.w(sp.out_w), bias=st.w(sp.out_b), residual=x)
+        h2, mean2, rstd2 = K.layernorm_fwd(x2, st.w(sp.ln2_w), st.w(sp.ln2_b), sp.eps)
+        pre = torch.empty((M, I), device=x.device, dtype=x.dtype)
+        a = K.mm_nt(h2, st.w(sp.fc1_w), bias=st.w(sp.fc1_b), act=L.ACT_GELU_ERF, aux_out=pre)
+        if sp.ls2 is not None:
+            mlp = K.mm_nt(a, st.w(sp.fc2_w), bias=st.w(sp.fc2_b))
+            y = K.layerscale_residual_fwd(x2, mlp, st.w(sp.ls2))
+        else:
+            mlp, y = none, K.mm_nt(a, st.w(sp.fc2_w), bias=st.w(sp.fc2_b), residual=x2)
+        return y, (mean1, rstd1, h1, qkv, o, lse, att, x2, mean2, rstd2, h2, pre, a, mlp)
+
+    @staticmethod
+    def forward(ctx, x, anchor, st: ParamStore, sp: PeBlockSpec):
+        N, T, C_ = sp.N, sp.T, sp.H * sp.D
+        x = x.reshape(N * T, C_).contiguous()
+        y, saved = PeBlockFn._run(st, sp, x)
+        ctx.st, ctx.sp = st, sp
+        # the tables belong to this call: the spec's are replaced when the tower next sees another grid
+        ctx.geom, ctx.tables = (N, T), (sp.cos, sp.sin)
+        _use(ctx, st, sp.ln1_w, sp.ln1_b, sp.qkv_w, sp.qkv_b, sp.out_w, sp.out_b, sp.ln2_w, sp.ln2_b, sp.fc1_w, sp.fc1_b,
+             sp.fc2_w, sp.fc2_b, sp.ls1, sp.ls2)
+        ctx.recompute = _recompute(ctx, st)
+        if ctx.recompute:
+            ctx.save_for_backward(x)
+        else:
+            ctx.save_for_backward(x, *saved)
+        return y.view(N, T, C_)
+
+    @staticmethod
+    def backward(ctx, dy):
+        st, sp = ctx.st, ctx.sp
+        (sp.N, sp.T), (sp.cos, sp.sin) = ctx.geom, ctx.tables
+        if ctx.recompute:
+            (x,) = ctx.saved_tensors
+            mean1, rstd1, h1, qkv, o, lse, att, x2, mean2, rstd2, h2, pre, a, mlp = PeBlockFn._run(st, sp, x)[1]
+        else:
+            x, mean1, rstd1, h1, qkv, o, lse, att, x2, mean2, rstd2, h2, pre, a, mlp = ctx.saved_tensors
+        N, T, H, D, I = sp.N, sp.T, sp.H, sp.D, sp.I
+        C_ = H * D
+        M = N * T
+        dy = dy.reshape(M, C_).contiguous()
+        # ---- MLP (activation gradient fused into the dX GEMM epilogue)
+        dm = dy
+        if sp.ls2 is not None:
+            dm, part = K.layerscale_residual_bwd(dy, mlp, st.w(sp.ls2))
+            _fold_gamma(st, sp.ls2, part)
+        dpre = _dx(st, sp.fc2_w, (C_, I), dm, mulgrad=pre, act=L.ACT_GELU_ERF)
+        _wgrad(st, sp.fc2_w, dm, a, (C_, I))
+        _bgrad(st, sp.fc2_b, dm)
+        dh2 = _dx(st, sp.fc1_w, (I, C_), dpre)
+        _wgrad(st, sp.fc1_w, dpre, h2, (I, C_))
+        _bgrad(st, sp.fc1_b, dpre)
+        del dpre, dm
+        dx2 = _ln_bwd(st, dh2, x2, sp.ln2_w, sp.ln2_b, mean2, rstd2, residual=dy)
+        del dh2
+        # ---- attention
+        da = dx2
+        if sp.ls1 is not None:
+            da, part = K.layerscale_residual_bwd(dx2, att, st.w(sp.ls1))
+            _fold_gamma(st, sp.ls1, part)
+        do = _dx(st, sp.out_w, (C_, C_), da)                    # [M, C] token-major
+        Dp = o.shape[-1]                                          # padded head width of the forward (== D normally)
+        o_in = o if Dp == D else K.copy2d(o.view(M * H, Dp), torch.empty((M * H, D), device=o.device, dtype=o.dtype), D, D)
+        _wgrad(st, sp.out_w, da, o_in.view(M, C_), (C_, C_))
+        _bgrad(st, sp.out_b, da)
+        if Dp != D:
+            do = K.copy2d(do.view(M * H, D), torch.empty((M * H, Dp), device=o.device, dtype=o.dtype), D, Dp)
+        dqkv = torch.empty_like(qkv)
+        q5, d5 = qkv.view(N, T, 3, H, Dp), dqkv.view(N, T, 3, H, Dp)
+        q, k, v = (q5[:, :, i].permute(0, 2, 1, 3) for i in range(3))
+        dq, dk, dv = (d5[:, :, i].permute(0, 2, 1, 3) for i in range(3))
+        K.attn_bwd(q, k, v, o.permute(0, 2, 1, 3), lse, do.view(N, T, H, Dp).permute(0, 2, 1, 3), dq, dk, dv,
+                   causal=False, scale=D ** -0.5)
+        if Dp != D:
+            dqkv = K.copy2d(dqkv.view(M * 3 * H, Dp), torch.empty((M * 3 * H, D), device=o.device, dtype=o.dtype), D, D)
+        dqkv = dqkv.view(M, 3 * C_)
+        K.rope2d_(dqkv, sp.cos, sp.sin, N, T, H, D, backward=True)
+        dh1 = _dx(st, sp.qkv_w, (3 * C_, C_), dqkv)
+        _wgrad(st, sp.qkv_w, dqkv, h1, (3 * C_, C_))
+        _bgrad(st, sp.qkv_b, dqkv)
+        del dqkv
+        dx = _ln_bwd(st, dh1, x, sp.ln1_w, sp.ln1_b, mean1, rstd1, residual=dx2)
+        return dx.view(N, T, C_), None, None, None
+
+
+class Conv3x3s2Fn(_StoreFn):
+    """nn.Conv2d(C, C', kernel_size=3, stride=2, padding=1) over a token-major T x T grid (vit_downsampler1 / 2,
+    mm_vision/pe/pe_model.py:445-458,554-565): x [B, T*T, C] -> [B, To*To, C'].  im2col rows in the weight's own (c, ky, kx) column
+    order times the weight as it lies [C', 9C], bias in the GEMM epilogue; dW and db land in the parameter's layout, dX is the
+    adjoint gather of dY W."""
+
+    @staticmethod
+    def forward(ctx, x, anchor, st: ParamStore, wn: str, bn: str, T: int):
+        x = x.contiguous()
+        B, _, C_ = x.shape
+        Co = st.slots[wn].shape[0]
+        rows = K.conv3x3s2_im2col(x, T)
+        y = K.mm_nt(rows, st.w(wn, shape=(Co, 9 * C_)), bias=st.w(bn))
+        ctx.st, ctx.wn, ctx.bn, ctx.geom = st, wn, bn, (B, T, C_, Co)
+        _use(ctx, st, wn, bn)
+        ctx.save_for_backward(rows)
+        return y.view(B, -1, Co)
+
+    @staticmethod
+    def backward(ctx, dy):
+        st, wn, bn = ctx.st, ctx.wn, ctx.bn
+        B, T, C_, Co = ctx.geom
+        (rows,) = ctx.saved_tensors
+        dy2 = dy.reshape(-1, Co).contiguous()
+        _wgrad(st, wn, dy2, rows, (Co, 9 * C_))
+        _bgrad(st, bn, dy2)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = K.conv3x3s2_col2im(_dx(st, wn, (Co, 9 * C_), dy2), B, T)
+        return dx, None, None, None, None, None
+
+
+class VitEmbedTensorFn(Function):
+    """dxa_vit_embed on TENSORS: x[n, 0] = cls + pos[0], x[n, 1 + p] = patch[n, p] + pos[1 + p] with a position table that is itself
+    a function of the parameter (the Perception Encoder's resampled embedding at a non-native input size, pe_model.py:475-500)."""
+
+    @staticmethod
+    def forward(ctx, patch, cls, pos, N: int, np_: int):
+        ctx.geom = (N, np_)
+        return K.vit_embed_fwd(patch.contiguous(), cls.contiguous(), pos.contiguous(), N, np_)
+
+    @staticmethod
+    def backward(ctx, dx):
+        N, np_ = ctx.geom
+        dx = dx.contiguous()
+        C_ = dx.shape[-1]
+        s = K.colsum(dx.view(N, (np_ + 1) * C_))
+        if dx.dtype != torch.float32:
+            s = K.cast(s, dx.dtype)
+        return K.vit_embed_bwd(dx, N, np_), s[:C_], s.view(np_ + 1, C_), None, None
+
+
 # --------------------------------------------------------------------------------------- generic pieces
 class LinearFn(_StoreFn):
     """y = act(x W^T + b) (+ residual).  nn.Linear call sites of the path that are not inside a block:

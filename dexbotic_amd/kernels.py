@@ -1027,6 +1027,86 @@ def vit_embed_bwd(dx: torch.Tensor, N: int, np_: int) -> torch.Tensor:
     return dpatch
 
 
+# ------------------------------------------------------------------------- Perception Encoder tower pieces
+def rope2d_tables(grid_h: int, grid_w: int, D: int, max_h: int, max_w: int, cls: bool, device, theta: float = 10000.0):
+    """fp32 (cos, sin) [T, D] of the reference's Rope2D (pe_model.py:75-128) for a grid_h x grid_w input on a tower whose native
+    grid is max_h x max_w: the native table's rows picked at r * max_w + c.  Host-side, once per grid (callers cache it)."""
+    half = D // 2
+    inv = 1.0 / (theta ** (torch.arange(0, half, 2)[: half // 2].float() / half))
+    hr, wr = torch.arange(max_h, dtype=torch.float), torch.arange(max_w, dtype=torch.float)
+    if cls:
+        hr, wr = hr + 1, wr + 1
+    fh = (hr[:, None] * inv[None, :]).repeat_interleave(2, dim=-1)[:, None].expand(max_h, max_w, -1)
+    fw = (wr[:, None] * inv[None, :]).repeat_interleave(2, dim=-1)[None, :].expand(max_h, max_w, -1)
+    freqs = torch.cat([fw, fh], dim=-1).reshape(max_h * max_w, -1)
+    if (grid_h, grid_w) != (max_h, max_w):
+        rows = (torch.arange(grid_h).view(-1, 1) * max_w + torch.arange(grid_w).view(1, -1)).reshape(-1)
+        freqs = freqs.index_select(0, rows)
+    if cls:
+        freqs = torch.cat([torch.zeros(1, freqs.shape[-1]), freqs], dim=0)
+    return freqs.cos().contiguous().to(device), freqs.sin().contiguous().to(device)
+
+
+def rope2d_(qkv: torch.Tensor, cos_t: torch.Tensor, sin_t: torch.Tensor, N: int, T: int, H: int, D: int, backward: bool = False):
+    """in-place 2-D RoPE of the q and k thirds of qkv [N, T, 3, H, D] (``backward``: the transposed rotation, on dqkv)"""
+    assert qkv.is_contiguous() and qkv.numel() == N * T * 3 * H * D
+    assert cos_t.dtype == torch.float32 and sin_t.dtype == torch.float32 and cos_t.is_contiguous() and sin_t.is_contiguous()
+    assert tuple(cos_t.shape) == (T, D) and tuple(sin_t.shape) == (T, D)
+    fn = lib.dxa_rope2d_bwd if backward else lib.dxa_rope2d_fwd
+    L.check(fn(_ptr(qkv), _ptr(cos_t), _ptr(sin_t), N, T, H, D, dt(qkv), _stream()), "dxa_rope2d_bwd" if backward else "dxa_rope2d_fwd")
+    return qkv
+
+
+def layerscale_residual_fwd(x: torch.Tensor, h: torch.Tensor, gamma: torch.Tensor) -> torch.Tensor:
+    """x + gamma[c] * h"""
+    x2, h2 = x.reshape(-1, x.shape[-1]), h.reshape(-1, x.shape[-1])
+    rows, cols = x2.shape
+    assert x2.is_contiguous() and h2.is_contiguous() and h2.shape == x2.shape and h2.dtype == x2.dtype
+    assert gamma.is_contiguous() and gamma.numel() == cols and gamma.dtype == x2.dtype
+    y = torch.empty_like(x2)
+    L.check(lib.dxa_layerscale_residual_fwd(_ptr(x2), _ptr(h2), _ptr(gamma), _ptr(y), rows, cols, dt(x2), _stream()),
+            "dxa_layerscale_residual_fwd")
+    return y.view(x.shape)
+
+
+def layerscale_residual_bwd(dy: torch.Tensor, h: torch.Tensor, gamma: torch.Tensor):
+    """-> (dh = gamma * dy, partial sums [p, cols] fp32 of dy * h: the caller folds them into dgamma with colsum)"""
+    dy2, h2 = dy.reshape(-1, dy.shape[-1]), h.reshape(-1, dy.shape[-1])
+    rows, cols = dy2.shape
+    assert dy2.is_contiguous() and h2.is_contiguous() and h2.shape == dy2.shape and h2.dtype == dy2.dtype
+    assert gamma.is_contiguous() and gamma.numel() == cols and gamma.dtype == dy2.dtype
+    dh = torch.empty_like(dy2)
+    part = torch.empty((int(lib.dxa_layerscale_bwd_rows(rows)), cols), device=dy.device, dtype=torch.float32)
+    L.check(lib.dxa_layerscale_residual_bwd(_ptr(dy2), _ptr(h2), _ptr(gamma), _ptr(dh), _ptr(part), part.numel() * 4, rows, cols,
+                                            dt(dy2), _stream()), "dxa_layerscale_residual_bwd")
+    return dh.view(dy.shape), part
+
+
+def conv_out_grid(T: int) -> int:
+    """output side of a 3x3 / stride 2 / pad 1 convolution over a T x T grid"""
+    return (T - 1) // 2 + 1
+
+
+def conv3x3s2_im2col(x: torch.Tensor, T: int) -> torch.Tensor:
+    """x [B, T*T, C] token-major -> rows [B*To*To, 9*C], column order (c, ky, kx)"""
+    assert x.dim() == 3 and x.is_contiguous() and x.shape[1] == T * T
+    B, _, C_ = x.shape
+    To = conv_out_grid(T)
+    rows = torch.empty((B * To * To, 9 * C_), device=x.device, dtype=x.dtype)
+    L.check(lib.dxa_conv3x3s2_im2col(_ptr(x), _ptr(rows), B, T, C_, dt(x), _stream()), "dxa_conv3x3s2_im2col")
+    return rows
+
+
+def conv3x3s2_col2im(drows: torch.Tensor, B: int, T: int) -> torch.Tensor:
+    """adjoint of conv3x3s2_im2col: drows [B*To*To, 9*C] -> dx [B, T*T, C]"""
+    To = conv_out_grid(T)
+    assert drows.dim() == 2 and drows.is_contiguous() and drows.shape[0] == B * To * To and drows.shape[1] % 9 == 0
+    C_ = drows.shape[1] // 9
+    dx = torch.empty((B, T * T, C_), device=drows.device, dtype=drows.dtype)
+    L.check(lib.dxa_conv3x3s2_col2im(_ptr(drows), _ptr(dx), B, T, C_, dt(drows), _stream()), "dxa_conv3x3s2_col2im")
+    return dx
+
+
 # ------------------------------------------------------------------------------------- diffusion glue
 def qsample(x0, noise, a, s):
     assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (x0, noise, a, s))

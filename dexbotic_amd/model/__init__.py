@@ -1,5 +1,5 @@
-"""Policy classes.  The NaVILA, MuVLA, DM0 and pi0.5 families are exported by name (resolved on first use, so importing one policy module
-does not import the others)."""
+"""Policy classes.  The NaVILA, MuVLA, DM0 and pi0.5 families and the Perception Encoder tower are exported by name (resolved on first
+use, so importing one policy module does not import the others)."""
 
 
 def __getattr__(name):
@@ -15,8 +15,12 @@ def __getattr__(name):
     if name in ("Pi05Config", "Pi05ForCausalLM", "Pi05Model"):
         from . import pi05
         return getattr(pi05, name)
+    if name in ("PerceptionEncoderConfig", "PEVisionTower"):
+        from .modules.mm_vision import pe
+        return getattr(pe, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 __all__ = ["NaVILAConfig", "NaVILAForCausalLM", "NaVILAModel", "MUVLAConfig", "MUVLAForCausalLM", "MUVLAModel",
-           "DM0Config", "DM0ForCausalLM", "DM0Model", "Pi05Config", "Pi05ForCausalLM", "Pi05Model"]
+           "DM0Config", "DM0ForCausalLM", "DM0Model", "Pi05Config", "Pi05ForCausalLM", "Pi05Model",
+           "PerceptionEncoderConfig", "PEVisionTower"]

@@ -412,6 +412,36 @@ int dxa_vit_embed_fwd(const void* patch, const void* cls, const void* pos, void*
                       int dtype, int w_dtype, dxa_stream_t stream);
 int dxa_vit_embed_bwd(const void* dx, void* dpatch, int N, int np, int C, int dtype, dxa_stream_t stream);
 
+/* Perception Encoder vision tower (dexbotic/model/modules/mm_vision/pe/pe_model.py), the pieces between its GEMMs.
+ *
+ * 2-D RoPE (Rope2D.forward + apply_rotary_emb + rotate_half, pe_model.py:17-47,114-128): rotates, in place, the q and k thirds of
+ * the packed projection qkv [N, T, 3, H, D]; v is not touched.  cos / sin: fp32 tables [T, D] of the token's angles, built on the
+ * host for the grid in use (the first D/2 columns turn with the token's column index, the last D/2 with its row index, each
+ * frequency twice; the rows picked out of the native grid's table for another grid).  Per interleaved pair
+ *   fwd:  y[2i] = x[2i] cos[2i] - x[2i+1] sin[2i],      y[2i+1] = x[2i+1] cos[2i+1] + x[2i] sin[2i+1]
+ *   bwd:  dx[2i] = dy[2i] cos[2i] + dy[2i+1] sin[2i+1],  dx[2i+1] = dy[2i+1] cos[2i+1] - dy[2i] sin[2i]   (the transposed rotation)
+ * each product rounded to fp32, added, rounded once to `dtype`.  A chunk whose angles are all zero (the CLS row) is not written:
+ * it stays bit-identical.  Nothing is saved for the backward.  Refused with DXA_ERR_BAD_ARG: a null pointer, D % 4 != 0, sizes <= 0. */
+int dxa_rope2d_fwd(void* qkv, const float* cos_t, const float* sin_t, int64_t N, int T, int H, int D, int dtype, dxa_stream_t stream);
+int dxa_rope2d_bwd(void* dqkv, const float* cos_t, const float* sin_t, int64_t N, int T, int H, int D, int dtype, dxa_stream_t stream);
+/* LayerScale + residual (ResidualAttentionBlock.forward, pe_model.py:311-312 with LayerScale.forward :138-139):
+ *   fwd:  y = x + gamma[c] * h          x, h, y [rows, cols]; gamma [cols], all of `dtype`
+ *   bwd:  dh = gamma * dy, and partial [dxa_layerscale_bwd_rows(rows)][cols] fp32: per-column sums of dy * h over disjoint row sets,
+ *         each in row order (no atomics; `partial` 16-byte aligned).  Their column sum (dxa_colsum) is dgamma; the gradient of x is
+ *         dy itself. */
+int dxa_layerscale_residual_fwd(const void* x, const void* h, const void* gamma, void* y, int64_t rows, int64_t cols, int dtype,
+                                dxa_stream_t stream);
+int dxa_layerscale_residual_bwd(const void* dy, const void* h, const void* gamma, void* dh, float* partial, size_t partial_bytes,
+                                int64_t rows, int64_t cols, int dtype, dxa_stream_t stream);
+int dxa_layerscale_bwd_rows(int64_t rows);
+/* Rows of the 3x3 / stride 2 / pad 1 convolutions vit_downsampler1 / 2 (pe_model.py:445-458,554-565) over a token-major T x T grid:
+ *   im2col:  x [B, T*T, C] -> rows [B*To*To, 9*C], To = (T - 1) / 2 + 1, column c*9 + ky*3 + kx = x[b, 2 oy + ky - 1, 2 ox + kx - 1, c]
+ *            (zero outside the grid): the flattening of the Conv2d weight [C', C, 3, 3], so the convolution is dxa_gemm (NT) with
+ *            the weight as it lies, its bias epilogue, and a token-major result [B, To*To, C'].
+ *   col2im:  the adjoint as a gather per input element: dx [B, T*T, C] from drows [B*To*To, 9*C]; every dx element is written. */
+int dxa_conv3x3s2_im2col(const void* x, void* rows, int64_t B, int T, int C, int dtype, dxa_stream_t stream);
+int dxa_conv3x3s2_col2im(const void* drows, void* dx, int64_t B, int T, int C, int dtype, dxa_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Diffusion action expert glue (fp32).  cogact/action_model/{action_models,dit,diffusion}.py.
  * ---------------------------------------------------------------------------------------------- */
