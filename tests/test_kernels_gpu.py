@@ -712,6 +712,69 @@ def test_diffusion_glue():
     del per
 
 
+@pytest.mark.parametrize("weights", ["ones", "mixed", "zeros"])
+@pytest.mark.parametrize("cols", [1, 7, 112])
+@pytest.mark.parametrize("rows", [1, 5, 1025])
+def test_mse_loss_rows(rows, cols, weights):
+    """sum_r w_r mean_c(d^2) / (sum w + 1e-6) and its gradient against float64; at 1025 rows the weight loop of the 1024-thread
+    block takes a second trip"""
+    pred, tgt = rnd(rows, cols, seed=103), rnd(rows, cols, seed=104)
+    if weights == "ones":
+        w = torch.ones(rows, device=DEV)
+    elif weights == "zeros":
+        w = torch.zeros(rows, device=DEV)
+    else:
+        w = rnd(rows, seed=105).abs() + 0.25
+        if rows > 1:
+            w[::3] = 0
+            w[rows - 1] = 1.5
+    d = pred.double() - tgt.double()
+    den = w.double().sum() + 1e-6
+    ref = (w.double() * d.square().mean(1)).sum() / den
+    K_ = -(-rows * cols // 1024)                                 # terms one of the 1024 threads accumulates
+    rtol, atol = tol_for(torch.float32, K_)
+    for gscale in (1.0, 0.25):
+        loss, dpred = K.mse_loss_rows(pred, tgt, w, gscale=gscale)
+        gref = 2 * w.double()[:, None] * d / (cols * den) * gscale
+        if float(w.sum()) == 0:
+            assert loss.item() == 0 and bool((dpred == 0).all())
+        assert_close(loss, ref.view(1), rtol, atol, f"mse_loss_rows {rows}x{cols} {weights}")
+        # one term per element: the relative bound alone (the absolute one of the neighbouring mse gradient check)
+        assert_close(dpred, gref, rtol, 1e-9, f"mse_loss_rows grad {rows}x{cols} {weights} gscale {gscale}")
+    loss2, none = K.mse_loss_rows(pred, tgt, w, want_grad=False)
+    assert none is None and loss2.item() == loss.item()
+
+
+@pytest.mark.parametrize("sdt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("ddt", [torch.float32, torch.bfloat16])
+def test_copy2d(sdt, ddt):
+    def same(a, b):
+        view = torch.int32 if a.dtype == torch.float32 else torch.int16
+        return a.dtype == b.dtype and torch.equal(a.contiguous().view(view), b.contiguous().view(view))
+
+    for rows, cols, cp in [(3, 5, 8), (70, 130, 136), (51, 72, 128)]:
+        src = rnd(rows, cols, dtype=sdt, seed=106)
+        # zero padding of columns cols .. cols_padded
+        dst = torch.full((rows, cp), 77.0, device=DEV, dtype=ddt)
+        assert K.copy2d(src, dst, cols, cp) is dst
+        assert same(dst[:, :cols], src.to(ddt)) and bool((dst[:, cols:] == 0).all()) and cp > cols
+        # cols_padded == cols into a column slice (odd offset) of a wider destination: nothing outside the slice changes
+        wide = (torch.arange(rows * (cp + 5), device=DEV) % 120 + 130).to(ddt).view(rows, cp + 5)
+        keep = wide.clone()
+        K.copy2d(src, wide[:, 3:3 + cols], cols, cols)
+        assert same(wide[:, 3:3 + cols], src.to(ddt))
+        assert same(wide[:, :3], keep[:, :3]) and same(wide[:, 3 + cols:], keep[:, 3 + cols:])
+        # strided source view, padded destination
+        big = rnd(rows, cols + 11, dtype=sdt, seed=107)
+        dst = torch.full((rows, cp), 77.0, device=DEV, dtype=ddt)
+        K.copy2d(big[:, 5:5 + cols], dst, cols, cp)
+        assert same(dst[:, :cols], big[:, 5:5 + cols].to(ddt)) and bool((dst[:, cols:] == 0).all())
+        # shrinking: the source is wider than cols
+        dst = torch.full((rows, cols), 77.0, device=DEV, dtype=ddt)
+        K.copy2d(big, dst, cols, cols)
+        assert same(dst, big[:, :cols].to(ddt))
+
+
 # --------------------------------------------------------------------------------------------- optimizer
 def test_adamw_matches_torch():
     torch.manual_seed(0)
