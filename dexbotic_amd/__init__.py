@@ -33,6 +33,7 @@ def model_registry():
     from .model.dm0.dm0_arch import DM0Config, DM0ForCausalLM
     from .model.memvla.memvla_arch import MemVLAConfig, MemVLAForCausalLM
     from .model.navila.navila_arch import NaVILAConfig, NaVILAForCausalLM
+    from .model.oft.oft_arch import OFTConfig, OFTForCausalLM
     from .model.pi0.pi0_arch import Pi0Config, Pi0ForCausalLM
     from .model.pi05.pi05_arch import Pi05Config, Pi05ForCausalLM
     return {"dexbotic": (DexboticConfig, DexboticForCausalLM),
@@ -41,7 +42,8 @@ def model_registry():
             "dexbotic_memvla": (MemVLAConfig, MemVLAForCausalLM),
             "dexbotic_navila": (NaVILAConfig, NaVILAForCausalLM),
             "dexbotic_dm0": (DM0Config, DM0ForCausalLM),
-            "dexbotic_pi05": (Pi05Config, Pi05ForCausalLM)}
+            "dexbotic_pi05": (Pi05Config, Pi05ForCausalLM),
+            "dexbotic_oft": (OFTConfig, OFTForCausalLM)}
 
 
 def __getattr__(name):

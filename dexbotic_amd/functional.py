@@ -1025,26 +1025,147 @@ class SpliceFn(_StoreFn):
 
     @staticmethod
     def backward(ctx, dout):
-        st = ctx.st
         (plan,) = ctx.saved_tensors
+        return _splice_backward(ctx.st, ctx.embed_n, plan, dout.contiguous(), ctx.ishape, ctx.needs_input_grad[0]), None, None, None, None
+
+
+def _splice_backward(st: ParamStore, embed_n: str, plan: torch.Tensor, dout: torch.Tensor, ishape, want_img: bool):
+    """the splice's backward launches (SpliceFn, OftSpliceFn): the image rows' gradient, or None; the token rows' gradient is added
+    into the embedding's slot.  Rows the plan marks as padding (PLAN_PAD) are ignored."""
+    d_img = None
+    if want_img:
+        d_img = torch.zeros(ishape, device=dout.device, dtype=dout.dtype)
+    d_embed = None
+    if st.trainable(embed_n):
+        d_embed = st.g(embed_n)
+        if not st.accum_flag(embed_n):
+            # dense nn.Embedding gradient of which only <= B*S_text rows are ever non-zero: re-zero just the rows
+            # the previous step touched when the store tracks them (single GPU), the whole slice otherwise
+            st.zero_embed_grad(embed_n)
+        st.note_embed_rows(embed_n, plan)
+    K.splice_bwd(plan, dout, d_embed, d_img)
+    if d_embed is not None:
+        # AFTER the scatter-add is enqueued: embed_tokens is alone in its bucket, so this fires the reducer / the
+        # grad-norm fold, which order themselves after everything enqueued so far on this stream
+        st.mark_written(embed_n)
+    return d_img
+
+
+class OftSpliceFn(_StoreFn):
+    """SpliceFn followed by ``insert_action_embedding`` (dexbotic/model/oft/oft_arch.py:105,118-123,169-201) on the SAME buffer: the
+    plan (splice.build_oft_splice_plan) reserves Q rows behind each sample's rows, dxa_splice_fwd zero-fills them and
+    dxa_action_put_fwd writes the sample's state row (``state`` [B, d], with proprio) and the shared ``action_query`` rows there.  No
+    [B, S, d] tensor is built and copied.  Backward: the query's gradient (sum over the batch, ascending) into its slot, the state
+    rows' gradient returned, then the splice's own backward, which ignores the reserved rows."""
+
+    @staticmethod
+    def forward(ctx, img_feats, state, anchor, st: ParamStore, embed_n: str, query_n: str, plan: torch.Tensor, off: torch.Tensor,
+                B: int, Sq: int):
+        d = img_feats.shape[-1]
+        out = K.splice_fwd(plan, st.w(embed_n), img_feats.reshape(-1, d).contiguous())
+        nq = st.slots[query_n].numel // d
+        K.action_put_(out.view(B, Sq, d), st.w(query_n, shape=(nq, d)), off, None if state is None else state.contiguous())
+        ctx.st, ctx.embed_n, ctx.query_n, ctx.ishape, ctx.geom = st, embed_n, query_n, img_feats.shape, (B, Sq, d, nq)
+        ctx.has_state = state is not None
+        _use(ctx, st, embed_n, query_n)
+        ctx.save_for_backward(plan, off)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        st = ctx.st
+        plan, off = ctx.saved_tensors
+        B, Sq, d, nq = ctx.geom
         dout = dout.contiguous()
-        d_img = None
-        if ctx.needs_input_grad[0]:
-            d_img = torch.zeros(ctx.ishape, device=dout.device, dtype=dout.dtype)
-        d_embed = None
-        if st.trainable(ctx.embed_n):
-            d_embed = st.g(ctx.embed_n)
-            if not st.accum_flag(ctx.embed_n):
-                # dense nn.Embedding gradient of which only <= B*S_text rows are ever non-zero: re-zero just the rows
-                # the previous step touched when the store tracks them (single GPU), the whole slice otherwise
-                st.zero_embed_grad(ctx.embed_n)
-            st.note_embed_rows(ctx.embed_n, plan)
-        K.splice_bwd(plan, dout, d_embed, d_img)
-        if d_embed is not None:
-            # AFTER the scatter-add is enqueued: embed_tokens is alone in its bucket, so this fires the reducer / the
-            # grad-norm fold, which order themselves after everything enqueued so far on this stream
-            st.mark_written(ctx.embed_n)
-        return d_img, None, None, None, None
+        tr = st.trainable(ctx.query_n)
+        want_state = ctx.has_state and ctx.needs_input_grad[1]
+        dstate = None
+        if tr or want_state:
+            _, dstate = K.action_put_bwd(dout.view(B, Sq, d), off, nq, ctx.has_state,
+                                         dquery=st.g(ctx.query_n, shape=(nq, d)) if tr else None,
+                                         accumulate=st.accum_flag(ctx.query_n) if tr else False, want_dstate=want_state)
+            if tr:
+                st.mark_written(ctx.query_n)
+        d_img = _splice_backward(st, ctx.embed_n, plan, dout, ctx.ishape, ctx.needs_input_grad[0])
+        return d_img, dstate, None, None, None, None, None, None, None, None
+
+
+class ActionNormFn(_StoreFn):
+    """``extract_action_hidden_states`` + ``reshape(B, T, A d)`` + ``MLPResNet.layer_norm1`` (oft_arch.py:137-140,203-210,
+    oft/action_model/model.py:119,158) in one launch per direction: h [B, Sq, d] -> [B T, A d].  The backward writes the whole
+    gradient of h (zero off the action rows): the head is the only consumer of the decoder output in this policy.  Only h and the
+    row statistics are kept."""
+
+    @staticmethod
+    def forward(ctx, h, anchor, st: ParamStore, wn: str, bn: str, off: torch.Tensor, T: int, A: int, skip: bool, eps: float):
+        h = h.contiguous()
+        y, mean, rstd = K.action_layernorm_fwd(h, off, st.w(wn), st.w(bn), T, A, skip, eps)
+        ctx.st, ctx.wn, ctx.bn, ctx.geom = st, wn, bn, (T, A, skip)
+        _use(ctx, st, wn, bn)
+        ctx.save_for_backward(h, off, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        st, wn, bn = ctx.st, ctx.wn, ctx.bn
+        h, off, mean, rstd = ctx.saved_tensors
+        T, A, skip = ctx.geom
+        dh, part = K.action_layernorm_bwd(dy.contiguous(), h, off, st.w(wn), mean, rstd, T, A, skip)
+        if st.trainable(wn):
+            _fold_ln_partials(st, wn, bn, part)
+        return dh, None, None, None, None, None, None, None, None, None
+
+
+class ResidualLinearFn(_StoreFn):
+    """act(LN(x) W^T + b) + x: one ``MLPResNetBlock`` (oft/action_model/model.py:83-101: Pre-LN, Linear, ReLU, skip) as
+    dxa_layernorm_fwd then ONE product with bias, activation and residual in its epilogue (``aux_out`` keeps the pre-activation for
+    the backward); the skip's gradient is added inside the LayerNorm backward."""
+
+    @staticmethod
+    def forward(ctx, x, anchor, st: ParamStore, ln_w: str, ln_b: str, wn: str, bn: str, act: int, eps: float):
+        x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        hn, mean, rstd = K.layernorm_fwd(x2, st.w(ln_w), st.w(ln_b), eps)
+        W = st.w(wn)
+        pre = torch.empty((x2.shape[0], W.shape[0]), device=x.device, dtype=x.dtype)
+        y = K.mm_nt(hn, W, bias=st.w(bn), act=act, aux_out=pre, residual=x2)
+        ctx.st, ctx.names, ctx.act, ctx.xshape = st, (ln_w, ln_b, wn, bn), act, x.shape
+        _use(ctx, st, ln_w, ln_b, wn, bn)
+        ctx.save_for_backward(x2, hn, mean, rstd, pre)
+        return y.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        st = ctx.st
+        ln_w, ln_b, wn, bn = ctx.names
+        x2, hn, mean, rstd, pre = ctx.saved_tensors
+        W = st.w(wn)
+        dy2 = dy.reshape(-1, W.shape[0]).contiguous()
+        dpre = K.act_bwd(pre, dy2, ctx.act)
+        _wgrad(st, wn, dpre, hn, W.shape)
+        _bgrad(st, bn, dpre)
+        dhn = _dx(st, wn, W.shape, dpre)
+        dx = _ln_bwd(st, dhn, x2, ln_w, ln_b, mean, rstd, residual=dy2)
+        return dx.view(ctx.xshape), None, None, None, None, None, None, None, None
+
+
+class L1LossFn(Function):
+    """loss = |pred - target|.mean() (torch.nn.L1Loss(), oft_arch.py:152); the gradient is the sign (0 at a tie) over n"""
+
+    @staticmethod
+    def forward(ctx, pred, target):
+        ctx.dtype = pred.dtype
+        pred = pred.contiguous()
+        if pred.dtype != torch.float32:              # bf16 compute: the loss itself is taken in fp32 (oft_arch.py:149)
+            pred = K.cast(pred, torch.float32)
+        loss, dpred = K.l1_loss(pred, target.contiguous(), 1.0, want_grad=True)
+        ctx.save_for_backward(dpred)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (dpred,) = ctx.saved_tensors
+        d = K.scale_dev_(dpred.clone(), g.reshape(1).float().contiguous())
+        return (d if ctx.dtype == torch.float32 else K.cast(d, ctx.dtype)), None
 
 
 class GatherRowsFn(Function):

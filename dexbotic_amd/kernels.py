@@ -660,6 +660,81 @@ def downsample_layernorm_bwd(dy, x, w, mean, rstd, out: Optional[torch.Tensor] =
     return dx, part
 
 
+# ------------------------------------------------------------------------------------------------- OFT
+def _action_off(off: torch.Tensor, B: int) -> torch.Tensor:
+    assert off.dtype == torch.int64 and off.is_contiguous() and off.numel() == B, (off.dtype, off.shape, B)
+    return off
+
+
+def action_put_(x: torch.Tensor, query: torch.Tensor, off: torch.Tensor, state: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [B, Sq, d] in place: x[b, off[b] + s + j] = query[j] (query [n, d] in x's dtype or fp32, shared by the batch); with ``state``
+    [B, d]: x[b, off[b]] = state[b] and s = 1, else s = 0.  ``off`` [B] int64 on the device."""
+    B, Sq, d = x.shape
+    assert x.is_contiguous() and query.is_contiguous() and query.dim() == 2 and query.shape[1] == d
+    if state is not None:
+        assert state.is_contiguous() and state.shape == (B, d) and state.dtype == x.dtype
+    L.check(lib.dxa_action_put_fwd(_ptr(x), _ptr(query), _ptr(state), _ptr(_action_off(off, B)), B, Sq, d, query.shape[0], dt(x),
+                                   dt(query), _stream()), "dxa_action_put_fwd")
+    return x
+
+
+def action_put_bwd(dx: torch.Tensor, off: torch.Tensor, n_query: int, skip: bool, dquery: Optional[torch.Tensor] = None,
+                   accumulate: bool = False, want_dstate: bool = False):
+    """-> (dquery [n_query, d] fp32 = sum over the samples in ascending order, written to / accumulated into ``dquery`` when given;
+    dstate [B, d] in dx's dtype or None)"""
+    B, Sq, d = dx.shape
+    assert dx.is_contiguous()
+    if dquery is None:
+        dquery = torch.empty((n_query, d), device=dx.device, dtype=torch.float32)
+        accumulate = False
+    assert dquery.dtype == torch.float32 and dquery.is_contiguous() and dquery.numel() == n_query * d
+    dstate = torch.empty((B, d), device=dx.device, dtype=dx.dtype) if (want_dstate and skip) else None
+    L.check(lib.dxa_action_put_bwd(_ptr(dx), _ptr(_action_off(off, B)), _ptr(dquery), _ptr(dstate), B, Sq, d, n_query, int(skip),
+                                   int(accumulate), dt(dx), _stream()), "dxa_action_put_bwd")
+    return dquery, dstate
+
+
+def action_layernorm_fwd(h: torch.Tensor, off: torch.Tensor, w, b, T: int, A: int, skip: bool, eps: float):
+    """h [B, Sq, d] -> (y [B*T, A*d], mean [B*T], rstd [B*T]): row (b, t) = LayerNorm of the A*d elements from h[b, off[b] + skip + t*A]"""
+    B, Sq, d = h.shape
+    assert h.is_contiguous()
+    y = torch.empty((B * T, A * d), device=h.device, dtype=h.dtype)
+    mean = torch.empty(B * T, device=h.device, dtype=torch.float32)
+    rstd = torch.empty_like(mean)
+    L.check(lib.dxa_action_layernorm_fwd(_ptr(h), _ptr(_action_off(off, B)), _ptr(w), _ptr(b), _ptr(y), _ptr(mean), _ptr(rstd), B, Sq,
+                                         d, T, A, int(skip), eps, dt(h), dt(w) if w is not None else dt(h), _stream()),
+            "dxa_action_layernorm_fwd")
+    return y, mean, rstd
+
+
+def action_layernorm_bwd(dy: torch.Tensor, h: torch.Tensor, off: torch.Tensor, w, mean, rstd, T: int, A: int, skip: bool,
+                         out: Optional[torch.Tensor] = None):
+    """-> (dh [B, Sq, d], every element written: dx on the action rows, zero elsewhere; partial sums [blocks, dw | db] fp32 or None
+    without w: the caller folds them with colsum)"""
+    B, Sq, d = h.shape
+    dy2 = dy.reshape(B * T, A * d)
+    assert h.is_contiguous() and dy2.is_contiguous() and dy2.dtype == h.dtype
+    dh = torch.empty_like(h) if out is None else out
+    assert dh.shape == h.shape and dh.dtype == h.dtype and dh.is_contiguous()
+    part = None
+    if w is not None:
+        part = torch.empty((int(lib.dxa_action_layernorm_bwd_blocks(B * T)), 2 * A * d), device=h.device, dtype=torch.float32)
+    L.check(lib.dxa_action_layernorm_bwd(_ptr(dy2), _ptr(h), _ptr(_action_off(off, B)), _ptr(w), _ptr(mean), _ptr(rstd), _ptr(dh),
+                                         _ptr(part), B, Sq, d, T, A, int(skip), dt(h), dt(w) if w is not None else dt(h), _stream()),
+            "dxa_action_layernorm_bwd")
+    return dh, part
+
+
+def l1_loss(pred, target, gscale: float = 1.0, want_grad: bool = True):
+    """mean |pred - target| -> (loss [1], dpred = sign(pred - target) gscale / n or None)"""
+    assert pred.is_contiguous() and target.is_contiguous() and pred.dtype == torch.float32 and target.dtype == torch.float32
+    assert pred.numel() == target.numel()
+    loss = torch.empty(1, device=pred.device, dtype=torch.float32)
+    dpred = torch.empty_like(pred) if want_grad else None
+    L.check(lib.dxa_l1_loss(_ptr(pred), _ptr(target), _ptr(loss), _ptr(dpred), pred.numel(), gscale, _stream()), "dxa_l1_loss")
+    return loss, dpred
+
+
 def colsum(x: torch.Tensor, out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
     """out[c] (+)= sum_r x[r, c]  (fp32 result)"""
     ld = _row_major(x, "x")

@@ -1,4 +1,4 @@
-"""Policy classes.  The NaVILA, MuVLA, DM0 and pi0.5 families and the Perception Encoder tower are exported by name (resolved on first
+"""Policy classes.  The NaVILA, MuVLA, DM0, pi0.5 and OFT families and the Perception Encoder tower are exported by name (resolved on first
 use, so importing one policy module does not import the others)."""
 
 
@@ -15,6 +15,9 @@ def __getattr__(name):
     if name in ("Pi05Config", "Pi05ForCausalLM", "Pi05Model"):
         from . import pi05
         return getattr(pi05, name)
+    if name in ("OFTConfig", "OFTForCausalLM", "OFTModel"):
+        from . import oft
+        return getattr(oft, name)
     if name in ("PerceptionEncoderConfig", "PEVisionTower"):
         from .modules.mm_vision import pe
         return getattr(pe, name)
@@ -23,4 +26,4 @@ def __getattr__(name):
 
 __all__ = ["NaVILAConfig", "NaVILAForCausalLM", "NaVILAModel", "MUVLAConfig", "MUVLAForCausalLM", "MUVLAModel",
            "DM0Config", "DM0ForCausalLM", "DM0Model", "Pi05Config", "Pi05ForCausalLM", "Pi05Model",
-           "PerceptionEncoderConfig", "PEVisionTower"]
+           "OFTConfig", "OFTForCausalLM", "OFTModel", "PerceptionEncoderConfig", "PEVisionTower"]

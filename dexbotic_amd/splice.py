@@ -177,6 +177,35 @@ def build_navila_splice_plan(input_ids: np.ndarray, attention_mask: Optional[np.
     return SplicePlan(plan, new_mask, new_labels, lengths, kv_start, kv_end, last)
 
 
+def build_oft_splice_plan(input_ids: np.ndarray, attention_mask: Optional[np.ndarray], labels: Optional[np.ndarray],
+                          n_img_rows: int, n_query_rows: int, max_length: Optional[int] = None,
+                          padding_side: str = "right") -> SplicePlan:
+    """OFT's sequence (dexbotic/model/oft/oft_arch.py:169-201, ``insert_action_embedding``) as ONE plan: the base rule's rows of
+    sample b, then Q = ``n_query_rows`` reserved rows (``PLAN_PAD``: the splice kernel zero-fills them, dxa_action_put_fwd writes the
+    state / query rows there in place), then padding up to S + Q.  The mask is true on [0, len_b + Q), the key range ends at
+    len_b + Q, the labels of the new rows are IGNORE_INDEX, ``last_index`` = len_b + Q - 1 and ``lengths`` stays len_b — the offset
+    of the reserved block.  Left padding is refused: the reference's insertion counts from the left edge and is wrong there."""
+    if padding_side != "right":
+        raise ValueError(f"OFT: tokenizer_padding_side={padding_side!r} is not supported (the action rows follow each sample's "
+                         "un-padded rows counted from the left edge); use right padding")
+    Q = int(n_query_rows)
+    if Q <= 0:
+        raise ValueError(f"OFT: n_query_rows must be positive, got {n_query_rows}")
+    base = build_splice_plan(input_ids, attention_mask, labels, n_img_rows, max_length, "right")
+    B, S = base.plan.shape
+    plan = np.full((B, S + Q), PLAN_PAD, dtype=np.int64)
+    new_mask = np.zeros((B, S + Q), dtype=bool)
+    new_labels = np.full((B, S + Q), IGNORE_INDEX, dtype=np.int64)
+    for b in range(B):
+        n = int(base.lengths[b])
+        plan[b, :n] = base.plan[b, :n]
+        new_labels[b, :n] = base.labels[b, :n]
+        new_mask[b, :n + Q] = True
+    kv_end = (base.lengths + Q).astype(np.int32)
+    return SplicePlan(plan, new_mask, new_labels, base.lengths.copy(), np.zeros(B, dtype=np.int32), kv_end,
+                      (base.lengths + Q - 1).astype(np.int64))
+
+
 class PlanCache:
     """Splice plans keyed by the CONTENT of the integer inputs (ids / mask / labels are a few KB), plus an identity
     shortcut for device-resident id tensors so that a batch object seen before costs no device->host copy (the
@@ -210,18 +239,24 @@ class PlanCache:
         return arr
 
     def get(self, ids, mask, labels, n_img_rows: int, max_length, padding_side: str, rule: str = "base",
-            n_feature_samples: Optional[int] = None) -> SplicePlan:
-        """``rule``: "base" (``build_splice_plan``: one block of ``n_img_rows`` per placeholder, counted across the batch) or
-        "navila" (``build_navila_splice_plan``: ``n_img_rows`` rows per SAMPLE, split between its placeholders).  The rule is part
-        of the key: the same ids mean different plans under the two."""
-        if rule not in ("base", "navila"):
+            n_feature_samples: Optional[int] = None, n_query_rows: Optional[int] = None) -> SplicePlan:
+        """``rule``: "base" (``build_splice_plan``: one block of ``n_img_rows`` per placeholder, counted across the batch),
+        "navila" (``build_navila_splice_plan``: ``n_img_rows`` rows per SAMPLE, split between its placeholders) or "oft"
+        (``build_oft_splice_plan``: the base rule plus ``n_query_rows`` reserved rows behind each sample's rows).  The rule and the
+        number of reserved rows are part of the key: the same ids mean different plans under them."""
+        if rule not in ("base", "navila", "oft"):
             raise ValueError(f"unknown splice rule {rule!r}")
+        if (rule == "oft") != (n_query_rows is not None):
+            raise ValueError('n_query_rows goes with rule="oft" and with no other rule')
         ids, mask, labels = self.host(ids), self.host(mask), self.host(labels)
         key = (ids.shape, ids.tobytes(), None if mask is None else mask.tobytes(),
-               None if labels is None else labels.tobytes(), n_img_rows, max_length, padding_side, rule, n_feature_samples)
+               None if labels is None else labels.tobytes(), n_img_rows, max_length, padding_side, rule, n_feature_samples,
+               n_query_rows)
         plan = self._by_content.get(key)
         if plan is None:
-            if rule == "navila":
+            if rule == "oft":
+                plan = build_oft_splice_plan(ids, mask, labels, n_img_rows, n_query_rows, max_length, padding_side)
+            elif rule == "navila":
                 plan = build_navila_splice_plan(ids, mask, labels, n_img_rows, n_feature_samples, max_length, padding_side)
             else:
                 plan = build_splice_plan(ids, mask, labels, n_img_rows, max_length, padding_side)

@@ -212,6 +212,36 @@ int dxa_downsample_layernorm_fwd(const void* x, const void* w, const void* b, vo
 int dxa_downsample_layernorm_bwd(const void* dy, const void* x, const void* w, const float* mean, const float* rstd,
                                  void* dx, float* partial_dwdb, int64_t N, int64_t G, int64_t C, int dtype, int w_dtype,
                                  dxa_stream_t stream);
+/* OFT policy (dexbotic/model/oft/oft_arch.py).  `off` [B] int64 on the device: the un-padded length of each sample's spliced rows,
+ * i.e. the first row of its block of skip + n_query rows in a [B, Sq, d] tensor.  A sample whose block does not lie inside [0, Sq)
+ * is left alone by every kernel below (no access outside the tensor).
+ *
+ * dxa_action_put_fwd: insert_action_embedding (oft_arch.py:169-201) into rows the splice kernel reserved (zero filled):
+ * x[b, off[b] + skip + j, :] = query[j, :] for j < n_query (action_query.expand over the batch, :105; `query` in `q_dtype`: the
+ * dtype of x or fp32); with `state` [B, d] (the proprio projector's row, :118-121) skip = 1 and x[b, off[b], :] = state[b, :],
+ * else skip = 0.  Nothing else is written.
+ * dxa_action_put_bwd: dquery[j, :] (+)= sum_b dx[b, off[b] + skip + j, :] (fp32, the samples in ascending order; `accumulate`: added
+ * to what dquery holds, else replaced); dstate[b, :] = dx[b, off[b], :] (dtype of dx; NULL: not wanted). */
+int dxa_action_put_fwd(void* x, const void* query, const void* state, const int64_t* off, int64_t B, int64_t Sq, int64_t d,
+                       int64_t n_query, int dtype, int q_dtype, dxa_stream_t stream);
+int dxa_action_put_bwd(const void* dx, const int64_t* off, float* dquery, void* dstate, int64_t B, int64_t Sq, int64_t d,
+                       int64_t n_query, int skip, int accumulate, int dtype, dxa_stream_t stream);
+/* extract_action_hidden_states (oft_arch.py:203-210, [:, 1:] with proprio :139-140) + reshape(B, T, A*d)
+ * (oft/action_model/model.py:158) + MLPResNet.layer_norm1 (:108,119) in one launch per direction.  Row (b, t) is the A*d contiguous
+ * elements from h[b, off[b] + skip + t*A, 0] of the decoder output h [B, Sq, d]; y [B*T, A*d]; mean / rstd [B*T] as
+ * dxa_layernorm_fwd writes them (rows of up to 4096 columns: its summation order, hence its bits).
+ * bwd writes dh [B, Sq, d] COMPLETELY (dx on the action rows, zero on every other row) and partial dw | db
+ * [dxa_action_layernorm_bwd_blocks(B*T), 2*A*d] fp32, folded by dxa_colsum. */
+int dxa_action_layernorm_fwd(const void* h, const int64_t* off, const void* w, const void* b, void* y, float* mean, float* rstd,
+                             int64_t B, int64_t Sq, int64_t d, int64_t T, int64_t A, int skip, float eps, int dtype, int w_dtype,
+                             dxa_stream_t stream);
+int dxa_action_layernorm_bwd(const void* dy, const void* h, const int64_t* off, const void* w, const float* mean, const float* rstd,
+                             void* dh, float* partial_dwdb, int64_t B, int64_t Sq, int64_t d, int64_t T, int64_t A, int skip,
+                             int dtype, int w_dtype, dxa_stream_t stream);
+int dxa_action_layernorm_bwd_blocks(int64_t rows);
+/* loss = mean(|pred - target|) (torch.nn.L1Loss(), oft_arch.py:152); dpred = sign(pred - target) / n * gscale with sign(0) = 0
+ * (NULL: not wanted).  One workgroup, fixed reduction tree. */
+int dxa_l1_loss(const float* pred, const float* target, float* loss, float* dpred, int64_t n, float gscale, dxa_stream_t stream);
 /* Adaptive RMSNorm and gated residual of the pi0.5 action expert (dexbotic/model/pi05/transformers_pi05/gemma/modeling_gemma.py:
  * 38-120): no gain, a per-SAMPLE modulation mod [B, 3*cols] = [scale | shift | gate] in `dtype` (fp32 or bf16, like every row
  * tensor here).  Row `i` of the [rows, cols] tensors belongs to sample i / rows_per_sample (rows % rows_per_sample == 0).  All
