@@ -34,6 +34,7 @@ def model_registry():
     from .model.memvla.memvla_arch import MemVLAConfig, MemVLAForCausalLM
     from .model.navila.navila_arch import NaVILAConfig, NaVILAForCausalLM
     from .model.oft.oft_arch import OFTConfig, OFTForCausalLM
+    from .model.oft.oft_discrete_arch import OFTDiscreteConfig, OFTDiscreteForCausalLM
     from .model.pi0.pi0_arch import Pi0Config, Pi0ForCausalLM
     from .model.pi05.pi05_arch import Pi05Config, Pi05ForCausalLM
     return {"dexbotic": (DexboticConfig, DexboticForCausalLM),
@@ -43,13 +44,17 @@ def model_registry():
             "dexbotic_navila": (NaVILAConfig, NaVILAForCausalLM),
             "dexbotic_dm0": (DM0Config, DM0ForCausalLM),
             "dexbotic_pi05": (Pi05Config, Pi05ForCausalLM),
-            "dexbotic_oft": (OFTConfig, OFTForCausalLM)}
+            "dexbotic_oft": (OFTConfig, OFTForCausalLM),
+            "dexbotic_oft_discrete": (OFTDiscreteConfig, OFTDiscreteForCausalLM)}
 
 
 def __getattr__(name):
     if name in ("Pi05Config", "Pi05ForCausalLM", "Pi05Model"):
         from .model import pi05
         return getattr(pi05, name)
+    if name in ("OFTDiscreteConfig", "OFTDiscreteForCausalLM", "OFTDiscreteModel"):
+        from .model import oft
+        return getattr(oft, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

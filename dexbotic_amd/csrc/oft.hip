@@ -39,9 +39,11 @@ __device__ __forceinline__ int64_t block_start(const int64_t* __restrict__ off, 
 
 // ------------------------------------------------------------------------------------------------ action_put
 // one workgroup per (sample, block row): row 0 of a block with `skip` is the sample's state row, the rest the shared query rows
+// (`qstride` = d), or one shared row for all of them (action_fill: `qstride` = 0)
 template <typename T, typename TQ, int VEC>
 __global__ __launch_bounds__(256) void action_put_fwd_k(T* __restrict__ x, const TQ* __restrict__ query, const T* __restrict__ state,
-                                                        const int64_t* __restrict__ off, int64_t Sq, int64_t d, int64_t nq, int skip) {
+                                                        const int64_t* __restrict__ off, int64_t Sq, int64_t d, int64_t nq, int skip,
+                                                        int64_t qstride) {
   const int64_t Q = nq + skip;
   const int64_t b = blockIdx.x / Q, j = blockIdx.x - b * Q;
   const int64_t o = block_start(off, b, Q, Sq);
@@ -56,7 +58,7 @@ __global__ __launch_bounds__(256) void action_put_fwd_k(T* __restrict__ x, const
     }
     return;
   }
-  const TQ* qr = query + (j - skip) * d;
+  const TQ* qr = query + (j - skip) * qstride;
   for (int64_t c = (int64_t)threadIdx.x * VEC; c < d; c += 256 * VEC) {
     float v[VEC];
     ldv<TQ, VEC>(v, qr + c);
@@ -398,7 +400,7 @@ extern "C" int dxa_action_put_fwd(void* x, const void* query, const void* state,
   const int vec = dtype == DXA_BF16 ? 8 : 4;
   const bool vec_ok = al16(x) && al16(query) && (!state || al16(state)) && d % vec == 0;
   dim3 grid((unsigned)(B * (n_query + skip)));
-#define PUT(T_, TQ_, V_) hipLaunchKernelGGL((action_put_fwd_k<T_, TQ_, V_>), grid, dim3(256), 0, st, (T_*)x, (const TQ_*)query, (const T_*)state, off, Sq, d, n_query, skip)
+#define PUT(T_, TQ_, V_) hipLaunchKernelGGL((action_put_fwd_k<T_, TQ_, V_>), grid, dim3(256), 0, st, (T_*)x, (const TQ_*)query, (const T_*)state, off, Sq, d, n_query, skip, d)
   if (dtype == DXA_BF16 && q_dtype == DXA_BF16) { if (vec_ok) PUT(bf16_t, bf16_t, 8); else PUT(bf16_t, bf16_t, 1); }
   else if (dtype == DXA_BF16) { if (vec_ok) PUT(bf16_t, float, 8); else PUT(bf16_t, float, 1); }
   else { if (vec_ok) PUT(float, float, 4); else PUT(float, float, 1); }
@@ -519,6 +521,414 @@ extern "C" int dxa_l1_loss(const float* pred, const float* target, float* loss, 
                            dxa_stream_t stream) {
   DXA_CHECK_ARG(pred && target && loss && n > 0, "dxa_l1_loss: bad args (null pred / target / loss, or n <= 0)");
   hipLaunchKernelGGL(l1_loss_k, dim3(1), dim3(1024), 0, (hipStream_t)stream, pred, target, loss, dpred, n, gscale);
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
+}
+
+// ================================================================================================ OFT-discrete
+// (dexbotic/model/oft/oft_discrete_arch.py): the action rows as the dense operand of the lm_head product, the shared embedding row
+// written into the reserved rows, and the inference head over the last num_bins - 1 rows of lm_head.weight.
+namespace {
+
+// ------------------------------------------------------------------------------------------------ action_rows
+// one workgroup per action row: y[b*R + j] = h[b, off[b] + skip + j], zeros for a sample whose block is out of range
+template <typename T, int VEC>
+__global__ __launch_bounds__(256) void action_rows_fwd_k(const T* __restrict__ h, const int64_t* __restrict__ off, T* __restrict__ y,
+                                                         int64_t Sq, int64_t d, int64_t R, int skip) {
+  const int64_t b = blockIdx.x / R, j = blockIdx.x - b * R;
+  const int64_t o = block_start(off, b, R + skip, Sq);
+  const T* hr = h + ((b * Sq + (o < 0 ? 0 : o + skip + j)) * d);
+  T* yr = y + (int64_t)blockIdx.x * d;
+  for (int64_t c = (int64_t)threadIdx.x * VEC; c < d; c += 256 * VEC) {
+    float v[VEC];
+    if (o >= 0) {
+      ldv<T, VEC>(v, hr + c);
+    } else {
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) v[i] = 0.f;
+    }
+    stv<T, VEC>(yr + c, v);
+  }
+}
+
+// every row of dh, the workgroups striding over them: the dy row on an action row, zero elsewhere
+template <typename T, int VEC>
+__global__ __launch_bounds__(256) void action_rows_bwd_k(const T* __restrict__ dy, const int64_t* __restrict__ off, T* __restrict__ dh,
+                                                         int64_t B, int64_t Sq, int64_t d, int64_t R, int skip) {
+  for (int64_t r = blockIdx.x; r < B * Sq; r += gridDim.x) {
+    const int64_t b = r / Sq, p = r - b * Sq;
+    const int64_t o = block_start(off, b, R + skip, Sq);
+    const bool act = o >= 0 && p >= o + skip && p < o + skip + R;          // (uniform over the workgroup)
+    const T* src = dy + (act ? (b * R + (p - o - skip)) * d : 0);
+    T* dst = dh + r * d;
+    for (int64_t c = (int64_t)threadIdx.x * VEC; c < d; c += 256 * VEC) {
+      float v[VEC];
+      if (act) {
+        ldv<T, VEC>(v, src + c);
+      } else {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) v[i] = 0.f;
+      }
+      stv<T, VEC>(dst + c, v);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ action_fill (backward)
+constexpr int FILL_CHUNK = 16;      // action rows summed by one workgroup of the first stage
+
+// stage 1, grid (column blocks, chunks [+ B]): workgroup (x, g < chunks) sums the dx rows of the action rows g*16 ... g*16 + 15
+// (numbered b*R + j, ascending; the rows of an out-of-range sample contribute nothing) into partial[g, its columns];
+// workgroup (x, chunks + b): the state row's gradient of sample b
+template <typename T, int VEC>
+__global__ __launch_bounds__(256) void action_fill_bwd_part_k(const T* __restrict__ dx, const int64_t* __restrict__ off,
+                                                              float* __restrict__ partial, T* __restrict__ dstate, int64_t B,
+                                                              int64_t Sq, int64_t d, int64_t R, int skip, int64_t chunks) {
+  const int64_t c = ((int64_t)blockIdx.x * 256 + threadIdx.x) * VEC;
+  if (c >= d) return;
+  const int64_t g = blockIdx.y;
+  if (g >= chunks) {
+    const int64_t b = g - chunks;
+    const int64_t o = block_start(off, b, R + skip, Sq);
+    float v[VEC];
+    if (o >= 0) {
+      ldv<T, VEC>(v, dx + ((b * Sq + o) * d + c));
+    } else {
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) v[i] = 0.f;
+    }
+    stv<T, VEC>(dstate + b * d + c, v);
+    return;
+  }
+  float s[VEC];
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) s[i] = 0.f;
+  const int64_t r1 = (g + 1) * FILL_CHUNK < B * R ? (g + 1) * FILL_CHUNK : B * R;
+  for (int64_t r = g * FILL_CHUNK; r < r1; ++r) {
+    const int64_t b = r / R, j = r - b * R;
+    const int64_t o = block_start(off, b, R + skip, Sq);
+    if (o < 0) continue;
+    float v[VEC];
+    ldv<T, VEC>(v, dx + ((b * Sq + o + skip + j) * d + c));
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) s[i] += v[i];
+  }
+  stv<float, VEC>(partial + g * d + c, s);
+}
+
+// stage 2: drow (+)= the chunks' partial rows in ascending order
+template <int VEC>
+__global__ __launch_bounds__(256) void action_fill_bwd_fold_k(const float* __restrict__ partial, float* __restrict__ drow, int64_t d,
+                                                              int64_t chunks, int accumulate) {
+  const int64_t c = ((int64_t)blockIdx.x * 256 + threadIdx.x) * VEC;
+  if (c >= d) return;
+  float s[VEC];
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) s[i] = 0.f;
+  for (int64_t g = 0; g < chunks; ++g) {
+    float v[VEC];
+    ldv<float, VEC>(v, partial + g * d + c);
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) s[i] += v[i];
+  }
+  if (accumulate) {
+    float old[VEC];
+    ldv<float, VEC>(old, drow + c);
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) s[i] = old[i] + s[i];
+  }
+  stv<float, VEC>(drow + c, s);
+}
+
+// ------------------------------------------------------------------------------------------------ action_bins
+// Workgroup (row group rg, bin group bg) computes TM x TM tiles of 16 x 16: logits[(rg*TM + m)*16 .., (bg*TM + n)*16 ..] = H W^T with
+// MFMA fragments loaded straight from global memory (no operand is shared between the waves: an LDS stage would be a round trip for
+// nothing): lane (r = lane & 15, q = lane >> 4) holds k-group q of action row r of each row tile (A) and of bin row r of each bin
+// tile (B).  bf16: 8 consecutive k per lane, one v_mfma_f32_16x16x32_bf16 per 32 k.  fp32: 4 consecutive k per lane, element i of
+// both operands goes to the i-th of four v_mfma_f32_16x16x4_f32 (the k order inside a step is permuted the same way on both sides).
+// The 4 waves take the k-steps w, w + 4, ... in ascending order; their partial tiles are added in the order ((0 + 1) + 2) + 3
+// through LDS, rounded once and stored: an element's bits do not depend on TM.  TM = 1 spreads a single request's 112 rows over
+// 7 x 16 workgroups; TM = 2 halves the operand bytes each workgroup pulls through its L1 per output, for the large batches.
+// The bin groups of one row group then meet at a counter (agent-scope release by every workgroup, acquire by the one that draws
+// the last ticket, which nobody waits for): that workgroup reads the finished logit rows back and writes bin and action.
+template <typename T, int TM>
+__global__ __launch_bounds__(256) void action_bins_k(const T* __restrict__ h, const int64_t* __restrict__ off, const T* __restrict__ w,
+                                                     T* __restrict__ logits, int64_t* __restrict__ bin, float* __restrict__ action,
+                                                     int* __restrict__ cnt, int64_t rows, int64_t Sq, int64_t d, int64_t R, int skip,
+                                                     int NB, int nbg) {
+  constexpr int KL = sizeof(T) == 2 ? 8 : 4;        // k per lane and step
+  constexpr int KS = 4 * KL;                        // k per step
+  constexpr int NT = TM * TM;                       // tiles per workgroup
+  constexpr int FLAG = 4 * NT * 16 * 17;
+  __shared__ float red[FLAG + 1];                   // per wave NT partial tiles of 16 x 16 (rows padded to 17), and the "last ticket" word
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int lr = lane & 15, lq = lane >> 4;
+  const int64_t rg = blockIdx.x / nbg;
+  const int bg = (int)(blockIdx.x - rg * nbg);
+  // operand rows of this lane; a lane without one reads row 0 (always there) and its values are replaced by zeros
+  const T* hp[TM];
+  const T* wp[TM];
+  bool a_ok[TM], b_ok[TM];
+#pragma unroll
+  for (int m = 0; m < TM; ++m) {
+    const int64_t arow = (rg * TM + m) * 16 + lr;
+    a_ok[m] = arow < rows;
+    hp[m] = h;
+    if (a_ok[m]) {
+      const int64_t b = arow / R, j = arow - b * R;
+      const int64_t o = block_start(off, b, R + skip, Sq);
+      a_ok[m] = o >= 0;
+      if (a_ok[m]) hp[m] = h + (b * Sq + o + skip + j) * d;
+    }
+    const int n_l = (bg * TM + m) * 16 + lr;
+    b_ok[m] = n_l < NB;
+    wp[m] = w + (b_ok[m] ? (int64_t)n_l * d : 0);
+  }
+  f32x4_t acc[TM][TM];
+#pragma unroll
+  for (int m = 0; m < TM; ++m)
+#pragma unroll
+    for (int n = 0; n < TM; ++n) acc[m][n] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  const uint4 z4 = make_uint4(0, 0, 0, 0);
+  // 16 bytes of each operand at element k of the lane's rows (`ok` false: k is past the row, nothing is read there)
+  auto load = [&](int64_t k, bool ok, uint4 (&a)[TM], uint4 (&bb)[TM]) {
+#pragma unroll
+    for (int m = 0; m < TM; ++m) {
+      a[m] = *reinterpret_cast<const uint4*>(hp[m] + (ok ? k : 0));
+      bb[m] = *reinterpret_cast<const uint4*>(wp[m] + (ok ? k : 0));
+      if (!(a_ok[m] && ok)) a[m] = z4;
+      if (!(b_ok[m] && ok)) bb[m] = z4;
+    }
+  };
+  auto mma = [&](const uint4 (&a)[TM], const uint4 (&bb)[TM]) {
+#pragma unroll
+    for (int m = 0; m < TM; ++m)
+#pragma unroll
+      for (int n = 0; n < TM; ++n) {
+        if constexpr (sizeof(T) == 2) {
+          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a[m]), __builtin_bit_cast(bf16x8_t, bb[n]),
+                                                              acc[m][n], 0, 0, 0);
+        } else {
+          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[m].x), __uint_as_float(bb[n].x), acc[m][n], 0, 0, 0);
+          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[m].y), __uint_as_float(bb[n].y), acc[m][n], 0, 0, 0);
+          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[m].z), __uint_as_float(bb[n].z), acc[m][n], 0, 0, 0);
+          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[m].w), __uint_as_float(bb[n].w), acc[m][n], 0, 0, 0);
+        }
+      }
+  };
+  const int64_t d_full = d / KS * KS;
+  int64_t k0 = (int64_t)wv * KS;
+  constexpr int U = 4;                              // steps whose loads are issued together
+  for (; k0 + (U - 1) * 4 * KS < d_full; k0 += U * 4 * KS) {
+    uint4 a[U][TM], bb[U][TM];
+#pragma unroll
+    for (int u = 0; u < U; ++u) load(k0 + u * 4 * KS + lq * KL, true, a[u], bb[u]);
+#pragma unroll
+    for (int u = 0; u < U; ++u) mma(a[u], bb[u]);
+  }
+  for (; k0 < d_full; k0 += 4 * KS) {
+    uint4 a[TM], bb[TM];
+    load(k0 + lq * KL, true, a, bb);
+    mma(a, bb);
+  }
+  if (k0 < d) {                                     // the tail step (d % KL == 0: a lane's group lies inside the row or outside)
+    uint4 a[TM], bb[TM];
+    load(k0 + lq * KL, k0 + lq * KL < d, a, bb);
+    mma(a, bb);
+  }
+  // C/D fragment: column (bin) = lane & 15, row (action row) = 4 * (lane >> 4) + i
+#pragma unroll
+  for (int m = 0; m < TM; ++m)
+#pragma unroll
+    for (int n = 0; n < TM; ++n)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) red[((wv * NT + m * TM + n) * 16 + 4 * lq + i) * 17 + lr] = acc[m][n][i];
+  __syncthreads();
+#pragma unroll
+  for (int m = 0; m < TM; ++m)
+#pragma unroll
+    for (int n = 0; n < TM; ++n) {
+      const int row = tid >> 4, col = tid & 15;
+      const int e = ((m * TM + n) * 16 + row) * 17 + col;
+      const float s = ((red[e] + red[NT * 272 + e]) + red[2 * NT * 272 + e]) + red[3 * NT * 272 + e];
+      const int64_t r = (rg * TM + m) * 16 + row;
+      const int nn = (bg * TM + n) * 16 + col;
+      if (r < rows && nn < NB) stf<T>(logits + r * NB + nn, s);
+    }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const int ticket = __hip_atomic_fetch_add(cnt + rg, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool last = ticket == nbg - 1;
+    if (last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    red[FLAG] = last ? 1.f : 0.f;
+  }
+  __syncthreads();
+  if (red[FLAG] == 0.f) return;
+  // the first index of the row's maximum (a NaN counts as the maximum, as in torch.argmax): 16 lanes per row
+  auto better = [](float v, int i, float bv, int bj) {
+    const bool vn = v != v, bn = bv != bv;
+    const bool gt = (vn && !bn) || (!vn && !bn && v > bv);
+    const bool eq = (vn && bn) || v == bv;
+    return gt || (eq && i < bj);
+  };
+#pragma unroll
+  for (int m = 0; m < TM; ++m) {
+    const int64_t r = (rg * TM + m) * 16 + (tid >> 4);
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    if (r < rows) {
+      for (int n = tid & 15; n < NB; n += 16) {
+        const float v = ldf<T>(logits + r * NB + n);
+        if (better(v, n, best, bi)) { best = v; bi = n; }
+      }
+    }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(best, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (better(ov, oi, best, bi)) { best = ov; bi = oi; }
+    }
+    if (r < rows && (tid & 15) == 0) {
+      bin[r] = bi;
+      action[r] = ((float)bi / (float)NB) * 2.f - 1.f;
+    }
+  }
+}
+
+constexpr int64_t ACTION_BINS_WIDE_MIN_TILES = 1024;   // 16 x 16 output tiles from which a workgroup takes 2 x 2 of them
+
+}  // namespace
+
+extern "C" int dxa_action_rows_fwd(const void* h, const int64_t* off, void* y, int64_t B, int64_t Sq, int64_t d, int64_t n_rows,
+                                   int skip, int dtype, dxa_stream_t stream) {
+  if (int rc = check_action_dtypes("dxa_action_rows_fwd", dtype, dtype)) return rc;
+  DXA_CHECK_ARG(h && off && y, "dxa_action_rows_fwd: null h / off / y");
+  if (int rc = check_action_sizes("dxa_action_rows_fwd", B, Sq, d, n_rows, 1, skip)) return rc;
+  if (B == 0) return DXA_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int vec = dtype == DXA_BF16 ? 8 : 4;
+  const bool vec_ok = al16(h) && al16(y) && d % vec == 0;
+  dim3 grid((unsigned)(B * n_rows));
+#define ROWS(T_, V_) hipLaunchKernelGGL((action_rows_fwd_k<T_, V_>), grid, dim3(256), 0, st, (const T_*)h, off, (T_*)y, Sq, d, n_rows, skip)
+  if (dtype == DXA_BF16) { if (vec_ok) ROWS(bf16_t, 8); else ROWS(bf16_t, 1); }
+  else { if (vec_ok) ROWS(float, 4); else ROWS(float, 1); }
+#undef ROWS
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
+}
+
+extern "C" int dxa_action_rows_bwd(const void* dy, const int64_t* off, void* dh, int64_t B, int64_t Sq, int64_t d, int64_t n_rows,
+                                   int skip, int dtype, dxa_stream_t stream) {
+  if (int rc = check_action_dtypes("dxa_action_rows_bwd", dtype, dtype)) return rc;
+  DXA_CHECK_ARG(dy && off && dh, "dxa_action_rows_bwd: null dy / off / dh");
+  if (int rc = check_action_sizes("dxa_action_rows_bwd", B, Sq, d, n_rows, 1, skip)) return rc;
+  if (B == 0) return DXA_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int vec = dtype == DXA_BF16 ? 8 : 4;
+  const bool vec_ok = al16(dy) && al16(dh) && d % vec == 0;
+  dim3 grid((unsigned)dxa_grid1d(B * Sq, 1, 256 * 8));
+#define ROWSB(T_, V_) hipLaunchKernelGGL((action_rows_bwd_k<T_, V_>), grid, dim3(256), 0, st, (const T_*)dy, off, (T_*)dh, B, Sq, d, n_rows, skip)
+  if (dtype == DXA_BF16) { if (vec_ok) ROWSB(bf16_t, 8); else ROWSB(bf16_t, 1); }
+  else { if (vec_ok) ROWSB(float, 4); else ROWSB(float, 1); }
+#undef ROWSB
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
+}
+
+extern "C" int dxa_action_fill_fwd(void* x, const void* row, const void* state, const int64_t* off, int64_t B, int64_t Sq, int64_t d,
+                                   int64_t n_rows, int dtype, int row_dtype, dxa_stream_t stream) {
+  if (int rc = check_action_dtypes("dxa_action_fill_fwd", dtype, row_dtype == DXA_F32 ? DXA_F32 : dtype)) return rc;
+  DXA_CHECK_ARG(row_dtype == DXA_F32 || row_dtype == dtype, "dxa_action_fill_fwd: the row is fp32 or in the dtype of x (%d,%d)", dtype, row_dtype);
+  DXA_CHECK_ARG(x && row && off, "dxa_action_fill_fwd: null x / row / off");
+  const int skip = state ? 1 : 0;
+  if (int rc = check_action_sizes("dxa_action_fill_fwd", B, Sq, d, n_rows, 1, skip)) return rc;
+  if (B == 0) return DXA_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int vec = dtype == DXA_BF16 ? 8 : 4;
+  const bool vec_ok = al16(x) && al16(row) && (!state || al16(state)) && d % vec == 0;
+  dim3 grid((unsigned)(B * (n_rows + skip)));
+#define FILL(T_, TQ_, V_) hipLaunchKernelGGL((action_put_fwd_k<T_, TQ_, V_>), grid, dim3(256), 0, st, (T_*)x, (const TQ_*)row, (const T_*)state, off, Sq, d, n_rows, skip, (int64_t)0)
+  if (dtype == DXA_BF16 && row_dtype == DXA_BF16) { if (vec_ok) FILL(bf16_t, bf16_t, 8); else FILL(bf16_t, bf16_t, 1); }
+  else if (dtype == DXA_BF16) { if (vec_ok) FILL(bf16_t, float, 8); else FILL(bf16_t, float, 1); }
+  else { if (vec_ok) FILL(float, float, 4); else FILL(float, float, 1); }
+#undef FILL
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
+}
+
+extern "C" int dxa_action_fill_bwd_blocks(int64_t rows) {
+  if (rows < 1) rows = 1;
+  return (int)((rows + FILL_CHUNK - 1) / FILL_CHUNK);
+}
+
+extern "C" int dxa_action_fill_bwd(const void* dx, const int64_t* off, float* drow, void* dstate, float* partial, int64_t B, int64_t Sq,
+                                   int64_t d, int64_t n_rows, int skip, int accumulate, int dtype, dxa_stream_t stream) {
+  if (int rc = check_action_dtypes("dxa_action_fill_bwd", dtype, dtype)) return rc;
+  DXA_CHECK_ARG(dx && off && drow && partial, "dxa_action_fill_bwd: null dx / off / drow / partial");
+  DXA_CHECK_ARG(!dstate || skip == 1, "dxa_action_fill_bwd: dstate without a state row (skip = 0)");
+  if (int rc = check_action_sizes("dxa_action_fill_bwd", B, Sq, d, n_rows, 1, skip)) return rc;
+  DXA_CHECK_ARG(B >= 1 && B <= 32767 && B * n_rows <= (1ll << 19),                 // (chunks + B workgroups along grid y)
+                "dxa_action_fill_bwd: B = %lld outside [1, 32767] or B * n_rows = %lld above 2^19", (long long)B, (long long)(B * n_rows));
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t chunks = dxa_action_fill_bwd_blocks(B * n_rows);
+  const int vec = dtype == DXA_BF16 ? 8 : 4;
+  const bool vec_ok = al16(dx) && al16(partial) && (!dstate || al16(dstate)) && d % vec == 0;
+  {
+    const int v = vec_ok ? vec : 1;
+    dim3 grid((unsigned)dxa_cdiv(d, 256 * v), (unsigned)(chunks + (dstate ? B : 0)));
+#define FILLB(T_, V_) hipLaunchKernelGGL((action_fill_bwd_part_k<T_, V_>), grid, dim3(256), 0, st, (const T_*)dx, off, partial, (T_*)dstate, B, Sq, d, n_rows, skip, chunks)
+    if (dtype == DXA_BF16) { if (vec_ok) FILLB(bf16_t, 8); else FILLB(bf16_t, 1); }
+    else { if (vec_ok) FILLB(float, 4); else FILLB(float, 1); }
+#undef FILLB
+    DXA_CHECK_LAUNCH();
+  }
+  const bool v4 = al16(partial) && al16(drow) && d % 4 == 0;
+  if (v4) hipLaunchKernelGGL((action_fill_bwd_fold_k<4>), dim3((unsigned)dxa_cdiv(d, 1024)), dim3(256), 0, st, partial, drow, d, chunks, accumulate);
+  else hipLaunchKernelGGL((action_fill_bwd_fold_k<1>), dim3((unsigned)dxa_cdiv(d, 256)), dim3(256), 0, st, partial, drow, d, chunks, accumulate);
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
+}
+
+extern "C" int dxa_action_bins_counters(int64_t rows) {
+  if (rows < 1) rows = 1;
+  return (int)(((rows + 15) / 16 + 3) / 4 * 4);
+}
+
+extern "C" int dxa_action_bins_fwd(const void* h, const int64_t* off, const void* w_bins, void* bin_logits, int64_t* bin, float* action,
+                                   int32_t* counters, int64_t B, int64_t Sq, int64_t d, int64_t n_rows, int skip, int64_t n_bins,
+                                   int dtype, dxa_stream_t stream) {
+  if (int rc = check_action_dtypes("dxa_action_bins_fwd", dtype, dtype)) return rc;
+  DXA_CHECK_ARG(h && off && w_bins && bin_logits && bin && action && counters,
+                "dxa_action_bins_fwd: null h / off / w_bins / bin_logits / bin / action / counters");
+  if (int rc = check_action_sizes("dxa_action_bins_fwd", B, Sq, d, n_rows, 1, skip)) return rc;
+  DXA_CHECK_ARG(n_bins >= 1 && n_bins <= (1 << 16), "dxa_action_bins_fwd: n_bins = %lld outside [1, 65536]", (long long)n_bins);
+  DXA_CHECK_ARG(B * n_rows <= (1ll << 24), "dxa_action_bins_fwd: B * n_rows = %lld above 2^24", (long long)(B * n_rows));
+  const int kl = dtype == DXA_BF16 ? 8 : 4;
+  if (d % kl != 0 || !al16(h) || !al16(w_bins) || (reinterpret_cast<uintptr_t>(counters) & 15) != 0) {
+    dxa_set_error("dxa_action_bins_fwd: d = %lld must be a multiple of %d and h / w_bins / counters 16-byte aligned (the MFMA operands "
+                  "are loaded 16 bytes per lane)", (long long)d, kl);
+    return DXA_ERR_UNSUPPORTED;
+  }
+  if (B == 0) return DXA_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t rows = B * n_rows;
+  const int64_t nbt = (n_bins + 15) / 16, rtiles = (rows + 15) / 16;
+  const int tm = rtiles * nbt >= ACTION_BINS_WIDE_MIN_TILES ? 2 : 1;
+  const int nbg = (int)((nbt + tm - 1) / tm);
+  const int64_t rgroups = (rtiles + tm - 1) / tm;
+  // the tickets of this call: zeroed on the stream ahead of the launch, every call
+  DXA_CHECK_HIP(hipMemsetAsync(counters, 0, (size_t)dxa_action_bins_counters(rows) * sizeof(int32_t), st));
+  dim3 grid((unsigned)(rgroups * nbg));
+#define BINS(T_, M_) hipLaunchKernelGGL((action_bins_k<T_, M_>), grid, dim3(256), 0, st, (const T_*)h, off, (const T_*)w_bins, (T_*)bin_logits, bin, action, (int*)counters, rows, Sq, d, n_rows, skip, (int)n_bins, nbg)
+  if (dtype == DXA_BF16) { if (tm == 2) BINS(bf16_t, 2); else BINS(bf16_t, 1); }
+  else { if (tm == 2) BINS(float, 2); else BINS(float, 1); }
+#undef BINS
   DXA_CHECK_LAUNCH();
   return DXA_OK;
 }

@@ -1029,9 +1029,12 @@ class SpliceFn(_StoreFn):
         return _splice_backward(ctx.st, ctx.embed_n, plan, dout.contiguous(), ctx.ishape, ctx.needs_input_grad[0]), None, None, None, None
 
 
-def _splice_backward(st: ParamStore, embed_n: str, plan: torch.Tensor, dout: torch.Tensor, ishape, want_img: bool):
-    """the splice's backward launches (SpliceFn, OftSpliceFn): the image rows' gradient, or None; the token rows' gradient is added
-    into the embedding's slot.  Rows the plan marks as padding (PLAN_PAD) are ignored."""
+def _splice_backward(st: ParamStore, embed_n: str, plan: torch.Tensor, dout: torch.Tensor, ishape, want_img: bool,
+                     extra_rows: Optional[torch.Tensor] = None, add_rows=None):
+    """the splice's backward launches (SpliceFn, OftSpliceFn, OftDiscreteSpliceFn): the image rows' gradient, or None; the token
+    rows' gradient is added into the embedding's slot.  Rows the plan marks as padding (PLAN_PAD) are ignored.
+    ``extra_rows`` (int64 token ids on the device) / ``add_rows(d_embed)``: embedding rows that receive a gradient from outside the
+    plan — they are re-zeroed with the plan's rows on the next step, and the add is enqueued before the slot is reported written."""
     d_img = None
     if want_img:
         d_img = torch.zeros(ishape, device=dout.device, dtype=dout.dtype)
@@ -1043,8 +1046,12 @@ def _splice_backward(st: ParamStore, embed_n: str, plan: torch.Tensor, dout: tor
             # the previous step touched when the store tracks them (single GPU), the whole slice otherwise
             st.zero_embed_grad(embed_n)
         st.note_embed_rows(embed_n, plan)
+        if extra_rows is not None:
+            st.note_embed_rows(embed_n, extra_rows)
     K.splice_bwd(plan, dout, d_embed, d_img)
     if d_embed is not None:
+        if add_rows is not None:
+            add_rows(d_embed)
         # AFTER the scatter-add is enqueued: embed_tokens is alone in its bucket, so this fires the reducer / the
         # grad-norm fold, which order themselves after everything enqueued so far on this stream
         st.mark_written(embed_n)
@@ -1088,6 +1095,67 @@ class OftSpliceFn(_StoreFn):
                 st.mark_written(ctx.query_n)
         d_img = _splice_backward(st, ctx.embed_n, plan, dout, ctx.ishape, ctx.needs_input_grad[0])
         return d_img, dstate, None, None, None, None, None, None, None, None
+
+
+class OftDiscreteSpliceFn(_StoreFn):
+    """SpliceFn followed by the discrete head's ``insert_action_embedding`` (dexbotic/model/oft/oft_discrete_arch.py:125-143) on the
+    SAME buffer: ``action_query`` is ``torch.ones(1, T A)`` used as token ids, so every one of the R = T A query rows of every sample
+    is the embedding row of token ``token_rows[0]`` (= 1).  dxa_action_fill_fwd writes that row (and the sample's state row) into the
+    rows the plan reserved.  The token is NOT put into the plan: dxa_splice_bwd would add the B R duplicate rows serially.
+    Backward: the fixed-order sum of the R rows' gradients over the batch (dxa_action_fill_bwd) is added onto the token's row of the
+    embedding gradient after the splice's own scatter-add and before the slot is reported written; ``token_rows`` (int64 [1] on the
+    device) joins the rows that are re-zeroed on the next step."""
+
+    @staticmethod
+    def forward(ctx, img_feats, state, anchor, st: ParamStore, embed_n: str, token: int, token_rows: torch.Tensor,
+                plan: torch.Tensor, off: torch.Tensor, B: int, Sq: int, n_rows: int):
+        d = img_feats.shape[-1]
+        embed = st.w(embed_n)
+        out = K.splice_fwd(plan, embed, img_feats.reshape(-1, d).contiguous())
+        K.action_fill_(out.view(B, Sq, d), embed[token], off, n_rows, None if state is None else state.contiguous())
+        ctx.st, ctx.embed_n, ctx.token, ctx.ishape, ctx.geom = st, embed_n, token, img_feats.shape, (B, Sq, d, n_rows)
+        ctx.has_state = state is not None
+        _use(ctx, st, embed_n)
+        ctx.save_for_backward(plan, off, token_rows)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        st = ctx.st
+        plan, off, token_rows = ctx.saved_tensors
+        B, Sq, d, n_rows = ctx.geom
+        dout = dout.contiguous()
+        want_state = ctx.has_state and ctx.needs_input_grad[1]
+        got = {}
+
+        def add_rows(d_embed):
+            _, got["dstate"] = K.action_fill_bwd(dout.view(B, Sq, d), off, n_rows, ctx.has_state, drow=d_embed[ctx.token],
+                                                 accumulate=True, want_dstate=want_state)
+
+        d_img = _splice_backward(st, ctx.embed_n, plan, dout, ctx.ishape, ctx.needs_input_grad[0], extra_rows=token_rows,
+                                 add_rows=add_rows)
+        if want_state and "dstate" not in got:            # frozen embedding: only the state rows' gradient is wanted
+            _, got["dstate"] = K.action_fill_bwd(dout.view(B, Sq, d), off, n_rows, True, want_dstate=True)
+        return (d_img, got.get("dstate")) + (None,) * 10
+
+
+class ActionRowsFn(Function):
+    """``extract_action_hidden_states`` (+ ``[:, 1:]`` with proprio; oft_discrete_arch.py:157-162) as the dense [B R, d] operand of the
+    lm_head product, one launch per direction.  The backward writes the whole gradient of h (zero off the action rows): the head is
+    the only consumer of the decoder output in this policy."""
+
+    @staticmethod
+    def forward(ctx, h, off: torch.Tensor, n_rows: int, skip: bool):
+        h = h.contiguous()
+        ctx.geom = (h.shape[0], h.shape[1], n_rows, skip)
+        ctx.save_for_backward(off)
+        return K.action_rows_fwd(h, off, n_rows, skip)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (off,) = ctx.saved_tensors
+        B, Sq, n_rows, skip = ctx.geom
+        return K.action_rows_bwd(dy.contiguous(), off, B, Sq, n_rows, skip), None, None, None
 
 
 class ActionNormFn(_StoreFn):

@@ -735,6 +735,73 @@ def l1_loss(pred, target, gscale: float = 1.0, want_grad: bool = True):
     return loss, dpred
 
 
+def action_rows_fwd(h: torch.Tensor, off: torch.Tensor, n_rows: int, skip: bool) -> torch.Tensor:
+    """h [B, Sq, d] -> y [B * n_rows, d]: y[b * n_rows + j] = h[b, off[b] + skip + j]; zero rows for an out-of-range sample"""
+    B, Sq, d = h.shape
+    assert h.is_contiguous()
+    y = torch.empty((B * n_rows, d), device=h.device, dtype=h.dtype)
+    L.check(lib.dxa_action_rows_fwd(_ptr(h), _ptr(_action_off(off, B)), _ptr(y), B, Sq, d, n_rows, int(skip), dt(h), _stream()),
+            "dxa_action_rows_fwd")
+    return y
+
+
+def action_rows_bwd(dy: torch.Tensor, off: torch.Tensor, B: int, Sq: int, n_rows: int, skip: bool,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dy [B * n_rows, d] -> dh [B, Sq, d], every element written: the dy rows on the action rows, zero elsewhere"""
+    d = dy.shape[-1]
+    assert dy.is_contiguous() and dy.numel() == B * n_rows * d
+    dh = torch.empty((B, Sq, d), device=dy.device, dtype=dy.dtype) if out is None else out
+    assert dh.shape == (B, Sq, d) and dh.dtype == dy.dtype and dh.is_contiguous()
+    L.check(lib.dxa_action_rows_bwd(_ptr(dy), _ptr(_action_off(off, B)), _ptr(dh), B, Sq, d, n_rows, int(skip), dt(dy), _stream()),
+            "dxa_action_rows_bwd")
+    return dh
+
+
+def action_fill_(x: torch.Tensor, row: torch.Tensor, off: torch.Tensor, n_rows: int, state: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [B, Sq, d] in place: x[b, off[b] + s + j] = row for j < n_rows (row [d] in x's dtype or fp32); with ``state`` [B, d]:
+    x[b, off[b]] = state[b] and s = 1, else s = 0"""
+    B, Sq, d = x.shape
+    assert x.is_contiguous() and row.is_contiguous() and row.numel() == d
+    if state is not None:
+        assert state.is_contiguous() and state.shape == (B, d) and state.dtype == x.dtype
+    L.check(lib.dxa_action_fill_fwd(_ptr(x), _ptr(row), _ptr(state), _ptr(_action_off(off, B)), B, Sq, d, n_rows, dt(x), dt(row),
+                                    _stream()), "dxa_action_fill_fwd")
+    return x
+
+
+def action_fill_bwd(dx: torch.Tensor, off: torch.Tensor, n_rows: int, skip: bool, drow: Optional[torch.Tensor] = None,
+                    accumulate: bool = False, want_dstate: bool = False):
+    """-> (drow [d] fp32 = sum over every sample's action rows of dx, in a fixed order, written to / accumulated into ``drow`` when
+    given; dstate [B, d] in dx's dtype or None)"""
+    B, Sq, d = dx.shape
+    assert dx.is_contiguous()
+    if drow is None:
+        drow = torch.empty(d, device=dx.device, dtype=torch.float32)
+        accumulate = False
+    assert drow.dtype == torch.float32 and drow.is_contiguous() and drow.numel() == d
+    dstate = torch.empty((B, d), device=dx.device, dtype=dx.dtype) if (want_dstate and skip) else None
+    partial = torch.empty((int(lib.dxa_action_fill_bwd_blocks(B * n_rows)), d), device=dx.device, dtype=torch.float32)
+    L.check(lib.dxa_action_fill_bwd(_ptr(dx), _ptr(_action_off(off, B)), _ptr(drow), _ptr(dstate), _ptr(partial), B, Sq, d, n_rows,
+                                    int(skip), int(accumulate), dt(dx), _stream()), "dxa_action_fill_bwd")
+    return drow, dstate
+
+
+def action_bins_fwd(h: torch.Tensor, off: torch.Tensor, w_bins: torch.Tensor, n_rows: int, skip: bool):
+    """h [B, Sq, d], w_bins [NB, d] (contiguous rows: the tail of lm_head.weight) -> (bin_logits [B * n_rows, NB] in h's dtype,
+    bin int64 [B * n_rows] = first index of the row's maximum, action fp32 [B * n_rows] = bin / NB * 2 - 1).  Semantics:
+    include/dexbotic_amd.h"""
+    B, Sq, d = h.shape
+    assert h.is_contiguous() and w_bins.is_contiguous() and w_bins.dim() == 2 and w_bins.shape[1] == d and w_bins.dtype == h.dtype
+    NB, rows = w_bins.shape[0], B * n_rows
+    logits = torch.empty((rows, NB), device=h.device, dtype=h.dtype)
+    bins = torch.empty(rows, device=h.device, dtype=torch.int64)
+    action = torch.empty(rows, device=h.device, dtype=torch.float32)
+    counters = torch.empty(int(lib.dxa_action_bins_counters(rows)), device=h.device, dtype=torch.int32)
+    L.check(lib.dxa_action_bins_fwd(_ptr(h), _ptr(_action_off(off, B)), _ptr(w_bins), _ptr(logits), _ptr(bins), _ptr(action),
+                                    _ptr(counters), B, Sq, d, n_rows, int(skip), NB, dt(h), _stream()), "dxa_action_bins_fwd")
+    return logits, bins, action
+
+
 def colsum(x: torch.Tensor, out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
     """out[c] (+)= sum_r x[r, c]  (fp32 result)"""
     ld = _row_major(x, "x")

@@ -15,7 +15,7 @@ def __getattr__(name):
     if name in ("Pi05Config", "Pi05ForCausalLM", "Pi05Model"):
         from . import pi05
         return getattr(pi05, name)
-    if name in ("OFTConfig", "OFTForCausalLM", "OFTModel"):
+    if name in ("OFTConfig", "OFTForCausalLM", "OFTModel", "OFTDiscreteConfig", "OFTDiscreteForCausalLM", "OFTDiscreteModel"):
         from . import oft
         return getattr(oft, name)
     if name in ("PerceptionEncoderConfig", "PEVisionTower"):
@@ -26,4 +26,5 @@ def __getattr__(name):
 
 __all__ = ["NaVILAConfig", "NaVILAForCausalLM", "NaVILAModel", "MUVLAConfig", "MUVLAForCausalLM", "MUVLAModel",
            "DM0Config", "DM0ForCausalLM", "DM0Model", "Pi05Config", "Pi05ForCausalLM", "Pi05Model",
-           "OFTConfig", "OFTForCausalLM", "OFTModel", "PerceptionEncoderConfig", "PEVisionTower"]
+           "OFTConfig", "OFTForCausalLM", "OFTModel", "OFTDiscreteConfig", "OFTDiscreteForCausalLM", "OFTDiscreteModel",
+           "PerceptionEncoderConfig", "PEVisionTower"]

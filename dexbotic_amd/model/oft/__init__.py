@@ -1,4 +1,6 @@
-"""OFT, the parallel-decoding VLA with an L1-regression head (dexbotic/model/oft): see oft_arch.py."""
+"""OFT, the parallel-decoding VLA (dexbotic/model/oft): the L1-regression head in oft_arch.py, the discrete
+(vocabulary-bin) head in oft_discrete_arch.py."""
 from .oft_arch import OFTConfig, OFTForCausalLM, OFTModel
+from .oft_discrete_arch import OFTDiscreteConfig, OFTDiscreteForCausalLM, OFTDiscreteModel
 
-__all__ = ["OFTConfig", "OFTForCausalLM", "OFTModel"]
+__all__ = ["OFTConfig", "OFTForCausalLM", "OFTModel", "OFTDiscreteConfig", "OFTDiscreteForCausalLM", "OFTDiscreteModel"]

@@ -3,13 +3,16 @@
 ``L1RegressionActionHead`` (:129-160): ``action_query`` [1, T A, d], the learned rows placed behind every sample's prompt, and an
 ``MLPResNet`` (:104-126) that reads the A hidden rows of one time step as ONE row of A d columns: layer_norm1 -> fc1 -> ReLU -> two
 ``MLPResNetBlock`` (:83-101, LayerNorm -> Linear -> ReLU, plus the skip) -> layer_norm2 -> fc2.  ``ProprioProjector`` (:12-30):
-fc1 -> GELU(erf) -> fc2.  Parameter names as in the reference's modules.  The products run in the compute dtype (the reference runs
+fc1 -> GELU(erf) -> fc2.  ``DiscreteActionHead`` (:273-347): no trunk at all — the LLM's vocabulary is the head; it carries the bin
+<-> action helpers and the optional projector.  Parameter names as in the reference's modules.  The products run in the compute dtype (the reference runs
 them under autocast), the LayerNorm statistics in fp32.
 """
 from __future__ import annotations
 
+import re
 from typing import Optional
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -64,6 +67,53 @@ class MLPResNet(nn.Module):
             x = Fn.ResidualLinearFn.apply(x, anchor, st, b + "0.weight", b + "0.bias", b + "1.weight", b + "1.bias", L.ACT_RELU, LN_EPS)
         x = Fn.NormFn.apply(x, anchor, st, "ln", p + "layer_norm2.weight", p + "layer_norm2.bias", LN_EPS)
         return Fn.LinearFn.apply(x, anchor, st, p + "fc2.weight", p + "fc2.bias", L.ACT_NONE, None)
+
+
+class DiscreteActionHead(nn.Module):
+    """discrete actions read off the LLM's own vocabulary (model.py:273-347): no parameters except the optional
+    ``proprio_projector``.  ``action_query`` is ``torch.ones(1, T A)`` — token ids, not a parameter and not in the state dict: every
+    query row is the embedding row of token ``QUERY_TOKEN``.  Bin b of ``num_bins`` stands for the action b / (num_bins - 1) * 2 - 1;
+    the decoders read the LAST num_bins - 1 vocabulary logits (oft_discrete_arch.py:222-224)."""
+
+    QUERY_TOKEN = 1
+
+    def __init__(self, store: ParamStore, prefix: str, input_dim: int, vocab_size: int, action_dim: int, action_chunk: int,
+                 num_bins: int = 256, use_proprio: bool = False, proprio_dim: Optional[int] = None):
+        super().__init__()
+        self.store, self.p = store, prefix
+        self.input_dim, self.vocab_size, self.action_dim, self.action_chunk = input_dim, vocab_size, action_dim, action_chunk
+        self.num_bins, self.use_proprio = int(num_bins), bool(use_proprio)
+        self.action_query = torch.ones(1, action_chunk * action_dim)
+        self.proprio_projector = None
+        if use_proprio:
+            if not proprio_dim:
+                raise ValueError("OFT: use_proprio=True needs config.proprio_dim")
+            store.new_bucket()
+            self.proprio_projector = ProprioProjector(store, prefix + "proprio_projector.", input_dim, int(proprio_dim))
+
+    @property
+    def num_query_rows(self) -> int:
+        return self.action_chunk * self.action_dim
+
+    def discretize_actions(self, actions: torch.Tensor) -> torch.Tensor:
+        """[B, T, A] in [-1, 1] (clipped) -> bin indices in [0, num_bins - 1]"""
+        actions = torch.clamp(actions, -1, 1)
+        return ((actions + 1) / 2 * (self.num_bins - 1)).round().long()
+
+    def continuous_to_discrete_tokens(self, actions: torch.Tensor) -> torch.Tensor:
+        """[B, T, A] -> [B, T A] bin indices"""
+        discrete = self.discretize_actions(actions)
+        return discrete.reshape(discrete.size(0), -1)
+
+    def discrete_tokens_to_continuous(self, token_ids) -> torch.Tensor:
+        """[B, T A] bin indices, or a text string holding them -> [B, T, A] actions in [-1, 1]"""
+        if isinstance(token_ids, str):
+            found = re.findall(r"\d+", token_ids)[: self.action_chunk * self.action_dim]
+            actions = np.array([int(a) for a in found], dtype=np.float32).reshape(1, self.action_chunk, self.action_dim)
+            actions = torch.from_numpy(actions)
+        else:
+            actions = token_ids.reshape(token_ids.size(0), self.action_chunk, self.action_dim).float()
+        return (actions / (self.num_bins - 1)) * 2 - 1
 
 
 class L1RegressionActionHead(nn.Module):

@@ -9,7 +9,8 @@ Sequence layout (``insert_action_embedding``, :169-201): sample b has len_b spli
 len_b ... len_b + Q - 1, padding follows; the mask is true on [0, len_b + Q); position ids are arange(S + Q).  Here the splice plan
 reserves those rows (splice.build_oft_splice_plan), dxa_splice_fwd zero-fills them and dxa_action_put_fwd writes them in place
 (functional.OftSpliceFn); the head's first LayerNorm reads its rows out of the decoder output at the same offsets
-(functional.ActionNormFn).  Left padding is refused.  Only the ``Linear`` head is built (action_model/builder.py).
+(functional.ActionNormFn).  Left padding is refused.  This class runs the ``Linear`` head; the ``Discrete`` head belongs to
+oft_discrete_arch.py, ``DiT`` is not built (action_model/builder.py).
 """
 from __future__ import annotations
 

@@ -242,6 +242,44 @@ int dxa_action_layernorm_bwd_blocks(int64_t rows);
 /* loss = mean(|pred - target|) (torch.nn.L1Loss(), oft_arch.py:152); dpred = sign(pred - target) / n * gscale with sign(0) = 0
  * (NULL: not wanted).  One workgroup, fixed reduction tree. */
 int dxa_l1_loss(const float* pred, const float* target, float* loss, float* dpred, int64_t n, float gscale, dxa_stream_t stream);
+/* OFT-discrete policy (dexbotic/model/oft/oft_discrete_arch.py).  `off`, `skip` and the out-of-range rule as above; a sample's block
+ * is skip + n_rows rows (n_rows = chunk_size * action_dim), its action rows are h[b, off[b] + skip + j, :], j < n_rows.
+ *
+ * dxa_action_rows_fwd: extract_action_hidden_states (+ [:, 1:] with proprio) as the dense operand of the lm_head product:
+ * y[b * n_rows + j, :] = h[b, off[b] + skip + j, :] for h [B, Sq, d], y [B * n_rows, d]; the rows of an out-of-range sample are zero.
+ * dxa_action_rows_bwd writes dh [B, Sq, d] COMPLETELY: dy[b * n_rows + j, :] on the action rows, zero on every other row (as
+ * dxa_action_layernorm_bwd does).  fp32 and bf16, any d (scalar accesses when a row is not a multiple of 16 bytes). */
+int dxa_action_rows_fwd(const void* h, const int64_t* off, void* y, int64_t B, int64_t Sq, int64_t d, int64_t n_rows, int skip,
+                        int dtype, dxa_stream_t stream);
+int dxa_action_rows_bwd(const void* dy, const int64_t* off, void* dh, int64_t B, int64_t Sq, int64_t d, int64_t n_rows, int skip,
+                        int dtype, dxa_stream_t stream);
+/* dxa_action_fill_fwd: the discrete head's action_query is torch.ones(1, T*A) used as token ids (oft_discrete_arch.py:125-130): every
+ * query row is the embedding row of token 1.  x[b, off[b] + skip + j, :] = row[:] for j < n_rows, into rows the splice kernel
+ * reserved (`row` [d] in `row_dtype`: the dtype of x or fp32); with `state` [B, d] skip = 1 and x[b, off[b], :] = state[b, :].
+ * dxa_action_fill_bwd: drow[:] (+)= sum_b sum_j dx[b, off[b] + skip + j, :] in fp32, in a fixed order and without atomics (the same
+ * bits on every run): the action rows, numbered b * n_rows + j, are summed ascending in chunks of 16 into `partial`
+ * [dxa_action_fill_bwd_blocks(B * n_rows), d] fp32, and the chunks are then added ascending (`accumulate`: onto what drow holds).
+ * dstate [B, d] as dxa_action_put_bwd writes it (NULL: not wanted). */
+int dxa_action_fill_fwd(void* x, const void* row, const void* state, const int64_t* off, int64_t B, int64_t Sq, int64_t d,
+                        int64_t n_rows, int dtype, int row_dtype, dxa_stream_t stream);
+int dxa_action_fill_bwd(const void* dx, const int64_t* off, float* drow, void* dstate, float* partial, int64_t B, int64_t Sq,
+                        int64_t d, int64_t n_rows, int skip, int accumulate, int dtype, dxa_stream_t stream);
+int dxa_action_fill_bwd_blocks(int64_t rows);
+/* The inference head of the discrete policy in one launch (oft_discrete_arch.py:213-230): for every action row, read in place, the
+ * n_bins = num_bins - 1 logits against w_bins [n_bins, d] (the last n_bins rows of lm_head.weight, which are contiguous), without a
+ * gathered copy of the rows and without any [rows, vocab] tensor.
+ *   bin_logits [B * n_rows, n_bins] in `dtype`: fp32 accumulation in a fixed order (MFMA over k in four interleaved strands, added
+ *       in order), rounded once;
+ *   bin [B * n_rows] int64: the FIRST index of the maximum of the rounded row (torch.argmax; a NaN counts as the maximum);
+ *   action [B * n_rows] fp32: ((float)bin / n_bins) * 2 - 1, each operation rounded to fp32 (IEEE division, as torch's CPU kernels).
+ * The rows of an out-of-range sample are computed as zero rows: logits 0, bin 0, action -1.
+ * `counters`: dxa_action_bins_counters(B * n_rows) int32 words of scratch, 16-byte aligned, zeroed by the call on the stream.
+ * DXA_ERR_UNSUPPORTED when d is not a multiple of 8 (bf16) / 4 (fp32) or h / w_bins / counters are not 16-byte aligned;
+ * DXA_ERR_BAD_ARG for a null pointer, n_bins outside [1, 65536] or B * n_rows above 2^24. */
+int dxa_action_bins_fwd(const void* h, const int64_t* off, const void* w_bins, void* bin_logits, int64_t* bin, float* action,
+                        int32_t* counters, int64_t B, int64_t Sq, int64_t d, int64_t n_rows, int skip, int64_t n_bins, int dtype,
+                        dxa_stream_t stream);
+int dxa_action_bins_counters(int64_t rows);
 /* Adaptive RMSNorm and gated residual of the pi0.5 action expert (dexbotic/model/pi05/transformers_pi05/gemma/modeling_gemma.py:
  * 38-120): no gain, a per-SAMPLE modulation mod [B, 3*cols] = [scale | shift | gate] in `dtype` (fp32 or bf16, like every row
  * tensor here).  Row `i` of the [rows, cols] tensors belongs to sample i / rows_per_sample (rows % rows_per_sample == 0).  All
