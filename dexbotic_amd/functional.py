@@ -17,6 +17,7 @@ order: bit-identical gradients) — ~0.75 GB -> 33 MB kept per decoder layer at 
 from __future__ import annotations
 
 
+from collections import namedtuple
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -1481,6 +1482,7 @@ class ScaleFn(Function):
         return ScaleFn._mul(dy, ctx.s), None
 
 
+# ------------------------------------------------------------------- mixture-of-transformers layer (pi0, pi0.5, DM0)
 @dataclass
 class GemmaLayerSpec:
     """parameter names + shapes of one Gemma decoder layer of one expert (model/llm/gemma.py)"""
@@ -1500,8 +1502,8 @@ def gemma_norm_w(st: ParamStore, name: str) -> torch.Tensor:
     forms it.  One tensor per name, allocated once and re-formed IN PLACE when the weights have moved since that name was last
     formed (ParamStore.weights_key): forward and backward of a step share it (the two aten launches per use were 290 launches of a
     pi0 step), and its address never changes, so nothing a captured graph holds is ever freed under it.  The refresh itself is host
-    code: whoever replays a captured graph that reads these tensors calls ``gemma_norm_refresh`` first (Pi0ForCausalLM.inference_action
-    does), or the replay normalises with the 1 + w of the capture."""
+    code: whoever replays a captured graph that reads these tensors calls ``gemma_norm_refresh`` first (model/mot.py's
+    ``_run_sampler`` does), or the replay normalises with the 1 + w of the capture."""
     key = st.weights_key()
     cache = st.__dict__.setdefault("_gemma_norm_cache", {})
     ent = cache.get(name)
@@ -1536,126 +1538,6 @@ def gemma_post_attention(st: ParamStore, sp: GemmaLayerSpec, x, a):
     return K.mm_nt(act, st.w(sp.down), residual=r), (r, rstd2, h2, gu, act)
 
 
-class Pi0MotLayerFn(_StoreFn):
-    """One layer of the pi0 mixture of transformers (pi0_arch.py:130-216) for its two experts at once: per expert
-    GemmaRMSNorm -> fused q/k/v -> RoPE; ONE attention over the concatenated tokens with the block-prefix mask; per
-    expert o_proj + residual -> GemmaRMSNorm -> GeGLU -> residual.  Inputs/outputs are the experts' [B*S_e, d_e]
-    activations.  ``skip_post0``: the last layer's llm half after attention feeds only prefix_out, which the loss
-    never reads — it is not computed (the reference computes it and its parameters get no gradient)."""
-
-    @staticmethod
-    def _run(st: ParamStore, sps, geom, skip_post0: bool, x0, x1, cos_t, sin_t, pos0, pos1, q_limit, key_valid):
-        """the layer's forward launches -> ((y0, y1), what the backward reads besides x0, x1)"""
-        B, S0, S1, Hq, Hkv, D = geom
-        nq = (Hq + 2 * Hkv) * D
-        xs, Ss, poss = (x0, x1), (S0, S1), (pos0, pos1)
-        h1, rstd1 = [], []
-        # both experts' RoPE launches write straight into ONE q / k / v (round 6: no concatenation around the shared attention call)
-        q = torch.empty((B, Hq, S0 + S1, D), device=x0.device, dtype=x0.dtype)
-        k = torch.empty((B, Hkv, S0 + S1, D), device=x0.device, dtype=x0.dtype)
-        v = torch.empty((B, Hkv, S0 + S1, D), device=x0.device, dtype=x0.dtype)
-        off = 0
-        for x, sp, S, pos in zip(xs, sps, Ss, poss):
-            h, r, qkv = gemma_pre_attention(st, sp, x, nq)
-            K.rope_split_into(qkv, q, k, v, off, cos_t, sin_t, pos, B, S, Hq, Hkv, D)
-            del qkv
-            off += S
-            h1.append(h); rstd1.append(r)
-        o = torch.empty((B, S0 + S1, Hq, D), device=x0.device, dtype=x0.dtype)
-        lse = K.attn_fwd(q, k, v, o.permute(0, 2, 1, 3), causal=False, scale=D ** -0.5, q_limit=q_limit, key_valid=key_valid)
-        ys, saved = [], []
-        off = 0
-        for i, (x, sp, S) in enumerate(zip(xs, sps, Ss)):
-            a = o[:, off:off + S].reshape(B * S, Hq * D).contiguous()
-            off += S
-            if i == 0 and skip_post0:
-                ys.append(x.new_zeros((0,)))                   # placeholder, never read downstream
-                saved += [a, a.new_empty(0), a.new_empty(0), a.new_empty(0), a.new_empty(0), a.new_empty(0)]
-                continue
-            y, kept = gemma_post_attention(st, sp, x, a)
-            ys.append(y)
-            saved += [a, *kept]
-        return (ys[0], ys[1]), (h1[0], h1[1], rstd1[0], rstd1[1], q, k, v, o, lse, *saved)
-
-    @staticmethod
-    def forward(ctx, x0, x1, anchor, st: ParamStore, sp0: GemmaLayerSpec, sp1: GemmaLayerSpec, geom, cos_t, sin_t,
-                pos0, pos1, q_limit, key_valid, skip_post0: bool):
-        sps = (sp0, sp1)
-        ys, saved = Pi0MotLayerFn._run(st, sps, geom, skip_post0, x0, x1, cos_t, sin_t, pos0, pos1, q_limit, key_valid)
-        ctx.st, ctx.sps, ctx.geom, ctx.skip_post0 = st, sps, geom, skip_post0
-        for i, sp in enumerate(sps):
-            _use(ctx, st, sp.ln1, sp.qkv)
-            if not (i == 0 and skip_post0):
-                _use(ctx, st, sp.o, sp.ln2, sp.gu, sp.down)
-        ctx.aux = (cos_t, sin_t, pos0, pos1, q_limit, key_valid)
-        ctx.recompute = _recompute(ctx, st)
-        if ctx.recompute:
-            ctx.save_for_backward(x0, x1)
-        else:
-            ctx.save_for_backward(x0, x1, *saved)
-        return ys
-
-    @staticmethod
-    def backward(ctx, dy0, dy1):
-        st, sps, skip_post0 = ctx.st, ctx.sps, ctx.skip_post0
-        B, S0, S1, Hq, Hkv, D = ctx.geom
-        cos_t, sin_t, pos0, pos1, q_limit, key_valid = ctx.aux
-        sv = ctx.saved_tensors
-        if ctx.recompute:
-            sv = tuple(sv) + tuple(Pi0MotLayerFn._run(st, sps, ctx.geom, skip_post0, sv[0], sv[1], cos_t, sin_t, pos0, pos1,
-                                                       q_limit, key_valid)[1])
-        xs, h1, rstd1 = sv[0:2], sv[2:4], sv[4:6]
-        q, k, v, o, lse = sv[6:11]
-        per = [sv[11:17], sv[17:23]]
-        nq = (Hq + 2 * Hkv) * D
-        Ss, poss, dys = (S0, S1), (pos0, pos1), (dy0, dy1)
-        S = S0 + S1
-        do = torch.zeros((B, S, Hq, D), device=q.device, dtype=q.dtype)
-        drs = []
-        off = 0
-        for i, (sp, Sn, dy) in enumerate(zip(sps, Ss, dys)):
-            a, r, rs2, h2, gu, act = per[i]
-            if i == 0 and skip_post0:
-                drs.append(None)
-                off += Sn
-                continue
-            dy = dy.contiguous()
-            dact = _dx(st, sp.down, (sp.d, sp.F), dy)
-            _wgrad(st, sp.down, dy, act, (sp.d, sp.F))
-            dgu = K.glu_bwd(gu, dact, L.ACT_GELU_TANH)
-            dh2 = _dx(st, sp.gu, (2 * sp.F, sp.d), dgu)
-            _wgrad(st, sp.gu, dgu, h2, (2 * sp.F, sp.d))
-            tr = st.trainable(sp.ln2)
-            dr, _ = K.rmsnorm_bwd(dh2, r, gemma_norm_w(st, sp.ln2), rs2, dw_out=st.g(sp.ln2) if tr else None,
-                                  accumulate=st.accum_flag(sp.ln2), want_dw=tr, residual=dy)
-            if tr:
-                st.mark_written(sp.ln2)
-            da = _dx(st, sp.o, (sp.d, Hq * D), dr)
-            _wgrad(st, sp.o, dr, a, (sp.d, Hq * D))
-            do[:, off:off + Sn].copy_(da.view(B, Sn, Hq, D))
-            off += Sn
-            drs.append(dr)
-        do_h = K.permute_bshd(do, B, S, Hq, D, True)                       # head-major dO for the GQA fold
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        K.attn_bwd(q, k, v, o.permute(0, 2, 1, 3), lse, do_h, dq, dk, dv, causal=False, scale=D ** -0.5,
-                   q_limit=q_limit, key_valid=key_valid)
-        dxs = []
-        off = 0
-        for i, (sp, Sn, pos) in enumerate(zip(sps, Ss, poss)):
-            dqkv = K.rope_merge_from(dq, dk, dv, off, cos_t, sin_t, pos, B, Sn, Hq, Hkv, D)      # (no slicing copies)
-            off += Sn
-            dh = _dx(st, sp.qkv, (nq, sp.d), dqkv)
-            _wgrad(st, sp.qkv, dqkv, h1[i], (nq, sp.d))
-            tr = st.trainable(sp.ln1)
-            dxn, _ = K.rmsnorm_bwd(dh, xs[i], gemma_norm_w(st, sp.ln1), rstd1[i], dw_out=st.g(sp.ln1) if tr else None,
-                                   accumulate=st.accum_flag(sp.ln1), want_dw=tr, residual=drs[i])
-            if tr:
-                st.mark_written(sp.ln1)
-            dxs.append(dxn)
-        return (dxs[0], dxs[1]) + (None,) * 12
-
-
-# ------------------------------------------------------------------------------- Qwen3 mixture layer (DM0)
 def qwen3_pre_attention(st: ParamStore, sp: Qwen2LayerSpec, x):
     """first half of one expert's Qwen3 layer on x [M, d]: input RMSNorm (plain weight), then the fused q/k/v product without bias
     -> (h, rstd, qkv [M, (Hq + 2 Hkv) * D]); the per-head q/k norm runs in the RoPE / split pass that follows"""
@@ -1679,151 +1561,6 @@ def qwen3_post_attention(st: ParamStore, sp: Qwen2LayerSpec, x, a, keep: bool = 
     return K.mm_nt(act, st.w(sp.down_w), residual=r), (r, rstd2, h2, gu, act)
 
 
-class Qwen3MotLayerFn(_StoreFn):
-    """One layer of DM0's mixture of two Qwen3 experts (dm0_arch.py:145-268), the counterpart of Pi0MotLayerFn: per expert RMSNorm ->
-    fused q/k/v -> per-head q/k RMSNorm + RoPE written by ONE launch straight into the q / k / v both experts share
-    (dxa_qknorm_rope_split_at); ONE attention over all tokens with the block mask as q_limit / key_valid; per expert o_proj +
-    residual -> RMSNorm -> SwiGLU -> residual.  The rotary tables are the llm's for both experts.  ``skip_post0``: the last layer's
-    llm half after attention feeds only prefix_out, which nothing reads — it is not computed; that layer's q_proj / q_norm still get
-    their (zero) gradient written, like the reference."""
-
-    @staticmethod
-    def _run(st: ParamStore, sps, geom, skip_post0: bool, x0, x1, cos_t, sin_t, pos0, pos1, q_limit, key_valid, keep: bool = True,
-             kv=None, kv0: int = 0):
-        """the layer's forward launches -> ((y0, y1), what the backward reads besides x0, x1): the training forward, its recompute,
-        the no-grad forward and the sampler all run this one sequence.  An expert whose x is None (its S in ``geom`` is 0) is left
-        out (the sampler: the prefix pass runs the llm alone, the Euler steps the action expert alone).  ``keep`` = False: nothing
-        is kept for a backward (no rstd of the heads, no SwiGLU pre-activations).  ``kv`` (with ``keep`` = False only) = (k, v)
-        [B, Hkv, cap, D] buffers: this call's keys / values are WRITTEN at [kv0, kv0 + S) and attention reads [0, kv0 + S) — the
-        sampler's prefix pass fills [0, P), every Euler step the slots behind it; no concatenation, no copy."""
-        assert kv is None or not keep, "a backward must not read keys / values out of a buffer that the next step overwrites"
-        B, S0, S1, Hq, Hkv, D = geom
-        S = S0 + S1
-        live = [i for i, x in enumerate((x0, x1)) if x is not None]
-        xs, Ss, poss = (x0, x1), (S0, S1), (pos0, pos1)
-        assert all(Ss[i] > 0 for i in live) and sum(Ss[i] for i in live) == S
-        dev, dtype = xs[live[0]].device, xs[live[0]].dtype
-        q = torch.empty((B, Hq, S, D), device=dev, dtype=dtype)
-        if kv is None:
-            k = torch.empty((B, Hkv, S, D), device=dev, dtype=dtype)
-            v = torch.empty((B, Hkv, S, D), device=dev, dtype=dtype)
-        else:
-            k, v = kv
-        h1, rstd1, qkvs, rstd_qk = [None, None], [None, None], [None, None], [None, None]
-        off = 0
-        for i in live:
-            sp = sps[i]
-            h1[i], rstd1[i], qkvs[i] = qwen3_pre_attention(st, sp, xs[i])
-            rstd_qk[i] = K.qknorm_rope_split_into(qkvs[i], q, k, v, off, kv0 + off, st.w(sp.qk_norm[0]), st.w(sp.qk_norm[1]), sp.eps,
-                                                  cos_t, sin_t, poss[i], B, Ss[i], Hq, Hkv, D, want_rstd=keep)
-            if not keep:
-                qkvs[i] = None
-            off += Ss[i]
-        o = torch.empty((B, S, Hq, D), device=dev, dtype=dtype)
-        ka, va = (k, v) if kv is None or k.shape[2] == kv0 + S else (k[:, :, :kv0 + S], v[:, :, :kv0 + S])
-        lse = K.attn_fwd(q, ka, va, o.permute(0, 2, 1, 3), causal=False, scale=D ** -0.5, q_limit=q_limit, key_valid=key_valid)
-        ys, saved = [None, None], []
-        off = 0
-        for i in range(2):
-            if i not in live or (i == 0 and skip_post0):
-                saved += [None] * 6
-                off += Ss[i] if i in live else 0
-                continue
-            a = o[:, off:off + Ss[i]].reshape(B * Ss[i], Hq * D).contiguous()
-            off += Ss[i]
-            ys[i], kept = qwen3_post_attention(st, sps[i], xs[i], a, keep=keep)
-            saved += [a, *kept]
-        return (ys[0], ys[1]), (*h1, *rstd1, q, k, v, o, lse, *saved, *qkvs, *rstd_qk)
-
-    @staticmethod
-    def forward(ctx, x0, x1, anchor, st: ParamStore, sp0: Qwen2LayerSpec, sp1: Qwen2LayerSpec, geom, cos_t, sin_t,
-                pos0, pos1, q_limit, key_valid, skip_post0: bool):
-        sps = (sp0, sp1)
-        ys, saved = Qwen3MotLayerFn._run(st, sps, geom, skip_post0, x0, x1, cos_t, sin_t, pos0, pos1, q_limit, key_valid)
-        ctx.st, ctx.sps, ctx.geom, ctx.skip_post0 = st, sps, geom, skip_post0
-        for i, sp in enumerate(sps):
-            _use(ctx, st, sp.ln1, sp.qkv_w, sp.qk_norm)
-            if not (i == 0 and skip_post0):
-                _use(ctx, st, sp.o_w, sp.ln2, sp.gu_w, sp.down_w)
-        ctx.aux = (cos_t, sin_t, pos0, pos1, q_limit, key_valid)
-        ctx.recompute = _recompute(ctx, st)
-        if ctx.recompute:
-            ctx.save_for_backward(x0, x1)
-        else:
-            ctx.save_for_backward(x0, x1, *saved)
-        if skip_post0:
-            return x0.new_zeros((0,)), ys[1]                   # placeholder, never read downstream
-        return ys
-
-    @staticmethod
-    def backward(ctx, dy0, dy1):
-        st, sps, skip_post0 = ctx.st, ctx.sps, ctx.skip_post0
-        B, S0, S1, Hq, Hkv, D = ctx.geom
-        cos_t, sin_t, pos0, pos1, q_limit, key_valid = ctx.aux
-        sv = ctx.saved_tensors
-        if ctx.recompute:
-            sv = tuple(sv) + tuple(Qwen3MotLayerFn._run(st, sps, ctx.geom, skip_post0, sv[0], sv[1], cos_t, sin_t, pos0, pos1,
-                                                         q_limit, key_valid)[1])
-        xs, h1, rstd1 = sv[0:2], sv[2:4], sv[4:6]
-        q, k, v, o, lse = sv[6:11]
-        per = [sv[11:17], sv[17:23]]
-        qkvs, rstd_qk = sv[23:25], sv[25:27]
-        nq = (Hq + 2 * Hkv) * D
-        Ss, poss, dys = (S0, S1), (pos0, pos1), (dy0, dy1)
-        S = S0 + S1
-        do = torch.zeros((B, S, Hq, D), device=q.device, dtype=q.dtype)
-        drs = []
-        off = 0
-        for i, (sp, Sn, dy) in enumerate(zip(sps, Ss, dys)):
-            a, r, rs2, h2, gu, act = per[i]
-            if i == 0 and skip_post0:
-                drs.append(None)
-                off += Sn
-                continue
-            dy = dy.contiguous()
-            dact = _dx(st, sp.down_w, (sp.d, sp.F), dy)
-            _wgrad(st, sp.down_w, dy, act, (sp.d, sp.F))
-            dgu = K.swiglu_bwd(gu, dact)
-            del dact
-            dh2 = _dx(st, sp.gu_w, (2 * sp.F, sp.d), dgu)
-            _wgrad(st, sp.gu_w, dgu, h2, (2 * sp.F, sp.d))
-            del dgu
-            tr = st.trainable(sp.ln2)
-            dr, _ = K.rmsnorm_bwd(dh2, r, st.w(sp.ln2), rs2, dw_out=st.g(sp.ln2) if tr else None,
-                                  accumulate=st.accum_flag(sp.ln2), want_dw=tr, residual=dy)
-            if tr:
-                st.mark_written(sp.ln2)
-            da = _dx(st, sp.o_w, (sp.d, Hq * D), dr)
-            _wgrad(st, sp.o_w, dr, a, (sp.d, Hq * D))
-            do[:, off:off + Sn].copy_(da.view(B, Sn, Hq, D))
-            off += Sn
-            drs.append(dr)
-        do_h = K.permute_bshd(do, B, S, Hq, D, True)                       # head-major dO for the GQA fold
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        K.attn_bwd(q, k, v, o.permute(0, 2, 1, 3), lse, do_h, dq, dk, dv, causal=False, scale=D ** -0.5,
-                   q_limit=q_limit, key_valid=key_valid)
-        dxs = []
-        off = 0
-        for i, (sp, Sn, pos) in enumerate(zip(sps, Ss, poss)):
-            tr_qk = all(st.trainable(n) for n in sp.qk_norm)
-            dqkv, part = K.qknorm_rope_merge_from(dq, dk, dv, off, qkvs[i], rstd_qk[i], st.w(sp.qk_norm[0]), st.w(sp.qk_norm[1]),
-                                                  cos_t, sin_t, pos, B, Sn, Hq, Hkv, D, want_dw=tr_qk)      # (no slicing copies)
-            if tr_qk:
-                _bgrad(st, sp.qk_norm, part)       # rows of (dw_q | dw_k) partial sums, folded by the column sum as Qwen2LayerFn does
-            off += Sn
-            dh = _dx(st, sp.qkv_w, (nq, sp.d), dqkv)
-            _wgrad(st, sp.qkv_w, dqkv, h1[i], (nq, sp.d))
-            del dqkv
-            tr = st.trainable(sp.ln1)
-            dxn, _ = K.rmsnorm_bwd(dh, xs[i], st.w(sp.ln1), rstd1[i], dw_out=st.g(sp.ln1) if tr else None,
-                                   accumulate=st.accum_flag(sp.ln1), want_dw=tr, residual=drs[i])
-            if tr:
-                st.mark_written(sp.ln1)
-            dxs.append(dxn)
-        return (dxs[0], dxs[1]) + (None,) * 12
-
-
-# ------------------------------------------------------------------------------- pi0.5 mixture layer (adaRMS expert)
 def adarms_pre_attention(st: ParamStore, sp: GemmaLayerSpec, x, mod1, nq: int):
     """first half of the pi0.5 action expert's layer on x [M, d]: adaptive RMSNorm with mod1 [B, 3 d] = [scale | shift | gate], then
     the fused q/k/v product -> (h, rstd, qkv [M, nq])"""
@@ -1843,155 +1580,272 @@ def adarms_post_attention(st: ParamStore, sp: GemmaLayerSpec, x, a, mod1, mod2):
     return K.gated_residual_fwd(r, mb, mod2[:, 2 * d:]), (ob, r, rstd2, h2, gu, act, mb)
 
 
-class Pi05MotLayerFn(_StoreFn):
-    """One layer of the pi0.5 mixture (pi05_arch.py:134-238) for its two experts at once, the counterpart of Pi0MotLayerFn: expert 0
-    (the llm) is gemma_pre_attention / gemma_post_attention unchanged; expert 1 (the action expert) has no norm gains — its two
-    norms are adaptive (``mod1`` / ``mod2`` [B, 3 d_a] = [scale | shift | gate], dense layers of the flow-time embedding evaluated
-    OUTSIDE the layer) and its two residual adds are gated.  ONE attention over both experts' tokens.  The backward returns dmod1 /
-    dmod2; the dense layers' weight / bias gradients and the gradient of the time embedding are ordinary linear-layer work upstream.
-    ``skip_post0`` as in Pi0MotLayerFn."""
+# The three kinds of expert a mixture layer runs, told from the layer spec.  Each kind is four plain functions with one signature per
+# role (the forward halves above, their backwards below); MotLayerFn is the sequence around them.  ``dst`` = (q, k, v, q0, kv0): the
+# shared q / k / v and this expert's first slot in them; ``rope`` = (cos_t, sin_t, pos); ``tok`` = (B, S_e, Hq, Hkv, D); ``mods`` /
+# ``dmods`` = (mod1, mod2) and their gradients, None for the kinds without adaptive norms.
+def _mot_kind(sp) -> str:
+    if isinstance(sp, Qwen2LayerSpec):
+        assert sp.qk_norm is not None, "the mixture's Qwen experts are Qwen3 layers (per-head q/k norm)"
+        return "qwen3"
+    return "adarms" if sp.ln1 is None else "gemma"            # (AdaRMSGemmaExpert's norms own no gain: ln1 / ln2 are None)
+
+
+def _mot_params(sp):
+    """(what the pre-attention half's backward writes, what the post-attention half's does)"""
+    if isinstance(sp, Qwen2LayerSpec):
+        return (sp.ln1, sp.qkv_w, sp.qk_norm), (sp.o_w, sp.ln2, sp.gu_w, sp.down_w)
+    return (sp.ln1, sp.qkv), (sp.o, sp.ln2, sp.gu, sp.down)
+
+
+def _nq(tok) -> int:
+    _, _, Hq, Hkv, D = tok
+    return (Hq + 2 * Hkv) * D
+
+
+def _rope_pre(h, rstd, qkv, dst, rope, tok):
+    """RoPE of one expert's fused q/k/v into the shared tensors.  dxa_rope_split_at writes q, k and v at ONE offset"""
+    q, k, v, q0, kv0 = dst
+    assert q0 == kv0
+    K.rope_split_into(qkv, q, k, v, kv0, *rope, *tok)
+    return h, rstd
+
+
+def _gemma_pre(st, sp, x, mods, dst, rope, tok, keep):
+    return _rope_pre(*gemma_pre_attention(st, sp, x, _nq(tok)), dst, rope, tok)
+
+
+def _adarms_pre(st, sp, x, mods, dst, rope, tok, keep):
+    return _rope_pre(*adarms_pre_attention(st, sp, x, mods[0], _nq(tok)), dst, rope, tok)
+
+
+def _qwen3_pre(st, sp, x, mods, dst, rope, tok, keep):
+    """the per-head q/k norm + RoPE launch has offsets of its own for q and for k / v; its backward reads qkv and the heads' rstd"""
+    h, rstd, qkv = qwen3_pre_attention(st, sp, x)
+    rstd_qk = K.qknorm_rope_split_into(qkv, *dst, st.w(sp.qk_norm[0]), st.w(sp.qk_norm[1]), sp.eps, *rope, *tok, want_rstd=keep)
+    return h, rstd, qkv if keep else None, rstd_qk
+
+
+def _gemma_post(st, sp, x, a, mods, keep):
+    return gemma_post_attention(st, sp, x, a)
+
+
+def _adarms_post(st, sp, x, a, mods, keep):
+    return adarms_post_attention(st, sp, x, a, *mods)
+
+
+def _qwen3_post(st, sp, x, a, mods, keep):
+    return qwen3_post_attention(st, sp, x, a, keep=keep)
+
+
+def _lin_bwd(st: ParamStore, names, shape, dy, x) -> torch.Tensor:
+    """backward of y = x W^T for the fused view W over ``names``: -> dX; dW goes into the arena"""
+    dx = _dx(st, names, shape, dy)
+    _wgrad(st, names, dy, x, shape)
+    return dx
+
+
+def _rms_bwd(st: ParamStore, name: str, w, dy, x, rstd, residual) -> torch.Tensor:
+    """backward of an RMSNorm with gain ``w`` (parameter ``name``) on the row x it normalised: -> dx + residual; dw into the arena"""
+    tr = st.trainable(name)
+    dx, _ = K.rmsnorm_bwd(dy, x, w, rstd, dw_out=st.g(name) if tr else None, accumulate=st.accum_flag(name), want_dw=tr,
+                          residual=residual)
+    if tr:
+        st.mark_written(name)
+    return dx
+
+
+def _gemma_post_bwd(st, sp, dy, a, kept, mods, dmods):
+    """-> (da, dr): the gradient of this expert's attention rows and of the residual stream between the two halves"""
+    r, rstd2, h2, gu, act = kept
+    dgu = K.glu_bwd(gu, _lin_bwd(st, sp.down, (sp.d, sp.F), dy, act), L.ACT_GELU_TANH)
+    dh2 = _lin_bwd(st, sp.gu, (2 * sp.F, sp.d), dgu, h2)
+    del dgu
+    dr = _rms_bwd(st, sp.ln2, gemma_norm_w(st, sp.ln2), dh2, r, rstd2, dy)
+    return _lin_bwd(st, sp.o, (sp.d, a.shape[1]), dr, a), dr
+
+
+def _qwen3_post_bwd(st, sp, dy, a, kept, mods, dmods):
+    r, rstd2, h2, gu, act = kept
+    dgu = K.swiglu_bwd(gu, _lin_bwd(st, sp.down_w, (sp.d, sp.F), dy, act))
+    dh2 = _lin_bwd(st, sp.gu_w, (2 * sp.F, sp.d), dgu, h2)
+    del dgu
+    dr = _rms_bwd(st, sp.ln2, st.w(sp.ln2), dh2, r, rstd2, dy)
+    return _lin_bwd(st, sp.o_w, (sp.d, a.shape[1]), dr, a), dr
+
+
+def _adarms_post_bwd(st, sp, dy, a, kept, mods, dmods):
+    """gated add, GeGLU, fused adaptive norm + gated add, o_proj; writes all of dmod2 and the gate third of dmod1"""
+    ob, r, rstd2, h2, gu, act, mb = kept
+    (mod1, mod2), (dmod1, dmod2), d = mods, dmods, sp.d
+    dmb = K.gated_residual_bwd(dy, mb, mod2[:, 2 * d:], dmod2[:, 2 * d:])
+    dgu = K.glu_bwd(gu, _lin_bwd(st, sp.down, (d, sp.F), dmb, act), L.ACT_GELU_TANH)
+    dh2 = _lin_bwd(st, sp.gu, (2 * sp.F, d), dgu, h2)
+    del dgu
+    dr, dob = K.adarms_bwd(dh2, r, mod2, rstd2, dmod2, residual=dy, branch=ob, gate_prev=mod1[:, 2 * d:], dgate_prev=dmod1[:, 2 * d:])
+    return _lin_bwd(st, sp.o, (d, a.shape[1]), dob, a), dr
+
+
+def _gemma_pre_bwd(st, sp, x, kept, dr, dqkv3, off, rope, tok, mods, dmods):
+    """-> dx: this expert's slots [off, off + S_e) of the shared dq / dk / dv back through RoPE, the q/k/v product and the norm"""
+    h, rstd = kept
+    dh = _lin_bwd(st, sp.qkv, (_nq(tok), sp.d), K.rope_merge_from(*dqkv3, off, *rope, *tok), h)              # (no slicing copies)
+    return _rms_bwd(st, sp.ln1, gemma_norm_w(st, sp.ln1), dh, x, rstd, dr)
+
+
+def _qwen3_pre_bwd(st, sp, x, kept, dr, dqkv3, off, rope, tok, mods, dmods):
+    h, rstd, qkv, rstd_qk = kept
+    tr_qk = all(st.trainable(n) for n in sp.qk_norm)
+    dqkv, part = K.qknorm_rope_merge_from(*dqkv3, off, qkv, rstd_qk, st.w(sp.qk_norm[0]), st.w(sp.qk_norm[1]), *rope, *tok,
+                                          want_dw=tr_qk)
+    if tr_qk:
+        _bgrad(st, sp.qk_norm, part)       # rows of (dw_q | dw_k) partial sums, folded by the column sum as Qwen2LayerFn does
+    dh = _lin_bwd(st, sp.qkv_w, (_nq(tok), sp.d), dqkv, h)
+    del dqkv
+    return _rms_bwd(st, sp.ln1, st.w(sp.ln1), dh, x, rstd, dr)
+
+
+def _adarms_pre_bwd(st, sp, x, kept, dr, dqkv3, off, rope, tok, mods, dmods):
+    """writes the scale and shift thirds of dmod1"""
+    h, rstd = kept
+    dh = _lin_bwd(st, sp.qkv, (_nq(tok), sp.d), K.rope_merge_from(*dqkv3, off, *rope, *tok), h)
+    return K.adarms_bwd(dh, x, mods[0], rstd, dmods[0], residual=dr)[0]
+
+
+# q_apart: the kind's RoPE launch takes an offset for q apart from the one for k / v
+_MotKind = namedtuple("_MotKind", "pre post post_bwd pre_bwd q_apart")
+_MOT_KINDS = {
+    "gemma": _MotKind(_gemma_pre, _gemma_post, _gemma_post_bwd, _gemma_pre_bwd, False),
+    "qwen3": _MotKind(_qwen3_pre, _qwen3_post, _qwen3_post_bwd, _qwen3_pre_bwd, True),
+    "adarms": _MotKind(_adarms_pre, _adarms_post, _adarms_post_bwd, _adarms_pre_bwd, False),
+}
+
+
+class MotLayerFn(_StoreFn):
+    """One layer of a mixture of transformers for its two experts at once (pi0 pi0_arch.py:130-216, pi0.5 pi05_arch.py:134-238, DM0
+    dm0_arch.py:145-268): per expert norm -> fused q/k/v -> RoPE written straight into the q / k / v both experts share; ONE
+    attention over all tokens with the block mask as q_limit / key_valid; per expert o_proj + residual -> norm -> gated MLP ->
+    residual.  What an expert's halves are is its kind (_mot_kind): Gemma (pi0's two experts, the pi0.5 llm), Qwen3 (DM0: plain
+    gains, per-head q/k norm inside the RoPE launch, SwiGLU) or the pi0.5 action expert, whose norms are adaptive (``mod1`` /
+    ``mod2`` [B, 3 d_a] = [scale | shift | gate], dense layers of the flow-time embedding evaluated OUTSIDE the layer; None for the
+    other policies) and whose residual adds are gated.  The rotary tables are the llm's for both experts.  ``skip_post0``: the last
+    layer's llm half after attention feeds only prefix_out, which the loss never reads — it is not computed (the reference computes
+    it and its parameters get no gradient); that layer's llm q_proj (and DM0's q_norm) still get their zero gradient written."""
 
     @staticmethod
     def _run(st: ParamStore, sps, geom, skip_post0: bool, x0, x1, mod1, mod2, cos_t, sin_t, pos0, pos1, q_limit, key_valid,
              keep: bool = True, kv=None, kv0: int = 0):
-        """the layer's forward launches -> ((y0, y1), what the backward reads besides x0, x1, mod1, mod2): the training forward, its
-        recompute, the no-grad forward and the sampler all run this one sequence.  An expert whose x is None (its S in ``geom`` is 0)
-        is left out.  ``kv`` (with ``keep`` = False only) = (k, v) [B, Hkv, cap, D] buffers: this call's keys / values are WRITTEN at
-        [kv0, kv0 + S) and attention reads [0, kv0 + S) (the sampler: the prefix pass fills [0, P), every Euler step the slots
-        behind it).  dxa_rope_split_at writes q, k and v at ONE offset, so the queries then get a scratch tensor of the same
-        capacity, of which attention reads the window."""
+        """the layer's forward launches -> ((y0, y1), what the backward reads besides its inputs, or None): the training forward,
+        its recompute, the no-grad forward and the sampler all run this one sequence.  An expert whose x is None (its S in ``geom``
+        is 0) is left out (the sampler: the prefix pass runs the llm alone, the Euler steps the action expert alone).  ``keep`` =
+        False: nothing is kept for a backward (no rstd of the heads, no SwiGLU pre-activations).  ``kv`` (with ``keep`` = False
+        only) = (k, v) [B, Hkv, cap, D] buffers: this call's keys / values are WRITTEN at [kv0, kv0 + S) and attention reads
+        [0, kv0 + S) — the sampler's prefix pass fills [0, P), every Euler step the slots behind it; no concatenation, no copy."""
         assert kv is None or not keep, "a backward must not read keys / values out of a buffer that the next step overwrites"
         B, S0, S1, Hq, Hkv, D = geom
         S = S0 + S1
-        nq = (Hq + 2 * Hkv) * D
-        live = [i for i, x in enumerate((x0, x1)) if x is not None]
-        xs, Ss, poss = (x0, x1), (S0, S1), (pos0, pos1)
+        xs, Ss, poss, mods = (x0, x1), (S0, S1), (pos0, pos1), (mod1, mod2)
+        live = [i for i in range(2) if xs[i] is not None]
         assert all(Ss[i] > 0 for i in live) and sum(Ss[i] for i in live) == S
+        kinds = {i: _MOT_KINDS[_mot_kind(sps[i])] for i in live}
         dev, dtype = xs[live[0]].device, xs[live[0]].dtype
-        if kv is None:
-            qb = torch.empty((B, Hq, S, D), device=dev, dtype=dtype)
-            k = torch.empty((B, Hkv, S, D), device=dev, dtype=dtype)
-            v = torch.empty((B, Hkv, S, D), device=dev, dtype=dtype)
-        else:
-            k, v = kv
-            qb = torch.empty((B, Hq, k.shape[2], D), device=dev, dtype=dtype)
-        h1, rstd1 = [None, None], [None, None]
-        off = kv0
+        k, v = kv if kv is not None else (torch.empty((B, Hkv, S, D), device=dev, dtype=dtype) for _ in range(2))
+        # the queries' offset: a kind whose RoPE launch writes q, k and v at ONE offset gets, with ``kv``, a scratch tensor of the
+        # buffer's capacity for its queries, of which attention reads the window
+        q0, q_cap = (0, S) if kv is None or all(kd.q_apart for kd in kinds.values()) else (kv0, k.shape[2])
+        qb = torch.empty((B, Hq, q_cap, D), device=dev, dtype=dtype)
+        pre, off = [None, None], 0
         for i in live:
-            if i == 0:
-                h1[i], rstd1[i], qkv = gemma_pre_attention(st, sps[i], xs[i], nq)
-            else:
-                h1[i], rstd1[i], qkv = adarms_pre_attention(st, sps[i], xs[i], mod1, nq)
-            K.rope_split_into(qkv, qb, k, v, off, cos_t, sin_t, poss[i], B, Ss[i], Hq, Hkv, D)
-            del qkv
+            pre[i] = kinds[i].pre(st, sps[i], xs[i], mods, (qb, k, v, q0 + off, kv0 + off), (cos_t, sin_t, poss[i]),
+                                  (B, Ss[i], Hq, Hkv, D), keep)
             off += Ss[i]
-        q = qb if kv is None else qb[:, :, kv0:kv0 + S]
+        q = qb if q_cap == S else qb[:, :, q0:q0 + S]
         ka, va = (k, v) if k.shape[2] == kv0 + S else (k[:, :, :kv0 + S], v[:, :, :kv0 + S])
         o = torch.empty((B, S, Hq, D), device=dev, dtype=dtype)
         lse = K.attn_fwd(q, ka, va, o.permute(0, 2, 1, 3), causal=False, scale=D ** -0.5, q_limit=q_limit, key_valid=key_valid)
-        ys, saved0, saved1 = [None, None], [None] * 6, [None] * 8
-        off = 0
+        ys, post, off = [None, None], [None, None], 0
         for i in live:
-            a = o[:, off:off + Ss[i]].reshape(B * Ss[i], Hq * D).contiguous()
+            if not (i == 0 and skip_post0):
+                a = o[:, off:off + Ss[i]].reshape(B * Ss[i], Hq * D).contiguous()
+                ys[i], kept = kinds[i].post(st, sps[i], xs[i], a, mods, keep)
+                post[i] = (a, *kept)
             off += Ss[i]
-            if i == 0:
-                if not skip_post0:
-                    ys[0], kept = gemma_post_attention(st, sps[0], x0, a)
-                    saved0 = [a, *kept]
-                else:
-                    saved0[0] = a
-            else:
-                ys[1], kept = adarms_post_attention(st, sps[1], x1, a, mod1, mod2)
-                saved1 = [a, *kept]
-        if not keep:
-            return (ys[0], ys[1]), None
-        return (ys[0], ys[1]), (*h1, *rstd1, q, k, v, o, lse, *saved0, *saved1)
+        return (ys[0], ys[1]), ((q, k, v, o, lse), pre[0], pre[1], post[0], post[1]) if keep else None
 
     @staticmethod
-    def forward(ctx, x0, x1, mod1, mod2, anchor, st: ParamStore, sp0: GemmaLayerSpec, sp1: GemmaLayerSpec, geom, cos_t, sin_t,
-                pos0, pos1, q_limit, key_valid, skip_post0: bool):
+    def forward(ctx, x0, x1, mod1, mod2, anchor, st: ParamStore, sp0, sp1, geom, cos_t, sin_t, pos0, pos1, q_limit, key_valid,
+                skip_post0: bool):
         sps = (sp0, sp1)
-        ys, saved = Pi05MotLayerFn._run(st, sps, geom, skip_post0, x0, x1, mod1, mod2, cos_t, sin_t, pos0, pos1, q_limit, key_valid)
+        ys, kept = MotLayerFn._run(st, sps, geom, skip_post0, x0, x1, mod1, mod2, cos_t, sin_t, pos0, pos1, q_limit, key_valid)
         ctx.st, ctx.sps, ctx.geom, ctx.skip_post0 = st, sps, geom, skip_post0
-        _use(ctx, st, sp0.ln1, sp0.qkv, sp1.qkv, sp1.o, sp1.gu, sp1.down)
-        if not skip_post0:
-            _use(ctx, st, sp0.o, sp0.ln2, sp0.gu, sp0.down)
+        for i, sp in enumerate(sps):
+            before, after = _mot_params(sp)
+            _use(ctx, st, *before)
+            if not (i == 0 and skip_post0):
+                _use(ctx, st, *after)
         ctx.aux = (cos_t, sin_t, pos0, pos1, q_limit, key_valid)
         ctx.recompute = _recompute(ctx, st)
         if ctx.recompute:
             ctx.save_for_backward(x0, x1, mod1, mod2)
         else:
-            ctx.save_for_backward(x0, x1, mod1, mod2, *saved)
+            ctx.counts = [len(g or ()) for g in kept]           # the layout of what is saved: each group's length, by kind
+            ctx.save_for_backward(x0, x1, mod1, mod2, *[t for g in kept for t in g or ()])
         if skip_post0:
             return x0.new_zeros((0,)), ys[1]                   # placeholder, never read downstream
         return ys
 
     @staticmethod
     def backward(ctx, dy0, dy1):
-        st, (sp0, sp1), skip_post0 = ctx.st, ctx.sps, ctx.skip_post0
+        """post-attention backward for expert 0 then 1, the attention backward, pre-attention backward for expert 0 then 1: the
+        weight-gradient coalescing (_wgrad, _bgrad) goes by this order"""
+        st, sps, skip_post0 = ctx.st, ctx.sps, ctx.skip_post0
         B, S0, S1, Hq, Hkv, D = ctx.geom
         cos_t, sin_t, pos0, pos1, q_limit, key_valid = ctx.aux
-        sv = ctx.saved_tensors
+        x0, x1, mod1, mod2, *flat = ctx.saved_tensors
         if ctx.recompute:
-            sv = tuple(sv) + tuple(Pi05MotLayerFn._run(st, ctx.sps, ctx.geom, skip_post0, sv[0], sv[1], sv[2], sv[3], cos_t, sin_t,
-                                                        pos0, pos1, q_limit, key_valid)[1])
-        x0, x1, mod1, mod2 = sv[0:4]
-        h1, rstd1 = sv[4:6], sv[6:8]
-        q, k, v, o, lse = sv[8:13]
-        a0, r0, rs2_0, h2_0, gu0, act0 = sv[13:19]
-        a1, ob, r1, rs2_1, h2_1, gu1, act1, mb = sv[19:27]
-        nq = (Hq + 2 * Hkv) * D
+            kept = MotLayerFn._run(st, sps, ctx.geom, skip_post0, x0, x1, mod1, mod2, cos_t, sin_t, pos0, pos1, q_limit, key_valid)[1]
+        else:
+            it = iter(flat)
+            kept = [tuple(next(it) for _ in range(n)) for n in ctx.counts]
+        (q, k, v, o, lse), pre, post = kept[0], kept[1:3], kept[3:5]
+        del flat, kept
+        kinds = [_MOT_KINDS[_mot_kind(sp)] for sp in sps]
+        xs, Ss, poss, dys, mods = (x0, x1), (S0, S1), (pos0, pos1), (dy0, dy1), (mod1, mod2)
+        dmods = (None, None) if mod1 is None else (torch.empty_like(mod1), torch.empty_like(mod2))
         S = S0 + S1
         do = torch.zeros((B, S, Hq, D), device=q.device, dtype=q.dtype)
-        # ---- expert 0 (the llm), Pi0MotLayerFn's sequence
-        dr0 = None
-        if not skip_post0:
-            dy = dy0.contiguous()
-            dact = _dx(st, sp0.down, (sp0.d, sp0.F), dy)
-            _wgrad(st, sp0.down, dy, act0, (sp0.d, sp0.F))
-            dgu = K.glu_bwd(gu0, dact, L.ACT_GELU_TANH)
-            dh2 = _dx(st, sp0.gu, (2 * sp0.F, sp0.d), dgu)
-            _wgrad(st, sp0.gu, dgu, h2_0, (2 * sp0.F, sp0.d))
-            tr = st.trainable(sp0.ln2)
-            dr0, _ = K.rmsnorm_bwd(dh2, r0, gemma_norm_w(st, sp0.ln2), rs2_0, dw_out=st.g(sp0.ln2) if tr else None,
-                                   accumulate=st.accum_flag(sp0.ln2), want_dw=tr, residual=dy)
-            if tr:
-                st.mark_written(sp0.ln2)
-            da = _dx(st, sp0.o, (sp0.d, Hq * D), dr0)
-            _wgrad(st, sp0.o, dr0, a0, (sp0.d, Hq * D))
-            do[:, :S0].copy_(da.view(B, S0, Hq, D))
-        # ---- expert 1 (the action expert): gated add, GeGLU, fused adaptive norm + gated add, o_proj
-        d = sp1.d
-        dmod1, dmod2 = torch.empty_like(mod1), torch.empty_like(mod2)
-        dy = dy1.contiguous()
-        dmb = K.gated_residual_bwd(dy, mb, mod2[:, 2 * d:], dmod2[:, 2 * d:])
-        dact = _dx(st, sp1.down, (d, sp1.F), dmb)
-        _wgrad(st, sp1.down, dmb, act1, (d, sp1.F))
-        dgu = K.glu_bwd(gu1, dact, L.ACT_GELU_TANH)
-        dh2 = _dx(st, sp1.gu, (2 * sp1.F, d), dgu)
-        _wgrad(st, sp1.gu, dgu, h2_1, (2 * sp1.F, d))
-        dr1, dob = K.adarms_bwd(dh2, r1, mod2, rs2_1, dmod2, residual=dy, branch=ob, gate_prev=mod1[:, 2 * d:],
-                                dgate_prev=dmod1[:, 2 * d:])
-        da = _dx(st, sp1.o, (d, Hq * D), dob)
-        _wgrad(st, sp1.o, dob, a1, (d, Hq * D))
-        do[:, S0:].copy_(da.view(B, S1, Hq, D))
+        drs, off = [None, None], 0
+        for i in range(2):
+            if not (i == 0 and skip_post0):
+                a, *kept_i = post[i]
+                da, drs[i] = kinds[i].post_bwd(st, sps[i], dys[i].contiguous(), a, kept_i, mods, dmods)
+                do[:, off:off + Ss[i]].copy_(da.view(B, Ss[i], Hq, D))
+                del a, kept_i, da
+            off += Ss[i]
+        del post
         do_h = K.permute_bshd(do, B, S, Hq, D, True)                       # head-major dO for the GQA fold
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         K.attn_bwd(q, k, v, o.permute(0, 2, 1, 3), lse, do_h, dq, dk, dv, causal=False, scale=D ** -0.5,
                    q_limit=q_limit, key_valid=key_valid)
-        dqkv = K.rope_merge_from(dq, dk, dv, 0, cos_t, sin_t, pos0, B, S0, Hq, Hkv, D)
-        dh = _dx(st, sp0.qkv, (nq, sp0.d), dqkv)
-        _wgrad(st, sp0.qkv, dqkv, h1[0], (nq, sp0.d))
-        tr = st.trainable(sp0.ln1)
-        dx0, _ = K.rmsnorm_bwd(dh, x0, gemma_norm_w(st, sp0.ln1), rstd1[0], dw_out=st.g(sp0.ln1) if tr else None,
-                               accumulate=st.accum_flag(sp0.ln1), want_dw=tr, residual=dr0)
-        if tr:
-            st.mark_written(sp0.ln1)
-        dqkv = K.rope_merge_from(dq, dk, dv, S0, cos_t, sin_t, pos1, B, S1, Hq, Hkv, D)
-        dh = _dx(st, sp1.qkv, (nq, d), dqkv)
-        _wgrad(st, sp1.qkv, dqkv, h1[1], (nq, d))
-        dx1, _ = K.adarms_bwd(dh, x1, mod1, rstd1[1], dmod1, residual=dr1)
-        return (dx0, dx1, dmod1, dmod2) + (None,) * 12
+        dxs, off = [], 0
+        for i in range(2):
+            dxs.append(kinds[i].pre_bwd(st, sps[i], xs[i], pre[i], drs[i], (dq, dk, dv), off, (cos_t, sin_t, poss[i]),
+                                   (B, Ss[i], Hq, Hkv, D), mods, dmods))
+            off += Ss[i]
+        return (dxs[0], dxs[1], *dmods) + (None,) * 12
+
+
+def mot_layer(st: ParamStore, sps, geom, skip_post0: bool, x0, x1, mod1, mod2, cos_t, sin_t, pos0, pos1, q_limit, key_valid,
+              kv=None, kv0: int = 0):
+    """one mixture layer as the policies call it -> (y0, y1): through autograd when gradients are on, MotLayerFn._run alone
+    otherwise (the same launches: the same bits) — and then with the sampler's ``kv`` / ``kv0``"""
+    if torch.is_grad_enabled():
+        assert kv is None
+        anchor = st.params[_mot_params(sps[1])[1][-1]]                     # the action expert's down_proj
+        return MotLayerFn.apply(x0, x1, mod1, mod2, anchor, st, sps[0], sps[1], geom, cos_t, sin_t, pos0, pos1, q_limit, key_valid,
+                                skip_post0)
+    return MotLayerFn._run(st, sps, geom, skip_post0, x0, x1, mod1, mod2, cos_t, sin_t, pos0, pos1, q_limit, key_valid, keep=False,
+                           kv=kv, kv0=kv0)[0]
 
 
 class AdaRMSNormFn(Function):

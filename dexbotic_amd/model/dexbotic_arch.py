@@ -348,9 +348,9 @@ class NativePreTrainedMixin:
     def gradient_checkpointing_enable(self, gradient_checkpointing_kwargs=None) -> None:
         """HF ``PreTrainedModel.gradient_checkpointing_enable`` as base_exp.py:245 / trainer.py:101,120 switch it on (HF then
         checkpoints every Qwen2 decoder layer and every CLIP encoder layer: only the layer input is kept and the layer's forward
-        runs again inside its backward).  Native form: ``ParamStore.recompute`` — the decoder / vision / pi0 layer Functions keep
+        runs again inside its backward).  Native form: ``ParamStore.recompute`` — the decoder / vision / mixture layer Functions keep
         their INPUT only and re-run their forward launches at the top of their backward (functional.Qwen2LayerFn / VitBlockFn /
-        Pi0MotLayerFn; same kernels in the same order, so the gradients are bit-identical to the resident-activation step).
+        MotLayerFn; same kernels in the same order, so the gradients are bit-identical to the resident-activation step).
         Kept activations drop from ~0.75 GB to 33 MB per decoder layer at 16 x 287 tokens, for one more forward per step.
         ``gradient_checkpointing_kwargs`` (``use_reentrant``) has no meaning here and is accepted.  Resident activations remain
         the default: on a 288 GB part the CogACT recipe keeps 25 GB of them; DEXBOTIC_AMD_ACCEPT_GRAD_CHECKPOINTING=1 /

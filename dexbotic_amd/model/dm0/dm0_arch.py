@@ -7,14 +7,14 @@ dexbotic/model/dm0/dm0_arch.py on libdexbotic_amd kernels.
 pi0 recipe on Qwen3 experts, and what differs from model/pi0/pi0_arch.py follows the reference:
 
 * every prefix token opens a block of its own (``attn_mask`` = 1), so the prefix is CAUSAL; the suffix is [1, 0, 0, ...], one
-  bidirectional block that sees every valid prefix key.  cumsum is still non-decreasing, so the mask is ``Pi0ForCausalLM``'s
-  per-query key count + per-key validity, computed by the same ``_mask_tensors``;
+  bidirectional block that sees every valid prefix key.  cumsum is still non-decreasing, so the mask is pi0's per-query key
+  count + per-key validity, computed by the same ``mot.mask_tensors``;
 * the suffix is the ``chunk_size`` action tokens alone: no state token, no ``state_proj`` (``states`` only gives the batch size);
 * each expert's layer is HF Qwen3DecoderLayer arithmetic (plain RMSNorm gains, no projection bias, per-head q/k RMSNorm before RoPE,
   SwiGLU), the rotary tables are the llm's.
 
-Every layer is ``functional.Qwen3MotLayerFn``: both experts' q/k-norm + RoPE launches write into ONE q / k / v
-(``dxa_qknorm_rope_split_at``), one attention, two GEMM halves per expert.  The sampler keeps ONE key / value buffer
+Every layer is ``functional.MotLayerFn`` with two experts of its Qwen3 kind: both experts' q/k-norm + RoPE launches write into ONE
+q / k / v (``dxa_qknorm_rope_split_at``), one attention, two GEMM halves per expert; model/mot.py holds what pi0, pi0.5 and DM0 share.  The sampler keeps ONE key / value buffer
 [B, Hkv, P + chunk, D] per layer: the prefix pass writes its keys at [0, P), every Euler step the suffix keys at [P, P + chunk) —
 no concatenation and no copy for any batch size and any number of key / value heads — and the loop is replayed as one HIP graph.
 
@@ -23,6 +23,7 @@ arena; as everywhere here the fp32 masters stay and the kernels read bf16 shadow
 """
 from __future__ import annotations
 
+from itertools import takewhile
 from typing import List, Optional
 
 import numpy as np
@@ -36,7 +37,8 @@ from ...engine import ParamStore
 from ..dexbotic_arch import (ActionOutputForCausalLM, CausalLMOutputDexbotic, DexboticConfig, DexboticForCausalLM, DexboticVLMModel,
                              register_model_with_hf, register_with_hf)
 from ..llm.qwen3 import Qwen3Expert, llm_config_from_any
-from ..pi0.pi0_arch import Pi0ForCausalLM, posemb_sincos
+from ..mot import MotPolicy, flow_times, mask_tensors
+from ..pi0.pi0_arch import posemb_sincos
 
 _GEOMETRY = ("num_hidden_layers", "num_attention_heads", "num_key_value_heads", "head_dim")
 
@@ -104,7 +106,7 @@ class DM0Model(DexboticVLMModel):
             store.register([(f"model.{name}.weight", shape), (f"model.{name}.bias", (shape[0],))])
 
 
-class DM0ForCausalLM(DexboticForCausalLM, ActionOutputForCausalLM):
+class DM0ForCausalLM(DexboticForCausalLM, ActionOutputForCausalLM, MotPolicy):
     config_class = DM0Config
     _tied_weights_keys: list = []
     gradient_side_stream = True          # as Pi0ForCausalLM: the small column sums beside the dX chain
@@ -161,10 +163,6 @@ class DM0ForCausalLM(DexboticForCausalLM, ActionOutputForCausalLM):
                                 input_ids.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()).view(*input_ids.shape, -1)
         return torch.cat([img_tok.to(cdt), txt.to(cdt)], dim=1)
 
-    def _lin(self, x, n: str, act=L.ACT_NONE):
-        st = self.store
-        return Fn.LinearFn.apply(x, st.params[f"model.{n}.weight"], st, f"model.{n}.weight", f"model.{n}.bias", act, None)
-
     def get_suffix_hidden_states(self, noisy_actions: torch.Tensor, time: Optional[np.ndarray], te: Optional[torch.Tensor] = None):
         """-> suffix tokens [B, chunk, d_a]: action_time_mlp_out(silu(action_time_mlp_in(cat(action_in_proj(x_t), time_emb)))).
         ``te``: the sin/cos time embedding [B, d_a] already on the device (the sampler precomputes its schedule)."""
@@ -178,44 +176,16 @@ class DM0ForCausalLM(DexboticForCausalLM, ActionOutputForCausalLM):
         h = self._lin(h.contiguous(), "action_time_mlp_in", L.ACT_SILU)
         return self._lin(h, "action_time_mlp_out").view(B, n, da)
 
-    def _v_t(self, suf: torch.Tensor) -> torch.Tensor:
-        B, n = suf.shape[0], self.config.chunk_size
-        return self._lin(suf[:, -n:].reshape(B * n, -1).contiguous(), "action_out_proj").view(B, n, -1).float()
-
     # ------------------------------------------------------------------------------ mixture forward
-    def _geom(self, B: int, S0: int, S1: int):
-        c = self.config.llm_config
-        return (B, S0, S1, c.num_attention_heads, c.num_key_value_heads, c.head_dim)
-
     def _final_norm(self, x: torch.Tensor) -> torch.Tensor:
         exp = self.model.action_expert
         return Fn.NormFn.apply(x, self.store.params[exp.p + "norm.weight"], self.store, "rms", exp.p + "norm.weight", None,
                                exp.config.rms_norm_eps)
 
     def _mot(self, ptok, stok, positions: np.ndarray, q_limit, key_valid) -> torch.Tensor:
-        """_merged_attention_forward over both experts (dm0_arch.py:270-298): one Qwen3MotLayerFn per layer — through autograd when
-        gradients are on, its ``_run`` alone otherwise (the same launches: the same bits); only the action expert's final norm is
-        evaluated (prefix_out is never read).  -> suffix_out [B, chunk, d_a]"""
-        llm, exp, st = self.model.llm, self.model.action_expert, self.store
-        B, P, Sx = ptok.shape[0], ptok.shape[1], stok.shape[1]
-        geom = self._geom(B, P, Sx)
-        dev = st.device
-        cos_t, sin_t = llm.rope_tables(int(positions.max()) + 1, dev)
-        pos0 = hostcpu.upload(positions[:, :P].astype(np.int32), dev).reshape(-1)
-        pos1 = hostcpu.upload(positions[:, P:].astype(np.int32), dev).reshape(-1)
-        x0 = ptok.reshape(B * P, -1).contiguous()
-        x1 = stok.reshape(B * Sx, -1).contiguous()
-        n = llm.config.num_hidden_layers
-        grad = torch.is_grad_enabled()
-        for li in range(n):
-            sp0, sp1 = llm.layer_specs[li], exp.layer_specs[li]
-            if grad:
-                x0, x1 = Fn.Qwen3MotLayerFn.apply(x0, x1, st.params[sp1.down_w], st, sp0, sp1, geom, cos_t, sin_t, pos0, pos1,
-                                                  q_limit, key_valid, li == n - 1)
-            else:
-                (x0, x1), _ = Fn.Qwen3MotLayerFn._run(st, (sp0, sp1), geom, li == n - 1, x0, x1, cos_t, sin_t, pos0, pos1,
-                                                      q_limit, key_valid, keep=False)
-        return self._final_norm(x1).view(B, Sx, -1)
+        """_merged_attention_forward over both experts (dm0_arch.py:270-298): one MotLayerFn per layer (mot.MotPolicy._mot_layers);
+        only the action expert's final norm is evaluated (prefix_out is never read).  -> suffix_out [B, chunk, d_a]"""
+        return self._final_norm(self._mot_rows(ptok, stok, positions, q_limit, key_valid)).view(*stok.shape[:2], -1)
 
     # ------------------------------------------------------------------------------------- training
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None, inputs_embeds=None,
@@ -238,7 +208,7 @@ class DM0ForCausalLM(DexboticForCausalLM, ActionOutputForCausalLM):
         input_mask = np.concatenate([pmask, np.ones((B, n), dtype=bool)], axis=1)
         # cumsum of attn_mask = [1] * P + [1, 0, 0, ...]: 1 .. P over the (causal) prefix, P + 1 over the whole suffix block
         cum = np.broadcast_to(np.concatenate([np.arange(1, P + 1), np.full(n, P + 1)]).astype(np.int64), input_mask.shape)
-        q_limit, key_valid = Pi0ForCausalLM._mask_tensors(cum, input_mask, cum, input_mask, dev)
+        q_limit, key_valid = mask_tensors(cum, input_mask, cum, input_mask, dev)
         positions = np.maximum(np.cumsum(input_mask, axis=1) - 1, 0)       # (a padded first token would read row -1; it is never a key)
         te = hostcpu.upload(time, dev)[:, None, None]
         x_t = te * noise + (1 - te) * acts
@@ -251,20 +221,6 @@ class DM0ForCausalLM(DexboticForCausalLM, ActionOutputForCausalLM):
         return CausalLMOutputDexbotic(loss=loss, logits=v_t)
 
     # ------------------------------------------------------------------------------------ inference
-    def sampler_kv_buffers(self, B: int, cap: int):
-        """the sampler's per-layer (k, v) [B, Hkv, cap = P + chunk, D] buffers for this shape: allocated once and kept (a captured
-        graph holds their addresses), filled by the prefix pass and by every Euler step"""
-        c, st = self.config.llm_config, self.store
-        pool = self.__dict__.setdefault("_sampler_kv", {})
-        key = (B, cap, st.compute_dtype)
-        if key not in pool:
-            if len(pool) >= 8:
-                pool.pop(next(iter(pool)))
-            shape = (B, c.num_key_value_heads, cap, c.head_dim)
-            pool[key] = [(torch.empty(shape, device=st.device, dtype=st.compute_dtype),
-                          torch.empty(shape, device=st.device, dtype=st.compute_dtype)) for _ in range(c.num_hidden_layers)]
-        return pool[key]
-
     @torch.no_grad()
     def inference_action(self, input_ids=None, attention_mask=None, states=None, images=None, image_masks=None,
                          diffusion_steps: int = 10, **kwargs):
@@ -272,7 +228,6 @@ class DM0ForCausalLM(DexboticForCausalLM, ActionOutputForCausalLM):
         Returns the [B, chunk, A] tensor."""
         c, st = self.config, self.store
         dev = st.device
-        llm, exp = self.model.llm, self.model.action_expert
         B, n = states.shape[0], c.chunk_size
         dt = -1.0 / diffusion_steps
         noise = kwargs.get("noise")
@@ -281,55 +236,40 @@ class DM0ForCausalLM(DexboticForCausalLM, ActionOutputForCausalLM):
         pmask = self.prefix_mask(attention_mask, image_masks)
         P = pmask.shape[1]
         pcum = np.broadcast_to(np.arange(1, P + 1, dtype=np.int64), pmask.shape)
-        p_limit, p_valid = Pi0ForCausalLM._mask_tensors(pcum, pmask, pcum, pmask, dev)
+        p_limit, p_valid = mask_tensors(pcum, pmask, pcum, pmask, dev)
         ppos = np.maximum(np.cumsum(pmask, axis=1) - 1, 0)
         smask = np.ones((B, n), dtype=bool)
         scum = np.full((B, n), P + 1, dtype=np.int64)
-        q_limit, key_valid = Pi0ForCausalLM._mask_tensors(scum, smask, np.concatenate([pcum, scum], axis=1),
-                                                          np.concatenate([pmask, smask], axis=1), dev)
+        q_limit, key_valid = mask_tensors(scum, smask, np.concatenate([pcum, scum], axis=1),
+                                          np.concatenate([pmask, smask], axis=1), dev)
         fpos = pmask.sum(-1)[:, None] + np.cumsum(smask, axis=-1) - 1
         n_pos = int(max(fpos.max(), ppos.max())) + 1
-        cos_t, sin_t = llm.rope_tables(n_pos, dev)
+        cos_t, sin_t = self.model.llm.rope_tables(n_pos, dev)
         ppos_d = hostcpu.upload(ppos.astype(np.int32), dev).reshape(-1)
         pos = hostcpu.upload(fpos.astype(np.int32), dev).reshape(-1)
-        times, time = [], np.float32(1.0)
-        while time >= -dt / 2:                                            # the reference's float32 schedule (dm0_arch.py:571)
-            times.append(time)
-            time = np.float32(time + np.float32(dt))
+        times = list(takewhile(lambda t: t >= -dt / 2, flow_times(dt)))   # the reference's float32 schedule (dm0_arch.py:571)
         da = c.action_config.hidden_size
         te_table = hostcpu.upload(np.stack([posemb_sincos(np.full(B, t, dtype=np.float32), da) for t in times]), dev
                                   ).to(st.compute_dtype)                                            # [steps, B, da]
-        n_layers = llm.config.num_hidden_layers
         kv = self.sampler_kv_buffers(B, P + n)
         # ---- prefix pass: the llm alone, each layer's keys / values written straight into [0, P) of its buffer
-        h = self.get_prefix_hidden_states(input_ids, images).reshape(B * P, -1).contiguous()
-        geom_p = self._geom(B, P, 0)
-        for li in range(n_layers):
-            (h, _), _ = Fn.Qwen3MotLayerFn._run(st, (llm.layer_specs[li], None), geom_p, li == n_layers - 1, h, None, cos_t, sin_t,
-                                                ppos_d, None, p_limit, p_valid, keep=False, kv=kv[li], kv0=0)
-        del h
+        ptok = self.get_prefix_hidden_states(input_ids, images)
+        self._mot_layers(self._geom(B, P, 0), ptok.reshape(B * P, -1).contiguous(), None, None, cos_t, sin_t, ppos_d, None,
+                         p_limit, p_valid, kv=kv, kv0=0)
+        del ptok
         geom_s = self._geom(B, 0, n)
 
-        # ---- the Euler loop: tensors in / tensors out, replayed as ONE HIP graph (graphs.GraphCache).  The key / value buffers are
-        #      not inputs (inputs are copied into the graph's own memory): the graph reads and writes them where they are
+        # ---- the Euler loop: tensors in / tensors out; every step writes the suffix keys / values at [P, P + chunk) of the buffers
         def euler(x, te_table, q_limit, key_valid, pos):
             for s in range(len(times)):
                 h = self.get_suffix_hidden_states(x, None, te=te_table[s]).reshape(B * n, -1).contiguous()
-                for li in range(n_layers):
-                    (_, h), _ = Fn.Qwen3MotLayerFn._run(st, (None, exp.layer_specs[li]), geom_s, False, None, h, cos_t, sin_t, None,
-                                                        pos, q_limit, key_valid, keep=False, kv=kv[li], kv0=P)
+                _, h = self._mot_layers(geom_s, None, h, None, cos_t, sin_t, None, pos, q_limit, key_valid, kv=kv, kv0=P)
                 v_t = self._v_t(self._final_norm(h).view(B, n, -1))
                 x = K.add(x, K.scale_(v_t.contiguous(), dt))             # Euler step x += v dt
             return x
         inputs = dict(x=x, te_table=te_table, q_limit=q_limit, key_valid=key_valid, pos=pos)
-        from ... import graphs
-        if dev.type == "cuda" and kwargs.get("use_graph", graphs.enabled()):
-            gc_ = self.__dict__.setdefault("_sampler_graphs", graphs.GraphCache(dev))
-            # (a weight change needs no new capture: the graph reads the arena in place, and the prefix pass above — host code — has
-            #  already brought the bf16 shadows up to date)
-            key = ("euler", int(diffusion_steps), P, cos_t.data_ptr(), kv[0][0].data_ptr())
-            return gc_.run(key, euler, inputs).clone()
-        return euler(**inputs)
+        key = ("euler", int(diffusion_steps), P, cos_t.data_ptr(), kv[0][0].data_ptr())
+        return self._run_sampler(euler, inputs, key, kwargs.get("use_graph"))
 
 
 register_model_with_hf(DM0ForCausalLM)

@@ -3,7 +3,7 @@
 With ``use_adarms=False`` it is a Gemma decoder (``GemmaExpert`` serves it).  With ``use_adarms=True`` no norm has a gain: every
 ``GemmaRMSNorm`` owns ``dense = nn.Linear(adarms_cond_dim, 3 * hidden)`` whose output, per sample, is [scale | shift | gate]
 (modeling_gemma.py:38-89) — ``AdaRMSGemmaExpert`` registers those parameters and names the layers; the arithmetic is
-``functional.Pi05MotLayerFn`` (kernels dxa_adarms_* / dxa_gated_residual_*).
+``functional.MotLayerFn``'s adaptive-norm kind, chosen by ``ln1 is None`` (kernels dxa_adarms_* / dxa_gated_residual_*).
 
 Arena order: the 2 L + 1 ``dense`` weights lie back to back, and so do their biases, so that ONE product evaluates every norm's
 modulation (``functional.FusedLinearFn`` over ``dense_w`` / ``dense_b``).  The state-dict order is the reference's all the same

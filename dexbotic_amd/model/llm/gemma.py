@@ -6,7 +6,8 @@ GemmaRMSNorm (fp32 normalise, scale by 1 + weight), bias-free q/k/v/o, rotate-ha
 (gelu_pytorch_tanh(gate) * up), final norm.  Parameter names are HF's.  This module registers the parameters and
 names them per layer (``layer_specs``); the layer's launches are the two halves the mixture needs,
 ``functional.gemma_pre_attention`` (norm + fused QKV) and ``functional.gemma_post_attention`` (o_proj + residual +
-norm + MLP + residual), around ONE attention over BOTH experts' tokens (pi0_arch.py:161-191).
+norm + MLP + residual), around ONE attention over BOTH experts' tokens (pi0_arch.py:161-191): the Gemma kind of
+``functional.MotLayerFn``, which a ``GemmaLayerSpec`` with norm gains selects.
 """
 from __future__ import annotations
 

@@ -66,7 +66,7 @@ class Qwen3Backbone(Qwen2Backbone):
 
 class Qwen3Expert(Qwen3Backbone):
     """``Qwen3ForCausalLM(config).model`` with ``embed_tokens = None`` (dm0_arch.py:79-80): the action expert of DM0's mixture, which
-    is only ever fed embeddings.  The layers run through ``functional.Qwen3MotLayerFn`` together with the llm's."""
+    is only ever fed embeddings.  The layers run through ``functional.MotLayerFn`` together with the llm's."""
     has_embed_tokens = False
 
 

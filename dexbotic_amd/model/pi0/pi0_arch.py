@@ -8,11 +8,14 @@ it).  What differs is underneath: parameters live in the flat arenas of engine.P
 halves per expert around ONE attention call over both experts' tokens, with the reference's block mask expressed as
 per-query key counts + per-key validity (cumsum(ar_mask) is non-decreasing, so "cumsum[j] <= cumsum[i]" is a prefix).
 
-Training: ``forward`` builds the flow-matching loss through ``functional.Pi0MotLayerFn`` (one autograd node per
-layer over both experts, gradients written straight into the arena); inference: ``inference_action``.
+Every layer is ``functional.MotLayerFn`` (one autograd node per layer over both experts, gradients written straight into the
+arena; its ``_run`` alone when gradients are off and in the sampler), driven by what model/mot.py shares with pi0.5 and DM0.  The
+sampler keeps ONE key / value buffer [B, Hkv, P + 1 + chunk, D] per layer: the prefix pass writes [0, P), every Euler step the
+suffix slots behind it, and the loop is replayed as one HIP graph.
 """
 from __future__ import annotations
 
+from itertools import takewhile
 from typing import List, Optional
 
 import numpy as np
@@ -30,6 +33,7 @@ from ..llm.gemma import GemmaConfig, GemmaExpert
 from ..modules.mm_projector.builder import build_vision_projector
 from ..modules.mm_vision.builder import build_vision_tower
 from ..modules.mm_vision.siglip.siglip_encoder import SiglipVisionConfig
+from ..mot import MotPolicy, flow_times, mask_tensors
 
 
 class Pi0Config(_hf_config_base()):
@@ -142,7 +146,7 @@ def posemb_sincos(time: np.ndarray, dim: int, min_period: float = 4e-3, max_peri
     return np.concatenate([np.sin(x), np.cos(x)], axis=-1)
 
 
-class Pi0ForCausalLM(NativePreTrainedMixin, nn.Module, ActionOutputForCausalLM):
+class Pi0ForCausalLM(NativePreTrainedMixin, nn.Module, ActionOutputForCausalLM, MotPolicy):
     config_class = Pi0Config
     # trainer.NativeTrainer: the bias gradients' column sums (and any fp32 dW product) beside the dX chain on a side stream:
     # 250.0 -> 245.3 ms per step, two alternating runs each in one box (profiles/r06_memvla_hostbound.txt)
@@ -218,117 +222,29 @@ class Pi0ForCausalLM(NativePreTrainedMixin, nn.Module, ActionOutputForCausalLM):
         st, c = self.store, self.config
         cdt = st.compute_dtype
         B, da = states.shape[0], c.action_config.hidden_size
-        lin = lambda x, n, act=L.ACT_NONE: Fn.LinearFn.apply(x, st.params[f"model.{n}.weight"], st, f"model.{n}.weight",
-                                                             f"model.{n}.bias", act, None)
-        state_tok = lin(states.to(cdt), "state_proj").view(B, 1, da)
+        state_tok = self._lin(states.to(cdt), "state_proj").view(B, 1, da)
         if te is None:
             te = self._to_dev(posemb_sincos(time, da), st.device).to(cdt)                       # [B, da]
-        act_tok = lin(noisy_actions.to(cdt).reshape(B * c.chunk_size, -1), "action_in_proj").view(B, c.chunk_size, da)
+        act_tok = self._lin(noisy_actions.to(cdt).reshape(B * c.chunk_size, -1), "action_in_proj").view(B, c.chunk_size, da)
         h = torch.cat([act_tok, te[:, None, :].expand(B, c.chunk_size, da)], dim=-1).reshape(B * c.chunk_size, 2 * da)
-        h = lin(h.contiguous(), "action_time_mlp_in", L.ACT_SILU)
-        h = lin(h, "action_time_mlp_out").view(B, c.chunk_size, da)
+        h = self._lin(h.contiguous(), "action_time_mlp_in", L.ACT_SILU)
+        h = self._lin(h, "action_time_mlp_out").view(B, c.chunk_size, da)
         tokens = torch.cat([state_tok, h], dim=1)
         mask = np.ones((B, 1 + c.chunk_size), dtype=bool)
         ar = np.array([True, True] + [False] * (c.chunk_size - 1))
         return tokens, mask, ar
 
     # ------------------------------------------------------------------------------ mixture forward
-    @staticmethod
-    def _mask_tensors(q_cum: np.ndarray, q_valid: np.ndarray, k_cum: np.ndarray, k_valid: np.ndarray, device):
-        """block mask (pi0_arch.py:22-28) as the kernels take it: q_limit[b,i] = #keys with cumsum <= the query's
-        (keys are ordered, cumsum non-decreasing), key_valid[b,j] = input_mask.  Invalid queries get limit 0."""
-        lim = (k_cum[:, None, :] <= q_cum[:, :, None]).sum(-1).astype(np.int32)
-        lim[~q_valid] = 0
-        return Pi0ForCausalLM._to_dev(lim, device), Pi0ForCausalLM._to_dev(k_valid.astype(np.uint8), device)
+    def _final_norm(self, x: torch.Tensor) -> torch.Tensor:
+        exp = self.model.action_expert
+        return Fn.NormFn.apply(x, self.store.params[exp.p + "norm.weight"], self.store, "rms1p", exp.p + "norm.weight", None,
+                               exp.config.rms_norm_eps)
 
-    @torch.no_grad()
-    def _mot_forward(self, xs: List[Optional[torch.Tensor]], positions: Optional[np.ndarray], q_limit: torch.Tensor,
-                     key_valid: torch.Tensor, past: Optional[list] = None, collect: bool = False, pos_parts=None, rope=None,
-                     past_len: Optional[int] = None):
-        """_inner_forward_mot (pi0_arch.py:116-216) without autograd: xs = [llm tokens | None, expert tokens | None],
-        positions [B, S_q] int (RoPE), masks over [past keys ; new keys].  Returns ([out per expert], K/V cache)."""
-        experts = [self.model.llm, self.model.action_expert]
-        c = self.config.llm_config
-        Hq, Hkv, D = c.num_attention_heads, c.num_key_value_heads, c.head_dim
-        nq = (Hq + 2 * Hkv) * D
-        st = self.store
-        live = [(e, x) for e, x in zip(experts, xs) if x is not None]
-        B = live[0][1].shape[0]
-        lens = [x.shape[1] for _, x in live]
-        S = sum(lens)
-        dev = self.store.device
-        offs = np.cumsum([0] + lens)
-        if pos_parts is None:              # (the sampler hands in device tensors: nothing host-side inside its captured loop)
-            rope = experts[0].rope_tables(int(positions.max()) + 1, dev)
-            pos_parts = [self._to_dev(positions[:, offs[i]:offs[i + 1]].astype(np.int32), dev).reshape(-1) for i in range(len(live))]
-        cos_t, sin_t = rope
-        hs = [x.reshape(B * n, -1).contiguous() for (_, x), n in zip(live, lens)]
-        cache = []
-        for li in range(c.num_hidden_layers):
-            qs, ks, vs = [], [], []
-            # one request, one key/value head, one live expert, a cache with room behind the prefix (the sampler's Euler steps):
-            # the new keys / values are written straight behind the cached ones — no concatenation (36 launches a step)
-            kf, vf = past[li] if past is not None else (None, None)
-            inplace = (past is not None and past_len is not None and len(live) == 1 and B == 1 and Hkv == 1
-                       and kf.shape[2] == past_len + lens[0])
-            for (e, _), h, n, pp in zip(live, hs, lens, pos_parts):
-                _, _, qkv = Fn.gemma_pre_attention(st, e.layer_specs[li], h, nq)
-                if inplace:
-                    q, k, v = K.rope_split(qkv, cos_t, sin_t, pp, B, n, Hq, Hkv, D,
-                                           k_out=kf[:, :, past_len:], v_out=vf[:, :, past_len:])
-                else:
-                    q, k, v = K.rope_split(qkv, cos_t, sin_t, pp, B, n, Hq, Hkv, D)
-                del qkv
-                qs.append(q); ks.append(k); vs.append(v)
-            q = qs[0] if len(qs) == 1 else torch.cat(qs, dim=2)
-            k = ks[0] if len(ks) == 1 else torch.cat(ks, dim=2)
-            v = vs[0] if len(vs) == 1 else torch.cat(vs, dim=2)
-            if collect:
-                cache.append((k, v))
-            if inplace:
-                k, v = kf, vf
-            elif past is not None:
-                k = torch.cat([kf[:, :, :past_len], k], dim=2)
-                v = torch.cat([vf[:, :, :past_len], v], dim=2)
-            o = torch.empty((B, S, Hq, D), device=dev, dtype=q.dtype)
-            K.attn_fwd(q, k, v, o.permute(0, 2, 1, 3), causal=False, scale=D ** -0.5, q_limit=q_limit, key_valid=key_valid)
-            nxt = []
-            for i, ((e, _), h, n) in enumerate(zip(live, hs, lens)):
-                a2 = o[:, offs[i]:offs[i + 1]].reshape(B * n, Hq * D)
-                y, _ = Fn.gemma_post_attention(st, e.layer_specs[li], h, a2.contiguous())
-                nxt.append(y)
-            hs = nxt
-        outs, it = [], iter(zip(live, hs, lens))
-        for x in xs:
-            if x is None:
-                outs.append(None)
-            else:
-                (e, _), h, n = next(it)
-                y, _ = K.rmsnorm_fwd(h, Fn.gemma_norm_w(st, e.p + "norm.weight"), e.config.rms_norm_eps)
-                outs.append(y.view(B, n, -1))
-        return outs, cache
-
-    def _mot_train(self, ptok, stok, positions, q_limit, key_valid) -> torch.Tensor:
-        """the mixture with autograd: one Pi0MotLayerFn per layer over both experts; only the action expert's final
-        norm is evaluated (prefix_out is never read by the loss, pi0_arch.py:372-388)"""
-        llm, exp, st = self.model.llm, self.model.action_expert, self.store
-        c = self.config.llm_config
-        B, P, Sx = ptok.shape[0], ptok.shape[1], stok.shape[1]
-        geom = (B, P, Sx, c.num_attention_heads, c.num_key_value_heads, c.head_dim)
-        dev = st.device
-        cos_t, sin_t = llm.rope_tables(int(positions.max()) + 1, dev)
-        pos0 = self._to_dev(positions[:, :P].astype(np.int32), dev).reshape(-1)
-        pos1 = self._to_dev(positions[:, P:].astype(np.int32), dev).reshape(-1)
-        x0 = ptok.reshape(B * P, -1).contiguous()
-        x1 = stok.reshape(B * Sx, -1).contiguous()
-        n = c.num_hidden_layers
-        for li in range(n):
-            sp0, sp1 = llm.layer_specs[li], exp.layer_specs[li]
-            x0, x1 = Fn.Pi0MotLayerFn.apply(x0, x1, st.params[sp1.down], st, sp0, sp1, geom, cos_t, sin_t, pos0, pos1,
-                                            q_limit, key_valid, li == n - 1)
-        y = Fn.NormFn.apply(x1, st.params[exp.p + "norm.weight"], st, "rms1p", exp.p + "norm.weight", None,
-                            exp.config.rms_norm_eps)
-        return y.view(B, Sx, -1)
+    def _mot(self, ptok, stok, positions: np.ndarray, q_limit, key_valid) -> torch.Tensor:
+        """_inner_forward_mot over both experts (pi0_arch.py:116-216): one MotLayerFn per layer (mot.MotPolicy._mot_layers); only the
+        action expert's final norm is evaluated (prefix_out is never read by the loss, pi0_arch.py:372-388)
+        -> suffix_out [B, 1 + chunk, d_a]"""
+        return self._final_norm(self._mot_rows(ptok, stok, positions, q_limit, key_valid)).view(*stok.shape[:2], -1)
 
     # ------------------------------------------------------------------------------------- training
     def forward(self, input_ids=None, attention_mask=None, actions=None, states=None, images=None, image_masks=None,
@@ -350,22 +266,15 @@ class Pi0ForCausalLM(NativePreTrainedMixin, nn.Module, ActionOutputForCausalLM):
         sar = np.array([True, True] + [False] * (c.chunk_size - 1))
         input_mask = np.concatenate([pmask, smask], axis=1)
         cum = np.broadcast_to(np.cumsum(np.concatenate([np.zeros(pmask.shape[1], dtype=bool), sar]).astype(np.int64)), input_mask.shape)
-        q_limit, key_valid = self._mask_tensors(cum, input_mask, cum, input_mask, dev)
-        positions = np.cumsum(input_mask, axis=1) - 1
+        q_limit, key_valid = mask_tensors(cum, input_mask, cum, input_mask, dev)
+        positions = np.maximum(np.cumsum(input_mask, axis=1) - 1, 0)       # (a padded first token would read row -1; it is never a key)
         te = self._to_dev(time, dev)[:, None, None]
         x_t = te * noise + (1 - te) * acts
         u_t = noise - acts
         ptok, pmask2, par = self.embed_prefix(input_ids, attention_mask, images, image_masks, input_mask=pmask)
         stok, smask2, sar2 = self.embed_suffix(states.to(dev).float(), x_t, time)
         assert smask2.shape == smask.shape and np.array_equal(sar2, sar) and not par.any()
-        st = self.store
-        if torch.is_grad_enabled():
-            suf = self._mot_train(ptok, stok, positions, q_limit, key_valid)
-        else:
-            (_, suf), _ = self._mot_forward([ptok, stok], positions, q_limit, key_valid)
-        v_t = Fn.LinearFn.apply(suf[:, -c.chunk_size:].reshape(B * c.chunk_size, -1).contiguous(),
-                                st.params["model.action_out_proj.weight"], st, "model.action_out_proj.weight",
-                                "model.action_out_proj.bias", L.ACT_NONE, None).view(B, c.chunk_size, -1).float()
+        v_t = self._v_t(self._mot(ptok, stok, positions, q_limit, key_valid))
         loss = Fn.MseLossFn.apply(v_t.contiguous(), u_t.contiguous())
         return CausalLMOutputDexbotic(loss=loss, logits=v_t)
 
@@ -373,69 +282,58 @@ class Pi0ForCausalLM(NativePreTrainedMixin, nn.Module, ActionOutputForCausalLM):
     @torch.no_grad()
     def inference_action(self, input_ids=None, attention_mask=None, states=None, images=None, image_masks=None,
                          diffusion_steps: int = 10, **kwargs):
-        """pi0_arch.py:402-491.  kwarg ``noise`` [B,chunk,A] injects the initial sample.  Returns the [B,chunk,A]
-        tensor (the exp layer de-normalises and slices, pi0_exp.py:484-514)."""
+        """pi0_arch.py:402-491.  kwarg ``noise`` [B,chunk,A] injects the initial sample, ``use_graph`` overrides the graph switch.
+        Returns the [B,chunk,A] tensor (the exp layer de-normalises and slices, pi0_exp.py:484-514)."""
         c, dev, st = self.config, self.store.device, self.store
-        B = states.shape[0]
+        B, n = states.shape[0], c.chunk_size
         dt = -1.0 / diffusion_steps
         noise = kwargs.get("noise")
-        x = (torch.randn(B, c.chunk_size, c.action_dim, device=dev) if noise is None else noise.to(dev)).float().contiguous()
+        x = (torch.randn(B, n, c.action_dim, device=dev) if noise is None else noise.to(dev)).float().contiguous()
         # host side first (masks, positions, the schedule's time embeddings: they depend on the input masks only), uploaded through
         # pinned memory — then the device work of the request is enqueued without a single wait on the stream
         pmask = self.prefix_mask(attention_mask, image_masks)
+        P, Sx = pmask.shape[1], 1 + n
         pcum = np.zeros(pmask.shape, dtype=np.int64)
-        p_limit, p_valid = self._mask_tensors(pcum, pmask, pcum, pmask, dev)
-        ppos = np.cumsum(pmask, axis=1) - 1
-        # ---- the Euler loop: everything that does not depend on x is prepared once (masks, positions, RoPE tables, the time
-        #      embeddings of the whole schedule), the loop itself is tensors in / tensors out and is replayed as ONE HIP graph
-        #      (graphs.GraphCache): 10 steps x 18 layers x ~14 tiny launches are host-bound when issued from Python
-        smask = np.ones((B, 1 + c.chunk_size), dtype=bool)
-        sar = np.array([True, True] + [False] * (c.chunk_size - 1))
+        p_limit, p_valid = mask_tensors(pcum, pmask, pcum, pmask, dev)
+        ppos = np.maximum(np.cumsum(pmask, axis=1) - 1, 0)
+        smask = np.ones((B, Sx), dtype=bool)
+        sar = np.array([True, True] + [False] * (n - 1))
         scum = np.broadcast_to(np.cumsum(sar.astype(np.int64)), smask.shape)
         # keys = [cached prefix (all visible where valid: cumsum 0) ; suffix]; queries = suffix (cumsum >= 1)
-        k_cum = np.concatenate([np.zeros_like(pmask, dtype=np.int64), scum], axis=1)
-        k_valid = np.concatenate([pmask, smask], axis=1)
-        q_limit, key_valid = self._mask_tensors(scum, smask, k_cum, k_valid, dev)
+        q_limit, key_valid = mask_tensors(scum, smask, np.concatenate([pcum, scum], axis=1),
+                                          np.concatenate([pmask, smask], axis=1), dev)
         fpos = pmask.sum(-1)[:, None] + np.cumsum(smask, axis=-1) - 1
-        rope = self.model.llm.rope_tables(int(fpos.max()) + 1, dev)
+        cos_t, sin_t = self.model.llm.rope_tables(int(max(fpos.max(), ppos.max())) + 1, dev)
+        ppos_d = self._to_dev(ppos.astype(np.int32), dev).reshape(-1)
         pos = self._to_dev(fpos.astype(np.int32), dev).reshape(-1)
-        times, time = [], np.float32(1.0)
-        while time > -dt / 2:                                             # the reference's float32 schedule (pi0_arch.py:470-489)
-            times.append(time)
-            time = np.float32(time + np.float32(dt))
+        times = list(takewhile(lambda t: t > -dt / 2, flow_times(dt)))    # the reference's float32 schedule (pi0_arch.py:470-489)
         da = c.action_config.hidden_size
         te_table = self._to_dev(np.stack([posemb_sincos(np.full(B, t, dtype=np.float32), da) for t in times]), dev
                                 ).to(st.compute_dtype)                                            # [steps, B, da]
+        kv = self.sampler_kv_buffers(B, P + Sx)
+        # ---- prefix pass: the llm alone, each layer's keys / values written straight into [0, P) of its buffer
         ptok, _, par = self.embed_prefix(input_ids, attention_mask, images, image_masks, input_mask=pmask)
         assert not par.any()
-        _, cache = self._mot_forward([ptok, None], ppos, p_limit, p_valid, collect=True)
+        self._mot_layers(self._geom(B, P, 0), ptok.reshape(B * P, -1).contiguous(), None, None, cos_t, sin_t, ppos_d, None,
+                         p_limit, p_valid, kv=kv, kv0=0)
         states_d = states.to(dev).float().contiguous()
-        n_layers = len(cache)
+        geom_s = self._geom(B, 0, Sx)
 
-        P_len, Sx = int(cache[0][0].shape[2]), int(smask.shape[1])
-
-        def euler(x, states_d, te_table, q_limit, key_valid, pos, **kv):
-            # per layer ONE buffer [prefix keys ; room for the suffix keys], filled behind the prefix by every step's RoPE kernel
-            past = [tuple(torch.cat([kv[f"{n}{i}"], kv[f"{n}{i}"].new_zeros(B, kv[f"{n}{i}"].shape[1], Sx, kv[f"{n}{i}"].shape[3])], dim=2)
-                          for n in ("k", "v")) for i in range(n_layers)]
+        # ---- the Euler loop: everything that does not depend on x is prepared above, the loop itself is tensors in / tensors out
+        #      (10 steps x 18 layers x ~14 tiny launches are host-bound when issued from Python); every step's RoPE launch writes the
+        #      suffix keys / values behind the prefix, at [P, P + 1 + chunk) of the layer's buffer
+        def euler(x, states_d, te_table, q_limit, key_valid, pos):
             for s in range(len(times)):
                 stok, _, _ = self.embed_suffix(states_d, x, None, te=te_table[s])
-                (_, suf), _ = self._mot_forward([None, stok], None, q_limit, key_valid, past=past, pos_parts=[pos], rope=rope,
-                                                past_len=P_len)
-                v_t = Fn.LinearFn.apply(suf[:, -c.chunk_size:].reshape(B * c.chunk_size, -1).contiguous(),
-                                        st.params["model.action_out_proj.weight"], st, "model.action_out_proj.weight",
-                                        "model.action_out_proj.bias", L.ACT_NONE, None).view(B, c.chunk_size, -1).float()
+                _, h = self._mot_layers(geom_s, None, stok.reshape(B * Sx, -1).contiguous(), None, cos_t, sin_t, None, pos,
+                                        q_limit, key_valid, kv=kv, kv0=P)
+                v_t = self._v_t(self._final_norm(h).view(B, Sx, -1))
                 x = K.add(x, K.scale_(v_t.contiguous(), dt))             # Euler step x += v dt
             return x
         inputs = dict(x=x, states_d=states_d, te_table=te_table, q_limit=q_limit, key_valid=key_valid, pos=pos)
-        for i, (k_, v_) in enumerate(cache):
-            inputs[f"k{i}"], inputs[f"v{i}"] = k_.contiguous(), v_.contiguous()
-        from ... import graphs
-        if dev.type == "cuda" and kwargs.get("use_graph", graphs.enabled()):
-            gc_ = self.__dict__.setdefault("_sampler_graphs", graphs.GraphCache(dev))
-            Fn.gemma_norm_refresh(st)      # the graph holds the action expert's (1 + w) tensors; only host code notices a weight change
-            return gc_.run(("euler", int(diffusion_steps), int(fpos.max()), rope[0].data_ptr()), euler, inputs).clone()
-        return euler(**inputs)
+        key = ("euler", int(diffusion_steps), P, cos_t.data_ptr(), kv[0][0].data_ptr())
+        return self._run_sampler(euler, inputs, key, kwargs.get("use_graph"))
+
 
 
 from ..dexbotic_arch import register_model_with_hf  # noqa: E402

@@ -11,14 +11,15 @@ adds of the layer are x + y gate.  So: no state token and no ``state_proj`` (``s
 ``chunk_size`` action tokens ([True, False, ...]: one bidirectional block behind the bidirectional prefix), the final norm is adaptive
 too (its gate is unused).
 
-Every layer is ``functional.Pi05MotLayerFn`` — through autograd when gradients are on, its ``_run`` alone otherwise and in the
-sampler.  The 2 L + 1 dense layers are ONE product (``functional.FusedLinearFn``: their weights lie back to back in the arena); the
+Every layer is ``functional.MotLayerFn`` — through autograd when gradients are on, its ``_run`` alone otherwise and in the
+sampler (the llm is its Gemma kind, the action expert its adaptive-norm kind; model/mot.py holds what pi0, pi0.5 and DM0 share).  The 2 L + 1 dense layers are ONE product (``functional.FusedLinearFn``: their weights lie back to back in the arena); the
 sampler evaluates it once for the whole Euler schedule, before the loop (the condition depends on the time alone).  The sampler
 keeps ONE key / value buffer [B, Hkv, P + chunk, D] per layer as DM0's does, and replays the loop as one HIP graph.
 """
 from __future__ import annotations
 
 from collections import OrderedDict
+from itertools import takewhile
 from typing import List, Optional
 
 import numpy as np
@@ -36,6 +37,7 @@ from ..llm.gemma import GemmaExpert
 from ..modules.mm_projector.builder import build_vision_projector
 from ..modules.mm_vision.builder import build_vision_tower
 from ..modules.mm_vision.siglip.siglip_encoder import SiglipVisionConfig
+from ..mot import flow_times, mask_tensors
 from ..pi0.pi0_arch import Pi0Config, Pi0ForCausalLM, posemb_sincos
 
 _GEOMETRY = ("num_hidden_layers", "num_attention_heads", "num_key_value_heads", "head_dim")
@@ -173,10 +175,6 @@ class Pi05ForCausalLM(Pi0ForCausalLM):
     # k / v projections and the llm's final norm get no gradient here either
 
     # ------------------------------------------------------------------------------------ embeddings
-    def _lin(self, x, n: str, act=L.ACT_NONE):
-        st = self.store
-        return Fn.LinearFn.apply(x, st.params[f"model.{n}.weight"], st, f"model.{n}.weight", f"model.{n}.bias", act, None)
-
     def modulations(self, te: torch.Tensor) -> torch.Tensor:
         """sin/cos time embeddings te [R, d_a] (one row per sample, or per (step, sample) of a schedule) -> the modulation of every
         adaptive norm [2 L + 1, R, 3 d_a]: adarms_cond = silu(time_mlp_out(silu(time_mlp_in(te)))) (pi05_arch.py:310-317), then all
@@ -196,42 +194,17 @@ class Pi05ForCausalLM(Pi0ForCausalLM):
         tok = self._lin(noisy_actions.to(cdt).reshape(B * n, -1), "action_in_proj").view(B, n, da)
         return tok, self.modulations(te)
 
-    def _v_t(self, suf: torch.Tensor) -> torch.Tensor:
-        B, n = suf.shape[0], self.config.chunk_size
-        return self._lin(suf[:, -n:].reshape(B * n, -1).contiguous(), "action_out_proj").view(B, n, -1).float()
-
     # ------------------------------------------------------------------------------ mixture forward
-    def _geom(self, B: int, S0: int, S1: int):
-        c = self.config.llm_config
-        return (B, S0, S1, c.num_attention_heads, c.num_key_value_heads, c.head_dim)
-
     def _mot(self, ptok, stok, mods, positions: np.ndarray, q_limit, key_valid) -> torch.Tensor:
-        """_inner_forward_mot over both experts: one Pi05MotLayerFn per layer — through autograd when gradients are on, its ``_run``
-        alone otherwise (the same launches: the same bits); only the action expert's final norm is evaluated.
-        -> suffix_out [B, chunk, d_a]"""
-        llm, exp, st = self.model.llm, self.model.action_expert, self.store
-        B, P, Sx = ptok.shape[0], ptok.shape[1], stok.shape[1]
-        geom = self._geom(B, P, Sx)
-        dev = st.device
-        cos_t, sin_t = llm.rope_tables(int(positions.max()) + 1, dev)
-        pos0 = hostcpu.upload(positions[:, :P].astype(np.int32), dev).reshape(-1)
-        pos1 = hostcpu.upload(positions[:, P:].astype(np.int32), dev).reshape(-1)
-        x0 = ptok.reshape(B * P, -1).contiguous()
-        x1 = stok.reshape(B * Sx, -1).contiguous()
-        n = llm.config.num_hidden_layers
-        eps = exp.config.rms_norm_eps
-        if torch.is_grad_enabled():
-            mods = mods.unbind(0)
-            for li in range(n):
-                sp0, sp1 = llm.layer_specs[li], exp.layer_specs[li]
-                x0, x1 = Fn.Pi05MotLayerFn.apply(x0, x1, mods[2 * li], mods[2 * li + 1], st.params[sp1.down], st, sp0, sp1, geom,
-                                                 cos_t, sin_t, pos0, pos1, q_limit, key_valid, li == n - 1)
-            return Fn.AdaRMSNormFn.apply(x1, mods[2 * n], eps).view(B, Sx, -1)
-        for li in range(n):
-            (x0, x1), _ = Fn.Pi05MotLayerFn._run(st, (llm.layer_specs[li], exp.layer_specs[li]), geom, li == n - 1, x0, x1,
-                                                 mods[2 * li], mods[2 * li + 1], cos_t, sin_t, pos0, pos1, q_limit, key_valid,
-                                                 keep=False)
-        return K.adarms_fwd(x1, mods[2 * n], eps)[0].view(B, Sx, -1)
+        """_inner_forward_mot over both experts: one MotLayerFn per layer (mot.MotPolicy._mot_layers) with the layer's two modulations;
+        only the action expert's final norm is evaluated.  -> suffix_out [B, chunk, d_a]"""
+        n, eps = self.model.llm.config.num_hidden_layers, self.model.action_expert.config.rms_norm_eps
+        grad = torch.is_grad_enabled()
+        if grad:
+            mods = mods.unbind(0)                 # (one autograd node for all 2 L + 1 modulations)
+        x1 = self._mot_rows(ptok, stok, positions, q_limit, key_valid, mods)
+        y = Fn.AdaRMSNormFn.apply(x1, mods[2 * n], eps) if grad else K.adarms_fwd(x1, mods[2 * n], eps)[0]
+        return y.view(*stok.shape[:2], -1)
 
     # ------------------------------------------------------------------------------------- training
     def forward(self, input_ids=None, attention_mask=None, actions=None, states=None, images=None, image_masks=None,
@@ -252,7 +225,7 @@ class Pi05ForCausalLM(Pi0ForCausalLM):
         input_mask = np.concatenate([pmask, np.ones((B, n), dtype=bool)], axis=1)
         # cumsum of ar_mask = [False] * P + [True, False, ...]: 0 over the (bidirectional) prefix, 1 over the whole suffix block
         cum = np.broadcast_to(np.concatenate([np.zeros(P), np.ones(n)]).astype(np.int64), input_mask.shape)
-        q_limit, key_valid = self._mask_tensors(cum, input_mask, cum, input_mask, dev)
+        q_limit, key_valid = mask_tensors(cum, input_mask, cum, input_mask, dev)
         positions = np.maximum(np.cumsum(input_mask, axis=1) - 1, 0)       # (a padded first token would read row -1; it is never a key)
         te = hostcpu.upload(time, dev)[:, None, None]
         x_t = te * noise + (1 - te) * acts
@@ -265,20 +238,6 @@ class Pi05ForCausalLM(Pi0ForCausalLM):
         return CausalLMOutputDexbotic(loss=loss, logits=v_t)
 
     # ------------------------------------------------------------------------------------ inference
-    def sampler_kv_buffers(self, B: int, cap: int):
-        """the sampler's per-layer (k, v) [B, Hkv, cap = P + chunk, D] buffers for this shape: allocated once and kept (a captured
-        graph holds their addresses), filled by the prefix pass and by every Euler step"""
-        c, st = self.config.llm_config, self.store
-        pool = self.__dict__.setdefault("_sampler_kv", {})
-        key = (B, cap, st.compute_dtype)
-        if key not in pool:
-            if len(pool) >= 8:
-                pool.pop(next(iter(pool)))
-            shape = (B, c.num_key_value_heads, cap, c.head_dim)
-            pool[key] = [(torch.empty(shape, device=st.device, dtype=st.compute_dtype),
-                          torch.empty(shape, device=st.device, dtype=st.compute_dtype)) for _ in range(c.num_hidden_layers)]
-        return pool[key]
-
     @torch.no_grad()
     def inference_action(self, input_ids=None, attention_mask=None, states=None, images=None, image_masks=None,
                          diffusion_steps: int = 10, **kwargs):
@@ -295,21 +254,18 @@ class Pi05ForCausalLM(Pi0ForCausalLM):
         pmask = self.prefix_mask(attention_mask, image_masks)
         P = pmask.shape[1]
         pcum = np.zeros(pmask.shape, dtype=np.int64)
-        p_limit, p_valid = self._mask_tensors(pcum, pmask, pcum, pmask, dev)
+        p_limit, p_valid = mask_tensors(pcum, pmask, pcum, pmask, dev)
         ppos = np.maximum(np.cumsum(pmask, axis=1) - 1, 0)
         smask = np.ones((B, n), dtype=bool)
         scum = np.ones((B, n), dtype=np.int64)
-        q_limit, key_valid = self._mask_tensors(scum, smask, np.concatenate([pcum, scum], axis=1),
+        q_limit, key_valid = mask_tensors(scum, smask, np.concatenate([pcum, scum], axis=1),
                                                 np.concatenate([pmask, smask], axis=1), dev)
         fpos = pmask.sum(-1)[:, None] + np.cumsum(smask, axis=-1) - 1
         n_pos = int(max(fpos.max(), ppos.max())) + 1
         cos_t, sin_t = llm.rope_tables(n_pos, dev)
         ppos_d = hostcpu.upload(ppos.astype(np.int32), dev).reshape(-1)
         pos = hostcpu.upload(fpos.astype(np.int32), dev).reshape(-1)
-        times, time = [], np.float32(1.0)
-        while time > -dt / 2:                                             # the reference's float32 schedule (pi05_arch.py:512)
-            times.append(time)
-            time = np.float32(time + np.float32(dt))
+        times = list(takewhile(lambda t: t > -dt / 2, flow_times(dt)))    # the reference's float32 schedule (pi05_arch.py:512)
         da = c.action_config.hidden_size
         te = hostcpu.upload(np.concatenate([posemb_sincos(np.full(B, t, dtype=np.float32), da) for t in times]), dev
                             ).to(st.compute_dtype)                                                  # [steps * B, da]
@@ -321,37 +277,23 @@ class Pi05ForCausalLM(Pi0ForCausalLM):
         # ---- prefix pass: the llm alone, each layer's keys / values written straight into [0, P) of its buffer
         ptok, _, par = self.embed_prefix(input_ids, attention_mask, images, image_masks, input_mask=pmask)
         assert not par.any()
-        h = ptok.reshape(B * P, -1).contiguous()
-        geom_p = self._geom(B, P, 0)
-        for li in range(n_layers):
-            (h, _), _ = Fn.Pi05MotLayerFn._run(st, (llm.layer_specs[li], None), geom_p, li == n_layers - 1, h, None, None, None,
-                                               cos_t, sin_t, ppos_d, None, p_limit, p_valid, keep=False, kv=kv[li], kv0=0)
-        del h
+        self._mot_layers(self._geom(B, P, 0), ptok.reshape(B * P, -1).contiguous(), None, None, cos_t, sin_t, ppos_d, None,
+                         p_limit, p_valid, kv=kv, kv0=0)
         geom_s = self._geom(B, 0, n)
         eps = exp.config.rms_norm_eps
 
-        # ---- the Euler loop: tensors in / tensors out, replayed as ONE HIP graph (graphs.GraphCache).  The key / value buffers are
-        #      not inputs (inputs are copied into the graph's own memory): the graph reads and writes them where they are
+        # ---- the Euler loop: tensors in / tensors out; every step writes the suffix keys / values at [P, P + chunk) of the buffers
         def euler(x, mods, q_limit, key_valid, pos):
             for s in range(len(times)):
                 h = self._lin(x.to(st.compute_dtype).reshape(B * n, -1), "action_in_proj")
-                for li in range(n_layers):
-                    (_, h), _ = Fn.Pi05MotLayerFn._run(st, (None, exp.layer_specs[li]), geom_s, False, None, h, mods[s, 2 * li],
-                                                       mods[s, 2 * li + 1], cos_t, sin_t, None, pos, q_limit, key_valid,
-                                                       keep=False, kv=kv[li], kv0=P)
+                _, h = self._mot_layers(geom_s, None, h, mods[s], cos_t, sin_t, None, pos, q_limit, key_valid, kv=kv, kv0=P)
                 v_t = self._v_t(K.adarms_fwd(h, mods[s, 2 * n_layers], eps)[0].view(B, n, -1))
                 x = K.add(x, K.scale_(v_t.contiguous(), dt))             # Euler step x += v dt
             return x
         inputs = dict(x=x, mods=mods, q_limit=q_limit, key_valid=key_valid, pos=pos)
-        from ... import graphs
-        if dev.type == "cuda" and kwargs.get("use_graph", graphs.enabled()):
-            gc_ = self.__dict__.setdefault("_sampler_graphs", graphs.GraphCache(dev))
-            # (a weight change needs no new capture: the graph reads the arena in place, the modulations are inputs formed above, and
-            #  the prefix pass — host code — has already brought the bf16 shadows up to date)
-            Fn.gemma_norm_refresh(st)
-            key = ("euler", int(diffusion_steps), P, cos_t.data_ptr(), kv[0][0].data_ptr())
-            return gc_.run(key, euler, inputs).clone()
-        return euler(**inputs)
+        # (a weight change needs no new capture: the modulations are inputs formed above)
+        key = ("euler", int(diffusion_steps), P, cos_t.data_ptr(), kv[0][0].data_ptr())
+        return self._run_sampler(euler, inputs, key, kwargs.get("use_graph"))
 
 
 register_model_with_hf(Pi05ForCausalLM)

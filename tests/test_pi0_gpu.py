@@ -91,6 +91,47 @@ def test_pi0_sampler_graph_follows_a_weight_change(golden_dir):
         assert not torch.equal(got, before), dtype
 
 
+def test_pi0_sampler_writes_suffix_keys_behind_the_cached_prefix_in_place(golden_dir, monkeypatch):
+    """pi0's sampler holds its keys as DM0's does: every mixture attention call of the request — the prefix pass and all ten Euler
+    steps — reads ONE buffer per layer, at the address it had before the request; the suffix slots [P, P + 1 + chunk) hold nothing
+    the sampler reads before it has written them (poisoned beforehand: the same result).  The toy fixture has B = 3 (not 2) and one
+    key / value head: with B > 1 each request's slots are a strided slice of the buffer."""
+    from dexbotic_amd import kernels as K
+    g, m = build(golden_dir, "float32")
+    c = m.config
+    B, Hkv, n, steps = g["input_ids"].shape[0], c.llm_config.num_key_value_heads, c.chunk_size, 10
+    assert B == 3 and Hkv == 1
+    P = g["image_masks"].shape[1] * m.model.mm_vision_tower.num_patches + g["input_ids"].shape[1]
+    kw = dict(input_ids=T(g["input_ids"]), attention_mask=T(g["attention_mask"]), states=T(g["states"]), images=T(g["images"]),
+              image_masks=T(g["image_masks"]), diffusion_steps=steps, noise=T(g["init_noise"]), use_graph=False)
+    want = m.inference_action(**kw).clone()
+    kv = m.sampler_kv_buffers(B, P + 1 + n)
+    layers = c.llm_config.num_hidden_layers
+    assert len(kv) == layers and all(t.shape == (B, Hkv, P + 1 + n, c.llm_config.head_dim) for pair in kv for t in pair)
+    ptrs = [(k.data_ptr(), v.data_ptr()) for k, v in kv]
+    for k, v in kv:
+        k[:, :, P:].fill_(float("nan"))
+        v[:, :, P:].fill_(float("nan"))
+    seen = []
+    real = K.attn_fwd
+
+    def spy(q, k, v, o, **kwargs):
+        seen.append((k.data_ptr(), v.data_ptr(), k.shape[2], q.shape[2]))
+        return real(q, k, v, o, **kwargs)
+    monkeypatch.setattr(K, "attn_fwd", spy)
+    got = m.inference_action(**kw)
+    monkeypatch.undo()
+    assert torch.equal(got, want)
+    tower_calls = len(seen) - layers * (1 + steps)
+    calls = seen[tower_calls:]                                   # the vision tower's attention comes first
+    assert tower_calls >= 0 and len(calls) == layers * (1 + steps)
+    for i, (kp, vp, Sk, Sq) in enumerate(calls):
+        li = i % layers
+        assert (kp, vp) == ptrs[li], (i, "a key / value tensor other than the layer's buffer was attended to")
+        assert (Sk, Sq) == ((P, P) if i < layers else (P + 1 + n, 1 + n)), i
+    assert [(k.data_ptr(), v.data_ptr()) for k, v in m.sampler_kv_buffers(B, P + 1 + n)] == ptrs
+
+
 def test_fp32_pi0_forward_loss_matches_reference(golden_dir):
     g, m = build(golden_dir, "float32")
     with torch.no_grad():
@@ -103,9 +144,9 @@ def test_fp32_pi0_forward_loss_matches_reference(golden_dir):
 
 @pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
 def test_pi0_forward_without_and_with_autograd_is_one_arithmetic(golden_dir, dtype):
-    """the loss under torch.no_grad() (_mot_forward, both experts live) and with gradients enabled (_mot_train, Pi0MotLayerFn) in
-    the same module mode: both callers run functional.gemma_pre_attention / gemma_post_attention around the same attention launch,
-    so the losses are the same bits"""
+    """the loss under torch.no_grad() (MotLayerFn._run alone) and with gradients enabled (through the Function) in the same module
+    mode: the same launches, functional.gemma_pre_attention / gemma_post_attention around the same attention launch, so the losses
+    are the same bits"""
     g, m = build(golden_dir, dtype, train=True)
     m.store.set_expected(m.unused_parameter_names())
     m.store.begin_step()

@@ -77,7 +77,7 @@ def test_recompute_under_two_micro_batch_accumulation_and_clip(golden_dir):
 
 
 def test_pi0_step_with_recompute_is_bit_identical(golden_dir):
-    """pi0 trains with gradient_checkpointing too (pi0_exp.py:97): the dual-expert layer (Pi0MotLayerFn) and the SigLIP blocks"""
+    """pi0 trains with gradient_checkpointing too (pi0_exp.py:97): the dual-expert layer (MotLayerFn) and the SigLIP blocks"""
     from tests.test_pi0_gpu import T, build
     res = {}
     for dtype in ("float32", "bfloat16"):
