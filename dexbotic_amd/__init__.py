@@ -31,6 +31,7 @@ def model_registry():
     from .model.cogact.cogact_arch import CogActConfig, CogACTForCausalLM
     from .model.dexbotic_arch import DexboticConfig, DexboticForCausalLM
     from .model.dm0.dm0_arch import DM0Config, DM0ForCausalLM
+    from .model.dm0.dm0_prog_arch import DM0ProgConfig, DM0ProgForCausalLM
     from .model.memvla.memvla_arch import MemVLAConfig, MemVLAForCausalLM
     from .model.navila.navila_arch import NaVILAConfig, NaVILAForCausalLM
     from .model.oft.oft_arch import OFTConfig, OFTForCausalLM
@@ -43,6 +44,7 @@ def model_registry():
             "dexbotic_memvla": (MemVLAConfig, MemVLAForCausalLM),
             "dexbotic_navila": (NaVILAConfig, NaVILAForCausalLM),
             "dexbotic_dm0": (DM0Config, DM0ForCausalLM),
+            "dexbotic_dm0_prog": (DM0ProgConfig, DM0ProgForCausalLM),
             "dexbotic_pi05": (Pi05Config, Pi05ForCausalLM),
             "dexbotic_oft": (OFTConfig, OFTForCausalLM),
             "dexbotic_oft_discrete": (OFTDiscreteConfig, OFTDiscreteForCausalLM)}

@@ -802,6 +802,60 @@ def action_bins_fwd(h: torch.Tensor, off: torch.Tensor, w_bins: torch.Tensor, n_
     return logits, bins, action
 
 
+def _sample_rows(t: torch.Tensor, B: int, cols: int, name: str) -> int:
+    """sample stride (elements) of an fp32 [B, cols] view whose rows are contiguous: a dense tensor or columns of a wider one"""
+    if t.dtype != torch.float32 or t.shape != (B, cols) or (cols > 1 and t.stride(1) != 1):
+        raise L.DxaError(f"{name}: expected fp32 [{B}, {cols}] with contiguous rows, got {t.dtype} {tuple(t.shape)} strides {t.stride()}")
+    return t.stride(0) if B > 1 else max(cols, t.stride(0))
+
+
+def flow_suffix_in(x: torch.Tensor, te: torch.Tensor, w_in: torch.Tensor, b_in: torch.Tensor, n: int, A: int,
+                   progress: Optional[torch.Tensor] = None, w_p: Optional[torch.Tensor] = None,
+                   b_p: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x fp32 [B, n * A] (rows may be columns of a wider tensor), te [B, da], w_in [da, A], b_in [da] -> the input of
+    action_time_mlp_in [B * (p + n), 2 * da] in te's dtype; ``progress`` fp32 [B, 1] with w_p [da, 1] / b_p [da] puts the progress
+    row in front of every sample's action rows (p = 1).  Semantics: include/dexbotic_amd.h"""
+    B, da = te.shape
+    p = 0 if progress is None else 1
+    assert te.is_contiguous() and w_in.is_contiguous() and b_in.is_contiguous() and w_in.shape == (da, A) and b_in.numel() == da
+    assert w_in.dtype == te.dtype == b_in.dtype
+    ldx = _sample_rows(x, B, n * A, "flow_suffix_in x")
+    ldp = 0
+    if p:
+        assert w_p is not None and b_p is not None and w_p.is_contiguous() and b_p.is_contiguous()
+        assert w_p.numel() == da == b_p.numel() and w_p.dtype == te.dtype == b_p.dtype
+        ldp = _sample_rows(progress, B, 1, "flow_suffix_in progress")
+    if out is None:
+        out = torch.empty((B * (p + n), 2 * da), device=te.device, dtype=te.dtype)
+    assert out.is_contiguous() and out.shape == (B * (p + n), 2 * da) and out.dtype == te.dtype
+    L.check(lib.dxa_flow_suffix_in(_ptr(x), ldx, _ptr(progress), ldp, _ptr(te), _ptr(w_in), _ptr(b_in), _ptr(w_p) if p else None,
+                                   _ptr(b_p) if p else None, _ptr(out), B, n, A, da, p, dt(te), _stream()), "dxa_flow_suffix_in")
+    return out
+
+
+def flow_euler_tail_(h: torch.Tensor, g: torch.Tensor, w_out: torch.Tensor, b_out: torch.Tensor, x: torch.Tensor, n: int, eps: float,
+                     dt_: float, prog_min: Optional[torch.Tensor] = None, w_q: Optional[torch.Tensor] = None,
+                     b_q: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """h [B * (p + n), da] (the expert's rows before its final norm), g [da], w_out [A, da], b_out [A]; x fp32 [B, n * A] IN PLACE:
+    x += dt * action_out_proj(rmsnorm(h)) on the action rows; with ``prog_min`` fp32 [B, 1] (p = 1, w_q [1, da], b_q [1]) the
+    progress row's prediction is folded into the running minimum in place.  Semantics: include/dexbotic_amd.h"""
+    A, da = w_out.shape
+    p = 0 if prog_min is None else 1
+    B = h.shape[0] // (p + n)
+    assert h.is_contiguous() and h.shape == (B * (p + n), da) and g.is_contiguous() and g.numel() == da
+    assert w_out.is_contiguous() and b_out.is_contiguous() and b_out.numel() == A and h.dtype == g.dtype == w_out.dtype == b_out.dtype
+    ldx = _sample_rows(x, B, n * A, "flow_euler_tail_ x")
+    ldm = 0
+    if p:
+        assert w_q is not None and b_q is not None and w_q.is_contiguous() and w_q.numel() == da and b_q.numel() == 1
+        assert w_q.dtype == h.dtype == b_q.dtype
+        ldm = _sample_rows(prog_min, B, 1, "flow_euler_tail_ prog_min")
+    L.check(lib.dxa_flow_euler_tail(_ptr(h), _ptr(g), _ptr(w_out), _ptr(b_out), _ptr(w_q) if p else None, _ptr(b_q) if p else None,
+                                    _ptr(x), ldx, _ptr(prog_min), ldm, B, n, A, da, p, eps, dt_, dt(h), _stream()),
+            "dxa_flow_euler_tail")
+    return x
+
+
 def colsum(x: torch.Tensor, out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
     """out[c] (+)= sum_r x[r, c]  (fp32 result)"""
     ld = _row_major(x, "x")

@@ -1,4 +1,4 @@
-"""Policy classes.  The NaVILA, MuVLA, DM0, pi0.5 and OFT families and the Perception Encoder tower are exported by name (resolved on first
+"""Policy classes.  The NaVILA, MuVLA, DM0, DM0-prog, pi0.5 and OFT families and the Perception Encoder tower are exported by name (resolved on first
 use, so importing one policy module does not import the others)."""
 
 
@@ -9,7 +9,7 @@ def __getattr__(name):
     if name in ("MUVLAConfig", "MUVLAForCausalLM", "MUVLAModel"):
         from . import muvla
         return getattr(muvla, name)
-    if name in ("DM0Config", "DM0ForCausalLM", "DM0Model"):
+    if name in ("DM0Config", "DM0ForCausalLM", "DM0Model", "DM0ProgConfig", "DM0ProgForCausalLM", "DM0ProgModel"):
         from . import dm0
         return getattr(dm0, name)
     if name in ("Pi05Config", "Pi05ForCausalLM", "Pi05Model"):
@@ -25,6 +25,6 @@ def __getattr__(name):
 
 
 __all__ = ["NaVILAConfig", "NaVILAForCausalLM", "NaVILAModel", "MUVLAConfig", "MUVLAForCausalLM", "MUVLAModel",
-           "DM0Config", "DM0ForCausalLM", "DM0Model", "Pi05Config", "Pi05ForCausalLM", "Pi05Model",
+           "DM0Config", "DM0ForCausalLM", "DM0Model", "DM0ProgConfig", "DM0ProgForCausalLM", "DM0ProgModel", "Pi05Config", "Pi05ForCausalLM", "Pi05Model",
            "OFTConfig", "OFTForCausalLM", "OFTModel", "OFTDiscreteConfig", "OFTDiscreteForCausalLM", "OFTDiscreteModel",
            "PerceptionEncoderConfig", "PEVisionTower"]

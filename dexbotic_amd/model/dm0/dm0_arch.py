@@ -24,6 +24,7 @@ arena; as everywhere here the fp32 masters stay and the kernels read bf16 shadow
 from __future__ import annotations
 
 from itertools import takewhile
+from types import SimpleNamespace
 from typing import List, Optional
 
 import numpy as np
@@ -221,25 +222,20 @@ class DM0ForCausalLM(DexboticForCausalLM, ActionOutputForCausalLM, MotPolicy):
         return CausalLMOutputDexbotic(loss=loss, logits=v_t)
 
     # ------------------------------------------------------------------------------------ inference
-    @torch.no_grad()
-    def inference_action(self, input_ids=None, attention_mask=None, states=None, images=None, image_masks=None,
-                         diffusion_steps: int = 10, **kwargs):
-        """dm0_arch.py:513-641.  kwarg ``noise`` [B, chunk, A] injects the initial sample, ``use_graph`` overrides the graph switch.
-        Returns the [B, chunk, A] tensor."""
+    def _sampler_plan(self, attention_mask, image_masks, B: int, S: int, diffusion_steps: int) -> SimpleNamespace:
+        """the host side of a sampling request whose suffix is ONE bidirectional block of ``S`` rows behind the causal prefix (masks,
+        positions, rotary tables, the schedule's time embeddings), uploaded through pinned memory, and the per-layer key / value
+        buffers [B, Hkv, P + S, D]"""
         c, st = self.config, self.store
         dev = st.device
-        B, n = states.shape[0], c.chunk_size
         dt = -1.0 / diffusion_steps
-        noise = kwargs.get("noise")
-        x = (torch.randn(B, n, c.action_dim, device=dev) if noise is None else noise.to(dev)).float().contiguous()
-        # host side first (masks, positions, the schedule's time embeddings), uploaded through pinned memory
         pmask = self.prefix_mask(attention_mask, image_masks)
         P = pmask.shape[1]
         pcum = np.broadcast_to(np.arange(1, P + 1, dtype=np.int64), pmask.shape)
         p_limit, p_valid = mask_tensors(pcum, pmask, pcum, pmask, dev)
         ppos = np.maximum(np.cumsum(pmask, axis=1) - 1, 0)
-        smask = np.ones((B, n), dtype=bool)
-        scum = np.full((B, n), P + 1, dtype=np.int64)
+        smask = np.ones((B, S), dtype=bool)
+        scum = np.full((B, S), P + 1, dtype=np.int64)
         q_limit, key_valid = mask_tensors(scum, smask, np.concatenate([pcum, scum], axis=1),
                                           np.concatenate([pmask, smask], axis=1), dev)
         fpos = pmask.sum(-1)[:, None] + np.cumsum(smask, axis=-1) - 1
@@ -251,23 +247,39 @@ class DM0ForCausalLM(DexboticForCausalLM, ActionOutputForCausalLM, MotPolicy):
         da = c.action_config.hidden_size
         te_table = hostcpu.upload(np.stack([posemb_sincos(np.full(B, t, dtype=np.float32), da) for t in times]), dev
                                   ).to(st.compute_dtype)                                            # [steps, B, da]
-        kv = self.sampler_kv_buffers(B, P + n)
-        # ---- prefix pass: the llm alone, each layer's keys / values written straight into [0, P) of its buffer
+        return SimpleNamespace(B=B, P=P, S=S, dt=dt, steps=len(times), p_limit=p_limit, p_valid=p_valid, ppos_d=ppos_d, q_limit=q_limit,
+                               key_valid=key_valid, pos=pos, cos_t=cos_t, sin_t=sin_t, te_table=te_table,
+                               kv=self.sampler_kv_buffers(B, P + S), geom_s=self._geom(B, 0, S))
+
+    def _prefix_pass(self, plan: SimpleNamespace, input_ids, images) -> None:
+        """the llm alone over the prefix, each layer's keys / values written straight into [0, P) of its buffer"""
+        B, P = plan.B, plan.P
         ptok = self.get_prefix_hidden_states(input_ids, images)
-        self._mot_layers(self._geom(B, P, 0), ptok.reshape(B * P, -1).contiguous(), None, None, cos_t, sin_t, ppos_d, None,
-                         p_limit, p_valid, kv=kv, kv0=0)
-        del ptok
-        geom_s = self._geom(B, 0, n)
+        self._mot_layers(self._geom(B, P, 0), ptok.reshape(B * P, -1).contiguous(), None, None, plan.cos_t, plan.sin_t, plan.ppos_d,
+                         None, plan.p_limit, plan.p_valid, kv=plan.kv, kv0=0)
+
+    @torch.no_grad()
+    def inference_action(self, input_ids=None, attention_mask=None, states=None, images=None, image_masks=None,
+                         diffusion_steps: int = 10, **kwargs):
+        """dm0_arch.py:513-641.  kwarg ``noise`` [B, chunk, A] injects the initial sample, ``use_graph`` overrides the graph switch.
+        Returns the [B, chunk, A] tensor."""
+        c, dev = self.config, self.store.device
+        B, n = states.shape[0], c.chunk_size
+        noise = kwargs.get("noise")
+        x = (torch.randn(B, n, c.action_dim, device=dev) if noise is None else noise.to(dev)).float().contiguous()
+        pl = self._sampler_plan(attention_mask, image_masks, B, n, diffusion_steps)
+        self._prefix_pass(pl, input_ids, images)
+        P, dt, kv, cos_t, sin_t = pl.P, pl.dt, pl.kv, pl.cos_t, pl.sin_t
 
         # ---- the Euler loop: tensors in / tensors out; every step writes the suffix keys / values at [P, P + chunk) of the buffers
         def euler(x, te_table, q_limit, key_valid, pos):
-            for s in range(len(times)):
+            for s in range(pl.steps):
                 h = self.get_suffix_hidden_states(x, None, te=te_table[s]).reshape(B * n, -1).contiguous()
-                _, h = self._mot_layers(geom_s, None, h, None, cos_t, sin_t, None, pos, q_limit, key_valid, kv=kv, kv0=P)
+                _, h = self._mot_layers(pl.geom_s, None, h, None, cos_t, sin_t, None, pos, q_limit, key_valid, kv=kv, kv0=P)
                 v_t = self._v_t(self._final_norm(h).view(B, n, -1))
                 x = K.add(x, K.scale_(v_t.contiguous(), dt))             # Euler step x += v dt
             return x
-        inputs = dict(x=x, te_table=te_table, q_limit=q_limit, key_valid=key_valid, pos=pos)
+        inputs = dict(x=x, te_table=pl.te_table, q_limit=pl.q_limit, key_valid=pl.key_valid, pos=pl.pos)
         key = ("euler", int(diffusion_steps), P, cos_t.data_ptr(), kv[0][0].data_ptr())
         return self._run_sampler(euler, inputs, key, kwargs.get("use_graph"))
 

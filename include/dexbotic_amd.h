@@ -280,6 +280,30 @@ int dxa_action_bins_fwd(const void* h, const int64_t* off, const void* w_bins, v
                         int32_t* counters, int64_t B, int64_t Sq, int64_t d, int64_t n_rows, int skip, int64_t n_bins, int dtype,
                         dxa_stream_t stream);
 int dxa_action_bins_counters(int64_t rows);
+/* The two ends of one Euler step of the DM0-prog sampler (dexbotic/model/dm0/dm0_prog_arch.py:360-400, 567-576), one launch each.
+ * A sample's suffix is p + n rows: p in {0, 1} progress rows in front of the n = chunk_size action rows; A = action_dim, da = the
+ * action expert's width.  Weights, te, h and out are in `dtype` (fp32 or bf16), x / progress / prog_min fp32 with explicit sample
+ * strides in elements (ldx >= n * A; the sampler keeps x and the running minimum in ONE [B, n * A + 1] tensor).  All arithmetic
+ * fp32, fixed summation orders, no atomics.
+ *   dxa_flow_suffix_in -> out [B * (p + n), 2 * da], the input of action_time_mlp_in:
+ *       progress row:  out[:da] = progress[b] * w_p + b_p          (progress_in_proj, w_p [da, 1], b_p [da])
+ *       action row i:  out[:da] = W_in . x[b, i, :] + b_in         (action_in_proj, W_in [da, A]; x rounded to `dtype` first, the
+ *                                                                   sum rounded once on store)
+ *       every row:     out[da:] = te[b, :]                         (te [B, da]: the step's row of the time-embedding table)
+ *   dxa_flow_euler_tail, h [B * (p + n), da] the expert's rows before its final norm, g [da] the norm's gain:
+ *       y = h * rsqrt(mean(h^2) + eps) * g
+ *       action row i:  x[b, i, :] += dt * (W_out . y + b_out)      in place (W_out [A, da], b_out [A])
+ *       progress row:  prog_min[b] = min(prog_min[b], w_q . y + b_q), a NaN prediction wins (w_q [1, da], b_q [1]); the caller
+ *                      starts prog_min at +inf.  p = 0 leaves prog_min alone.
+ *       y and the velocity stay fp32 in between (the composed path rounds both to `dtype`).
+ * DXA_ERR_BAD_ARG before any launch: a null pointer, p outside {0, 1}, p = 1 without progress / prog_min / w_p, b_p / w_q, b_q or
+ * with a stride < 1, a non-positive size, ldx < n * A, da > 8192 (a row is staged in LDS), A > 1024, B * (p + n) > 2^24. */
+int dxa_flow_suffix_in(const float* x, int64_t ldx, const float* progress, int64_t ldp, const void* te, const void* w_in,
+                       const void* b_in, const void* w_p, const void* b_p, void* out, int64_t B, int64_t n, int64_t A, int64_t da,
+                       int p, int dtype, dxa_stream_t stream);
+int dxa_flow_euler_tail(const void* h, const void* g, const void* w_out, const void* b_out, const void* w_q, const void* b_q, float* x,
+                        int64_t ldx, float* prog_min, int64_t ldm, int64_t B, int64_t n, int64_t A, int64_t da, int p, float eps,
+                        float dt, int dtype, dxa_stream_t stream);
 /* Adaptive RMSNorm and gated residual of the pi0.5 action expert (dexbotic/model/pi05/transformers_pi05/gemma/modeling_gemma.py:
  * 38-120): no gain, a per-SAMPLE modulation mod [B, 3*cols] = [scale | shift | gate] in `dtype` (fp32 or bf16, like every row
  * tensor here).  Row `i` of the [rows, cols] tensors belongs to sample i / rows_per_sample (rows % rows_per_sample == 0).  All

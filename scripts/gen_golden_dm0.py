@@ -86,16 +86,9 @@ def recompute_sampler(m, U, ids, mask, images, image_masks, x, steps):
     return x
 
 
-def main():
-    from oracle.gen_golden import GOLD, REF, install_timm_shim
-    from tests.muvla_weights import checksums, make_images, make_weights, pack_shapes
-    sys.path.insert(0, REF)
-    install_timm_shim()
+def tiny_dirs():
+    """locally saved tiny CLIP / Qwen3 llm / Qwen3 action-expert directories (module docstring: Pinned) -> their three paths"""
     from transformers import CLIPImageProcessor, CLIPVisionConfig, CLIPVisionModel, Qwen3Config
-    from dexbotic.model.dm0 import dm0_arch as arch
-    from dexbotic.model.dm0 import dm0_utils as U
-
-    torch.manual_seed(SEED)
     tmp = tempfile.mkdtemp()
     d_clip, d_llm, d_act = (os.path.join(tmp, n) for n in ("tiny_clip", "tiny_qwen3", "tiny_qwen3_action"))
     vcfg = CLIPVisionConfig(hidden_size=V_HIDDEN, intermediate_size=V_INTER, num_hidden_layers=V_LAYERS,
@@ -107,6 +100,19 @@ def main():
               attention_bias=False)
     Qwen3Config(hidden_size=HIDDEN, intermediate_size=INTER, **q3).save_pretrained(d_llm)
     Qwen3Config(hidden_size=A_HIDDEN, intermediate_size=A_INTER, **q3).save_pretrained(d_act)
+    return d_clip, d_llm, d_act
+
+
+def main():
+    from oracle.gen_golden import GOLD, REF, install_timm_shim
+    from tests.muvla_weights import checksums, make_images, make_weights, pack_shapes
+    sys.path.insert(0, REF)
+    install_timm_shim()
+    from dexbotic.model.dm0 import dm0_arch as arch
+    from dexbotic.model.dm0 import dm0_utils as U
+
+    torch.manual_seed(SEED)
+    d_clip, d_llm, d_act = tiny_dirs()
 
     def build(bf16):
         cfg = arch.DM0Config(llm_config=d_llm, action_config=d_act, mm_vision_tower=d_clip, mm_projector_type="mlp2x_gelu",
