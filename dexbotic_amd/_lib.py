@@ -145,6 +145,9 @@ SIGNATURES = {
     "dxa_action_fill_bwd_blocks": (_int, [_i64]),
     "dxa_action_bins_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _i64, _int, _vp]),
     "dxa_action_bins_counters": (_int, [_i64]),
+    "dxa_bin_logprob_fwd": (_int, [_vp, _i64, _vp, _f32, _vp, _vp, _vp, _i64, _i64, _int, _vp]),
+    "dxa_bin_logprob_bwd": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _f32, _vp, _i64, _i64, _int, _vp]),
+    "dxa_ppo_clip_fwd": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _f32, _f32, _f32, _vp, _vp, _vp, _vp]),
     "dxa_flow_suffix_in": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _vp]),
     "dxa_flow_euler_tail": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _int, _f32, _f32, _int, _vp]),
     "dxa_adarms_fwd": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _int, _vp]),

@@ -1424,6 +1424,50 @@ def _lm_head_loss_bwd(ctx, g):
     return dh
 
 
+class BinPolicyLossFn(_StoreFn):
+    """The clipped GRPO policy loss of the discrete policy on its action rows (dexbotic/exp/rl/rl_trainer.py:380-399, 488-506):
+    bin logits = rows W_b^T with W_b the last NB = num_bins - 1 rows of ``lm_head.weight`` as their own operand, log-probability and
+    entropy of the taken bins at ``temperature`` (dxa_bin_logprob_fwd), the four masked sums and d loss / d log_prob
+    (dxa_ppo_clip_fwd).  Returns (loss = sums[0] / denom, logp [rows], entropy [rows], sums [4]); only the loss is differentiable.
+    ``denom`` None: the mask's own count.  The reference forms the [rows, V] logits and slices them; every vocabulary row outside
+    the slice gets a zero gradient there, so here the three head products run over NB columns and nothing V wide is kept: the
+    backward writes dZ over Z in place, dW_b into the last NB rows of the gradient slot and exact zeros into the rows before them
+    when this is the slot's first write of the step (they are left alone when accumulating)."""
+
+    @staticmethod
+    def forward(ctx, rows, anchor, st: ParamStore, wn: str, NB: int, bins, old_logp, adv, mask, temperature: float,
+                clip_low: float, clip_high: float, denom: Optional[float]):
+        rows = rows.contiguous()
+        W = st.w(wn)
+        Z = K.mm_nt(rows, W[W.shape[0] - NB:])
+        logp, entropy, lse = K.bin_logprob_fwd(Z, bins, temperature)
+        loss, sums, coef = K.ppo_clip_fwd(logp, old_logp, adv, mask, clip_low, clip_high, denom)
+        ctx.st, ctx.wn, ctx.NB, ctx.temperature = st, wn, NB, float(temperature)
+        _use(ctx, st, wn)
+        ctx.save_for_backward(rows, Z, lse, bins, coef)
+        ctx.mark_non_differentiable(logp, entropy, sums)
+        return loss.view(()), logp, entropy, sums
+
+    @staticmethod
+    def backward(ctx, g, _g_logp, _g_entropy, _g_sums):
+        st, wn, NB = ctx.st, ctx.wn, ctx.NB
+        rows, Z, lse, bins, coef = ctx.saved_tensors
+        W = st.w(wn)
+        V = W.shape[0]
+        dz = K.bin_logprob_bwd(Z, bins, lse, coef, g.reshape(1).float().contiguous(), ctx.temperature, out=Z)
+        if st.trainable(wn):
+            gw, acc, mir = st.g(wn), st.accum_flag(wn), st.mirror_out(wn)
+            if not acc and V > NB:
+                gw[:V - NB].zero_()
+                st._own_grad_write()
+                if mir is not None:
+                    mir[:V - NB].zero_()
+            K.mm_tn(dz, rows, out=gw[V - NB:], accumulate=acc, mirror=None if mir is None else mir[V - NB:])
+            st.mark_written(wn)
+        dh = K.mm_nn(dz, W[V - NB:]) if ctx.needs_input_grad[0] else None
+        return (dh,) + (None,) * 12
+
+
 class AddPosFn(_StoreFn):
     """x[N,T,C] + pos[T,C] (learned position embedding of the SigLIP tower, HF siglip/modeling_siglip.py
     SiglipVisionEmbeddings); d_pos = sum over N of dy."""

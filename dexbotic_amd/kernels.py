@@ -802,6 +802,58 @@ def action_bins_fwd(h: torch.Tensor, off: torch.Tensor, w_bins: torch.Tensor, n_
     return logits, bins, action
 
 
+def bin_logprob_fwd(logits: torch.Tensor, bins: torch.Tensor, temperature: float = 1.0):
+    """logits [rows, NB] (fp32 / bf16, rows contiguous, any row stride), bins [rows] int64 BIN indices -> (logp, entropy, lse), each
+    [rows] fp32, of softmax(logits / temperature).  Semantics: include/dexbotic_amd.h"""
+    rows, NB = logits.shape
+    ld = _row_major(logits, "bin_logprob_fwd: logits")
+    assert bins.dtype == torch.int64 and bins.is_contiguous() and bins.numel() == rows
+    logp, entropy, lse = (torch.empty(rows, device=logits.device, dtype=torch.float32) for _ in range(3))
+    L.check(lib.dxa_bin_logprob_fwd(_ptr(logits), ld, _ptr(bins), 1.0 / float(temperature), _ptr(logp), _ptr(entropy), _ptr(lse),
+                                    rows, NB, dt(logits), _stream()), "dxa_bin_logprob_fwd")
+    return logp, entropy, lse
+
+
+def bin_logprob_bwd(logits: torch.Tensor, bins: torch.Tensor, lse: torch.Tensor, coef: torch.Tensor, gscale: Optional[torch.Tensor],
+                    temperature: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dlogits = coef[r] gscale[0] / temperature (onehot(bin) - softmax(logits / temperature)); ``out`` may be ``logits`` itself (in
+    place) and otherwise has its row stride"""
+    rows, NB = logits.shape
+    ld = _row_major(logits, "bin_logprob_bwd: logits")
+    if out is None:
+        out = torch.empty_strided(logits.shape, logits.stride(), device=logits.device, dtype=logits.dtype)
+    assert out.shape == logits.shape and out.dtype == logits.dtype and _row_major(out, "bin_logprob_bwd: out") == ld
+    for t in (lse, coef):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == rows
+    assert bins.dtype == torch.int64 and bins.is_contiguous() and bins.numel() == rows
+    assert gscale is None or (gscale.dtype == torch.float32 and gscale.numel() == 1)
+    L.check(lib.dxa_bin_logprob_bwd(_ptr(logits), ld, _ptr(bins), _ptr(lse), _ptr(coef), _ptr(gscale), 1.0 / float(temperature),
+                                    _ptr(out), rows, NB, dt(logits), _stream()), "dxa_bin_logprob_bwd")
+    return out
+
+
+def ppo_clip_fwd(logp: torch.Tensor, old_logp: torch.Tensor, adv: torch.Tensor, mask: torch.Tensor, clip_low: float, clip_high: float,
+                 denom: Optional[float] = None):
+    """the clipped policy loss over n tokens (fp32; ``mask`` fp32 0/1, uint8 or bool) -> (loss [1] = sums[0] / denom, sums [4] =
+    (sum max(pg1, pg2), clipped count, sum (old - logp), valid count), coef [n] = d loss / d logp).  ``denom`` None: the mask's own
+    count (a masked mean; an empty mask gives loss 0 and coef 0).  Semantics: include/dexbotic_amd.h"""
+    n = logp.numel()
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    assert mask.dtype in (torch.float32, torch.uint8) and mask.is_contiguous() and mask.numel() == n
+    for t in (logp, old_logp, adv):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
+    if denom is not None and not denom > 0:
+        raise L.DxaError(f"ppo_clip_fwd: denom {denom} (a positive number, or None for the mask's own count)")
+    sums = torch.empty(4, device=logp.device, dtype=torch.float32)
+    loss = torch.empty(1, device=logp.device, dtype=torch.float32)
+    coef = torch.empty(n, device=logp.device, dtype=torch.float32)
+    L.check(lib.dxa_ppo_clip_fwd(_ptr(logp), _ptr(old_logp), _ptr(adv), _ptr(mask), int(mask.dtype == torch.uint8), n, float(clip_low),
+                                 float(clip_high), 0.0 if denom is None else 1.0 / float(denom), _ptr(sums), _ptr(loss), _ptr(coef),
+                                 _stream()), "dxa_ppo_clip_fwd")
+    return loss, sums, coef
+
+
 def _sample_rows(t: torch.Tensor, B: int, cols: int, name: str) -> int:
     """sample stride (elements) of an fp32 [B, cols] view whose rows are contiguous: a dense tensor or columns of a wider one"""
     if t.dtype != torch.float32 or t.shape != (B, cols) or (cols > 1 and t.stride(1) != 1):

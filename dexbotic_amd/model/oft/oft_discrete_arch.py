@@ -12,7 +12,10 @@ What runs where:
   ``rule="oft"`` plan reserves; ``functional.ActionRowsFn`` hands the R rows of every sample to ``functional.LmHeadLossFn`` as one
   dense [B R, d] operand, on the UN-shifted targets (``F.cross_entropy`` over the rows, ignore_index -100, mean);
 * ``inference_action`` / ``generate_action`` run the decoder pass and then dxa_action_bins_fwd on the decoder output in place: the
-  ``num_bins - 1`` logits, their first-index argmax and the action value, in one launch.  The vocabulary logits are never formed.
+  ``num_bins - 1`` logits, their first-index argmax and the action value, in one launch.  The vocabulary logits are never formed;
+* the GRPO policy update (dexbotic/exp/rl/rl_trainer.py): ``action_log_probs`` scores taken bins with dxa_bin_logprob_fwd on those
+  bin logits, and ``forward`` with ``old_log_probs`` returns the clipped policy loss through ``functional.BinPolicyLossFn`` (the bin
+  rows of ``lm_head.weight`` as their own operand); the loop around them is ``exp/rl.py``.
 
 Quirks kept from the reference: the loss is computed only when ``actions`` is given (and needs the targets cut from ``labels``:
 ``actions`` without ``labels`` raises ValueError here, where the reference dies with an unbound name); ``get_output_embeddings()`` is
@@ -130,11 +133,17 @@ class OFTDiscreteForCausalLM(OFTForCausalLM):
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None, inputs_embeds=None,
                 labels=None, use_cache=None, output_attentions=None, output_hidden_states=None, images=None,
                 return_dict=None, cache_position=None, actions=None, states=None, noisy_dict=None,
-                **kwargs) -> CausalLMOutputDexbotic:
+                responses=None, old_log_probs=None, advantages=None, response_mask=None, temperature: float = 1.0,
+                clip_ratio_low: float = 0.2, clip_ratio_high: float = 0.28, loss_denominator: Optional[float] = None,
+                token_offset: Optional[int] = None, **kwargs) -> CausalLMOutputDexbotic:
         """``logits`` [B, R, V] as in the reference.  With ``labels`` and ``actions``: the loss; with ``labels`` alone: no loss (the
-        action tokens are still cut out of the prompt); with ``actions`` alone: ValueError."""
+        action tokens are still cut out of the prompt); with ``actions`` alone: ValueError.  With ``old_log_probs``: the GRPO policy
+        update (``_policy_forward``)."""
         cfg, st = self.config, self.store
         R = cfg.chunk_size * cfg.action_dim
+        if old_log_probs is not None:
+            return self._policy_forward(input_ids, attention_mask, images, states, responses, old_log_probs, advantages,
+                                        response_mask, temperature, clip_ratio_low, clip_ratio_high, loss_denominator, token_offset)
         targets = None
         if labels is not None:
             if attention_mask is None:
@@ -159,6 +168,61 @@ class OFTDiscreteForCausalLM(OFTForCausalLM):
                                       attentions=None)
 
     __call__ = nn.Module.__call__
+
+    # ------------------------------------------------------------------------------------------------ GRPO policy update
+    def _response_bins(self, responses, rows: int, token_offset: Optional[int]) -> torch.Tensor:
+        """token ids [N, R] -> bin indices [N R] int64 on the device: ``responses - (len(tokenizer) - num_bins + 1)``
+        (rl_trainer.py:355); ``token_offset`` defaults to what ``generate_action`` adds"""
+        cfg = self.config
+        off = cfg.vocab_size - cfg.num_bins + 1 if token_offset is None else int(token_offset)
+        r = torch.as_tensor(responses).to(device=self.store.device, dtype=torch.int64).reshape(-1)
+        if r.numel() != rows:
+            raise ValueError(f"OFT-discrete: {r.numel()} response tokens for {rows} action rows")
+        return (r - off).contiguous()
+
+    def _policy_forward(self, input_ids, attention_mask, images, states, responses, old_log_probs, advantages, response_mask,
+                        temperature, clip_low, clip_high, denom, token_offset) -> CausalLMOutputDexbotic:
+        """One update chunk of the reference's ``update_policy`` (rl_trainer.py:591-634): the log-probabilities of the taken bins
+        under the current weights and the clipped policy loss against ``old_log_probs`` / ``advantages`` over ``response_mask``
+        (each N R values, any shape), through functional.BinPolicyLossFn.  ``loss`` = sum / ``loss_denominator`` (None: the mask's
+        own count, the reference's masked_mean; an empty mask gives 0 and zero gradients).  The output also carries ``sums`` [4]
+        (sum of max(pg1, pg2), clipped count, sum of old - new log-prob, valid count), ``log_probs`` and ``entropy`` [N, R] fp32.
+        No labels and no actions: a rollout prompt holds no action tokens.  ``logits`` is None: not even the bin logits outlive
+        the backward."""
+        cfg, st = self.config, self.store
+        if responses is None or advantages is None or response_mask is None:
+            raise ValueError("OFT-discrete: old_log_probs needs responses, advantages and response_mask")
+        R = cfg.chunk_size * cfg.action_dim
+        hidden, off = self._decode(input_ids, attention_mask, images, states)
+        N = hidden.shape[0]
+        rows = Fn.ActionRowsFn.apply(hidden, off, R, bool(cfg.use_proprio))               # [N R, d]
+        dev = hidden.device
+
+        def f32(t, what):
+            t = torch.as_tensor(t).to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+            if t.numel() != N * R:
+                raise ValueError(f"OFT-discrete: {what} holds {t.numel()} values for {N * R} action rows")
+            return t
+
+        loss, logp, entropy, sums = Fn.BinPolicyLossFn.apply(
+            rows, st.params["lm_head.weight"], st, "lm_head.weight", cfg.num_bins - 1, self._response_bins(responses, N * R, token_offset),
+            f32(old_log_probs, "old_log_probs"), f32(advantages, "advantages"), f32(response_mask, "response_mask"),
+            float(temperature), float(clip_low), float(clip_high), None if denom is None else float(denom))
+        out = CausalLMOutputDexbotic(loss=loss, logits=None, past_key_values=None, hidden_states=(hidden,), attentions=None)
+        out.sums, out.log_probs, out.entropy = sums, logp.view(N, R), entropy.view(N, R)
+        return out
+
+    @torch.no_grad()
+    def action_log_probs(self, input_ids, attention_mask, images, responses, temperature, states=None,
+                         token_offset: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(entropy, log_probs), each [N, R] fp32, of the taken bins ``responses`` (token ids [N, R]) under softmax(bin logits /
+        temperature): the reference's ``_forward_micro_batch`` without its masking (rl_trainer.py:343-359).  One decoder pass,
+        dxa_action_bins_fwd on the decoder output in place, dxa_bin_logprob_fwd; the vocabulary logits are never formed."""
+        bin_logits, _, _ = self._bins(input_ids, attention_mask, images, states)
+        rows = bin_logits.shape[0]
+        logp, entropy, _ = K.bin_logprob_fwd(bin_logits, self._response_bins(responses, rows, token_offset), float(temperature))
+        R = self.config.chunk_size * self.config.action_dim
+        return entropy.view(-1, R), logp.view(-1, R)
 
     # ------------------------------------------------------------------------------------------------ action requests
     def _bins(self, input_ids, attention_mask, images, states):

@@ -280,6 +280,39 @@ int dxa_action_bins_fwd(const void* h, const int64_t* off, const void* w_bins, v
                         int32_t* counters, int64_t B, int64_t Sq, int64_t d, int64_t n_rows, int skip, int64_t n_bins, int dtype,
                         dxa_stream_t stream);
 int dxa_action_bins_counters(int64_t rows);
+/* GRPO policy update of the discrete policy (dexbotic/exp/rl/rl_trainer.py: _forward_micro_batch_update, _compute_policy_loss), on the
+ * n_bins = num_bins - 1 bin logits alone: the bin rows of lm_head.weight are their own [NB, d] operand, so no [rows, vocab] tensor
+ * and none of its gradient exists.  No atomics, fixed reduction order: two runs give the same bits.
+ *
+ * dxa_bin_logprob_fwd: logits [rows, NB] in `dtype` (fp32 or bf16), row stride ld >= NB elements, any alignment; bins [rows] int64
+ * are BIN indices (token id minus the offset of the first bin token).  With z = (float)logit * inv_temperature, all in fp32 with
+ * the row maximum subtracted:
+ *   lse[r] = logsumexp(z),  logp[r] = z[bins[r]] - lse[r],  entropy[r] = lse[r] - sum_j softmax(z)_j z_j
+ * (logprobs_from_logits_naive / entropy_from_logits, rl_trainer.py:46-55).  A bin outside [0, NB) reads nothing and gives
+ * logp = NaN (the reference's gather raises); the other rows are unaffected.  One wave per row, four rows per workgroup, a loop over
+ * the row for NB > 64; NB in [1, 65536].
+ *
+ * dxa_bin_logprob_bwd: dlogits[r, j] = coef[r] * gscale[0] * inv_temperature * ([j == bins[r]] - exp(z_j - lse[r])) in `dtype`, row
+ * stride ld; dlogits may be logits itself.  gscale: DEVICE scalar, NULL = 1.  A row with coef[r] == 0 is written as zeros whatever
+ * its logits hold.  The entropy has no gradient: the reference's update never puts it into the loss.
+ *
+ * dxa_ppo_clip_fwd: all of logp, old_logp, adv, coef fp32 [n]; mask [n] fp32 (mask_u8 = 0) or uint8 (mask_u8 = 1), non-zero = valid.
+ *   ratio = exp(logp - old_logp),  pg1 = -adv * ratio,  pg2 = -adv * clamp(ratio, 1 - clip_low, 1 + clip_high)
+ *   sums[4] = (sum max(pg1, pg2), sum [pg2 > pg1], sum (old_logp - logp), count) over the valid tokens
+ *   inv = inv_denom when inv_denom > 0, else 1 / count (masked_mean; 0 for an empty mask);  loss[0] = inv * sums[0] (NULL: not wanted)
+ *   coef[i] = d loss / d logp[i] = inv * (pg1 >= pg2 ? pg1 : 0) on a valid token, 0 on a masked one
+ * The coefficient is what torch.maximum / torch.clamp autograd give, ties included: inside the clip range and on its bounds pg1 and
+ * pg2 are the same number and both halves of the split gradient are -adv * ratio; outside it a tie needs adv = 0, where both are 0.
+ * A masked token contributes exactly 0 also where its values are not finite.  One workgroup, fixed reduction tree (n is a trajectory
+ * chunk x chunk_size x action_dim: hundreds to a few thousand).
+ * All three: DXA_ERR_BAD_ARG with a message, before any launch, for a null pointer, NB outside [1, 65536], ld < NB, rows < 0, n <= 0,
+ * a non-positive or non-finite inv_temperature, a clip range outside [0, 1) x [0, inf), a dtype other than DXA_F32 / DXA_BF16. */
+int dxa_bin_logprob_fwd(const void* logits, int64_t ld, const int64_t* bins, float inv_temperature, float* logp, float* entropy,
+                        float* lse, int64_t rows, int64_t NB, int dtype, dxa_stream_t stream);
+int dxa_bin_logprob_bwd(const void* logits, int64_t ld, const int64_t* bins, const float* lse, const float* coef, const float* gscale,
+                        float inv_temperature, void* dlogits, int64_t rows, int64_t NB, int dtype, dxa_stream_t stream);
+int dxa_ppo_clip_fwd(const float* logp, const float* old_logp, const float* adv, const void* mask, int mask_u8, int64_t n,
+                     float clip_low, float clip_high, float inv_denom, float* sums, float* loss, float* coef, dxa_stream_t stream);
 /* The two ends of one Euler step of the DM0-prog sampler (dexbotic/model/dm0/dm0_prog_arch.py:360-400, 567-576), one launch each.
  * A sample's suffix is p + n rows: p in {0, 1} progress rows in front of the n = chunk_size action rows; A = action_dim, da = the
  * action expert's width.  Weights, te, h and out are in `dtype` (fp32 or bf16), x / progress / prog_min fp32 with explicit sample
