@@ -54,7 +54,8 @@ def __getattr__(name):
     if name in ("Pi05Config", "Pi05ForCausalLM", "Pi05Model"):
         from .model import pi05
         return getattr(pi05, name)
-    if name in ("OFTDiscreteConfig", "OFTDiscreteForCausalLM", "OFTDiscreteModel"):
+    if name in ("OFTDiscreteConfig", "OFTDiscreteForCausalLM", "OFTDiscreteModel",
+                "OFTDiffusionConfig", "OFTDiffusionForCausalLM", "OFTDiffusionModel"):
         from .model import oft
         return getattr(oft, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
@@ -85,6 +86,10 @@ def from_pretrained(path: str, **kw):
     import json
     import os
     with open(os.path.join(path, "config.json")) as f:
-        mt = json.load(f).get("model_type", "dexbotic")
+        cfg = json.load(f)
+    mt = cfg.get("model_type", "dexbotic")
     _, cls = model_registry()[mt]
+    if mt == "dexbotic_oft" and "DiT" in str(cfg.get("action_model_type")):
+        # the diffusion head shares the reference's model_type string with the Linear head (oft_diffusion_arch.py)
+        from .model.oft.oft_diffusion_arch import OFTDiffusionForCausalLM as cls
     return cls.from_pretrained(path, **kw)

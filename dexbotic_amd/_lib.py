@@ -148,6 +148,12 @@ SIGNATURES = {
     "dxa_bin_logprob_fwd": (_int, [_vp, _i64, _vp, _f32, _vp, _vp, _vp, _i64, _i64, _int, _vp]),
     "dxa_bin_logprob_bwd": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _f32, _vp, _i64, _i64, _int, _vp]),
     "dxa_ppo_clip_fwd": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _f32, _f32, _f32, _vp, _vp, _vp, _vp]),
+    "dxa_noisy_embed_fwd": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _vp]),
+    "dxa_noisy_embed_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _vp]),
+    "dxa_noisy_embed_bwd_blocks": (_int, [_i64]),
+    "dxa_diffusion_put_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp]),
+    "dxa_diffusion_put_bwd": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _vp]),
+    "dxa_ddim_step_embed": (_int, [_vp, _vp, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _vp]),
     "dxa_flow_suffix_in": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _vp]),
     "dxa_flow_euler_tail": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _int, _f32, _f32, _int, _vp]),
     "dxa_adarms_fwd": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _int, _vp]),

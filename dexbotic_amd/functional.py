@@ -1140,6 +1140,64 @@ class OftDiscreteSpliceFn(_StoreFn):
         return (d_img, got.get("dstate")) + (None,) * 10
 
 
+class NoisyEmbedFn(_StoreFn):
+    """fc1 and the GELU of ``NoisyActionProjector`` (oft/action_model/model.py:46-53) on the R = B T A noisy-action scalars: a
+    Linear(1, d) is one multiply per element, so the product, the bias and the activation are ONE pass (dxa_noisy_embed_fwd) that
+    writes the [R, d] operand of fc2.  Nothing but the scalars is kept: the backward recomputes the pre-activation and writes
+    dw1 | db1 as fixed-order two-stage sums into their slots.  The noisy actions are inputs: no gradient for them."""
+
+    @staticmethod
+    def forward(ctx, a, anchor, st: ParamStore, w1n: str, b1n: str):
+        a = a.reshape(-1).contiguous()
+        ctx.st, ctx.names = st, (w1n, b1n)
+        _use(ctx, st, w1n, b1n)
+        ctx.save_for_backward(a)
+        return K.noisy_embed_fwd(a, st.w(w1n), st.w(b1n), st.compute_dtype)
+
+    @staticmethod
+    def backward(ctx, dh):
+        st = ctx.st
+        w1n, b1n = ctx.names
+        (a,) = ctx.saved_tensors
+        if st.trainable(w1n):
+            K.noisy_embed_bwd(dh.contiguous(), a, st.w(w1n), st.w(b1n), dw1=st.g(w1n).view(-1), db1=st.g(b1n),
+                              accumulate=st.accum_flag(w1n))
+            st.mark_written(w1n, b1n)
+        return None, None, None, None, None
+
+
+class DiffusionSpliceFn(_StoreFn):
+    """SpliceFn followed by the diffusion head's ``insert_action_embedding`` (oft_arch.py:106-123) on the SAME buffer: the plan
+    reserves 1 + R (+ 1) rows behind each sample's rows and dxa_diffusion_put_fwd writes the sample's state row (``state`` [B, d], with
+    proprio), its time row (``time`` [B, d]) and its R projected noisy-action rows (``proj`` [B R, d]) there.  Backward: the dense
+    gradient of the projected rows and of the state rows (the time row has none), then the splice's own backward."""
+
+    @staticmethod
+    def forward(ctx, img_feats, proj, time, state, anchor, st: ParamStore, embed_n: str, plan: torch.Tensor, off: torch.Tensor,
+                B: int, Sq: int):
+        d = img_feats.shape[-1]
+        out = K.splice_fwd(plan, st.w(embed_n), img_feats.reshape(-1, d).contiguous())
+        K.diffusion_put_(out.view(B, Sq, d), proj.contiguous(), time.contiguous(), off, None if state is None else state.contiguous())
+        ctx.st, ctx.embed_n, ctx.ishape, ctx.geom = st, embed_n, img_feats.shape, (B, Sq, d, proj.shape[0] // B)
+        ctx.has_state = state is not None
+        _use(ctx, st, embed_n)
+        ctx.save_for_backward(plan, off)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        st = ctx.st
+        plan, off = ctx.saved_tensors
+        B, Sq, d, R = ctx.geom
+        dout = dout.contiguous()
+        want_state = ctx.has_state and ctx.needs_input_grad[3]
+        dproj = dstate = None
+        if ctx.needs_input_grad[1] or want_state:
+            dproj, dstate = K.diffusion_put_bwd(dout.view(B, Sq, d), off, R, ctx.has_state, want_dstate=want_state)
+        d_img = _splice_backward(st, ctx.embed_n, plan, dout, ctx.ishape, ctx.needs_input_grad[0])
+        return (d_img, dproj if ctx.needs_input_grad[1] else None, None, dstate) + (None,) * 7
+
+
 class ActionRowsFn(Function):
     """``extract_action_hidden_states`` (+ ``[:, 1:]`` with proprio; oft_discrete_arch.py:157-162) as the dense [B R, d] operand of the
     lm_head product, one launch per direction.  The backward writes the whole gradient of h (zero off the action rows): the head is
@@ -1291,11 +1349,16 @@ class DitAssembleFn(_StoreFn):
 
 
 class MseLossFn(Function):
-    """loss = ((eps_hat - eps)**2).mean()  (action_models.py:119-121)."""
+    """loss = ((eps_hat - eps)**2).mean()  (action_models.py:119-121; the OFT diffusion head, oft_arch.py:154, whose bf16 prediction
+    is cast first: the loss is taken in fp32)."""
 
     @staticmethod
     def forward(ctx, pred, target):
-        loss, dpred = K.mse_loss(pred.contiguous(), target.contiguous(), 1.0, want_grad=True)
+        ctx.dtype = pred.dtype
+        pred = pred.contiguous()
+        if pred.dtype != torch.float32:
+            pred = K.cast(pred, torch.float32)
+        loss, dpred = K.mse_loss(pred, target.contiguous(), 1.0, want_grad=True)
         ctx.save_for_backward(dpred)
         return loss.view(())
 
@@ -1304,7 +1367,8 @@ class MseLossFn(Function):
         (dpred,) = ctx.saved_tensors
         # g is the scalar upstream gradient (1.0 for loss.backward(); 1/accum under gradient
         # accumulation): applied on the device, no host sync
-        return K.scale_dev_(dpred.clone(), g.reshape(1).float().contiguous()), None
+        d = K.scale_dev_(dpred.clone(), g.reshape(1).float().contiguous())
+        return (d if ctx.dtype == torch.float32 else K.cast(d, ctx.dtype)), None
 
 
 class ExpectileLossFn(Function):

@@ -802,6 +802,78 @@ def action_bins_fwd(h: torch.Tensor, off: torch.Tensor, w_bins: torch.Tensor, n_
     return logits, bins, action
 
 
+def _embed_args(a: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor) -> int:
+    d = w1.numel()
+    assert a.dtype == torch.float32 and a.is_contiguous() and w1.is_contiguous() and b1.is_contiguous()
+    assert b1.numel() == d and w1.dtype == b1.dtype
+    return d
+
+
+def noisy_embed_fwd(a: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """a fp32 (R scalars, any shape), w1 [d, 1] / b1 [d] -> h [R, d] in ``dtype``: gelu_erf(a_r w1 + b1) with a and the pre-activation
+    rounded to ``dtype``.  Semantics: include/dexbotic_amd.h"""
+    d = _embed_args(a, w1, b1)
+    h = torch.empty((a.numel(), d), device=a.device, dtype=dtype)
+    L.check(lib.dxa_noisy_embed_fwd(_ptr(a), _ptr(w1), _ptr(b1), _ptr(h), a.numel(), d, dt(h), dt(w1), _stream()), "dxa_noisy_embed_fwd")
+    return h
+
+
+def noisy_embed_bwd(dh: torch.Tensor, a: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, dw1: Optional[torch.Tensor] = None,
+                    db1: Optional[torch.Tensor] = None, accumulate: bool = False):
+    """-> (dw1 [d], db1 [d]) fp32, fixed-order sums over the R rows, written to / accumulated into ``dw1`` / ``db1`` when given"""
+    d = _embed_args(a, w1, b1)
+    R = a.numel()
+    assert dh.is_contiguous() and dh.shape == (R, d)
+    if dw1 is None or db1 is None:
+        dw1, db1 = (torch.empty(d, device=dh.device, dtype=torch.float32) for _ in range(2))
+        accumulate = False
+    for t in (dw1, db1):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == d
+    partial = torch.empty((int(lib.dxa_noisy_embed_bwd_blocks(R)), 2 * d), device=dh.device, dtype=torch.float32)
+    L.check(lib.dxa_noisy_embed_bwd(_ptr(dh), _ptr(a), _ptr(w1), _ptr(b1), _ptr(dw1), _ptr(db1), _ptr(partial), R, d, int(accumulate),
+                                    dt(dh), dt(w1), _stream()), "dxa_noisy_embed_bwd")
+    return dw1, db1
+
+
+def diffusion_put_(x: torch.Tensor, proj: torch.Tensor, time: torch.Tensor, off: torch.Tensor,
+                   state: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [B, Sq, d] in place, at the block off[b]: [state[b], when given] [time[b]] [proj[b * R + j], j < R]; proj [B R, d], time [B, d]"""
+    B, Sq, d = x.shape
+    assert x.is_contiguous() and proj.is_contiguous() and time.is_contiguous() and proj.dtype == x.dtype and time.dtype == x.dtype
+    assert proj.dim() == 2 and proj.shape[1] == d and proj.shape[0] % max(B, 1) == 0 and time.shape == (B, d)
+    if state is not None:
+        assert state.is_contiguous() and state.shape == (B, d) and state.dtype == x.dtype
+    L.check(lib.dxa_diffusion_put_fwd(_ptr(x), _ptr(proj), _ptr(time), _ptr(state), _ptr(_action_off(off, B)), B, Sq, d,
+                                      proj.shape[0] // max(B, 1), dt(x), _stream()), "dxa_diffusion_put_fwd")
+    return x
+
+
+def diffusion_put_bwd(dx: torch.Tensor, off: torch.Tensor, n_rows: int, skip: bool, want_dstate: bool = False):
+    """-> (dproj [B n_rows, d], dstate [B, d] or None) in dx's dtype; zero rows for an out-of-range sample"""
+    B, Sq, d = dx.shape
+    assert dx.is_contiguous()
+    dproj = torch.empty((B * n_rows, d), device=dx.device, dtype=dx.dtype)
+    dstate = torch.empty((B, d), device=dx.device, dtype=dx.dtype) if (want_dstate and skip) else None
+    L.check(lib.dxa_diffusion_put_bwd(_ptr(dx), _ptr(_action_off(off, B)), _ptr(dproj), _ptr(dstate), B, Sq, d, n_rows, int(skip),
+                                      dt(dx), _stream()), "dxa_diffusion_put_bwd")
+    return dproj, dstate
+
+
+def ddim_step_embed_(eps: Optional[torch.Tensor], x: torch.Tensor, coef, clip: float, time_row: torch.Tensor, w1: torch.Tensor,
+                     b1: torch.Tensor, suffix: torch.Tensor, h: torch.Tensor) -> None:
+    """x [n] fp32 in place: with ``eps`` [n] (h's dtype) the DDIM update with ``coef`` = (c0, c1, c2, c3) and the clamp at +-``clip``;
+    then suffix[0] = time_row and h [n, d] = the projector's fc2 operand of the new x.  Semantics: include/dexbotic_amd.h"""
+    n, d = h.shape
+    assert _embed_args(x, w1, b1) == d and x.numel() == n and h.is_contiguous()
+    assert time_row.is_contiguous() and time_row.numel() == d and time_row.dtype == h.dtype
+    assert suffix.dtype == h.dtype and suffix.shape[-1] == d and suffix.stride(-1) == 1
+    if eps is not None:
+        assert eps.is_contiguous() and eps.numel() == n and eps.dtype == h.dtype
+    c0, c1, c2, c3 = (float(c) for c in coef)
+    L.check(lib.dxa_ddim_step_embed(_ptr(eps), _ptr(x), c0, c1, c2, c3, float(clip), _ptr(time_row), _ptr(w1), _ptr(b1), _ptr(suffix),
+                                    _ptr(h), n, d, dt(h), dt(w1), _stream()), "dxa_ddim_step_embed")
+
+
 def bin_logprob_fwd(logits: torch.Tensor, bins: torch.Tensor, temperature: float = 1.0):
     """logits [rows, NB] (fp32 / bf16, rows contiguous, any row stride), bins [rows] int64 BIN indices -> (logp, entropy, lse), each
     [rows] fp32, of softmax(logits / temperature).  Semantics: include/dexbotic_amd.h"""

@@ -15,7 +15,8 @@ def __getattr__(name):
     if name in ("Pi05Config", "Pi05ForCausalLM", "Pi05Model"):
         from . import pi05
         return getattr(pi05, name)
-    if name in ("OFTConfig", "OFTForCausalLM", "OFTModel", "OFTDiscreteConfig", "OFTDiscreteForCausalLM", "OFTDiscreteModel"):
+    if name in ("OFTConfig", "OFTForCausalLM", "OFTModel", "OFTDiscreteConfig", "OFTDiscreteForCausalLM", "OFTDiscreteModel",
+                "OFTDiffusionConfig", "OFTDiffusionForCausalLM", "OFTDiffusionModel"):
         from . import oft
         return getattr(oft, name)
     if name in ("PerceptionEncoderConfig", "PEVisionTower"):
@@ -27,4 +28,4 @@ def __getattr__(name):
 __all__ = ["NaVILAConfig", "NaVILAForCausalLM", "NaVILAModel", "MUVLAConfig", "MUVLAForCausalLM", "MUVLAModel",
            "DM0Config", "DM0ForCausalLM", "DM0Model", "DM0ProgConfig", "DM0ProgForCausalLM", "DM0ProgModel", "Pi05Config", "Pi05ForCausalLM", "Pi05Model",
            "OFTConfig", "OFTForCausalLM", "OFTModel", "OFTDiscreteConfig", "OFTDiscreteForCausalLM", "OFTDiscreteModel",
-           "PerceptionEncoderConfig", "PEVisionTower"]
+           "OFTDiffusionConfig", "OFTDiffusionForCausalLM", "OFTDiffusionModel", "PerceptionEncoderConfig", "PEVisionTower"]

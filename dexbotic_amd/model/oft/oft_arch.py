@@ -10,7 +10,7 @@ len_b ... len_b + Q - 1, padding follows; the mask is true on [0, len_b + Q); po
 reserves those rows (splice.build_oft_splice_plan), dxa_splice_fwd zero-fills them and dxa_action_put_fwd writes them in place
 (functional.OftSpliceFn); the head's first LayerNorm reads its rows out of the decoder output at the same offsets
 (functional.ActionNormFn).  Left padding is refused.  This class runs the ``Linear`` head; the ``Discrete`` head belongs to
-oft_discrete_arch.py, ``DiT`` is not built (action_model/builder.py).
+oft_discrete_arch.py, the ``DiT`` (diffusion) head to oft_diffusion_arch.py (action_model/builder.py).
 """
 from __future__ import annotations
 

@@ -313,6 +313,37 @@ int dxa_bin_logprob_bwd(const void* logits, int64_t ld, const int64_t* bins, con
                         float inv_temperature, void* dlogits, int64_t rows, int64_t NB, int dtype, dxa_stream_t stream);
 int dxa_ppo_clip_fwd(const float* logp, const float* old_logp, const float* adv, const void* mask, int mask_u8, int64_t n,
                      float clip_low, float clip_high, float inv_denom, float* sums, float* loss, float* coef, dxa_stream_t stream);
+/* OFT diffusion head (dexbotic/model/oft/oft_arch.py:106-116,224-250, oft/action_model/model.py:33-55,197-271).  A sample's
+ * reserved block is skip + 1 + n_rows rows: [state row, with proprio: skip = 1] [time row] [n_rows = chunk_size * action_dim
+ * noisy-action rows]; `off` and the out-of-range rule as for the OFT kernels above.  Every row of d elements is accessed 16 bytes at
+ * a time: d must be a multiple of 8 and every row operand 16-byte aligned (DXA_ERR_BAD_ARG otherwise, as for a null pointer; a bad
+ * dtype pair is DXA_ERR_UNSUPPORTED), checked before any launch.  fp32 arithmetic, fixed summation orders, no atomics.
+ *
+ * dxa_noisy_embed_fwd: fc1 (a Linear(1, d)) and the GELU of NoisyActionProjector in one pass, the operand of its fc2 product:
+ *   h[r, c] = gelu_erf(rnd(rnd(a[r]) * w1[c] + b1[c])) for a [R] fp32, w1 / b1 [d] in `w_dtype`, h [R, d] in `dtype`; rnd rounds to
+ *   `dtype` (the noisy action and the pre-activation as the reference's projector sees them in the compute dtype).
+ * dxa_noisy_embed_bwd: dpre = dh * gelu_erf'(pre), pre recomputed; dw1[c] (+)= sum_r dpre[r, c] * rnd(a[r]), db1[c] (+)= sum_r
+ *   dpre[r, c], both fp32: the rows are summed ascending in chunks of 16 into `partial` [dxa_noisy_embed_bwd_blocks(R), 2 d] fp32 and
+ *   the chunks are then added ascending (`accumulate`: onto what dw1 / db1 hold).  Two runs give the same bits.  a has no gradient.
+ * dxa_diffusion_put_fwd: into rows the splice kernel reserved, x [B, Sq, d]: x[b, off[b]] = state[b] (state [B, d] or NULL),
+ *   x[b, off[b] + skip] = time[b] (time [B, d]), x[b, off[b] + skip + 1 + j] = proj[b * n_rows + j] (proj [B * n_rows, d]).
+ * dxa_diffusion_put_bwd: dproj[b * n_rows + j] = dx[b, off[b] + skip + 1 + j], dstate[b] = dx[b, off[b]] (NULL: not wanted); the
+ *   rows of an out-of-range sample are written as zeros.  The time row has no gradient.
+ * dxa_ddim_step_embed: the two ends of one DDIM step of the sampler, one launch.  With eps [n] (`dtype`; NULL: the first step):
+ *   x0 = clamp(c0 * x - c1 * eps, -clip, clip) (clip <= 0: no clamp), x <- c2 * x0 + c3 * eps, x [n] fp32 in place.  Then
+ *   suffix[0, :] = time_row[:] (the next step's time row) and h[j, :] = gelu_erf(rnd(rnd(x[j]) * w1 + b1)) as dxa_noisy_embed_fwd. */
+int dxa_noisy_embed_fwd(const float* a, const void* w1, const void* b1, void* h, int64_t R, int64_t d, int dtype, int w_dtype,
+                        dxa_stream_t stream);
+int dxa_noisy_embed_bwd(const void* dh, const float* a, const void* w1, const void* b1, float* dw1, float* db1, float* partial,
+                        int64_t R, int64_t d, int accumulate, int dtype, int w_dtype, dxa_stream_t stream);
+int dxa_noisy_embed_bwd_blocks(int64_t R);
+int dxa_diffusion_put_fwd(void* x, const void* proj, const void* time, const void* state, const int64_t* off, int64_t B, int64_t Sq,
+                          int64_t d, int64_t n_rows, int dtype, dxa_stream_t stream);
+int dxa_diffusion_put_bwd(const void* dx, const int64_t* off, void* dproj, void* dstate, int64_t B, int64_t Sq, int64_t d,
+                          int64_t n_rows, int skip, int dtype, dxa_stream_t stream);
+int dxa_ddim_step_embed(const void* eps, float* x, float c0, float c1, float c2, float c3, float clip, const void* time_row,
+                        const void* w1, const void* b1, void* suffix, void* h, int64_t n, int64_t d, int dtype, int w_dtype,
+                        dxa_stream_t stream);
 /* The two ends of one Euler step of the DM0-prog sampler (dexbotic/model/dm0/dm0_prog_arch.py:360-400, 567-576), one launch each.
  * A sample's suffix is p + n rows: p in {0, 1} progress rows in front of the n = chunk_size action rows; A = action_dim, da = the
  * action expert's width.  Weights, te, h and out are in `dtype` (fp32 or bf16), x / progress / prog_min fp32 with explicit sample
