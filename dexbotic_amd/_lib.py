@@ -109,7 +109,7 @@ class DecodeDesc(C.Structure):
         ("layers", _vp), ("x_in", _vp), ("out", _vp), ("final_norm_w", _vp), ("cos_row", _vp), ("sin_row", _vp),
         ("workspace", _vp), ("workspace_bytes", _sz),
         ("n_layers", _i32), ("d", _i32), ("Hq", _i32), ("Hkv", _i32), ("D", _i32), ("F", _i32), ("slot", _i32), ("kv_lo", _i32),
-        ("max_len", _i32), ("eps", _f32),
+        ("max_len", _i32), ("eps", _f32), ("qk_norm", _vp),
     ]
 
 

@@ -22,6 +22,12 @@
 // GEMM epilogue): bf16 after the norm, after bias, after each RoPE product, after silu, after the gate product, after
 // the residual add.  Attention is fp32 from bf16 q / k / v (the flash kernel of the unfused path rounds the probabilities
 // to bf16 for its MFMA; this one does not), so the two paths agree to bf16 rounding, not bit for bit.
+//
+// Qwen3 (HF:qwen3/modeling_qwen3.py) differs in the attention block only: no q / k / v bias (the layer table's bias pointer is
+// NULL) and a per-head RMSNorm(D) of q and k between the projection and RoPE, one weight for all heads.  The kernel is a template
+// on QKN: the QKN instantiation's attention phase stages the raw q / k / v rows, takes the two sums of squares and normalises in
+// front of the rotation with the rounding points of the per-op pass (elementwise.hip qknorm_rope_split_k); the other one is the
+// Qwen2 code unchanged.  Phases, barriers, workspace and the GEMV code are shared.
 #include "common.h"
 #include "persistent.h"
 
@@ -36,7 +42,7 @@ typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 
 struct DecP {
-  const void* const* lp;          // [L][9]: ln1_w, qkv_w, qkv_b, o_w, ln2_w, gate_up_w, down_w, k_cache, v_cache
+  const void* const* lp;          // [L][9]: ln1_w, qkv_w, qkv_b (or NULL), o_w, ln2_w, gate_up_w, down_w, k_cache, v_cache
   const bf16_t* x_in;             // [d] embedding of the new token
   bf16_t* out;                    // [d] post final-norm hidden state
   const bf16_t* final_w;
@@ -45,6 +51,7 @@ struct DecP {
   unsigned* bar;
   int L, d, Hq, Hkv, D, F, slot, kv_lo, max_len;
   float eps, scale;
+  const void* const* qkn;         // [L][2]: q_norm_w, k_norm_w [D] (the QKN instantiation only; last: the Qwen2 kernel's argument offsets stay)
 };
 
 struct alignas(16) DSmem {
@@ -274,8 +281,9 @@ __device__ __forceinline__ void gemv_glu(DSmem& s, const bf16_t* W, int F, int K
 }
 
 // workgroup h < Hq: RoPE of q_h and of the new key, cache append (first head of a GQA group), softmax(q K^T scale) V over the
-// cached keys [kv_lo, slot) and the new one
-__device__ __forceinline__ void attention_phase(const DecP& p, DSmem& s, bf16_t* kc, bf16_t* vc) {
+// cached keys [kv_lo, slot) and the new one.  QKN: q_h and the new key go through RMSNorm(D) (weights wq, wk) before the rotation.
+template <bool QKN>
+__device__ __forceinline__ void attention_phase(const DecP& p, DSmem& s, bf16_t* kc, bf16_t* vc, const bf16_t* wq, const bf16_t* wk) {
   const int h = blockIdx.x;
   if (h >= p.Hq) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -309,6 +317,45 @@ __device__ __forceinline__ void attention_phase(const DecP& p, DSmem& s, bf16_t*
   (void)ta0; (void)ta1; (void)ta2; (void)ta3;
   DEC_T(ta0);
   if (j_first < T) request(j_first);
+  if constexpr (QKN) {
+    // ---- Qwen3: the raw q_h | k_g | v_g rows into LDS first (3 D values: more than the 512 threads at D = 256), then the per-head
+    //      RMSNorm of q and k (elementwise.hip qknorm_rope_split_k: rs in fp32 from the bf16 projections, y = bf16(w * bf16(x * rs)))
+    //      and the rotation of the Qwen2 branch below.  Every q-head workgroup of a GQA group recomputes the key's norm, as it
+    //      recomputes the key's rotation.
+    const int lgD = 31 - __clz(D);
+    for (int i = tid; i < 3 * D; i += 512) {
+      const int sel = i >> lgD, t = i & (D - 1);
+      const int base = sel == 0 ? h * D : (p.Hq + (sel - 1) * p.Hkv + g) * D;
+      float* dstv = sel == 0 ? s.q : sel == 1 ? s.kn : s.vn;
+      dstv[t] = ld_bf(rQ, base + t);
+    }
+    __syncthreads();
+    // sums of squares: D is a multiple of 64, so a wave holds values of q alone (waves [0, D / 64)) or of k alone ([D / 64, D / 32))
+    const int nw = D >> 6;
+    float sq = 0.f;
+    if (tid < 2 * D) {
+      const float x = tid < D ? s.q[tid] : s.kn[tid - D];
+      sq = x * x;
+    }
+    sq = wave_sum(sq);
+    if (lane == 0) s.wred[wave] = sq;
+    __syncthreads();
+    if (tid < D) {                                      // (a thread reads and rewrites its own two elements of s.q or s.kn)
+      const bool isk = tid >= half;
+      const int t = isk ? tid - half : tid;
+      float ss = 0.f;
+      for (int i = 0; i < nw; ++i) ss += s.wred[(isk ? nw : 0) + i];
+      const float rs = rsqrtf(ss / (float)D + p.eps);
+      float* xv = isk ? s.kn : s.q;
+      const bf16_t* w = isk ? wk : wq;
+      const float y1 = rnd<bf16_t>(bf2f(w[t]) * rnd<bf16_t>(xv[t] * rs));
+      const float y2 = rnd<bf16_t>(bf2f(w[t + half]) * rnd<bf16_t>(xv[t + half] * rs));
+      const float cc = rnd<bf16_t>(p.cosr[t]), sn = rnd<bf16_t>(p.sinr[t]);
+      const float o1 = rnd<bf16_t>(rnd<bf16_t>(y1 * cc) + rnd<bf16_t>(-y2 * sn));
+      const float o2 = rnd<bf16_t>(rnd<bf16_t>(y2 * cc) + rnd<bf16_t>(y1 * sn));
+      xv[t] = o1; xv[t + half] = o2;
+    }
+  } else
   // ---- RoPE (elementwise.hip rope_k: every product rounded to bf16, cos / sin rounded to bf16)
   if (tid < D) {
     const bool isk = tid >= half;
@@ -408,6 +455,7 @@ __device__ __forceinline__ void attention_phase(const DecP& p, DSmem& s, bf16_t*
   DEC_ATT(0, ta0, ta1); DEC_ATT(1, ta1, ta2); DEC_ATT(2, ta2, ta3);
 }
 
+template <bool QKN>
 __global__ __launch_bounds__(512) void decode_step_k(const DecP p) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   DSmem& s = *reinterpret_cast<DSmem*>(smem_raw);
@@ -427,7 +475,8 @@ __global__ __launch_bounds__(512) void decode_step_k(const DecP p) {
     DEC_PHASE_END(0); }
     // ---- attention over the cache
     { DEC_PHASE_BEGIN();
-    attention_phase(p, s, (bf16_t*)lw[7], (bf16_t*)lw[8]);
+    attention_phase<QKN>(p, s, (bf16_t*)lw[7], (bf16_t*)lw[8], QKN ? uni((const bf16_t*)p.qkn[2 * l]) : nullptr,
+                         QKN ? uni((const bf16_t*)p.qkn[2 * l + 1]) : nullptr);
     DEC_PHASE_SYNC();
     grid_sync(p.bar, nwg, epoch);
     DEC_PHASE_END(1); }
@@ -474,6 +523,20 @@ extern "C" size_t dxa_decode_step_workspace(int d, int Hq, int Hkv, int D, int F
   return ws_elems(d, Hq, Hkv, D, F) * sizeof(bf16_t);
 }
 
+// every workgroup must be resident at once (device-wide barrier): one per CU, at least one per attention head
+template <bool QKN>
+static int launch_step(const DecP& p, hipStream_t st) {
+  if (int rc = dxa_raise_lds<decode_step_k<QKN>>((int)sizeof(DSmem))) return rc;      // before the occupancy query
+  Residency r;
+  if (int rc = residency(reinterpret_cast<const void*>(&decode_step_k<QKN>), sizeof(DSmem), &r)) return rc;
+  DXA_CHECK_ARG(r.per_cu >= 1, "dxa_decode_step: the kernel does not fit on this device");
+  const int grid = r.cus;          // one workgroup per CU: the weight stream wants every CU's load queue, not more waves
+  DXA_CHECK_ARG(p.Hq <= grid, "dxa_decode_step: %d attention heads need at least as many workgroups (%d)", p.Hq, grid);
+  hipLaunchKernelGGL(decode_step_k<QKN>, dim3(grid), dim3(512), sizeof(DSmem), st, p);
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
+}
+
 extern "C" int dxa_decode_step(const dxa_decode_desc* q, dxa_stream_t stream) {
   DXA_CHECK_ARG(q && q->layers && q->x_in && q->out && q->final_norm_w && q->cos_row && q->sin_row && q->workspace,
                 "dxa_decode_step: null pointer");
@@ -494,7 +557,7 @@ extern "C" int dxa_decode_step(const dxa_decode_desc* q, dxa_stream_t stream) {
                 "dxa_decode_step: workspace must be 256-byte, x_in / out / final_norm_w 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   DecP p;
-  p.lp = q->layers;
+  p.lp = q->layers; p.qkn = q->qk_norm;
   p.x_in = (const bf16_t*)q->x_in; p.out = (bf16_t*)q->out; p.final_w = (const bf16_t*)q->final_norm_w;
   p.cosr = q->cos_row; p.sinr = q->sin_row;
   auto up = [](size_t v) { return (v + 127) / 128 * 128; };
@@ -506,16 +569,7 @@ extern "C" int dxa_decode_step(const dxa_decode_desc* q, dxa_stream_t stream) {
   p.L = q->n_layers; p.d = q->d; p.Hq = q->Hq; p.Hkv = q->Hkv; p.D = q->D; p.F = q->F;
   p.slot = q->slot; p.kv_lo = q->kv_lo; p.max_len = q->max_len;
   p.eps = q->eps; p.scale = 1.f / sqrtf((float)q->D);
-  // every workgroup must be resident at once (device-wide barrier): one per CU, at least one per attention head
-  if (int rc = dxa_raise_lds<decode_step_k>((int)sizeof(DSmem))) return rc;      // before the occupancy query
-  Residency r;
-  if (int rc = residency(reinterpret_cast<const void*>(&decode_step_k), sizeof(DSmem), &r)) return rc;
-  DXA_CHECK_ARG(r.per_cu >= 1, "dxa_decode_step: the kernel does not fit on this device");
-  const int grid = r.cus;          // one workgroup per CU: the weight stream wants every CU's load queue, not more waves
-  DXA_CHECK_ARG(q->Hq <= grid, "dxa_decode_step: %d attention heads need at least as many workgroups (%d)", q->Hq, grid);
-  hipLaunchKernelGGL(decode_step_k, dim3(grid), dim3(512), sizeof(DSmem), st, p);
-  DXA_CHECK_LAUNCH();
-  return DXA_OK;
+  return q->qk_norm ? launch_step<true>(p, st) : launch_step<false>(p, st);
 }
 
 #if defined(DXA_DEC_STAMPS)

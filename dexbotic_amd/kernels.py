@@ -1909,10 +1909,13 @@ def decode_step_supported(d: int, Hq: int, Hkv: int, D: int, F: int) -> bool:
 
 def decode_step(layer_table: torch.Tensor, x_in: torch.Tensor, out: torch.Tensor, final_w: torch.Tensor, cos_row: torch.Tensor,
                 sin_row: torch.Tensor, ws: torch.Tensor, n_layers: int, d: int, Hq: int, Hkv: int, D: int, F: int, slot: int,
-                kv_lo: int, max_len: int, eps: float) -> torch.Tensor:
+                kv_lo: int, max_len: int, eps: float, qk_norm_table: Optional[torch.Tensor] = None) -> torch.Tensor:
     """one new token of one sequence through every decoder layer + final norm in ONE persistent launch (dxa_decode_step);
-    `layer_table`: int64 device tensor of n_layers * 9 pointers (see include/dexbotic_amd.h); the caches are appended in place"""
+    `layer_table`: int64 device tensor of n_layers * 9 pointers (see include/dexbotic_amd.h); the caches are appended in place.
+    `qk_norm_table`: int64 device tensor of n_layers * 2 pointers (q_norm / k_norm weights [D]) for a Qwen3 decoder, None: no norm"""
     assert layer_table.dtype == torch.int64 and layer_table.numel() == n_layers * 9 and layer_table.is_cuda
+    if qk_norm_table is not None:
+        assert qk_norm_table.dtype == torch.int64 and qk_norm_table.numel() == n_layers * 2 and qk_norm_table.is_cuda
     for t in (x_in, out, final_w):
         assert t.dtype == torch.bfloat16 and t.is_contiguous() and t.numel() == d and t.is_cuda
     for t in (cos_row, sin_row):
@@ -1923,6 +1926,7 @@ def decode_step(layer_table: torch.Tensor, x_in: torch.Tensor, out: torch.Tensor
     q.workspace, q.workspace_bytes = _ptr(ws), ws.numel() * ws.element_size()
     q.n_layers, q.d, q.Hq, q.Hkv, q.D, q.F = n_layers, d, Hq, Hkv, D, F
     q.slot, q.kv_lo, q.max_len, q.eps = slot, kv_lo, max_len, float(eps)
+    q.qk_norm = _ptr(qk_norm_table) if qk_norm_table is not None else None
     L.check(lib.dxa_decode_step(C.byref(q), _stream()), "dxa_decode_step")
     return out
 

@@ -165,7 +165,8 @@ class Qwen2Backbone(nn.Module):
                 out = torch.empty(d, device=inputs_embeds.device, dtype=torch.bfloat16)
                 K.decode_step(fused["table"], inputs_embeds.reshape(d).contiguous(), out, fused["final_w"], cos_m[past - kv_lo],
                               sin_m[past - kv_lo], fused["ws"], c.num_hidden_layers, d, c.num_attention_heads,
-                              c.num_key_value_heads, c.head_dim, c.intermediate_size, past, kv_lo, cache.max_len, c.rms_norm_eps)
+                              c.num_key_value_heads, c.head_dim, c.intermediate_size, past, kv_lo, cache.max_len, c.rms_norm_eps,
+                              qk_norm_table=fused["qk_norm"])
                 cache.length = total
                 cache.fused_steps += 1
                 return out.view(1, 1, d)
@@ -192,7 +193,8 @@ class Qwen2Backbone(nn.Module):
 
     def _decode_state(self, cache: "KVCache"):
         """pointer table, final-norm weight and workspace of the persistent decode step for this cache (built at the first
-        single-token pass, kept on the cache), or None where the launch does not apply (DXA_DECODE_FUSED=0, widths outside the
+        single-token pass, kept on the cache; ``attention_bias = False``: bias pointer 0, ``qk_norm = True``: the ``[L][2]`` table
+        of q_norm / k_norm weights beside it), or None where the launch does not apply (DXA_DECODE_FUSED=0, widths outside the
         kernel's limits, a weight that is not 16-byte aligned, fp32 weights): the per-op path above then runs."""
         import os
         st, c = self.store, self.config
@@ -205,15 +207,19 @@ class Qwen2Backbone(nn.Module):
         if (os.environ.get("DXA_DECODE_FUSED", "1") != "0" and st.shadow is not None and cache.batch == 1 and
                 K.decode_step_supported(d, Hq, Hkv, D, F_) and cache.max_len - 1 <= K.DECODE_FUSED_MAX_KEYS):
             nq = (Hq + 2 * Hkv) * D
-            ptrs = []
+            ptrs, qkn = [], []
             for i, sp in enumerate(self.layer_specs):
-                ptrs += [st.w(sp.ln1).data_ptr(), st.w(*sp.qkv_w, shape=(nq, d)).data_ptr(), st.w(*sp.qkv_b, shape=(nq,)).data_ptr(),
+                bias = st.w(*sp.qkv_b, shape=(nq,)).data_ptr() if sp.qkv_b is not None else 0      # 0: no bias (Qwen3)
+                ptrs += [st.w(sp.ln1).data_ptr(), st.w(*sp.qkv_w, shape=(nq, d)).data_ptr(), bias,
                          st.w(sp.o_w).data_ptr(), st.w(sp.ln2).data_ptr(), st.w(*sp.gu_w, shape=(2 * F_, d)).data_ptr(),
                          st.w(sp.down_w).data_ptr(), cache.k[i].data_ptr(), cache.v[i].data_ptr()]
+                if sp.qk_norm is not None:                 # per-head RMSNorm of q and k (Qwen3): [L][2] weight pointers
+                    qkn += [st.w(sp.qk_norm[0]).data_ptr(), st.w(sp.qk_norm[1]).data_ptr()]
             final_w = st.w(self.p + "norm.weight")
-            if all(p_ % 16 == 0 for p_ in ptrs) and final_w.data_ptr() % 16 == 0:
+            if all(p_ % 16 == 0 for p_ in ptrs + qkn) and final_w.data_ptr() % 16 == 0:
                 dev = cache.k[0].device
                 state = {"table": torch.tensor(ptrs, dtype=torch.int64).to(dev), "final_w": final_w,
+                         "qk_norm": torch.tensor(qkn, dtype=torch.int64).to(dev) if qkn else None,
                          "ws": K.decode_step_workspace(d, Hq, Hkv, D, F_, dev)}
         cache.fused = {"key": key, "state": state}
         return state

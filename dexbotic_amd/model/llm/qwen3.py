@@ -12,15 +12,17 @@ Everything else is shared: registration and the two forward drivers are ``Qwen2B
 layer itself — with or without a key/value cache — is the one launch sequence of ``functional.Qwen2LayerFn._run``.
 Parameter names are HF's.
 
-Known gap: the persistent one-launch decode step (csrc/decode_fused.hip) has no q/k norm, so ``_decode_state`` returns None and every
-single-token pass runs the per-op cached path (``cache.fused_steps`` stays 0).
+Single-token decode (B = 1, bf16) is the persistent one-launch step of ``Qwen2Backbone.forward_cached`` (csrc/decode_fused.hip): its
+QKN instantiation normalises q and the new key per head in front of RoPE, the layer table's bias pointer is NULL and the ``[L][2]``
+table of q_norm / k_norm weights rides beside it (``dxa_decode_desc.qk_norm``).  It takes head_dim 64, 128 or 256; any other
+head_dim, ``DXA_DECODE_FUSED=0``, fp32 or a batch run the per-op cached path (``cache.fused_steps`` stays 0).
 """
 from __future__ import annotations
 
 from dataclasses import dataclass
 
 from ... import kernels as K
-from .qwen2 import KVCache, Qwen2Backbone, Qwen2Config
+from .qwen2 import Qwen2Backbone, Qwen2Config
 
 
 @dataclass
@@ -58,10 +60,6 @@ class Qwen3Backbone(Qwen2Backbone):
         if config.head_dim not in K.QKNORM_HEAD_DIMS:
             raise NotImplementedError(f"Qwen3 head_dim {config.head_dim}: the fused q/k-norm + RoPE kernels take {K.QKNORM_HEAD_DIMS}")
         super().__init__(store, prefix, config)
-
-    def _decode_state(self, cache: KVCache):
-        """None: the persistent decode launch does not know the q/k norm, the per-op cached path runs (module docstring)"""
-        return None
 
 
 class Qwen3Expert(Qwen3Backbone):

@@ -896,10 +896,16 @@ int dxa_dit_sample_bf16_per_fwd(float* x, const float* z_emb, const float* t_emb
  * discrete_vla_arch.py:24-50, dexbotic/model/dexbotic_arch.py:429-496): a grid of co-resident workgroups walks
  * [RMSNorm] qkv + bias | RoPE + cache append + attention | o + residual | [RMSNorm] gate / up + SiLU * up | down + residual
  * per layer with device-wide barriers in between (co-residency contract and watchdog of dxa_dit_blocks_fwd; dxa_decode_status
- * reports a launch that gave up).  bf16 weights, bf16 rounding points of the unfused kernels, fp32 accumulation.
- *   layers: DEVICE array of n_layers * 9 pointers — input_layernorm.weight [d], q|k|v weight [(Hq + 2 Hkv) D, d], q|k|v bias,
- *           o_proj.weight [d, Hq D], post_attention_layernorm.weight [d], gate|up weight [2 F, d], down_proj.weight [d, F] (all
- *           bf16, 16-byte aligned), key cache and value cache of the layer [Hkv, max_len, D] bf16 (post-RoPE keys).
+ * reports a launch that gave up).  bf16 weights, bf16 rounding points of the unfused kernels, fp32 accumulation.  D is 64, 128 or
+ * 256; Hq D need not equal d (Qwen3).
+ *   layers: DEVICE array of n_layers * 9 pointers — input_layernorm.weight [d], q|k|v weight [(Hq + 2 Hkv) D, d], q|k|v bias
+ *           [(Hq + 2 Hkv) D] or NULL for projections without a bias (Qwen3), o_proj.weight [d, Hq D],
+ *           post_attention_layernorm.weight [d], gate|up weight [2 F, d], down_proj.weight [d, F] (all bf16, 16-byte aligned),
+ *           key cache and value cache of the layer [Hkv, max_len, D] bf16 (post-RoPE keys).
+ *   qk_norm: NULL (a zero-initialised descriptor: no q / k norm, Qwen2), or a DEVICE array of n_layers * 2 pointers —
+ *           self_attn.q_norm.weight [D] and self_attn.k_norm.weight [D], bf16, 16-byte aligned: HF Qwen3RMSNorm(head_dim) of every q
+ *           head and of the new key between the projection and RoPE (eps as the layer norms); the cached key is the normalised,
+ *           rotated one.
  *   x_in [d] bf16: embedding of the new token; out [d] bf16: hidden state after the final norm (final_norm_w [d] bf16).
  *   cos_row / sin_row [D / 2] fp32: the rotary table row of the token's position.  slot: cache position the new key / value are
  *   written to; the token attends to the cached positions [kv_lo, slot) and itself.  workspace: dxa_decode_step_workspace bytes,
@@ -911,6 +917,7 @@ typedef struct dxa_decode_desc {
   void* workspace; size_t workspace_bytes;
   int32_t n_layers, d, Hq, Hkv, D, F, slot, kv_lo, max_len;
   float eps;
+  const void* const* qk_norm;
 } dxa_decode_desc;
 size_t dxa_decode_step_workspace(int d, int Hq, int Hkv, int D, int F);
 int dxa_decode_step(const dxa_decode_desc* desc, dxa_stream_t stream);
