@@ -23,6 +23,8 @@ F32, BF16 = 0, 1
 ACT_NONE, ACT_GELU_ERF, ACT_GELU_TANH, ACT_QUICK_GELU, ACT_SILU, ACT_RELU, ACT_SIGMOID = 0, 1, 2, 3, 4, 5, 6
 NT, NN, TN = 0, 1, 2
 FILTER_BICUBIC = 3
+FILTER_BILINEAR = 2
+JITTER_BRIGHTNESS, JITTER_CONTRAST, JITTER_SATURATION, JITTER_HUE = 0, 1, 2, 3
 FUSE_NONE, FUSE_SWIGLU = 0, 1
 
 _vp, _i64, _i32, _f32, _sz = C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_size_t
@@ -102,6 +104,10 @@ class ImageDesc(C.Structure):
         ("tmp", _vp), ("out", _vp), ("out_dtype", _i32), ("out_u8", _vp), ("rescale", C.c_double),
         ("mean", _f32 * 3), ("std", _f32 * 3),
     ]
+
+
+class JitterParams(C.Structure):
+    _fields_ = [("apply", _i32), ("order", _i32 * 4), ("brightness", _f32), ("contrast", _f32), ("saturation", _f32), ("hue", _f32)]
 
 
 class DecodeDesc(C.Structure):
@@ -236,6 +242,10 @@ SIGNATURES = {
     "dxa_resample_ksize":(_int, [_int, _int]),
     "dxa_resample_coeffs": (_int, [_int, _int, _int, _vp, _vp]),
     "dxa_image_preprocess": (_int, [C.POINTER(ImageDesc), _vp]),
+    "dxa_resample_ksize_filter": (_int, [_int, _int, _int]),
+    "dxa_image_crop_resize": (_int, [_vp, _int, _int, _int, _int, C.c_uint32, _vp, _vp, _int, _vp, _vp, _vp, _int, _int, _vp, _int, _vp, _vp]),
+    "dxa_color_jitter": (_int, [_vp, _int, _int, _int, _vp, _vp, _vp, _vp]),
+    "dxa_color_jitter_pixels_host": (_int, [_vp, _i64, _vp, _int]),
     "dxa_dit_blocks_workspace": (_sz, [_int, _int, _int]),
     "dxa_dit_blocks_fwd": (_int, [_vp, _vp, _int, _int, _int, _int, _int, _int, _f32, _vp, _sz, _vp]),
     "dxa_dit_blocks_status": (_int, [_vp, _vp]),

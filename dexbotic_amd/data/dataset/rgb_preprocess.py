@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from ... import kernels as K
+from .augmentations import PixelAug
 
 
 def _edge(v, key):
@@ -71,19 +72,76 @@ class PreprocessRGB:
             return (0, 0, 0)
         return tuple(int(x * 255) for x in self.image_processor.image_mean)  # rgb_preprocess.py:23
 
-    def batch(self, frames: torch.Tensor, want_u8: bool = False):
-        """frames: uint8 [n, h, w, 3] (host or device) -> [n, 3, H, W] on the device"""
+    def batch(self, frames: torch.Tensor, want_u8: bool = False, augment: bool = False):
+        """frames: uint8 [n, h, w, 3] (host or device) -> [n, 3, H, W] on the device.  With `augment` the frames first go
+        through the PixelAug policy given as `augmentations`, on the device, each frame with its own draw."""
         frames = frames.to(self.device, non_blocking=True)
+        if augment:
+            if not isinstance(self.augmentations, PixelAug):
+                raise ValueError("batch(augment=True) needs augmentations=PixelAug(...); a host callable works per frame through __call__")
+            if not self.augmentations.identity:
+                return self._augmented(frames, want_u8)
+        return self._preprocess(frames, want_u8)
+
+    def _preprocess(self, frames, want_u8):
         p = self.image_processor
         return K.image_preprocess(frames, pad=self.image_aspect_ratio == "pad", bg=self._bg(), size=self._short(),
                                   crop=self._crop(), mean=p.image_mean, std=p.image_std,
                                   rescale=getattr(p, "rescale_factor", 1 / 255), out_dtype=self.dtype, want_u8=want_u8)
 
+    def _augmented(self, frames, want_u8):
+        """expand2square with the processor's colour where the reference has it (before the augmentation), then the policy:
+        its own PadToSquare(fill=0) is a no-op on a square frame and a real zero pad otherwise.  A batch stays rectangular,
+        so the frames 'v3' crops (-> 384 x 384) and the ones it leaves at their size go through the launches as two groups."""
+        aug = self.augmentations
+        K._check_u8_frames(frames, "PreprocessRGB.batch")
+        n, h, w, _ = frames.shape
+        expand = self.image_aspect_ratio == "pad"
+        padded = (expand or aug.pads_to_square) and h != w
+        ph, pw = (max(h, w), max(h, w)) if padded else (h, w)
+        bg = self._bg() if expand else (0, 0, 0)
+        par = aug.sample(n, ph, pw)
+        groups = []                                              # (frame indices, boxes or None, output side)
+        cropped = np.flatnonzero(par.apply_crop)
+        whole = np.flatnonzero(par.apply_crop == 0)
+        if len(cropped):
+            groups.append((cropped, par.box[cropped], aug.crop_size))
+        if len(whole):
+            if aug.resize is not None or padded:                 # both only ever see square frames
+                box = np.tile(np.asarray([0, 0, ph], np.int32), (len(whole), 1))
+                groups.append((whole, box, aug.resize if aug.resize is not None else ph))
+            else:
+                groups.append((whole, None, None))
+        ch, cw = self._crop()
+        out = torch.empty(n, 3, ch, cw, device=self.device, dtype=self.dtype)
+        u8 = torch.empty(n, ch, cw, 3, device=self.device, dtype=torch.uint8) if want_u8 else None
+        for idx, box, side in groups:
+            everything = len(idx) == n
+            sel = None if everything else torch.from_numpy(idx).to(self.device)
+            sub = frames if everything else frames.index_select(0, sel)
+            if box is None:
+                sub = sub.clone() if everything else sub         # the jitter works in place: never on the caller's frames
+            else:
+                sub = K.image_crop_resize(sub, box, side, pad=padded, bg=bg)
+            q = par.take(idx)
+            K.image_color_jitter(sub, q.apply_jitter, q.order, q.factors, q.hue)
+            res = self._preprocess(sub, want_u8)
+            o, o8 = res if want_u8 else (res, None)
+            if everything:
+                out, u8 = o, o8
+            else:
+                out.index_copy_(0, sel, o)
+                if want_u8:
+                    u8.index_copy_(0, sel, o8)
+        return (out, u8) if want_u8 else out
+
     def __call__(self, image) -> torch.Tensor:
         if image is None:                                                   # rgb_preprocess.py:14-19
             ch, cw = self._crop()
             return torch.zeros(3, ch, cw, device=self.device, dtype=self.dtype)
-        if self.augmentations:                                              # PIL-level augmentations stay on the host
+        if isinstance(self.augmentations, PixelAug):                        # the device policies: one frame is a batch of one
+            return self.batch(to_uint8_hwc(image)[None], augment=True)[0]
+        if self.augmentations:                                              # any other callable works on PIL frames on the host
             if self.image_aspect_ratio == "pad":
                 from PIL import Image
                 w, h = image.size

@@ -10,6 +10,7 @@ import contextlib
 import ctypes as C
 from typing import Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -1792,6 +1793,86 @@ def image_preprocess(frames: torch.Tensor, *, pad: bool, bg: Sequence[int], size
     d.tmp, d.out, d.out_dtype, d.out_u8, d.rescale = _ptr(tmp), _ptr(out), dt(out), _ptr(u8), float(rescale)
     L.check(lib.dxa_image_preprocess(C.byref(d), _stream()), "dxa_image_preprocess")
     return (out, u8) if want_u8 else out
+
+
+# ------------------------------------------------------------------------------------------------ training augmentations
+_BILINEAR_TABLES: dict = {}
+
+
+def bilinear_tables(in_size: int, out_size: int):
+    """Pillow bilinear tap tables of one axis on the host: (ksize, bounds int32 [out,2], taps int32 [out,ksize])"""
+    key = (int(in_size), int(out_size))
+    hit = _BILINEAR_TABLES.get(key)
+    if hit is None:
+        ks = lib.dxa_resample_ksize_filter(key[0], key[1], L.FILTER_BILINEAR)
+        bounds = np.zeros((out_size, 2), np.int32)
+        taps = np.zeros((out_size, ks), np.int32)
+        L.check(lib.dxa_resample_coeffs(key[0], key[1], L.FILTER_BILINEAR, bounds.ctypes.data, taps.ctypes.data), "dxa_resample_coeffs")
+        hit = _BILINEAR_TABLES[key] = (ks, bounds, taps)
+    return hit
+
+
+def _check_u8_frames(frames, who):
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3 \
+            or not frames.is_contiguous():
+        raise L.DxaError(f"{who}: expected contiguous uint8 [n,h,w,3], got {getattr(frames, 'dtype', type(frames))} "
+                         f"{tuple(getattr(frames, 'shape', ()))}")
+
+
+def image_crop_resize(frames: torch.Tensor, boxes, size: int, *, pad: bool = False, bg: Sequence[int] = (0, 0, 0)) -> torch.Tensor:
+    """uint8 frames [n, h, w, 3] on the device -> uint8 [n, size, size, 3]: frame i's square box boxes[i] = (x0, y0, c) of
+    the (expand2square-padded when `pad`) frame, cropped and resized as Pillow's crop().resize(BILINEAR)"""
+    _check_u8_frames(frames, "image_crop_resize")
+    n, h, w, _ = frames.shape
+    boxes = np.ascontiguousarray(np.asarray(boxes, np.int32).reshape(-1, 3))
+    if boxes.shape[0] != n:
+        raise L.DxaError(f"image_crop_resize: {n} frames but {boxes.shape[0]} boxes")
+    size = int(size)
+    dev = frames.device
+    out = torch.empty(n, size, size, 3, device=dev, dtype=torch.uint8)
+    if n == 0:
+        return out
+    if size <= 0 or int(boxes[:, 2].min()) <= 0:
+        raise L.DxaError(f"image_crop_resize: sides must be positive (size {size}, smallest box {int(boxes[:, 2].min())})")
+    sides, which = np.unique(boxes[:, 2], return_inverse=True)          # one table per distinct crop side
+    tabs = [bilinear_tables(int(c), size) for c in sides]
+    ks = max(t[0] for t in tabs)
+    bounds = np.stack([t[1] for t in tabs])
+    taps = np.zeros((len(tabs), size, ks), np.int32)
+    for j, t in enumerate(tabs):
+        taps[j, :, :t[0]] = t[2]
+    boxes4 = np.ascontiguousarray(np.concatenate([boxes, which.reshape(-1, 1).astype(np.int32)], 1))
+    sides = np.ascontiguousarray(sides.astype(np.int32))
+    cmax = int(sides.max())
+    d_boxes, d_bounds, d_taps = (torch.from_numpy(a).to(dev) for a in (boxes4, bounds, taps))
+    tmp = torch.empty(n * cmax * size * 3, device=dev, dtype=torch.uint8)
+    bg_rgb = int(bg[0]) | (int(bg[1]) << 8) | (int(bg[2]) << 16)
+    L.check(lib.dxa_image_crop_resize(_ptr(frames), n, h, w, int(bool(pad)), bg_rgb, _ptr(d_boxes), boxes4.ctypes.data, size,
+                                      _ptr(d_bounds), _ptr(d_taps), sides.ctypes.data, len(tabs), ks, _ptr(tmp), cmax, _ptr(out),
+                                      _stream()), "dxa_image_crop_resize")
+    return out
+
+
+JITTER_DTYPE = np.dtype([("apply", np.int32), ("order", np.int32, 4), ("brightness", np.float32), ("contrast", np.float32),
+                         ("saturation", np.float32), ("hue", np.float32)])
+
+
+def image_color_jitter(frames: torch.Tensor, apply, order, factors, hue) -> torch.Tensor:
+    """ColorJitter in place on uint8 frames [n, h, w, 3] on the device, one parameter row per frame: apply [n], order [n,4]
+    (a permutation of brightness 0, contrast 1, saturation 2, hue 3), factors [n,3], hue [n] in turns.  Frames with
+    apply == 0 are not touched.  Pillow's ImageEnhance / HSV arithmetic, bit for bit."""
+    _check_u8_frames(frames, "image_color_jitter")
+    n, h, w, _ = frames.shape
+    tab = np.zeros(n, JITTER_DTYPE)
+    tab["apply"], tab["order"], tab["hue"] = np.asarray(apply).reshape(n), np.asarray(order).reshape(n, 4), np.asarray(hue).reshape(n)
+    f = np.asarray(factors, np.float32).reshape(n, 3)
+    tab["brightness"], tab["contrast"], tab["saturation"] = f[:, 0], f[:, 1], f[:, 2]
+    if n == 0 or not tab["apply"].any():
+        return frames
+    d_tab = torch.from_numpy(tab.view(np.uint8)).to(frames.device)
+    sums = torch.empty(n, device=frames.device, dtype=torch.int64)
+    L.check(lib.dxa_color_jitter(_ptr(frames), n, h, w, _ptr(d_tab), tab.ctypes.data, _ptr(sums), _stream()), "dxa_color_jitter")
+    return frames
 
 
 # ------------------------------------------------------------------------------------------------ fused DiT blocks

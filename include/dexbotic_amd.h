@@ -821,6 +821,47 @@ int dxa_resample_ksize(int in_size, int out_size);
 int dxa_resample_coeffs(int in_size, int out_size, int filter, int32_t* bounds, int32_t* kk);
 int dxa_image_preprocess(const dxa_image_desc* d, dxa_stream_t stream);
 
+/* ---- device-side training augmentations ---------------------------------------------------------------------------
+ * The reference augments every training frame on the host (dexbotic/data/dataset/augmentations.py, albumentations over
+ * cv2); the policies 'v3', 'color', 'color_dm0' and 'identity' are RandomResizedCrop / PadToSquare / Resize / ColorJitter
+ * only, and run here on uint8 frames already on the device, before dxa_image_preprocess.  The arithmetic is Pillow's
+ * (12.2.0), the package the resampler above is pinned to: crop + Image.resize(BILINEAR) (antialiased when it shrinks,
+ * which cv2's INTER_LINEAR is not) and the ImageEnhance / HSV sequence torchvision's PIL backend runs for ColorJitter.
+ * The random draws stay on the host; every frame brings its own parameters.
+ *
+ * dxa_resample_ksize_filter: dxa_resample_ksize for a given filter (DXA_FILTER_BILINEAR has support 1, bicubic 2).
+ * dxa_image_crop_resize: n frames of identical h x w; `pad` / bg_rgb (r | g << 8 | b << 16) as dxa_image_preprocess.
+ *   boxes[n][4] = (x0, y0, c, table): frame i's square box [x0, x0 + c) x [y0, y0 + c) of the (padded) frame is resized
+ *   to S x S with the taps of table `table`: bounds[n_tables][S][2] and taps[n_tables][S][ks] hold dxa_resample_coeffs(c, S,
+ *   DXA_FILTER_BILINEAR) of each distinct side, rows padded to the common stride ks; table_sides_host[n_tables] names the
+ *   side each table was built for.  boxes is a device array, boxes_host the same values on the host (checked before any
+ *   launch).  tmp is a uint8 scratch of n * tmp_rows * S * 3 bytes, tmp_rows >= the largest c.  out: uint8 [n, S, S, 3].
+ * dxa_color_jitter: in place on uint8 [n, h, w, 3].  params[n] (device, params_host the same on the host): frames with
+ *   apply == 0 are not touched; the others get brightness, contrast, saturation and hue in `order`.  Contrast blends with
+ *   int(mean L + 0.5) of the frame as the ops before it left it: pass 1 recomputes those per pixel and adds L up per frame in
+ *   sums[n] (uint64 scratch, zeroed here; integer sums do not depend on order), pass 2 applies all four in registers.
+ * dxa_color_jitter_pixels_host: HOST function, the same per-pixel code on k loose RGB pixels with a given contrast mean m.
+ * ---------------------------------------------------------------------------------------------- */
+#define DXA_FILTER_BILINEAR 2 /* PIL.Image.BILINEAR */
+#define DXA_JITTER_BRIGHTNESS 0
+#define DXA_JITTER_CONTRAST 1
+#define DXA_JITTER_SATURATION 2
+#define DXA_JITTER_HUE 3
+typedef struct dxa_jitter_params {
+  int32_t apply;
+  int32_t order[4];       /* a permutation of DXA_JITTER_* */
+  float brightness, contrast, saturation; /* blend factors, >= 0 */
+  float hue;              /* shift in turns, |hue| <= 0.5; trunc(hue * 255) levels of the 8-bit H plane */
+} dxa_jitter_params;
+int dxa_resample_ksize_filter(int in_size, int out_size, int filter);
+int dxa_image_crop_resize(const void* src, int n, int h, int w, int pad, uint32_t bg_rgb, const int32_t* boxes,
+                          const int32_t* boxes_host, int S, const int32_t* bounds, const int32_t* taps,
+                          const int32_t* table_sides_host, int n_tables, int ks, void* tmp, int tmp_rows, void* out,
+                          dxa_stream_t stream);
+int dxa_color_jitter(void* pixels, int n, int h, int w, const dxa_jitter_params* params,
+                     const dxa_jitter_params* params_host, uint64_t* sums, dxa_stream_t stream);
+int dxa_color_jitter_pixels_host(void* pixels, int64_t k, const dxa_jitter_params* params, int m);
+
 /* ---- persistent DiT blocks for the action sampler ---------------------------------------------------------------
  * All `depth` DiTBlocks of one denoising call (dexbotic/model/cogact/action_model/dit.py:137-162, walked by DiT.forward
  * :281-293 inside every DDIM step of cogact_arch.py:186-197) in ONE launch: h [N*T1, H] (fp32, in place) goes through
