@@ -246,6 +246,8 @@ SIGNATURES = {
     "dxa_image_crop_resize": (_int, [_vp, _int, _int, _int, _int, C.c_uint32, _vp, _vp, _int, _vp, _vp, _vp, _int, _int, _vp, _int, _vp, _vp]),
     "dxa_color_jitter": (_int, [_vp, _int, _int, _int, _vp, _vp, _vp, _vp]),
     "dxa_color_jitter_pixels_host": (_int, [_vp, _i64, _vp, _int]),
+    "dxa_image_affine": (_int, [_vp, _vp, _int, _int, _int, _vp, _vp, C.c_uint32, _vp]),
+    "dxa_image_affine_host": (_int, [_vp, _vp, _int, _int, _int, _vp, C.c_uint32]),
     "dxa_dit_blocks_workspace": (_sz, [_int, _int, _int]),
     "dxa_dit_blocks_fwd": (_int, [_vp, _vp, _int, _int, _int, _int, _int, _int, _f32, _vp, _sz, _vp]),
     "dxa_dit_blocks_status": (_int, [_vp, _vp]),

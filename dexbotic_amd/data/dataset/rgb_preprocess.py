@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from ... import kernels as K
-from .augmentations import PixelAug
+from .augmentations import DeviceAug, PixelAug
 
 
 def _edge(v, key):
@@ -74,11 +74,12 @@ class PreprocessRGB:
 
     def batch(self, frames: torch.Tensor, want_u8: bool = False, augment: bool = False):
         """frames: uint8 [n, h, w, 3] (host or device) -> [n, 3, H, W] on the device.  With `augment` the frames first go
-        through the PixelAug policy given as `augmentations`, on the device, each frame with its own draw."""
+        through the PixelAug or DeviceAug policy given as `augmentations`, on the device, each frame with its own draw."""
         frames = frames.to(self.device, non_blocking=True)
         if augment:
-            if not isinstance(self.augmentations, PixelAug):
-                raise ValueError("batch(augment=True) needs augmentations=PixelAug(...); a host callable works per frame through __call__")
+            if not isinstance(self.augmentations, (PixelAug, DeviceAug)):
+                raise ValueError("batch(augment=True) needs augmentations=PixelAug(...) or DeviceAug(...); a host callable works per "
+                                 "frame through __call__")
             if not self.augmentations.identity:
                 return self._augmented(frames, want_u8)
         return self._preprocess(frames, want_u8)
@@ -92,7 +93,9 @@ class PreprocessRGB:
     def _augmented(self, frames, want_u8):
         """expand2square with the processor's colour where the reference has it (before the augmentation), then the policy:
         its own PadToSquare(fill=0) is a no-op on a square frame and a real zero pad otherwise.  A batch stays rectangular,
-        so the frames 'v3' crops (-> 384 x 384) and the ones it leaves at their size go through the launches as two groups."""
+        so the frames 'v3' crops (-> 384 x 384) and the ones it leaves at their size go through the launches as two groups.
+        A DeviceAug's rotation comes after the crop or resize of its group and before the jitter, at whatever size the frames
+        then have; it fills with 0 whatever image_pad_mode is, as albumentations' Rotate does."""
         aug = self.augmentations
         K._check_u8_frames(frames, "PreprocessRGB.batch")
         n, h, w, _ = frames.shape
@@ -100,6 +103,8 @@ class PreprocessRGB:
         padded = (expand or aug.pads_to_square) and h != w
         ph, pw = (max(h, w), max(h, w)) if padded else (h, w)
         bg = self._bg() if expand else (0, 0, 0)
+        if aug.resize is not None and ph != pw:                  # an AugSpec can ask for this; the named policies pad first
+            raise ValueError(f"the Resize of an augmentation policy takes square frames, got {ph} x {pw}: pad them to a square first")
         par = aug.sample(n, ph, pw)
         groups = []                                              # (frame indices, boxes or None, output side)
         cropped = np.flatnonzero(par.apply_crop)
@@ -119,11 +124,20 @@ class PreprocessRGB:
             everything = len(idx) == n
             sel = None if everything else torch.from_numpy(idx).to(self.device)
             sub = frames if everything else frames.index_select(0, sel)
-            if box is None:
-                sub = sub.clone() if everything else sub         # the jitter works in place: never on the caller's frames
-            else:
-                sub = K.image_crop_resize(sub, box, side, pad=padded, bg=bg)
+            own = not everything                                 # index_select copied them
+            if box is not None:
+                sub, own = K.image_crop_resize(sub, box, side, pad=padded, bg=bg), True
             q = par.take(idx)
+            turn = np.flatnonzero(getattr(q, "apply_rotate", ()))
+            if len(turn) == len(idx):
+                sub, own = K.image_rotate(sub, q.angle), True
+            elif len(turn):
+                tsel = torch.from_numpy(turn).to(self.device)
+                sub = sub if own else sub.clone()
+                sub.index_copy_(0, tsel, K.image_rotate(sub.index_select(0, tsel), q.angle[turn]))
+                own = True
+            if not own:
+                sub = sub.clone()                                # the jitter works in place: never on the caller's frames
             K.image_color_jitter(sub, q.apply_jitter, q.order, q.factors, q.hue)
             res = self._preprocess(sub, want_u8)
             o, o8 = res if want_u8 else (res, None)
@@ -139,7 +153,7 @@ class PreprocessRGB:
         if image is None:                                                   # rgb_preprocess.py:14-19
             ch, cw = self._crop()
             return torch.zeros(3, ch, cw, device=self.device, dtype=self.dtype)
-        if isinstance(self.augmentations, PixelAug):                        # the device policies: one frame is a batch of one
+        if isinstance(self.augmentations, (PixelAug, DeviceAug)):           # the device policies: one frame is a batch of one
             return self.batch(to_uint8_hwc(image)[None], augment=True)[0]
         if self.augmentations:                                              # any other callable works on PIL frames on the host
             if self.image_aspect_ratio == "pad":

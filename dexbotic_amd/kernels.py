@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -1873,6 +1874,49 @@ def image_color_jitter(frames: torch.Tensor, apply, order, factors, hue) -> torc
     sums = torch.empty(n, device=frames.device, dtype=torch.int64)
     L.check(lib.dxa_color_jitter(_ptr(frames), n, h, w, _ptr(d_tab), tab.ctypes.data, _ptr(sums), _stream()), "dxa_color_jitter")
     return frames
+
+
+def image_affine(frames: torch.Tensor, mats, fill: Sequence[int] = (0, 0, 0)) -> torch.Tensor:
+    """uint8 frames [n, h, w, 3] on the device -> a new tensor of the same shape: frame i warped by its INVERSE matrix mats[i]
+    (6 doubles: output pixel (x, y) reads the source at m0 (x + .5) + m1 (y + .5) + m2, m3 (x + .5) + m4 (y + .5) + m5), bilinear,
+    `fill` where the source lies outside the frame.  Pillow's Image.transform(size, AFFINE, m, BILINEAR, fillcolor), bit for bit."""
+    _check_u8_frames(frames, "image_affine")
+    n, h, w, _ = frames.shape
+    mats = np.ascontiguousarray(np.asarray(mats, np.float64).reshape(-1, 6))
+    if mats.shape[0] != n:
+        raise L.DxaError(f"image_affine: {n} frames but {mats.shape[0]} matrices")
+    out = torch.empty_like(frames)
+    if n == 0:
+        return out
+    d_mats = torch.from_numpy(mats).to(frames.device)
+    fill_rgb = (int(fill[0]) & 255) | ((int(fill[1]) & 255) << 8) | ((int(fill[2]) & 255) << 16)
+    L.check(lib.dxa_image_affine(_ptr(frames), _ptr(out), n, h, w, _ptr(d_mats), mats.ctypes.data, fill_rgb, _stream()),
+            "dxa_image_affine")
+    return out
+
+
+def rotate_matrix(angle_deg: float, h: int, w: int):
+    """the inverse matrix Pillow's Image.rotate(angle) hands to transform() for a w x h image, in Python floats: the angle
+    mod 360, cos and sin rounded to 15 places, the centre (w / 2, h / 2) mapped onto itself"""
+    a = -math.radians(float(angle_deg) % 360.0)
+    m = [round(math.cos(a), 15), round(math.sin(a), 15), 0.0, round(-math.sin(a), 15), round(math.cos(a), 15), 0.0]
+    cx, cy = w / 2, h / 2
+    m[2] = m[0] * -cx + m[1] * -cy + m[2]
+    m[5] = m[3] * -cx + m[4] * -cy + m[5]
+    m[2] += cx
+    m[5] += cy
+    return m
+
+
+def image_rotate(frames: torch.Tensor, angles_deg, fill: Sequence[int] = (0, 0, 0)) -> torch.Tensor:
+    """uint8 frames [n, h, w, 3] on the device -> a new tensor: frame i rotated by angles_deg[i] degrees counter-clockwise about
+    its centre, as Pillow's Image.rotate(angle, BILINEAR, fillcolor=fill)"""
+    _check_u8_frames(frames, "image_rotate")
+    n, h, w, _ = frames.shape
+    angles = np.asarray(angles_deg, np.float64).reshape(-1)
+    if angles.shape[0] != n:
+        raise L.DxaError(f"image_rotate: {n} frames but {angles.shape[0]} angles")
+    return image_affine(frames, np.asarray([rotate_matrix(float(a), h, w) for a in angles], np.float64).reshape(n, 6), fill)
 
 
 # ------------------------------------------------------------------------------------------------ fused DiT blocks

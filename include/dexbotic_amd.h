@@ -841,6 +841,14 @@ int dxa_image_preprocess(const dxa_image_desc* d, dxa_stream_t stream);
  *   int(mean L + 0.5) of the frame as the ops before it left it: pass 1 recomputes those per pixel and adds L up per frame in
  *   sums[n] (uint64 scratch, zeroed here; integer sums do not depend on order), pass 2 applies all four in registers.
  * dxa_color_jitter_pixels_host: HOST function, the same per-pixel code on k loose RGB pixels with a given contrast mean m.
+ * dxa_image_affine: bilinear affine warp (the Rotate of 'pi0' and 'dm0'), out of place: uint8 [n, h, w, 3] -> the same shape.
+ *   mats[n][6] (device, mats_host the same on the host, checked to be finite before the launch) is frame i's INVERSE
+ *   matrix: output pixel (x, y) reads the source at xin = m0 (x + 0.5) + m1 (y + 0.5) + m2, yin = m3 (x + 0.5) + m4 (y + 0.5)
+ *   + m5.  The pixel is fill_rgb (r | g << 8 | b << 16) unless 0 <= xin < w and 0 <= yin < h; otherwise the four
+ *   neighbours of (xin - 0.5, yin - 0.5), clamped to the frame, are blended in double and the result is truncated: Pillow's
+ *   Image.transform(size, AFFINE, m, BILINEAR, fillcolor) bit for bit, and so Image.rotate(angle, BILINEAR).  src and dst
+ *   must not overlap; n <= 65535.
+ * dxa_image_affine_host: HOST function, the same per-pixel code on host buffers.
  * ---------------------------------------------------------------------------------------------- */
 #define DXA_FILTER_BILINEAR 2 /* PIL.Image.BILINEAR */
 #define DXA_JITTER_BRIGHTNESS 0
@@ -861,6 +869,9 @@ int dxa_image_crop_resize(const void* src, int n, int h, int w, int pad, uint32_
 int dxa_color_jitter(void* pixels, int n, int h, int w, const dxa_jitter_params* params,
                      const dxa_jitter_params* params_host, uint64_t* sums, dxa_stream_t stream);
 int dxa_color_jitter_pixels_host(void* pixels, int64_t k, const dxa_jitter_params* params, int m);
+int dxa_image_affine(const void* src, void* dst, int n, int h, int w, const double* mats, const double* mats_host,
+                     uint32_t fill_rgb, dxa_stream_t stream);
+int dxa_image_affine_host(const void* src, void* dst, int n, int h, int w, const double* mats, uint32_t fill_rgb);
 
 /* ---- persistent DiT blocks for the action sampler ---------------------------------------------------------------
  * All `depth` DiTBlocks of one denoising call (dexbotic/model/cogact/action_model/dit.py:137-162, walked by DiT.forward

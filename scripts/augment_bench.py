@@ -1,9 +1,11 @@
 #!/usr/bin/env python
-"""Training-augmentation micro-benchmark: the device route of PreprocessRGB with a PixelAug policy (crop-resize, colour
-jitter and preprocess launches; uint8 frames already in HBM) next to the same operations with Pillow on one host core
-(tests/augment_ref's Pillow helpers + a bicubic resize and the normalise in numpy), on the same frames, every frame cropped
-and jittered (p = 1).  Two workloads, 32 frames of 256 x 256 under 'v3' and 48 frames of 728 x 728 under 'color_dm0'; the
-device and the host legs alternate round by round inside one run, so both see the same machine.
+"""Training-augmentation micro-benchmark: the device route of PreprocessRGB with a PixelAug or DeviceAug policy (crop-resize,
+affine warp, colour jitter and preprocess launches; uint8 frames already in HBM) next to the same operations with Pillow on one
+host core (tests/augment_ref's and tests/affine_ref's Pillow helpers + a bicubic resize and the normalise in numpy), on the same
+frames, every frame cropped, rotated where the policy rotates, and jittered (p = 1).  Four workloads: 32 frames of 256 x 256
+under 'v3' and under 'pi0', 48 frames of 728 x 728 under 'color_dm0' and under 'dm0'; the device and the host legs alternate
+round by round inside one run, so both see the same machine.  For the rotating policies the affine launch is timed on the
+output of the crop-resize launch, so the two rows are launches over the same number of output bytes.
     python scripts/augment_bench.py [--rounds 7] [--reps 20] [--out report.txt]"""
 import argparse
 import json
@@ -17,11 +19,17 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from dexbotic_amd import kernels as K  # noqa: E402
-from dexbotic_amd.data.dataset.augmentations import PixelAug  # noqa: E402
+from dexbotic_amd.data.dataset.augmentations import DeviceAug, PixelAug  # noqa: E402
 from dexbotic_amd.data.dataset.rgb_preprocess import ImageProcessorSpec, PreprocessRGB  # noqa: E402
+from tests import affine_ref as A  # noqa: E402
 from tests import augment_ref as R  # noqa: E402
 
-WORKLOADS = (("v3", 32, 256), ("color_dm0", 48, 728))
+WORKLOADS = (("v3", 32, 256), ("color_dm0", 48, 728), ("pi0", 32, 256), ("dm0", 48, 728))
+
+
+def policy_of(name, **kw):
+    """the rotating policies are DeviceAug's; the others stay on PixelAug, as they were measured before"""
+    return DeviceAug(name, **kw) if name in ("pi0", "dm0") else PixelAug(name, **kw)
 
 
 def quartiles(x):
@@ -48,9 +56,10 @@ def timed(fn, reps, prepare=None):
 
 
 def host_batch(frames, policy, par, spec):
-    """the reference's order of work per frame with Pillow: [pad] -> crop / resize -> jitter -> bicubic resize -> normalise"""
+    """the reference's order of work per frame with Pillow: [pad] -> crop / resize -> [rotate] -> jitter -> bicubic resize ->
+    normalise"""
     from PIL import Image
-    aug = PixelAug(policy)
+    aug = policy_of(policy)
     mean, std = np.asarray(spec.image_mean, np.float32), np.asarray(spec.image_std, np.float32)
     size = spec.size["shortest_edge"]
     out = []
@@ -61,6 +70,8 @@ def host_batch(frames, policy, par, spec):
             f = R.pil_crop_resize(f, *(int(v) for v in par.box[i]), aug.crop_size)
         elif aug.resize is not None:
             f = np.asarray(Image.fromarray(f, "RGB").resize((aug.resize, aug.resize), Image.BILINEAR))
+        if getattr(par, "apply_rotate", None) is not None and par.apply_rotate[i]:
+            f = A.pil_rotate(f, float(par.angle[i]))
         if par.apply_jitter[i]:
             f = R.pil_color_jitter(f, par.order[i], par.factors[i], par.hue[i])
         u8 = np.asarray(Image.fromarray(f, "RGB").resize((size, size), Image.BICUBIC))
@@ -84,8 +95,8 @@ def main():
     for policy, n, side in WORKLOADS:
         frames = np.random.RandomState(side).randint(0, 256, (n, side, side, 3)).astype(np.uint8)
         dev = torch.from_numpy(frames).cuda()
-        pre = PreprocessRGB(spec, image_aspect_ratio="pad", augmentations=PixelAug(policy, p=1.0, seed=0), device="cuda")
-        par = PixelAug(policy, p=1.0, seed=1).sample(n, side, side)
+        pre = PreprocessRGB(spec, image_aspect_ratio="pad", augmentations=policy_of(policy, p=1.0, seed=0), device="cuda")
+        par = policy_of(policy, p=1.0, seed=1).sample(n, side, side)
         aug = pre.augmentations
         out_side = aug.crop_size or aug.resize
         boxes = par.box if aug.crop_size else np.tile(np.asarray([0, 0, side], np.int32), (n, 1))
@@ -97,6 +108,8 @@ def main():
             "preprocess": lambda resized=resized, pre=pre: pre.batch(resized),
             "batch": lambda dev=dev, pre=pre: pre.batch(dev, augment=True),
         }
+        if isinstance(aug, DeviceAug):                           # the warp over what the crop-resize launch wrote: the same bytes out
+            stages["affine"] = lambda resized=resized, par=par: K.image_rotate(resized, par.angle)
         for fn in stages.values():                               # warm every shape the timed window uses
             for _ in range(3):
                 fn()
