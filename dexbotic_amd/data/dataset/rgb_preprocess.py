@@ -84,6 +84,22 @@ class PreprocessRGB:
                 return self._augmented(frames, want_u8)
         return self._preprocess(frames, want_u8)
 
+    def process(self, images):
+        """the ``process_images`` of the policies: PIL / numpy / torch uint8 frames [h, w, 3] -> [n, 3, H, W].  Frames of equal size
+        share one launch pair; frames of unequal sizes go one by one and the result is stacked when all outputs have one shape
+        (a list otherwise), as in the reference."""
+        frames = [to_uint8_hwc(im) for im in images]
+        if frames and all(f.shape == frames[0].shape for f in frames):
+            if all(f.device.type == "cpu" for f in frames):
+                # host frames are stacked by numpy (one memcpy per frame): torch.stack above ATen's parallel grain wakes the whole
+                # OpenMP pool for 393 KB, and its spinning workers cost a serving process its cgroup CPU quota (hostcpu.py)
+                return self.batch(torch.from_numpy(np.stack([f.numpy() for f in frames])))
+            return self.batch(torch.stack(frames))
+        out = [self.batch(f[None])[0] for f in frames]
+        if out and all(x.shape == out[0].shape for x in out):
+            out = torch.stack(out, dim=0)
+        return out
+
     def _preprocess(self, frames, want_u8):
         p = self.image_processor
         return K.image_preprocess(frames, pad=self.image_aspect_ratio == "pad", bg=self._bg(), size=self._short(),

@@ -5,13 +5,73 @@ Mirror of ``ActionNormAnd2String`` (dexbotic/data/dataset/transform/action.py:28
 float64 values per episode and its contract is BIT-EXACT integers — ``np.round`` (round-half-to-even) decides bins on
 exact halves, so the arithmetic is kept in float64 numpy exactly as the reference evaluates it; the inverse
 (digit tokens -> bins -> [-1,1] -> physical units) is DiscreteVLAForCausalLM._discrete_action_to_continuous and
-ActionOutputForCausalLM._denorm (model/dexbotic_arch.py)."""
+ActionOutputForCausalLM._denorm (model/dexbotic_arch.py).
+
+``PadState`` / ``PadAction`` / ``ActionNorm`` (dexbotic/data/dataset/transform/action.py:5-58, 229-277) are the request side of the
+flow policies' server (serve.FlowInferenceServer): the state row padded to the model's action dimension and normalised with
+mean / std or quantile statistics, float32 out.  Their inverses are in output.py."""
 from __future__ import annotations
 
 import copy
 from typing import List
 
 import numpy as np
+
+
+def _pad_last(a: np.ndarray, ndim: int, axis: int) -> np.ndarray:
+    """zeros behind ``a`` along ``axis`` up to ``ndim`` entries; a wider array comes back as it is"""
+    if a.shape[axis] >= ndim:
+        return a
+    width = [(0, 0)] * a.ndim
+    width[axis] = (0, ndim - a.shape[axis])
+    return np.pad(a, width, mode="constant", constant_values=0)
+
+
+class PadState:
+    """``state`` zero-padded along ``axis`` to the model's action dimension (transform/action.py:5-30); the dtype is kept"""
+
+    key = "state"
+
+    def __init__(self, ndim: int = 32, axis: int = -1):
+        self.ndim, self.axis = ndim, axis
+
+    def __call__(self, episode_data_dict: dict, **kwargs) -> dict:
+        if self.key in episode_data_dict:
+            episode_data_dict[self.key] = _pad_last(episode_data_dict[self.key], self.ndim, self.axis)
+        return episode_data_dict
+
+
+class PadAction(PadState):
+    """the same for ``action`` (transform/action.py:33-58)"""
+
+    key = "action"
+
+
+class ActionNorm:
+    """every key of ``statistic_mapping`` found in the episode dict normalised with that key's statistics (transform/action.py:229-277):
+    (x - mean) / (std + 1e-6), or with ``use_quantiles`` (x - min) / (max - min + 1e-6) * 2 - 1; the result is float32 whatever came
+    in.  ``strict``: every key but ``default`` has to be there."""
+
+    def __init__(self, statistic_mapping: dict = {"default": {"min": -1, "max": 1}}, strict: bool = True,
+                 use_quantiles: bool = False):
+        self.statistic_mapping = statistic_mapping
+        self.strict = strict
+        self.use_quantiles = use_quantiles
+
+    def __call__(self, episode_data_dict: dict, **kwargs) -> dict:
+        for key, stats in self.statistic_mapping.items():
+            if self.strict and key == "default":
+                continue
+            if key in episode_data_dict:
+                episode_data_dict[key] = self._normalize(episode_data_dict[key], stats)
+            elif self.strict:
+                raise KeyError(f"{key} is not in the episode_data_dict, please check the statistic_mapping")
+        return episode_data_dict
+
+    def _normalize(self, data, stats):
+        if self.use_quantiles:
+            return ((data - stats["min"]) / (stats["max"] - stats["min"] + 1e-6) * 2.0 - 1.0).astype(np.float32)
+        return ((data - stats["mean"]) / (stats["std"] + 1e-6)).astype(np.float32)
 
 
 class ActionNormAnd2String:

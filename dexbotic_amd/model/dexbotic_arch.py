@@ -561,22 +561,10 @@ class DexboticForCausalLM(NativePreTrainedMixin, nn.Module):
         """dexbotic_arch.py:498-529 on the device: the uint8 frames are uploaded as they are and libdexbotic_amd pads,
         resizes (Pillow-exact bicubic), crops and normalises them (data/dataset/rgb_preprocess.py).  Frames of equal
         size share one launch; the result is stacked when all outputs have one shape, as in the reference."""
-        from ..data.dataset.rgb_preprocess import PreprocessRGB, to_uint8_hwc
+        from ..data.dataset.rgb_preprocess import PreprocessRGB
         proc = self.model.mm_vision_module.image_processor
         aspect = getattr(self.config, "image_aspect_ratio", "pad")
-        pre = PreprocessRGB(proc, image_aspect_ratio="pad" if aspect == "pad" else None, device=self.device)
-        frames = [to_uint8_hwc(im) for im in images]
-        if frames and all(f.shape == frames[0].shape for f in frames):
-            if all(f.device.type == "cpu" for f in frames):
-                # host frames are stacked by numpy (one memcpy per frame): torch.stack above ATen's parallel grain wakes the whole
-                # OpenMP pool for 393 KB, and its spinning workers cost a serving process its cgroup CPU quota (hostcpu.py)
-                import numpy as np
-                return pre.batch(torch.from_numpy(np.stack([f.numpy() for f in frames])))
-            return pre.batch(torch.stack(frames))
-        out = [pre.batch(f[None])[0] for f in frames]
-        if out and all(x.shape == out[0].shape for x in out):
-            out = torch.stack(out, dim=0)
-        return out
+        return PreprocessRGB(proc, image_aspect_ratio="pad" if aspect == "pad" else None, device=self.device).process(images)
 
     @staticmethod
     def expand2square(pil_img, background_color):

@@ -183,6 +183,19 @@ class Pi0ForCausalLM(NativePreTrainedMixin, nn.Module, ActionOutputForCausalLM, 
     def encode_images(self, images: torch.Tensor) -> torch.Tensor:
         return self.model.mm_projector(self.model.mm_vision_tower(images))
 
+    def process_images(self, images):
+        """pi0_arch.py:493-511 on the device, the contract of DexboticForCausalLM.process_images: PIL / numpy / torch uint8 frames
+        [h, w, 3] -> [n, 3, H, W] float32 on the device.  The frames are padded to a square with BLACK (the reference's own
+        expand2square colour here, not the processor's mean), resized with the Pillow-exact bicubic of the tower's
+        SiglipImageProcessor and normalised with its mean / std (data/dataset/rgb_preprocess.py: two launches).  Frames of equal size
+        share one launch pair; the result is stacked when all outputs have one shape, as in the reference."""
+        from ...data.dataset.rgb_preprocess import PreprocessRGB
+        if getattr(self.config, "image_aspect_ratio", "pad") != "pad":
+            raise NotImplementedError("process_images: without image_aspect_ratio='pad' the reference hands the frames to the SigLIP "
+                                      "processor, which stretches them to the tower's size; the device path pads to a square first")
+        return PreprocessRGB(self.model.mm_vision_module.image_processor, image_aspect_ratio="pad", image_pad_mode="zero",
+                             device=self.device).process(images)
+
     @staticmethod
     def _to_dev(a: np.ndarray, device) -> torch.Tensor:
         """small host array -> device through pinned memory, non-blocking (hostcpu.upload: a pageable source would make the copy wait
