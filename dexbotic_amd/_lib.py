@@ -86,6 +86,11 @@ class AttnDesc(C.Structure):
     ]
 
 
+class AttnPlanInfo(C.Structure):
+    _fields_ = [("family", C.c_char_p), ("D", _i32), ("DV", _i32), ("nw", _i32), ("nw_dkv", _i32), ("pf", _i32), ("nsplit", _i32),
+                ("vec", _i32), ("workspace", C.c_uint64)]
+
+
 class AdamWDesc(C.Structure):
     _fields_ = [
         ("p", _vp), ("g", _vp), ("m", _vp), ("v", _vp), ("shadow", _vp),
@@ -182,6 +187,7 @@ SIGNATURES = {
     "dxa_attn_fwd_ws": (_int, [C.POINTER(AttnDesc), _vp, _sz, _vp]),
     "dxa_attn_bwd_workspace": (_sz, [C.POINTER(AttnDesc)]),
     "dxa_attn_bwd": (_int, [C.POINTER(AttnDesc), _vp, _sz, _vp]),
+    "dxa_attn_plan": (_int, [C.POINTER(AttnDesc), _int, C.POINTER(AttnPlanInfo)]),
     "dxa_swiglu_fwd": (_int, [_vp, _vp, _i64, _i64, _int, _vp]),
     "dxa_swiglu_bwd": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp]),
     "dxa_axpby": (_int, [_vp, _vp, _vp, _i64, _f32, _f32, _int, _vp]),

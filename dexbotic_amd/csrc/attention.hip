@@ -1510,25 +1510,130 @@ static int fwd_flash_splits(const dxa_attn_desc* d) {
   return n >= 2 && (int64_t)d->B * n <= 65535 ? n : 1;
 }
 
-extern "C" size_t dxa_attn_fwd_workspace(const dxa_attn_desc* d) {
-  if (!d || d->B <= 0 || d->Sq <= 0 || d->Sk <= 0 || d->Hq <= 0 || d->Hkv <= 0 || d->Hq % d->Hkv) return 0;
-  if (const int ns = fwd_flash_splits(d); ns > 1) {
-    const size_t rows = (size_t)d->B * ns * d->Hq * d->Sq;
-    return align_up(rows * d->D * 2, 256) + align_up(rows * 4, 256);
+// fused flash backward eligibility: bf16, D in {64,128}, 16-byte aligned rows of q/k/v/dO, 8-byte rows of dq/dk/dv
+static bool bwd_flash_ok(const dxa_attn_desc* d) {
+  auto s8 = [](int64_t a, int64_t b, int64_t c) { return a % 8 == 0 && b % 8 == 0 && c % 8 == 0; };
+  auto s4 = [](int64_t a, int64_t b, int64_t c) { return a % 4 == 0 && b % 4 == 0 && c % 4 == 0; };
+  return !d->force_generic && !d->drop_mask && d->dtype == DXA_BF16 && flash_head_dim(d->D) && d->B <= 65535 && d->Hq <= 65535 &&
+         s8(d->q_sb, d->q_sh, d->q_ss) && s8(d->k_sb, d->k_sh, d->k_ss) && s8(d->v_sb, d->v_sh, d->v_ss) &&
+         s8(d->do_sb, d->do_sh, d->do_ss) && s4(d->o_sb, d->o_sh, d->o_ss) && s4(d->dq_sb, d->dq_sh, d->dq_ss) &&
+         s4(d->dk_sb, d->dk_sh, d->dk_ss) && s4(d->dv_sb, d->dv_sh, d->dv_ss) && al(d->q, 16) && al(d->k, 16) &&
+         al(d->v, 16) && al(d->d_o, 16) && al(d->o, 8) && al(d->dq, 8) && al(d->dk, 8) && al(d->dv, 8);
+}
+
+// head-sized fp32 attention without masks (the DiT heads' training backward): one launch
+static bool bwd_small_f32_ok(const dxa_attn_desc* d) {
+  auto s4 = [](int64_t a, int64_t b, int64_t c) { return a % 4 == 0 && b % 4 == 0 && c % 4 == 0; };
+  return !d->force_generic && d->dtype == DXA_F32 && d->Hq == d->Hkv && !d->causal && !d->kv_start && !d->kv_end &&
+         !d->q_limit && !d->key_valid && !d->drop_mask && d->Sq <= SB_MAXQ && d->Sk <= 4096 && d->D <= SB_MAXD && d->D % 4 == 0 &&
+         d->lse && d->Hq <= 65535 && d->B <= 65535 && al(d->q, 16) && al(d->k, 16) && al(d->v, 16) && al(d->d_o, 16) &&
+         s4(d->q_sb, d->q_sh, d->q_ss) && s4(d->k_sb, d->k_sh, d->k_ss) && s4(d->v_sb, d->v_sh, d->v_ss) &&
+         s4(d->do_sb, d->do_sh, d->do_ss) && d->o && al(d->o, 16) && s4(d->o_sb, d->o_sh, d->o_ss);
+}
+// ... more than one chunk of queries: the register-blocked kernel wants 16-byte aligned dq / dk / dv rows
+static bool bwd_small2_f32_ok(const dxa_attn_desc* d) {
+  auto s4 = [](int64_t a, int64_t b, int64_t c) { return a % 4 == 0 && b % 4 == 0 && c % 4 == 0; };
+  return al(d->dq, 16) && al(d->dk, 16) && al(d->dv, 16) && s4(d->dq_sb, d->dq_sh, d->dq_ss) && s4(d->dk_sb, d->dk_sh, d->dk_ss) &&
+         s4(d->dv_sb, d->dv_sh, d->dv_ss);
+}
+
+// ---- the route of a descriptor: every choice between kernels is made here, once per direction, from the descriptor's numbers
+// and pointer alignments alone (nothing is dereferenced and HIP is not touched, so dxa_attn_plan answers without a GPU).  The
+// launchers below launch what the plan says and hold no condition of their own.
+enum AttnFamily { FWD_TR, FWD_FLASH, FWD_SMALL_F32, FWD_MATERIALISED, FWD_GENERIC, BWD_FLASH, BWD_SMALL_F32, BWD_SMALL2_F32, BWD_COMPOSED };
+static const char* const ATTN_FAMILY_NAME[] = {"tr", "flash", "small_f32", "materialised", "generic", "flash", "small_f32", "small2_f32", "composed"};
+struct AttnPlan {
+  AttnFamily family;
+  int D, DV;            // tile width / real columns of the tr and flash kernels; head_dim elsewhere
+  int nw, nw_dkv;       // waves per workgroup: forward or dQ, dK/dV
+  bool pf;              // dK/dV register prefetch
+  int nsplit;           // key ranges of the split forward
+  int vec;              // generic forward: K load width
+  size_t ws;            // workspace bytes
+};
+
+// 8 waves (128 queries per staged K/V tile) where wide_tiles() allows them and there are enough such workgroups to fill the chip
+static int flash_waves(const dxa_attn_desc* d) {
+  const int64_t wgs8 = (int64_t)((d->Sq + 127) / 128) * d->Hq * d->B;
+  return wide_tiles(d) && wgs8 >= 256 ? 8 : 4;
+}
+
+// with_ws: the caller brings dxa_attn_fwd_workspace() bytes (dxa_attn_fwd_ws), which the key-range split and the materialised
+// path need; dxa_attn_fwd alone plans without them
+static AttnPlan attn_plan_fwd(const dxa_attn_desc* d, bool with_ws) {
+  AttnPlan pl{FWD_GENERIC, d->D, d->D, 4, 0, false, 1, 0, 0};
+  const bool sized = d->B > 0 && d->Sq > 0 && d->Sk > 0 && d->Hq > 0 && d->Hkv > 0 && d->Hq % d->Hkv == 0;
+  if (fwd_flash_ok(d)) {
+    pl.family = fwd_tr_ok(d) ? FWD_TR : FWD_FLASH;
+    pl.D = d->D == 72 ? 128 : d->D;
+    pl.nw = flash_waves(d);
+    if (const int ns = with_ws && sized ? fwd_flash_splits(d) : 1; ns > 1) {
+      const size_t rows = (size_t)d->B * ns * d->Hq * d->Sq;
+      pl.nsplit = ns;
+      pl.nw = 4;
+      pl.ws = align_up(rows * d->D * 2, 256) + align_up(rows * 4, 256);
+    }
+    return pl;
   }
-  if (!fwd_materialise(d)) return 0;
+  if (with_ws && sized && fwd_materialise(d)) {
+    const size_t n = (size_t)d->B * d->Hq * d->Sq * d->Sk;
+    pl.family = FWD_MATERIALISED;
+    pl.nw = 0;
+    pl.ws = align_up(n * 4, 256) + align_up(n * (d->dtype == DXA_BF16 ? 2 : 4), 256);
+    return pl;
+  }
+  if (fwd_small_f32_ok(d)) {
+    pl.family = FWD_SMALL_F32;
+    return pl;
+  }
+  const size_t es = d->dtype == DXA_BF16 ? 2 : 4;
+  pl.vec = d->D % 4 == 0 && d->k_ss % 4 == 0 && d->k_sb % 4 == 0 && d->k_sh % 4 == 0 && al(d->k, 4 * es) ? 4 : 1;
+  return pl;
+}
+
+static AttnPlan attn_plan_bwd(const dxa_attn_desc* d) {
+  AttnPlan pl{BWD_COMPOSED, d->D, d->D, 0, 0, false, 1, 0, 0};
+  if (bwd_flash_ok(d)) {
+    // head_dim 256, dK / dV: 0 = 4 waves, no register prefetch (rounds 2-4); 1 = 4 waves + prefetch (416 registers); 2 = 8 waves,
+    // the d range of dK / dV cut over wave pairs, + prefetch (256 registers, 7 spilled); 3 = 8 waves without the prefetch (248
+    // registers): dQ + dK/dV at B 16 x 8 heads x 816 keys 735 / 753 / 714 / 685 us (profiles/r05_attn_variants.txt; same results
+    // bit for bit) -> 3
+    // the 8-wave cut at head_dim 128 (182 registers without spills against 256 + 2 spilled): dQ + dK/dV of the decoder layer
+    // 177.5 -> 172.5 and 175.2 -> 166.5 us in two sessions, the one-request shape 194.5 -> 186 (profiles/r05_attn_variants.txt,
+    // r05_attn_nw_probe.txt; same results bit for bit)
+    pl.family = BWD_FLASH;
+    pl.D = d->D == 72 ? 128 : d->D;
+    pl.nw = flash_waves(d);
+    pl.nw_dkv = d->D == 256 || d->D == 128 ? 8 : 4;
+    pl.pf = d->D != 256;
+    pl.ws = align_up((size_t)d->B * d->Hq * d->Sq * 4, 256);
+    return pl;
+  }
   const size_t n = (size_t)d->B * d->Hq * d->Sq * d->Sk;
-  return align_up(n * 4, 256) + align_up(n * (d->dtype == DXA_BF16 ? 2 : 4), 256);
+  const size_t es = d->dtype == DXA_BF16 ? 2 : 4;
+  pl.ws = align_up(n * 4, 256) + 2 * align_up(n * es, 256) + align_up((size_t)d->B * d->Hq * d->Sq * 4, 256);
+  if (bwd_small_f32_ok(d)) {
+    // more than one chunk of queries: the register-blocked kernel (16-byte aligned dq / dk / dv rows; otherwise the
+    // one-element-per-thread kernel at 1024 threads, rounds 6a-b)
+    pl.family = d->Sq > SB_MAXT && bwd_small2_f32_ok(d) ? BWD_SMALL2_F32 : BWD_SMALL_F32;
+    pl.nw = d->Sq > SB_MAXT ? 16 : 4;
+  }
+  return pl;
+}
+
+extern "C" size_t dxa_attn_fwd_workspace(const dxa_attn_desc* d) {
+  return d ? attn_plan_fwd(d, true).ws : 0;
 }
 
 extern "C" int dxa_attn_fwd_ws(const dxa_attn_desc* d, void* workspace, size_t workspace_bytes, dxa_stream_t stream) {
   if (int rc = check_common(d, "dxa_attn_fwd_ws")) return rc;
   if (d->B == 0 || d->Sq == 0) return DXA_OK;
-  const size_t need = dxa_attn_fwd_workspace(d);
-  if (need == 0 || d->Sk == 0) return dxa_attn_fwd(d, stream);
+  const AttnPlan pl = attn_plan_fwd(d, true);
+  const size_t need = pl.ws;
+  if (need == 0) return dxa_attn_fwd(d, stream);
   DXA_CHECK_ARG(workspace && workspace_bytes >= need, "dxa_attn_fwd_ws: workspace too small (%zu < %zu)", workspace_bytes, need);
   hipStream_t st = (hipStream_t)stream;
-  if (const int ns = fwd_flash_splits(d); ns > 1) {
+  if (const int ns = pl.nsplit; ns > 1) {
     const size_t rows = (size_t)d->B * ns * d->Hq * d->Sq;
     bf16_t* op = (bf16_t*)workspace;
     float* lp = (float*)((char*)workspace + align_up(rows * d->D * 2, 256));
@@ -1539,16 +1644,16 @@ extern "C" int dxa_attn_fwd_ws(const dxa_attn_desc* d, void* workspace, size_t w
     p.o = (char*)op; p.o_sb = (int64_t)d->Hq * d->Sq * d->D; p.o_sh = (int64_t)d->Sq * d->D; p.o_ss = d->D;
     p.lse = lp;
     dim3 grid((unsigned)((d->Sq + 63) / 64), (unsigned)d->Hq, (unsigned)(d->B * ns));
-    if (fwd_tr_ok(d)) {
-      if (d->D == 256) hipLaunchKernelGGL((attn_fwd_tr_k<256, 4>), grid, dim3(256), 0, st, p);
-      else if (d->D == 128) hipLaunchKernelGGL((attn_fwd_tr_k<128, 4>), grid, dim3(256), 0, st, p);
+    if (pl.family == FWD_TR) {
+      if (pl.DV == 256) hipLaunchKernelGGL((attn_fwd_tr_k<256, 4>), grid, dim3(256), 0, st, p);
+      else if (pl.DV == 128) hipLaunchKernelGGL((attn_fwd_tr_k<128, 4>), grid, dim3(256), 0, st, p);
       else hipLaunchKernelGGL((attn_fwd_tr_k<64, 4>), grid, dim3(256), 0, st, p);
-    } else if (d->D == 256) hipLaunchKernelGGL((attn_fwd_flash_k<256, 4>), grid, dim3(256), 0, st, p);
-    else if (d->D == 128) hipLaunchKernelGGL((attn_fwd_flash_k<128, 4>), grid, dim3(256), 0, st, p);
+    } else if (pl.DV == 256) hipLaunchKernelGGL((attn_fwd_flash_k<256, 4>), grid, dim3(256), 0, st, p);
+    else if (pl.DV == 128) hipLaunchKernelGGL((attn_fwd_flash_k<128, 4>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((attn_fwd_flash_k<64, 4>), grid, dim3(256), 0, st, p);
     dim3 cgrid((unsigned)(((int64_t)d->B * d->Hq * d->Sq + 3) / 4));
-    if (d->D == 256) hipLaunchKernelGGL((attn_split_combine_k<256>), cgrid, dim3(256), 0, st, op, lp, (char*)d->o, d->o_sb, d->o_sh, d->o_ss, d->lse, d->B, d->Hq, d->Sq, ns);
-    else if (d->D == 128) hipLaunchKernelGGL((attn_split_combine_k<128>), cgrid, dim3(256), 0, st, op, lp, (char*)d->o, d->o_sb, d->o_sh, d->o_ss, d->lse, d->B, d->Hq, d->Sq, ns);
+    if (pl.DV == 256) hipLaunchKernelGGL((attn_split_combine_k<256>), cgrid, dim3(256), 0, st, op, lp, (char*)d->o, d->o_sb, d->o_sh, d->o_ss, d->lse, d->B, d->Hq, d->Sq, ns);
+    else if (pl.DV == 128) hipLaunchKernelGGL((attn_split_combine_k<128>), cgrid, dim3(256), 0, st, op, lp, (char*)d->o, d->o_sb, d->o_sh, d->o_ss, d->lse, d->B, d->Hq, d->Sq, ns);
     else hipLaunchKernelGGL((attn_split_combine_k<64>), cgrid, dim3(256), 0, st, op, lp, (char*)d->o, d->o_sb, d->o_sh, d->o_ss, d->lse, d->B, d->Hq, d->Sq, ns);
     DXA_CHECK_LAUNCH();
     return DXA_OK;
@@ -1594,36 +1699,34 @@ extern "C" int dxa_attn_fwd(const dxa_attn_desc* d, dxa_stream_t stream) {
   if (d->B == 0 || d->Sq == 0) return DXA_OK;
   hipStream_t st = (hipStream_t)stream;
   const AttnP p = make_params(d);
-  const bool flash_ok = fwd_flash_ok(d);
-  if (flash_ok) {
-    // 8-wave workgroups (128 queries per staged K/V tile) for head_dim 256 once there are enough queries to fill the chip that way
-    const int64_t wgs8 = (int64_t)((d->Sq + 127) / 128) * d->Hq * d->B;
-    const int nw = wide_tiles(d) && wgs8 >= 256 ? 8 : 4;
+  const AttnPlan pl = attn_plan_fwd(d, false);
+  if (pl.family == FWD_TR || pl.family == FWD_FLASH) {
+    const int nw = pl.nw;
     dim3 grid((unsigned)((d->Sq + 16 * nw - 1) / (16 * nw)), (unsigned)d->Hq, (unsigned)d->B);
-    if (fwd_tr_ok(d)) {
+    if (pl.family == FWD_TR) {
 #define LAUNCH_TR(D_, DV_)                                                                            \
   do {                                                                                                 \
     if (nw == 8) hipLaunchKernelGGL((attn_fwd_tr_k<D_, 8, DV_>), grid, dim3(512), 0, st, p);           \
     else hipLaunchKernelGGL((attn_fwd_tr_k<D_, 4, DV_>), grid, dim3(256), 0, st, p);                   \
   } while (0)
-      if (d->D == 256) LAUNCH_TR(256, 256); else if (d->D == 128) LAUNCH_TR(128, 128);
-      else if (d->D == 72) LAUNCH_TR(128, 72); else LAUNCH_TR(64, 64);
+      if (pl.DV == 256) LAUNCH_TR(256, 256); else if (pl.DV == 128) LAUNCH_TR(128, 128);
+      else if (pl.DV == 72) LAUNCH_TR(128, 72); else LAUNCH_TR(64, 64);
 #undef LAUNCH_TR
     } else if (nw == 8) {
-      if (d->D == 256) hipLaunchKernelGGL((attn_fwd_flash_k<256, 8>), grid, dim3(512), 0, st, p);
-      else if (d->D == 128) hipLaunchKernelGGL((attn_fwd_flash_k<128, 8>), grid, dim3(512), 0, st, p);
-      else if (d->D == 72) hipLaunchKernelGGL((attn_fwd_flash_k<128, 8, 72>), grid, dim3(512), 0, st, p);
+      if (pl.DV == 256) hipLaunchKernelGGL((attn_fwd_flash_k<256, 8>), grid, dim3(512), 0, st, p);
+      else if (pl.DV == 128) hipLaunchKernelGGL((attn_fwd_flash_k<128, 8>), grid, dim3(512), 0, st, p);
+      else if (pl.DV == 72) hipLaunchKernelGGL((attn_fwd_flash_k<128, 8, 72>), grid, dim3(512), 0, st, p);
       else hipLaunchKernelGGL((attn_fwd_flash_k<64, 8>), grid, dim3(512), 0, st, p);
     } else {
-      if (d->D == 256) hipLaunchKernelGGL((attn_fwd_flash_k<256, 4>), grid, dim3(256), 0, st, p);
-      else if (d->D == 128) hipLaunchKernelGGL((attn_fwd_flash_k<128, 4>), grid, dim3(256), 0, st, p);
-      else if (d->D == 72) hipLaunchKernelGGL((attn_fwd_flash_k<128, 4, 72>), grid, dim3(256), 0, st, p);
+      if (pl.DV == 256) hipLaunchKernelGGL((attn_fwd_flash_k<256, 4>), grid, dim3(256), 0, st, p);
+      else if (pl.DV == 128) hipLaunchKernelGGL((attn_fwd_flash_k<128, 4>), grid, dim3(256), 0, st, p);
+      else if (pl.DV == 72) hipLaunchKernelGGL((attn_fwd_flash_k<128, 4, 72>), grid, dim3(256), 0, st, p);
       else hipLaunchKernelGGL((attn_fwd_flash_k<64, 4>), grid, dim3(256), 0, st, p);
     }
     DXA_CHECK_LAUNCH();
     return DXA_OK;
   }
-  if (fwd_small_f32_ok(d)) {
+  if (pl.family == FWD_SMALL_F32) {
     const int srow = 16 * ((d->Sk + 15) / 16) + 4;
     const size_t lds_s = (size_t)16 * srow * sizeof(float);
     dim3 grid((unsigned)((d->Sq + 15) / 16), (unsigned)d->Hq, (unsigned)d->B);
@@ -1642,8 +1745,7 @@ extern "C" int dxa_attn_fwd(const dxa_attn_desc* d, dxa_stream_t stream) {
   DXA_CHECK_ARG(lds <= GENERIC_LDS, "dxa_attn_fwd: generic kernel supports Sk+D <= 10240 (got %d)", d->Sk + d->D);
   const int64_t rows = (int64_t)d->B * d->Hq * d->Sq;
   dim3 grid((unsigned)((rows + 3) / 4));
-  const size_t es = d->dtype == DXA_BF16 ? 2 : 4;
-  const bool vec = d->D % 4 == 0 && d->k_ss % 4 == 0 && d->k_sb % 4 == 0 && d->k_sh % 4 == 0 && al(d->k, 4 * es);
+  const bool vec = pl.vec == 4;
   int rc;
   if (d->dtype == DXA_BF16)
     rc = vec ? dxa_launch_lds<attn_fwd_generic_k<bf16_t, 4>>(GENERIC_LDS, grid, dim3(256), lds, st, p)
@@ -1656,23 +1758,8 @@ extern "C" int dxa_attn_fwd(const dxa_attn_desc* d, dxa_stream_t stream) {
   return DXA_OK;
 }
 
-// fused flash backward eligibility: bf16, D in {64,128}, 16-byte aligned rows of q/k/v/dO, 8-byte rows of dq/dk/dv
-static bool bwd_flash_ok(const dxa_attn_desc* d) {
-  auto s8 = [](int64_t a, int64_t b, int64_t c) { return a % 8 == 0 && b % 8 == 0 && c % 8 == 0; };
-  auto s4 = [](int64_t a, int64_t b, int64_t c) { return a % 4 == 0 && b % 4 == 0 && c % 4 == 0; };
-  return !d->force_generic && !d->drop_mask && d->dtype == DXA_BF16 && flash_head_dim(d->D) && d->B <= 65535 && d->Hq <= 65535 &&
-         s8(d->q_sb, d->q_sh, d->q_ss) && s8(d->k_sb, d->k_sh, d->k_ss) && s8(d->v_sb, d->v_sh, d->v_ss) &&
-         s8(d->do_sb, d->do_sh, d->do_ss) && s4(d->o_sb, d->o_sh, d->o_ss) && s4(d->dq_sb, d->dq_sh, d->dq_ss) &&
-         s4(d->dk_sb, d->dk_sh, d->dk_ss) && s4(d->dv_sb, d->dv_sh, d->dv_ss) && al(d->q, 16) && al(d->k, 16) &&
-         al(d->v, 16) && al(d->d_o, 16) && al(d->o, 8) && al(d->dq, 8) && al(d->dk, 8) && al(d->dv, 8);
-}
-
 extern "C" size_t dxa_attn_bwd_workspace(const dxa_attn_desc* d) {
-  if (!d) return 0;
-  if (bwd_flash_ok(d)) return align_up((size_t)d->B * d->Hq * d->Sq * 4, 256);
-  const size_t n = (size_t)d->B * d->Hq * d->Sq * d->Sk;
-  const size_t es = d->dtype == DXA_BF16 ? 2 : 4;
-  return align_up(n * 4, 256) + 2 * align_up(n * es, 256) + align_up((size_t)d->B * d->Hq * d->Sq * 4, 256);
+  return d ? attn_plan_bwd(d).ws : 0;
 }
 
 template <int D, int DV, int NW, bool PF>
@@ -1684,9 +1771,10 @@ static int launch_dkv(dim3 grid, hipStream_t st, const AttnBwdP& bp) {
 extern "C" int dxa_attn_bwd(const dxa_attn_desc* d, void* workspace, size_t workspace_bytes, dxa_stream_t stream) {
   if (int rc = check_common(d, "dxa_attn_bwd")) return rc;
   DXA_CHECK_ARG(d->d_o && d->dq && d->dk && d->dv, "dxa_attn_bwd: null gradient tensor");
-  DXA_CHECK_ARG(workspace && workspace_bytes >= dxa_attn_bwd_workspace(d), "dxa_attn_bwd: workspace too small");
+  const AttnPlan pl = attn_plan_bwd(d);
+  DXA_CHECK_ARG(workspace && workspace_bytes >= pl.ws, "dxa_attn_bwd: workspace too small");
   if (d->B == 0 || d->Sq == 0 || d->Sk == 0) return DXA_OK;
-  if (bwd_flash_ok(d)) {
+  if (pl.family == BWD_FLASH) {
     hipStream_t st = (hipStream_t)stream;
     float* delta = (float*)workspace;
     AttnBwdP bp;
@@ -1696,47 +1784,37 @@ extern "C" int dxa_attn_bwd(const dxa_attn_desc* d, void* workspace, size_t work
     bp.dq = (char*)d->dq; bp.dq_sb = d->dq_sb; bp.dq_sh = d->dq_sh; bp.dq_ss = d->dq_ss;
     bp.dk = (char*)d->dk; bp.dk_sb = d->dk_sb; bp.dk_sh = d->dk_sh; bp.dk_ss = d->dk_ss;
     bp.dv = (char*)d->dv; bp.dv_sb = d->dv_sb; bp.dv_sh = d->dv_sh; bp.dv_ss = d->dv_ss;
-    const int64_t wgs8 = (int64_t)((d->Sq + 127) / 128) * d->Hq * d->B;
-    const int nwq = wide_tiles(d) && wgs8 >= 256 ? 8 : 4;
+    const int nwq = pl.nw;
     dim3 gq((unsigned)((d->Sq + 16 * nwq - 1) / (16 * nwq)), (unsigned)d->Hq, (unsigned)d->B);
     dim3 gk((unsigned)d->Hkv, (unsigned)d->B, (unsigned)((d->Sk + 63) / 64));
-    // head_dim 256, dK / dV: 0 = 4 waves, no register prefetch (rounds 2-4); 1 = 4 waves + prefetch (416 registers); 2 = 8 waves,
-    // the d range of dK / dV cut over wave pairs, + prefetch (256 registers, 7 spilled); 3 = 8 waves without the prefetch (248
-    // registers): dQ + dK/dV at B 16 x 8 heads x 816 keys 735 / 753 / 714 / 685 us (profiles/r05_attn_variants.txt; same results
-    // bit for bit) -> 3
 #define LAUNCH_BWD(D_, DV_)                                                                                      \
   do {                                                                                                            \
     if (nwq == 8) hipLaunchKernelGGL((attn_bwd_dq_k<D_, 8, DV_>), gq, dim3(512), 0, st, bp);                      \
     else hipLaunchKernelGGL((attn_bwd_dq_k<D_, 4, DV_>), gq, dim3(256), 0, st, bp);                               \
   } while (0)
-    if (d->D == 256) {
+    // the dK / dV kernel the plan names (attn_plan_bwd says why each head width gets its waves and prefetch)
+    auto dkv_is = [&](int D_, int DV_, int NW_, bool PF_) { return pl.D == D_ && pl.DV == DV_ && pl.nw_dkv == NW_ && pl.pf == PF_; };
+    if (dkv_is(256, 256, 8, false)) {
       LAUNCH_BWD(256, 256);
       if (int rc = launch_dkv<256, 256, 8, false>(gk, st, bp)) return rc;
-    } else if (d->D == 128) {
-      // the 8-wave cut at head_dim 128 (182 registers without spills against 256 + 2 spilled): dQ + dK/dV of the decoder layer
-      // 177.5 -> 172.5 and 175.2 -> 166.5 us in two sessions, the one-request shape 194.5 -> 186 (profiles/r05_attn_variants.txt,
-      // r05_attn_nw_probe.txt; same results bit for bit)
+    } else if (dkv_is(128, 128, 8, true)) {
       LAUNCH_BWD(128, 128);
       if (int rc = launch_dkv<128, 128, 8, true>(gk, st, bp)) return rc;
-    } else if (d->D == 72) {
+    } else if (dkv_is(128, 72, 4, true)) {
       LAUNCH_BWD(128, 72);
       if (int rc = launch_dkv<128, 72, 4, true>(gk, st, bp)) return rc;
-    } else {
+    } else if (dkv_is(64, 64, 4, true)) {
       LAUNCH_BWD(64, 64);
       if (int rc = launch_dkv<64, 64, 4, true>(gk, st, bp)) return rc;
+    } else {
+      dxa_set_error("dxa_attn_bwd: no dK/dV kernel <%d,%d,%d,%s>", pl.D, pl.DV, pl.nw_dkv, pl.pf ? "PF" : "noPF");
+      return DXA_ERR_UNSUPPORTED;
     }
 #undef LAUNCH_BWD
     DXA_CHECK_LAUNCH();
     return DXA_OK;
   }
-  // head-sized fp32 attention without masks (the DiT heads' training backward): one launch
-  if (!d->force_generic && d->dtype == DXA_F32 && d->Hq == d->Hkv && !d->causal && !d->kv_start && !d->kv_end &&
-      !d->q_limit && !d->key_valid && !d->drop_mask && d->Sq <= SB_MAXQ && d->Sk <= 4096 && d->D <= SB_MAXD && d->D % 4 == 0 &&
-      d->lse && d->Hq <= 65535 && d->B <= 65535 &&
-      ((uintptr_t)d->q % 16 == 0) && ((uintptr_t)d->k % 16 == 0) && ((uintptr_t)d->v % 16 == 0) && ((uintptr_t)d->d_o % 16 == 0) &&
-      d->q_ss % 4 == 0 && d->k_ss % 4 == 0 && d->v_ss % 4 == 0 && d->do_ss % 4 == 0 && d->q_sh % 4 == 0 && d->k_sh % 4 == 0 &&
-      d->v_sh % 4 == 0 && d->do_sh % 4 == 0 && d->q_sb % 4 == 0 && d->k_sb % 4 == 0 && d->v_sb % 4 == 0 && d->do_sb % 4 == 0 &&
-      d->o && ((uintptr_t)d->o % 16 == 0) && d->o_ss % 4 == 0 && d->o_sh % 4 == 0 && d->o_sb % 4 == 0) {
+  if (pl.family == BWD_SMALL_F32 || pl.family == BWD_SMALL2_F32) {
     AttnBwdP bp;
     bp.f = make_params(d);
     bp.delta = nullptr;
@@ -1744,16 +1822,11 @@ extern "C" int dxa_attn_bwd(const dxa_attn_desc* d, void* workspace, size_t work
     bp.dq = (char*)d->dq; bp.dq_sb = d->dq_sb; bp.dq_sh = d->dq_sh; bp.dq_ss = d->dq_ss;
     bp.dk = (char*)d->dk; bp.dk_sb = d->dk_sb; bp.dk_sh = d->dk_sh; bp.dk_ss = d->dk_ss;
     bp.dv = (char*)d->dv; bp.dv_sb = d->dv_sb; bp.dv_sh = d->dv_sh; bp.dv_ss = d->dv_ss;
-    // more than one chunk of queries: the register-blocked kernel (16-byte aligned dq / dk / dv rows; otherwise the
-    // one-element-per-thread kernel at 1024 threads, rounds 6a-b)
-    const bool v2_ok = ((uintptr_t)d->dq % 16 == 0) && ((uintptr_t)d->dk % 16 == 0) && ((uintptr_t)d->dv % 16 == 0) &&
-                       d->dq_ss % 4 == 0 && d->dk_ss % 4 == 0 && d->dv_ss % 4 == 0 && d->dq_sh % 4 == 0 && d->dk_sh % 4 == 0 &&
-                       d->dv_sh % 4 == 0 && d->dq_sb % 4 == 0 && d->dk_sb % 4 == 0 && d->dv_sb % 4 == 0;
-    if (d->Sq > SB_MAXT && v2_ok) {
+    if (pl.family == BWD_SMALL2_F32) {
       if (int rc = dxa_launch_lds<attn_bwd_small2_f32_k>(S2_LDS_BYTES, dim3((unsigned)d->Hq, (unsigned)d->B), dim3(1024), S2_LDS_BYTES,
                                                          (hipStream_t)stream, bp))
         return rc;
-    } else if (d->Sq > SB_MAXT) hipLaunchKernelGGL(attn_bwd_small_f32_k<1024>, dim3((unsigned)d->Hq, (unsigned)d->B), dim3(1024), 0, (hipStream_t)stream, bp);
+    } else if (pl.nw == 16) hipLaunchKernelGGL(attn_bwd_small_f32_k<1024>, dim3((unsigned)d->Hq, (unsigned)d->B), dim3(1024), 0, (hipStream_t)stream, bp);
     else hipLaunchKernelGGL(attn_bwd_small_f32_k<256>, dim3((unsigned)d->Hq, (unsigned)d->B), dim3(256), 0, (hipStream_t)stream, bp);
     DXA_CHECK_LAUNCH();
     return DXA_OK;
@@ -1842,5 +1915,19 @@ extern "C" int dxa_attn_bwd(const dxa_attn_desc* d, void* workspace, size_t work
   g.C = d->dv; g.ldc = d->dv_ss; g.sC[0] = d->dv_sb; g.sC[1] = d->dv_sh;
   if ((rc = dxa_gemm(&g, stream))) return rc;
   DXA_CHECK_LAUNCH();
+  return DXA_OK;
+}
+
+extern "C" int dxa_attn_plan(const dxa_attn_desc* d, int backward, dxa_attn_plan_info* out) {
+  DXA_CHECK_ARG(out != nullptr, "dxa_attn_plan: null output");
+  memset(out, 0, sizeof(*out));
+  if (int rc = check_common(d, backward ? "dxa_attn_bwd" : "dxa_attn_fwd_ws")) return rc;
+  if (backward) DXA_CHECK_ARG(d->d_o && d->dq && d->dk && d->dv, "dxa_attn_bwd: null gradient tensor");
+  const AttnPlan pl = backward ? attn_plan_bwd(d) : attn_plan_fwd(d, true);
+  out->family = ATTN_FAMILY_NAME[pl.family];
+  out->D = pl.D; out->DV = pl.DV;
+  out->nw = pl.nw; out->nw_dkv = pl.nw_dkv;
+  out->pf = pl.pf; out->nsplit = pl.nsplit; out->vec = pl.vec;
+  out->workspace = pl.ws;
   return DXA_OK;
 }

@@ -458,7 +458,9 @@ int dxa_qknorm_rope_merge_from(const void* dq, const void* dk, const void* dv, c
  * Attention.  Replaces torch SDPA at HF:qwen2/modeling_qwen2.py:143-235 (causal + key padding, GQA),
  * HF:clip/modeling_clip.py:259-330 (full), timm Attention in dit.py:145-149 (full, 17 tokens).
  * Element (b,h,s,d) of q/k/v/o lives at base + b*sb + h*sh + s*ss + d (element strides).
- * softmax in fp32; keys j visible to query i iff kv_start[b] <= j < kv_end[b] and (!causal || j <= i).
+ * softmax in fp32; key j is visible to query i iff kv_start[b] <= j < min(kv_end[b], q_limit[b,i]), key_valid[b,j], and
+ * (!causal || j <= i + (Sk - Sq)): the last query sees the last key.  A query that sees no key gets o = 0, lse = 0 and dq = 0;
+ * a key no query sees gets dk = dv = 0 (tests/attn_ref.py restates the rule; tests/test_attention_masks_gpu.py runs its edges).
  * Forward: fused flash kernel (bf16, D in {64,72,128,256} — 72 = SigLIP-So400m's head width, run on the 128-wide tiles with
  * its 72 real columns only: K/V tiles staged in LDS, MFMA QK^T and PV,
  * wavefront-shuffle softmax reductions) or a generic fp32-accumulate kernel (any dtype / D).
@@ -504,6 +506,24 @@ size_t dxa_attn_fwd_workspace(const dxa_attn_desc* d);
 int dxa_attn_fwd_ws(const dxa_attn_desc* d, void* workspace, size_t workspace_bytes, dxa_stream_t stream);
 size_t dxa_attn_bwd_workspace(const dxa_attn_desc* d);
 int dxa_attn_bwd(const dxa_attn_desc* d, void* workspace, size_t workspace_bytes, dxa_stream_t stream);
+/* Which kernels a descriptor gets, without running them: the route of dxa_attn_fwd_ws given dxa_attn_fwd_workspace() bytes
+ * (backward = 0; dxa_attn_fwd alone takes the same route minus the key-range split and the materialised path) or of
+ * dxa_attn_bwd (backward != 0).  The launchers launch from the same plan.  Same argument checks, status and dxa_last_error
+ * text as the entry point itself.  Host arithmetic only: no pointer is dereferenced (tensor pointers count by their
+ * alignment, the mask pointers by being NULL or not), nothing is allocated and no GPU is needed. */
+typedef struct dxa_attn_plan_info {
+  const char* family;   /* static storage.  Forward: "tr" (attn_fwd_tr_k), "flash" (attn_fwd_flash_k), "small_f32"
+                           (attn_fwd_small_f32_k), "materialised" (GEMM, attn_softmax_rows_k, GEMM), "generic" (attn_fwd_generic_k).
+                           Backward: "flash" (attn_bwd_dq_k + attn_bwd_dkv_k), "small_f32" (attn_bwd_small_f32_k), "small2_f32"
+                           (attn_bwd_small2_f32_k), "composed" (batched GEMMs + elementwise kernels) */
+  int32_t D, DV;        /* tr / flash: width of the staged tiles and the real columns (72 on 128); otherwise both = head_dim */
+  int32_t nw, nw_dkv;   /* waves per workgroup of the forward / dQ kernel and of the dK / dV kernel (0: no such kernel) */
+  int32_t pf;           /* flash backward: the dK / dV kernel prefetches the next tile into registers */
+  int32_t nsplit;       /* key ranges of the split forward + attn_split_combine_k (1: not split) */
+  int32_t vec;          /* generic forward: elements per K load (4 or 1); 0 elsewhere */
+  uint64_t workspace;   /* bytes: dxa_attn_fwd_workspace() / dxa_attn_bwd_workspace() */
+} dxa_attn_plan_info;
+int dxa_attn_plan(const dxa_attn_desc* d, int backward, dxa_attn_plan_info* out);
 
 /* ------------------------------------------------------------------------------------------------
  * Elementwise / data-movement kernels (HBM-bound; 16-byte vector access).
