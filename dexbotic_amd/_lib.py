@@ -225,6 +225,10 @@ SIGNATURES = {
     "dxa_token_drop_bwd": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _int, _vp]),
     "dxa_dropout_mask": (_int, [_vp, _i64, _f32, C.c_uint64, C.c_uint64, _int, _vp]),
     "dxa_bank_consolidate": (_int, [_vp, _vp, _int, _i64, _i64, _int, _int, _vp, _vp]),
+    "dxa_bank_stage_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp]),
+    "dxa_bank_stage_bwd": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp]),
+    "dxa_bank_append": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp]),
+    "dxa_bank_consolidate_batched": (_int, [_vp, _vp, _vp, _int, _int, _int, _vp, _i64, _i64, _i64, _i64, _int, _vp]),
     "dxa_add_rows": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _f32, _int, _vp]),
     "dxa_token_sum": (_int, [_vp, _vp, _i64, _i64, _i64, _f32, _int, _vp]),
     "dxa_mse_loss": (_int, [_vp, _vp, _vp, _vp, _i64, _f32, _vp]),

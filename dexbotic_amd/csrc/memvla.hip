@@ -4,6 +4,10 @@
 //   dxa_bank_consolidate   the token-merge consolidation of one memory bank ENTIRELY on the device: cosine similarity of
 //                          every neighbouring pair of entries, arg-max, merge of that pair, compaction of entries and
 //                          timesteps — no host read-back, the bank's length evolves deterministically (host bookkeeping)
+//   dxa_bank_stage_fwd/bwd, dxa_bank_append, dxa_bank_consolidate_batched
+//                          'parallel_stream' (memvla_arch.py:340-361): batch slot b is its own episode, so the B banks of a role lie
+//                          side by side and staging what the retrieval reads, the append and the consolidation are one launch
+//                          (two for the token merge) over all B slots, lengths read from a device array of counts
 #include "common.h"
 
 namespace {
@@ -47,11 +51,10 @@ __global__ __launch_bounds__(TPB) void dropout_mask_k(T* __restrict__ out, int64
 // sims[i] = mean over the N tokens of cos(feat[i, n, :], feat[i + 1, n, :]), i < len - 1 (F.cosine_similarity, eps 1e-8 on each
 // norm, memvla_arch.py:263-275).  One workgroup per pair; a wave owns tokens wave, wave + 4, ...; fixed fold order.
 template <typename T>
-__global__ __launch_bounds__(TPB) void bank_sims_k(const T* __restrict__ feat, float* __restrict__ sims, int64_t N, int64_t D) {
+__device__ __forceinline__ void bank_pair_sim(const T* __restrict__ a, const T* __restrict__ b, float* __restrict__ out, int64_t N,
+                                              int64_t D) {
   __shared__ float red[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const T* a = feat + (int64_t)blockIdx.x * N * D;
-  const T* b = a + N * D;
   float acc = 0.f;
   for (int64_t n = wave; n < N; n += 4) {
     float dot = 0.f, na = 0.f, nb = 0.f;
@@ -64,7 +67,12 @@ __global__ __launch_bounds__(TPB) void bank_sims_k(const T* __restrict__ feat, f
   }
   if (lane == 0) red[wave] = acc;
   __syncthreads();
-  if (threadIdx.x == 0) sims[blockIdx.x] = ((red[0] + red[1]) + (red[2] + red[3])) / (float)N;
+  if (threadIdx.x == 0) *out = ((red[0] + red[1]) + (red[2] + red[3])) / (float)N;
+}
+template <typename T>
+__global__ __launch_bounds__(TPB) void bank_sims_k(const T* __restrict__ feat, float* __restrict__ sims, int64_t N, int64_t D) {
+  const T* a = feat + (int64_t)blockIdx.x * N * D;
+  bank_pair_sim<T>(a, a + N * D, sims + blockIdx.x, N, D);
 }
 
 // j = first arg-max of sims[0 .. len - 2] (numpy.argmax); entry j <- 0.5 (entry j + entry j + 1), entries j + 2 .. move down by
@@ -72,8 +80,8 @@ __global__ __launch_bounds__(TPB) void bank_sims_k(const T* __restrict__ feat, f
 // entries in ascending order (reads entry i + 1 before it writes entry i): in place, no barrier needed.
 // fifo = 1: the oldest entry is dropped instead (memvla_arch.py:300-303): every entry moves down by one, sims is not read.
 template <typename T>
-__global__ __launch_bounds__(TPB) void bank_merge_k(T* __restrict__ feat, float* __restrict__ ts, const float* __restrict__ sims,
-                                                    int len, int64_t E, int fifo) {
+__device__ __forceinline__ void bank_merge_slot(T* __restrict__ feat, float* __restrict__ ts, const float* __restrict__ sims, int len,
+                                                int64_t E, int fifo) {
   int j = -1;
   if (!fifo) {
     j = 0;
@@ -93,6 +101,86 @@ __global__ __launch_bounds__(TPB) void bank_merge_k(T* __restrict__ feat, float*
     if (j >= 0) ts[j] = 0.5f * (ts[j] + ts[j + 1]);
     for (int i = j + 1; i < len - 1; ++i) ts[i] = ts[i + 1];
   }
+}
+template <typename T>
+__global__ __launch_bounds__(TPB) void bank_merge_k(T* __restrict__ feat, float* __restrict__ ts, const float* __restrict__ sims,
+                                                    int len, int64_t E, int fifo) {
+  bank_merge_slot<T>(feat, ts, sims, len, E, fifo);
+}
+
+// ---- B banks side by side ('parallel_stream': batch slot b is its own running episode): feat [B, cap, N, D], ts [B, cap],
+// counts [B] int32 on the device.  blockIdx.y = slot.  A count read from the device is clamped to [0, cap] before it indexes.
+__device__ __forceinline__ int bank_count(const int32_t* __restrict__ counts, int b, int add, int cap) {
+  const int n = counts[b] + add;
+  return n < 0 ? 0 : (n > cap ? cap : n);
+}
+
+// what the retrieval of one step reads: mem [B, cap, E] = the slot's entries oldest first (no history: entry 0 = the slot's own
+// tokens, the frame retrieving from itself), zeros behind them; ts_eff [B, cap] the matching timesteps; kv_len [B] keys in use
+template <typename T>
+__global__ __launch_bounds__(TPB) void bank_stage_k(const T* __restrict__ feat, const float* __restrict__ ts,
+                                                    const int32_t* __restrict__ counts, const T* __restrict__ tokens,
+                                                    const float* __restrict__ timesteps, T* __restrict__ mem,
+                                                    float* __restrict__ ts_eff, int32_t* __restrict__ kv_len, int cap, int64_t N,
+                                                    int64_t E) {
+  const int b = blockIdx.y;
+  const int n = bank_count(counts, b, 0, cap);
+  const int64_t total = (int64_t)cap * E, live = (int64_t)(n > 0 ? n : 1) * E;
+  const T* src = n > 0 ? feat + (int64_t)b * total : tokens + (int64_t)b * E;
+  T* dst = mem + (int64_t)b * total;
+  for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < total; i += (int64_t)gridDim.x * TPB)
+    dst[i] = i < live ? src[i] : (T)0.f;
+  if (blockIdx.x == 0) {
+    for (int i = threadIdx.x; i < cap; i += TPB)
+      ts_eff[(int64_t)b * cap + i] = n > 0 ? (i < n ? ts[(int64_t)b * cap + i] : 0.f) : (i == 0 ? timesteps[b] : 0.f);
+    if (threadIdx.x == 0) kv_len[b] = (int32_t)((n > 0 ? n : 1) * N);
+  }
+}
+
+// dtokens[b] = dmem[b, 0] for a slot without history (its tokens were entry 0), 0 for the others (history is detached)
+template <typename T>
+__global__ __launch_bounds__(TPB) void bank_stage_bwd_k(const T* __restrict__ dmem, const int32_t* __restrict__ counts,
+                                                        T* __restrict__ dtokens, int cap, int64_t E) {
+  const int b = blockIdx.y;
+  const bool own = bank_count(counts, b, 0, cap) == 0;
+  const T* src = dmem + (int64_t)b * cap * E;
+  T* dst = dtokens + (int64_t)b * E;
+  for (int64_t e = (int64_t)blockIdx.x * TPB + threadIdx.x; e < E; e += (int64_t)gridDim.x * TPB) dst[e] = own ? src[e] : (T)0.f;
+}
+
+// feat[b, counts[b]] = src[b], ts[b, counts[b]] = timesteps[b]; a slot whose count says it is full (>= cap) is left alone
+template <typename T>
+__global__ __launch_bounds__(TPB) void bank_append_k(T* __restrict__ feat, float* __restrict__ ts, const int32_t* __restrict__ counts,
+                                                     const T* __restrict__ src, const float* __restrict__ timesteps, int cap,
+                                                     int64_t E) {
+  const int b = blockIdx.y;
+  const int n = bank_count(counts, b, 0, cap);
+  if (n >= cap) return;
+  T* dst = feat + ((int64_t)b * cap + n) * E;
+  const T* s = src + (int64_t)b * E;
+  for (int64_t e = (int64_t)blockIdx.x * TPB + threadIdx.x; e < E; e += (int64_t)gridDim.x * TPB) dst[e] = s[e];
+  if (blockIdx.x == 0 && threadIdx.x == 0) ts[(int64_t)b * cap + n] = timesteps[b];
+}
+
+// bank_sims_k / bank_merge_k over (pair, slot) / (elements, slot) for the slots whose length counts[b] + add exceeds mem_length;
+// the other slots' blocks return at once (the test is uniform over a block, so the barrier inside bank_pair_sim is safe)
+template <typename T>
+__global__ __launch_bounds__(TPB) void bank_sims_batched_k(const T* __restrict__ feat, const int32_t* __restrict__ counts, int add,
+                                                           int mem_length, float* __restrict__ sims, int cap, int64_t N, int64_t D) {
+  const int b = blockIdx.y, i = blockIdx.x;
+  const int len = bank_count(counts, b, add, cap);
+  if (len <= mem_length || i >= len - 1) return;
+  const T* a = feat + ((int64_t)b * cap + i) * N * D;
+  bank_pair_sim<T>(a, a + N * D, sims + (int64_t)b * (cap - 1) + i, N, D);
+}
+template <typename T>
+__global__ __launch_bounds__(TPB) void bank_merge_batched_k(T* __restrict__ feat, float* __restrict__ ts,
+                                                            const int32_t* __restrict__ counts, int add, int mem_length,
+                                                            const float* __restrict__ sims, int cap, int64_t E, int fifo) {
+  const int b = blockIdx.y;
+  const int len = bank_count(counts, b, add, cap);
+  if (len <= mem_length || len < 2) return;
+  bank_merge_slot<T>(feat + (int64_t)b * cap * E, ts + (int64_t)b * cap, sims + (int64_t)b * (cap - 1), len, E, fifo);
 }
 
 // out[r, n, c] = (x ? x[r, n, c] : 0) + alpha * g[r, c]: the timestep positional embedding added to every token of a bank entry
@@ -172,6 +260,90 @@ extern "C" int dxa_bank_consolidate(void* feat, float* ts, int len, int64_t N, i
   } else {
     if (!fifo) hipLaunchKernelGGL((bank_sims_k<float>), dim3(len - 1), dim3(TPB), 0, st, (const float*)feat, sims, N, D);
     hipLaunchKernelGGL((bank_merge_k<float>), dim3(dxa_grid1d(E, TPB, 256)), dim3(TPB), 0, st, (float*)feat, ts, sims, len, E, fifo);
+  }
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
+}
+
+// ---- 'parallel_stream': B banks per launch -----------------------------------------------------------------------------------
+#define DXA_BANK_CHECK(name, ptrs)                                                                                       \
+  do {                                                                                                                   \
+    DXA_CHECK_ARG(ptrs, name ": null pointer");                                                                          \
+    DXA_CHECK_ARG(B > 0 && N > 0 && D > 0 && cap > 0, name ": B, N, D and cap must be positive");                        \
+    DXA_CHECK_ARG(cap >= 2, name ": cap must be at least 2 (mem_length + 1)");                                           \
+    DXA_CHECK_ARG(B <= 65535 && cap <= 65536, name ": at most 65535 slots of 65536 entries");                            \
+    DXA_CHECK_ARG(dtype == DXA_F32 || dtype == DXA_BF16, name ": dtype must be fp32 or bf16");                           \
+  } while (0)
+
+extern "C" int dxa_bank_stage_fwd(const void* feat, const float* ts, const int32_t* counts, const void* tokens,
+                                  const float* timesteps, void* mem, float* ts_eff, int32_t* kv_len, int64_t B, int64_t cap,
+                                  int64_t N, int64_t D, int dtype, dxa_stream_t stream) {
+  DXA_BANK_CHECK("dxa_bank_stage_fwd", feat && ts && counts && tokens && timesteps && mem && ts_eff && kv_len);
+  DXA_CHECK_ARG(cap * N <= INT32_MAX, "dxa_bank_stage_fwd: cap * N keys do not fit kv_len");
+  const int64_t E = N * D;
+  const dim3 grid(dxa_grid1d(cap * E, TPB, 1024), (unsigned)B);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == DXA_BF16)
+    hipLaunchKernelGGL((bank_stage_k<bf16_t>), grid, dim3(TPB), 0, st, (const bf16_t*)feat, ts, counts, (const bf16_t*)tokens,
+                       timesteps, (bf16_t*)mem, ts_eff, kv_len, (int)cap, N, E);
+  else
+    hipLaunchKernelGGL((bank_stage_k<float>), grid, dim3(TPB), 0, st, (const float*)feat, ts, counts, (const float*)tokens,
+                       timesteps, (float*)mem, ts_eff, kv_len, (int)cap, N, E);
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
+}
+
+extern "C" int dxa_bank_stage_bwd(const void* dmem, const int32_t* counts, void* dtokens, int64_t B, int64_t cap, int64_t N,
+                                  int64_t D, int dtype, dxa_stream_t stream) {
+  DXA_BANK_CHECK("dxa_bank_stage_bwd", dmem && counts && dtokens);
+  const int64_t E = N * D;
+  const dim3 grid(dxa_grid1d(E, TPB, 256), (unsigned)B);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == DXA_BF16)
+    hipLaunchKernelGGL((bank_stage_bwd_k<bf16_t>), grid, dim3(TPB), 0, st, (const bf16_t*)dmem, counts, (bf16_t*)dtokens, (int)cap, E);
+  else
+    hipLaunchKernelGGL((bank_stage_bwd_k<float>), grid, dim3(TPB), 0, st, (const float*)dmem, counts, (float*)dtokens, (int)cap, E);
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
+}
+
+extern "C" int dxa_bank_append(void* feat, float* ts, const int32_t* counts, const void* src, const float* timesteps, int64_t B,
+                               int64_t cap, int64_t N, int64_t D, int dtype, dxa_stream_t stream) {
+  DXA_BANK_CHECK("dxa_bank_append", feat && ts && counts && src && timesteps);
+  const int64_t E = N * D;
+  const dim3 grid(dxa_grid1d(E, TPB, 256), (unsigned)B);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == DXA_BF16)
+    hipLaunchKernelGGL((bank_append_k<bf16_t>), grid, dim3(TPB), 0, st, (bf16_t*)feat, ts, counts, (const bf16_t*)src, timesteps,
+                       (int)cap, E);
+  else
+    hipLaunchKernelGGL((bank_append_k<float>), grid, dim3(TPB), 0, st, (float*)feat, ts, counts, (const float*)src, timesteps,
+                       (int)cap, E);
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
+}
+
+extern "C" int dxa_bank_consolidate_batched(void* feat, float* ts, const int32_t* counts, int count_add, int mem_length, int fifo,
+                                            float* sims, int64_t B, int64_t cap, int64_t N, int64_t D, int dtype,
+                                            dxa_stream_t stream) {
+  DXA_BANK_CHECK("dxa_bank_consolidate_batched", feat && ts && counts && (sims || fifo));
+  DXA_CHECK_ARG(mem_length >= 1 && mem_length < cap, "dxa_bank_consolidate_batched: mem_length must be in [1, cap)");
+  DXA_CHECK_ARG(count_add >= 0 && count_add <= cap, "dxa_bank_consolidate_batched: count_add must be in [0, cap]");
+  const int64_t E = N * D;
+  const dim3 gs((unsigned)(cap - 1), (unsigned)B), gm(dxa_grid1d(E, TPB, 256), (unsigned)B);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == DXA_BF16) {
+    if (!fifo)
+      hipLaunchKernelGGL((bank_sims_batched_k<bf16_t>), gs, dim3(TPB), 0, st, (const bf16_t*)feat, counts, count_add, mem_length, sims,
+                         (int)cap, N, D);
+    hipLaunchKernelGGL((bank_merge_batched_k<bf16_t>), gm, dim3(TPB), 0, st, (bf16_t*)feat, ts, counts, count_add, mem_length, sims,
+                       (int)cap, E, fifo);
+  } else {
+    if (!fifo)
+      hipLaunchKernelGGL((bank_sims_batched_k<float>), gs, dim3(TPB), 0, st, (const float*)feat, counts, count_add, mem_length, sims,
+                         (int)cap, N, D);
+    hipLaunchKernelGGL((bank_merge_batched_k<float>), gm, dim3(TPB), 0, st, (float*)feat, ts, counts, count_add, mem_length, sims,
+                       (int)cap, E, fifo);
   }
   DXA_CHECK_LAUNCH();
   return DXA_OK;

@@ -2059,16 +2059,17 @@ class AttnFn(Function):
     """softmax(q k^T / sqrt(D)) v for [B,S,H,D] VIEWS (any strides with D contiguous) -> [B,Sq,H*D]: the cross
     attention of CrossTransformerBlock (memvla_arch.py:84-127) and of the DiT per-attention (nn.MultiheadAttention,
     memvla/action_model/dit.py:158-185).  ``drop_mask`` ([B,H,Sq,Sk], entries 0 or 1/(1-p)): SDPA's dropout_p on the
-    attention weights (memvla_arch.py:120-123), the mask drawn by the caller."""
+    attention weights (memvla_arch.py:120-123), the mask drawn by the caller.  ``kv_end`` ([B] int32): sample b attends to its
+    keys [0, kv_end[b]) only (the padded banks of the 'parallel_stream' memory); dk = dv = 0 behind them."""
 
     @staticmethod
-    def forward(ctx, q, k, v, drop_mask=None):
+    def forward(ctx, q, k, v, drop_mask=None, kv_end=None):
         B, Sq, H, D = q.shape
         o = torch.empty((B, Sq, H, D), device=q.device, dtype=q.dtype)
         lse = K.attn_fwd(q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3), o.permute(0, 2, 1, 3),
-                         causal=False, scale=D ** -0.5, drop_mask=drop_mask)
+                         causal=False, scale=D ** -0.5, kv_end=kv_end, drop_mask=drop_mask)
         ctx.save_for_backward(q, k, v, o, lse)
-        ctx.drop_mask = drop_mask
+        ctx.drop_mask, ctx.kv_end = drop_mask, kv_end
         return o.view(B, Sq, H * D)
 
     @staticmethod
@@ -2079,9 +2080,9 @@ class AttnFn(Function):
         dq, dk, dv = torch.empty(q.shape, device=q.device, dtype=q.dtype), torch.empty(k.shape, device=q.device, dtype=q.dtype), \
             torch.empty(v.shape, device=q.device, dtype=q.dtype)
         P = lambda t: t.permute(0, 2, 1, 3)
-        K.attn_bwd(P(q), P(k), P(v), P(o), lse, P(do), P(dq), P(dk), P(dv), causal=False, scale=D ** -0.5,
+        K.attn_bwd(P(q), P(k), P(v), P(o), lse, P(do), P(dq), P(dk), P(dv), causal=False, scale=D ** -0.5, kv_end=ctx.kv_end,
                    drop_mask=ctx.drop_mask)
-        return dq, dk, dv, None
+        return dq, dk, dv, None, None
 
 
 class AttnPackedFn(Function):
@@ -2184,6 +2185,23 @@ class AddRowsFn(Function):
     def backward(ctx, dy):
         dy = dy.contiguous()
         return (dy if ctx.needs[0] else None), (K.token_sum(dy) if ctx.needs[1] else None)
+
+
+class BankStageFn(Function):
+    """what one 'parallel_stream' step of the memory bank retrieves from, for all B slots (K.bank_stage_fwd): (mem [B, cap, N, D],
+    ts_eff [B, cap], kv_len [B]).  The bank's entries are detached copies; only a slot WITHOUT history — its own tokens stand as
+    entry 0, memvla_arch.py:378-387 — hands a gradient back to ``tokens``."""
+
+    @staticmethod
+    def forward(ctx, tokens, feat, ts, counts, timesteps):
+        mem, ts_eff, kv_len = K.bank_stage_fwd(feat, ts, counts, tokens.contiguous(), timesteps)
+        ctx.counts = counts
+        ctx.mark_non_differentiable(ts_eff, kv_len)
+        return mem, ts_eff, kv_len
+
+    @staticmethod
+    def backward(ctx, dmem, _dts, _dkv):
+        return K.bank_stage_bwd(dmem.contiguous(), ctx.counts), None, None, None, None
 
 
 class UnbindRowsFn(Function):

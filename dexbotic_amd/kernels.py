@@ -393,6 +393,56 @@ def bank_consolidate(feat: torch.Tensor, ts: torch.Tensor, length: int, sims: to
                                      _ptr(sims), _stream()), "dxa_bank_consolidate")
 
 
+def _bank_dims(feat: torch.Tensor, ts: torch.Tensor, counts: torch.Tensor):
+    B, cap, N, D = feat.shape
+    assert feat.is_contiguous() and ts.is_contiguous() and ts.dtype == torch.float32 and ts.shape == (B, cap)
+    assert counts.is_contiguous() and counts.dtype == torch.int32 and counts.shape == (B,) and counts.device == feat.device
+    return B, cap, N, D
+
+
+def bank_stage_fwd(feat: torch.Tensor, ts: torch.Tensor, counts: torch.Tensor, tokens: torch.Tensor, timesteps: torch.Tensor):
+    """what one 'parallel_stream' step retrieves from, for all B slots in ONE launch: feat [B, cap, N, D], ts [B, cap], counts [B]
+    int32, tokens [B, N, D], timesteps [B] fp32 -> fresh (mem [B, cap, N, D], ts_eff [B, cap], kv_len [B] int32); a slot without
+    history holds its own tokens as entry 0, everything behind kv_len is zero"""
+    B, cap, N, D = _bank_dims(feat, ts, counts)
+    assert tokens.is_contiguous() and tokens.shape == (B, N, D) and tokens.dtype == feat.dtype
+    assert timesteps.is_contiguous() and timesteps.dtype == torch.float32 and timesteps.shape == (B,)
+    mem = torch.empty_like(feat)
+    ts_eff = torch.empty_like(ts)
+    kv_len = torch.empty(B, device=feat.device, dtype=torch.int32)
+    L.check(lib.dxa_bank_stage_fwd(_ptr(feat), _ptr(ts), _ptr(counts), _ptr(tokens), _ptr(timesteps), _ptr(mem), _ptr(ts_eff),
+                                   _ptr(kv_len), B, cap, N, D, dt(feat), _stream()), "dxa_bank_stage_fwd")
+    return mem, ts_eff, kv_len
+
+
+def bank_stage_bwd(dmem: torch.Tensor, counts: torch.Tensor) -> torch.Tensor:
+    """dtokens [B, N, D] = dmem[:, 0] for the slots without history, 0 for the others"""
+    B, cap, N, D = dmem.shape
+    assert dmem.is_contiguous() and counts.is_contiguous() and counts.dtype == torch.int32 and counts.shape == (B,)
+    out = torch.empty((B, N, D), device=dmem.device, dtype=dmem.dtype)
+    L.check(lib.dxa_bank_stage_bwd(_ptr(dmem), _ptr(counts), _ptr(out), B, cap, N, D, dt(dmem), _stream()), "dxa_bank_stage_bwd")
+    return out
+
+
+def bank_append(feat: torch.Tensor, ts: torch.Tensor, counts: torch.Tensor, src: torch.Tensor, timesteps: torch.Tensor) -> None:
+    """feat[b, counts[b]] = src[b], ts[b, counts[b]] = timesteps[b] for all B slots in ONE launch (in place)"""
+    B, cap, N, D = _bank_dims(feat, ts, counts)
+    assert src.is_contiguous() and src.shape == (B, N, D) and src.dtype == feat.dtype
+    assert timesteps.is_contiguous() and timesteps.dtype == torch.float32 and timesteps.shape == (B,)
+    L.check(lib.dxa_bank_append(_ptr(feat), _ptr(ts), _ptr(counts), _ptr(src), _ptr(timesteps), B, cap, N, D, dt(feat), _stream()),
+            "dxa_bank_append")
+
+
+def bank_consolidate_batched(feat: torch.Tensor, ts: torch.Tensor, counts: torch.Tensor, count_add: int, mem_length: int,
+                             sims: Optional[torch.Tensor], fifo: bool = False) -> None:
+    """bank_consolidate on every slot whose length counts[b] + count_add exceeds mem_length, the others untouched (in place; two
+    launches for all B slots; per slot bit-identical to bank_consolidate).  sims: B * (cap - 1) floats of scratch."""
+    B, cap, N, D = _bank_dims(feat, ts, counts)
+    assert fifo or (sims is not None and sims.dtype == torch.float32 and sims.is_contiguous() and sims.numel() >= B * (cap - 1))
+    L.check(lib.dxa_bank_consolidate_batched(_ptr(feat), _ptr(ts), _ptr(counts), int(count_add), int(mem_length), int(fifo),
+                                             _ptr(sims), B, cap, N, D, dt(feat), _stream()), "dxa_bank_consolidate_batched")
+
+
 def add_rows(x: Optional[torch.Tensor], g: torch.Tensor, Nn: int, alpha: float = 1.0) -> torch.Tensor:
     """x [R, Nn, C] + alpha * g [R, C] broadcast over the tokens (x None: the broadcast alone)"""
     R, C_ = g.shape

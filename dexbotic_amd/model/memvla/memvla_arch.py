@@ -109,7 +109,8 @@ class CrossTransformerBlock(nn.Module):
             return torch.as_tensor(m).to(device=like.device, dtype=like.dtype).reshape(shape).contiguous()
         return K.dropout_mask(shape, self.dropout, like.dtype, like.device)      # one launch (dxa_dropout_mask)
 
-    def forward(self, query: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+    def forward(self, query: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_end: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``kv_end`` ([B] int32, device): sample b attends to its first kv_end[b] keys only (padded 'parallel_stream' banks)"""
         st, p, D, H = self.store, self.p, self.D, self.H
         B, N, _ = query.shape
         M = k.shape[1]
@@ -120,7 +121,7 @@ class CrossTransformerBlock(nn.Module):
         qp = _lin(st, q2, p + "q_proj.weight", p + "q_proj.bias").view(B, N, H, hd)
         kp = _lin(st, k.reshape(B * M, D), p + "k_proj.weight", p + "k_proj.bias").view(B, M, H, hd)
         vp = _lin(st, v.reshape(B * M, D), p + "v_proj.weight", p + "v_proj.bias").view(B, M, H, hd)
-        o = Fn.AttnFn.apply(qp, kp, vp, self._mask((B, H, N, M), qp) if drop else None).reshape(B * N, D)
+        o = Fn.AttnFn.apply(qp, kp, vp, self._mask((B, H, N, M), qp) if drop else None, kv_end).reshape(B * N, D)
         anchor = st.params[p + "attn_norm.weight"]
         x = Fn.NormFn.apply(Fn.AddFn.apply(q2r, o), anchor, st, "ln", p + "attn_norm.weight", p + "attn_norm.bias", 1e-5)
         x, xr = Fn.ForkFn.apply(x)
@@ -146,10 +147,41 @@ class _BankBuf:
         self.sims = torch.empty(max(cap, 2), device=device, dtype=torch.float32)
         self.n = 0
 
+    @classmethod
+    def view_of(cls, feat: torch.Tensor, ts: torch.Tensor, sims: torch.Tensor) -> "_BankBuf":
+        b = cls.__new__(cls)
+        b.feat, b.ts, b.sims, b.n = feat, ts, sims, 0
+        return b
+
+
+class _SlotBanks:
+    """'parallel_stream': the banks of one role for the B slots of a batch, side by side in ONE device buffer (feat [B, cap, N, D],
+    ts [B, cap]); ``slots[b]`` is a _BankBuf VIEW of slot b whose ``n`` is the host-side count (no read-back)."""
+
+    def __init__(self, B: int, cap: int, N: int, D: int, dtype, device):
+        self.B, self.cap, self.N, self.D = B, cap, N, D
+        self.feat = torch.empty((B, cap, N, D), device=device, dtype=dtype)
+        self.ts = torch.empty((B, cap), device=device, dtype=torch.float32)
+        self.sims = torch.empty((B, max(cap, 2)), device=device, dtype=torch.float32)
+        self.slots = [_BankBuf.view_of(self.feat[b], self.ts[b], self.sims[b]) for b in range(B)]
+        self.keys: List[Optional[tuple]] = [None] * B
+
 
 class PerCogMemBank(nn.Module):
-    """memvla_arch.py:190-444.  'group' training batches (banks cleared per batch, :330-333) and the single-episode
-    eval path; 'gate' fusion; 'tome' (token merge) or 'fifo' consolidation; timestep PE."""
+    """memvla_arch.py:190-444.  The three dataloader modes of the reference (:329-361): 'group' (banks cleared per training
+    batch), 'stream' (episodes follow one another, the bank survives from batch to batch and is cleared when the episode
+    changes) and 'parallel_stream' (batch slot i is its own running episode, key (i, dataset, file), cleared when the slot's
+    episode changes); the single-episode eval path; 'gate' fusion; 'tome' (token merge) or 'fifo' consolidation; timestep PE.
+
+    'group' and 'stream' walk the samples of a batch in order (a frame retrieves from what the earlier frames left).  In
+    'parallel_stream' the B slots of a step are independent, so retrieval, gate fusion, append and consolidation each run ONCE
+    over all B banks (_process_slots): the banks are padded to [B, cap * N, D] keys and the attention is limited per slot by
+    kv_end.  Retrieval dropout masks are then drawn with the BATCHED shapes — ``set_mask_fn`` sees, per role and layer,
+    (B, H, N, cap * N), (B * N, 4 D), (B * N, D); mask columns behind a slot's keys are never read.  A one-slot batch (B = 1, the
+    served episode of ``inference_action``) has nothing to batch and takes the serial walk on slot 0's bank: the same kernels as
+    a 'group' model, hence the same bits.  The buffers are sized by the first batch after a reset(); another B raises ValueError.
+    Deviation: a slot's bank while training and while evaluating are two buffers, so a TRAINING key (i, 0, 0) does not share
+    the bank of the evaluation key (i, 0, 0) as the reference's dictionary would."""
 
     def __init__(self, store: ParamStore, dataloader_type: str, group_size: int, per_token_size: int, cog_token_size: int,
                  mem_length: int = 16, retrieval_layers: int = 2, use_timestep_pe: bool = True, fusion_type: str = "gate",
@@ -157,8 +189,6 @@ class PerCogMemBank(nn.Module):
         super().__init__()
         assert dataloader_type in ("stream", "group", "parallel_stream")
         assert fusion_type in ("gate", "add") and consolidate_type in ("fifo", "tome")
-        if dataloader_type != "group":
-            raise NotImplementedError("native PerCogMemBank: the 'group' dataloader mode (the reference trainer's sampler)")
         if not use_timestep_pe or fusion_type != "gate":
             raise NotImplementedError("native PerCogMemBank: timestep PE + gate fusion (the reference defaults)")
         self.store = store
@@ -188,9 +218,14 @@ class PerCogMemBank(nn.Module):
         # with their timesteps [mem_length + 1] (fp32, device: after a token merge a timestep is the mean of two, chosen on the
         # device); the host only keeps the COUNT, which evolves without reading anything back
         self.banks: Dict[str, Dict[tuple, "_BankBuf"]] = {r: {} for r in self.roles}
+        # 'stream': the episode the last training batch ended in (eid_stream, :258); 'parallel_stream': the slot banks of a role,
+        # one set for training and one for evaluation, each remembering the key of every slot (prev_eids, :257)
+        self.eid_stream: Dict[str, Optional[tuple]] = {r: None for r in self.roles}
+        self.slot_banks: Dict[str, Dict[bool, "_SlotBanks"]] = {r: {} for r in self.roles}
 
     def entries(self, role: str, eid=(0, 0)) -> List[Tuple[torch.Tensor, torch.Tensor]]:
-        """[(timestep, feat[N, D])] of one bank, oldest first (tests / inspection; the reference's list layout)"""
+        """[(timestep, feat[N, D])] of one bank, oldest first (tests / inspection; the reference's list layout).  ``eid``: the
+        reference's key — (dataset, file), or (slot, dataset, file) in 'parallel_stream' ((slot, 0, 0) when evaluating)"""
         b = self.banks[role].get(tuple(eid))
         return [] if b is None else [(b.ts[i], b.feat[i]) for i in range(b.n)]
 
@@ -203,7 +238,9 @@ class PerCogMemBank(nn.Module):
 
     def set_mask_fn(self, fn) -> None:
         """tests: ``fn(shape) -> array of 0 | 1/(1-p)`` replaces the device draw of every dropout mask of the retrieval blocks
-        (called in the order the blocks run: per sample, per role, per layer: attention, FFN hidden, FFN output)"""
+        (called in the order the blocks run: per sample, per role, per layer: attention, FFN hidden, FFN output; in
+        'parallel_stream' with B > 1 there is ONE call per role and layer for all B slots, with the batched shapes
+        (B, H, N, cap * N), (B * N, 4 D), (B * N, D) — columns of the attention mask behind a slot's keys are never read)"""
         for blks in self.blocks.values():
             for b in blks:
                 b.mask_fn = fn
@@ -241,12 +278,27 @@ class PerCogMemBank(nn.Module):
 
     def _process_batch(self, role: str, tokens: torch.Tensor, episode_ids, timesteps: torch.Tensor) -> torch.Tensor:
         """``timesteps``: ONE fp32 device tensor [B] (a single upload per batch)"""
+        B = tokens.shape[0]
+        mode = self.dataloader_type
+        if mode == "parallel_stream":
+            return self._process_slots(role, tokens, episode_ids, timesteps)
+        if not self.training:
+            episode_ids = [(0, 0) for _ in range(B)]
+        elif mode == "group":
+            self.banks[role].clear()                                   # 'group' (:330-333)
+        else:                                                          # 'stream' (:334-339)
+            episode_ids = [tuple(e) for e in episode_ids]
+            prev_active = self.eid_stream[role]
+            if prev_active is not None and prev_active != episode_ids[0]:
+                self.banks[role].pop(prev_active, None)
+            self.eid_stream[role] = episode_ids[0]
+        return self._walk(role, tokens, episode_ids, timesteps, stream=self.training and mode == "stream")
+
+    def _walk(self, role: str, tokens: torch.Tensor, episode_ids, timesteps: torch.Tensor, stream: bool = False) -> torch.Tensor:
+        """the samples of a batch in order, each retrieving from what the earlier frames of its episode left behind.
+        ``stream``: the bank of the previous sample's episode is cleared when the episode changes inside the batch (:352-355)"""
         st = self.store
         B, N, D = tokens.shape
-        if self.training:
-            self.banks[role].clear()                                   # 'group' (:330-333)
-        else:
-            episode_ids = [(0, 0) for _ in range(B)]
         gp = f"{BANK}gate_fusion_blocks.{role}."
         nl = len(self.blocks[role])
         grad = torch.is_grad_enabled() and tokens.requires_grad
@@ -254,6 +306,9 @@ class PerCogMemBank(nn.Module):
         outs = []
         for i in range(B):
             eid = tuple(episode_ids[i])
+            if stream and i > 0 and eid != tuple(episode_ids[i - 1]):
+                self.banks[role].pop(tuple(episode_ids[i - 1]), None)
+                self.eid_stream[role] = eid
             bank = self.banks[role].get(eid)
             has_hist = bank is not None and bank.n > 0
             # consumers of this sample's tokens: the query of block 0, the two gate-fusion operands (+ without history: the key
@@ -283,6 +338,65 @@ class PerCogMemBank(nn.Module):
             outs.append(fused)
             self._consolidate(role, eid, fused[0] if self.update_fused else tokens[i], timesteps[i:i + 1])
         return Fn.CatRowsFn.apply(*outs) if B > 1 else outs[0]
+
+    def _slot_state(self, role: str, tokens: torch.Tensor) -> "_SlotBanks":
+        B, N, D = tokens.shape
+        sb = self.slot_banks[role].get(self.training)
+        if sb is None:
+            sb = self.slot_banks[role][self.training] = _SlotBanks(B, self.mem_length + 1, N, D, tokens.dtype, tokens.device)
+        if (sb.B, sb.N, sb.D) != (B, N, D):
+            raise ValueError(f"parallel_stream: the '{role}' banks hold {sb.B} slots of [{sb.N}, {sb.D}] tokens (sized by the first "
+                             f"batch); this batch has {B} of [{N}, {D}] — reset() before changing the batch size")
+        return sb
+
+    def _process_slots(self, role: str, tokens: torch.Tensor, episode_ids, timesteps: torch.Tensor) -> torch.Tensor:
+        """'parallel_stream' (:340-361): slot i of the batch is its own episode.  Key bookkeeping on the host, then ONE pass over
+        the B banks: stage (dxa_bank_stage_fwd) -> timestep PE -> the retrieval blocks with kv_end -> gate fusion ->
+        append (dxa_bank_append) -> consolidation (dxa_bank_consolidate_batched)."""
+        st = self.store
+        B, N, D = tokens.shape
+        sb = self._slot_state(role, tokens)
+        if self.training:
+            keys = [(i, int(e[0]), int(e[1])) for i, e in enumerate(episode_ids)]
+        else:
+            keys = [(i, 0, 0) for i in range(B)]
+        for i, key in enumerate(keys):
+            prev = sb.keys[i]
+            if prev != key:
+                if prev is not None:                                   # the slot's episode changed: its bank is cleared (:357-359)
+                    self.banks[role].pop(prev, None)
+                    sb.slots[i].n = 0
+                sb.keys[i] = key
+            self.banks[role][key] = sb.slots[i]
+        if B == 1:
+            return self._walk(role, tokens, keys, timesteps)           # one slot: the serial walk on slot 0's bank
+        counts_host = [s.n for s in sb.slots]
+        assert max(counts_host) <= self.mem_length
+        counts = hostcpu.upload(torch.tensor(counts_host, dtype=torch.int32), tokens.device)     # (pinned; one upload per step)
+        gp = f"{BANK}gate_fusion_blocks.{role}."
+        nl = len(self.blocks[role])
+        cap = sb.cap
+        working, w_cat, w_fuse, w_mem = Fn.ForkFn.apply(tokens.contiguous(), 4)
+        mem, ts_eff, kv_len = Fn.BankStageFn.apply(w_mem, sb.feat, sb.ts, counts, timesteps)
+        pe = self._encode_time(role, ts_eff.view(B * cap), tokens.dtype)                           # (B cap, D)
+        fork = Fn.ForkFn.apply(mem, 1 + nl)                             # the key sum and one value operand per block
+        key = Fn.AddRowsFn.apply(fork[0].reshape(B * cap, N, D), pe).reshape(B, cap * N, D)
+        kfork = Fn.ForkFn.apply(key, nl) if nl > 1 else (key,)
+        q = working
+        for l, blk in enumerate(self.blocks[role]):
+            q = blk(q, kfork[l], fork[1 + l].reshape(B, cap * N, D), kv_end=kv_len)
+        q_cat, q_fuse = Fn.ForkFn.apply(q.reshape(B * N, D))
+        scale = _lin(st, Fn.CatLastFn.apply(w_cat.reshape(B * N, D), q_cat), gp + "proj.weight", gp + "proj.bias", L.ACT_SIGMOID)
+        fused = Fn.GateFuseFn.apply(scale, w_fuse.reshape(B * N, D), q_fuse).view(B, N, D)
+        with torch.no_grad():
+            src = (fused if self.update_fused else tokens).detach().contiguous()
+            K.bank_append(sb.feat, sb.ts, counts, src, timesteps)
+            if max(counts_host) + 1 > self.mem_length:
+                K.bank_consolidate_batched(sb.feat, sb.ts, counts, 1, self.mem_length, sb.sims,
+                                           fifo=self.consolidate_type == "fifo")
+            for s in sb.slots:
+                s.n = min(s.n + 1, self.mem_length)
+        return fused
 
     def process_batch_per(self, per_tokens, episode_ids, timesteps):
         return self._process_batch("per", per_tokens, episode_ids, timesteps)

@@ -649,6 +649,30 @@ int dxa_dropout_mask(void* out, int64_t n, float p, uint64_t seed, uint64_t offs
  * afterwards the first len - 1 entries are the bank.  `sims`: len - 1 floats of scratch.  No host read-back. */
 int dxa_bank_consolidate(void* feat, float* ts, int len, int64_t N, int64_t D, int dtype, int fifo, float* sims,
                          dxa_stream_t stream);      /* fifo = 1: drop the oldest entry instead (memvla_arch.py:300-303) */
+/* 'parallel_stream' (memvla_arch.py:340-361): batch slot b is its own running episode, so the B banks of a role live side by
+ * side — feat [B, cap, N, D] (dtype), ts [B, cap] fp32, cap = mem_length + 1 — and every step of the bank is ONE launch over
+ * the B slots.  counts [B] int32 (device): the entries each slot held when the step began; a count is clamped to [0, cap]
+ * before it indexes anything.  All four refuse null pointers, B / N / D / cap <= 0, cap < 2 and a dtype other than fp32 / bf16.
+ *
+ * stage_fwd: what the step's retrieval reads, written afresh (the append below overwrites the bank while the backward still
+ * needs it): mem [B, cap, N, D], ts_eff [B, cap], kv_len [B].  Slot with history: its counts[b] entries and their timesteps,
+ * kv_len = counts[b] N.  Slot without: entry 0 = tokens[b], timestep timesteps[b], kv_len = N (the frame retrieves from itself,
+ * :378-387).  Everything behind kv_len is written as zeros.
+ * stage_bwd: dtokens[b] = dmem[b, 0] for a slot without history, 0 for the others (history entries are detached copies). */
+int dxa_bank_stage_fwd(const void* feat, const float* ts, const int32_t* counts, const void* tokens, const float* timesteps,
+                       void* mem, float* ts_eff, int32_t* kv_len, int64_t B, int64_t cap, int64_t N, int64_t D, int dtype,
+                       dxa_stream_t stream);
+int dxa_bank_stage_bwd(const void* dmem, const int32_t* counts, void* dtokens, int64_t B, int64_t cap, int64_t N, int64_t D,
+                       int dtype, dxa_stream_t stream);
+/* feat[b, counts[b]] = src[b] ([B, N, D]), ts[b, counts[b]] = timesteps[b]; a slot whose count is already cap is left alone */
+int dxa_bank_append(void* feat, float* ts, const int32_t* counts, const void* src, const float* timesteps, int64_t B,
+                    int64_t cap, int64_t N, int64_t D, int dtype, dxa_stream_t stream);
+/* dxa_bank_consolidate on every slot whose length counts[b] + count_add exceeds mem_length (count_add: entries appended since
+ * `counts` was uploaded — 1 after dxa_bank_append), bit-identical per slot; the other slots are not touched.  Two launches:
+ * similarities over (pair, slot), merge over (element, slot).  sims: B (cap - 1) floats of scratch (may be NULL with fifo).
+ * Also refuses mem_length outside [1, cap). */
+int dxa_bank_consolidate_batched(void* feat, float* ts, const int32_t* counts, int count_add, int mem_length, int fifo,
+                                 float* sims, int64_t B, int64_t cap, int64_t N, int64_t D, int dtype, dxa_stream_t stream);
 /* out[r,n,:] = (x ? x[r,n,:] : 0) + alpha g[r,:]: the timestep embedding added to every token of a bank entry
  * (memvla_arch.py:352-360); x = NULL: broadcast of a row over the tokens (backward of the token mean, :139-141) */
 int dxa_add_rows(const void* x, const void* g, void* out, int64_t R, int64_t Nn, int64_t C, float alpha, int dtype,
