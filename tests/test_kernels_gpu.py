@@ -13,6 +13,8 @@ if torch.cuda.is_available():
     from dexbotic_amd import _lib as L
     from dexbotic_amd import kernels as K
 
+from tests.gemm_cases import family as gemm_family, tensor_route
+
 DEV = "cuda"
 
 
@@ -45,6 +47,18 @@ ACTS = {6: lambda x: torch.sigmoid(x), 0: lambda x: x, 1: lambda x: F.gelu(x), 2
 
 
 # ------------------------------------------------------------------------------------------------ GEMM
+def nt_step(a, w, f32out, seeds):
+    """the single step dxa_gemm_plan gives the product the NT tests below run: fp32 accumulate, or bf16 with bias + residual"""
+    if f32out:
+        r = tensor_route(L, "nt", a, w, torch.float32, accumulate=True)
+    else:
+        M, N = a.shape[0], w.shape[0]
+        r = tensor_route(L, "nt", a, w, torch.bfloat16, bias=rnd(N, dtype=torch.bfloat16, seed=seeds[0]),
+                         residual=rnd(M, N, dtype=torch.bfloat16, seed=seeds[1]))
+    assert r["nsteps"] == 1, r
+    return r["steps"][0]
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("layout", ["nt", "nn", "tn"])
 @pytest.mark.parametrize("shape", [(128, 128, 64), (256, 384, 256), (200, 136, 96), (130, 70, 588), (17, 7, 7),
@@ -108,9 +122,14 @@ def test_gemm_accumulate_f32out_strided(dtype):
 @pytest.mark.parametrize("shape", [(1100, 530, 2048), (700, 300, 4096), (4592, 4608, 2048), (4112, 1024, 4096)])
 @pytest.mark.parametrize("f32out", [False, True])
 def test_gemm_ring_split_tail(shape, f32out):
-    """bf16 NT ring kernel when the last round of 256x256 tiles is cut along K (fp32 partials + gatherer)"""
+    """bf16 NT products whose last round of tiles is cut along K (fp32 partials + gatherer).  K % 64 == 0 here, so since the
+    ping-pong kernels arrived these shapes run on them (pp on 256-row tiles, pp3 on 192-row tiles: dxa_gemm_plan says which), no
+    longer on the ring kernel the test is named after; the ring kernel's own split tail (K % 64 == 32) is run by
+    test_gemm_routes_gpu.py"""
     M, N, Kd = shape
     a, w = rnd(M, Kd, dtype=torch.bfloat16, seed=15), rnd(N, Kd, dtype=torch.bfloat16, seed=16, scale=0.1)
+    step = nt_step(a, w, f32out, seeds=(17, 18))
+    assert gemm_family(step["kernel"]) in ("pp", "pp3") and step["tail_r"] > 0 and step["split_s"] >= 2, step
     ref = a.double() @ w.double().t()
     for rep in range(3):                                   # the arrival counters must reset themselves
         if f32out:
@@ -132,9 +151,10 @@ def test_gemm_pingpong(shape, f32out):
     buffers alternate), ragged M / N edges, the split-K tail, fused epilogue, fp32 accumulate output; every output element
     against an fp64 reference, several repetitions (the staggered wave groups must never read a K tile early)"""
     M, N, Kd = shape
-    # dispatch: ping-pong main loop (more than 1024 rows: below that the few-row 128x128 kernel takes NT products)
-    assert M > 1024 and Kd % 64 == 0 and not (-(-M // 192) * 192 * 27 < -(-M // 256) * 256 * 25)
     a, w = rnd(M, Kd, dtype=torch.bfloat16, seed=35), rnd(N, Kd, dtype=torch.bfloat16, seed=36, scale=0.1)
+    # dispatch: the planner gives these shapes the ping-pong main loop on 256-row tiles (lean or full epilogue)
+    kernel = nt_step(a, w, f32out, seeds=(37, 38))["kernel"]
+    assert kernel.startswith("pp<") and kernel.endswith(",nt>"), kernel
     ref = a.double() @ w.double().t()
     first = None
     for rep in range(3):
@@ -192,6 +212,12 @@ def test_gemm_pingpong_strided_operands(case):
         assert_close(g, xg.grad, 3 * rtol, 3 * atol, f"nn mulgrad {case}")
 
 
+# the kernel dxa_gemm_plan gives each shape: the first and the third fit one round of 128x128 tiles with K <= 4096 and have
+# been the few-row kernel's since it arrived (test_gemm_few_rows_t128 runs them too); the others run on 192-row tiles
+ROWS_192 = {(543, 4608, 3584): "t128<", (543, 3584, 18944): "pp3<", (514, 1024, 4096): "t128<", (130, 300, 64): "pp3<",
+            (330, 260, 96): "ring<", (192, 256, 32): "ring<", (1050, 777, 2048): "pp3<"}
+
+
 @pytest.mark.parametrize("shape", [(543, 4608, 3584), (543, 3584, 18944), (514, 1024, 4096), (130, 300, 64), (330, 260, 96),
                                    (192, 256, 32), (1050, 777, 2048)])
 @pytest.mark.parametrize("f32out", [False, True])
@@ -201,8 +227,9 @@ def test_gemm_ring_192_row_tiles(shape, f32out):
     (K % 64 != 0); with and without the split-K tail, ragged M and N edges.  The two kernels agree bit for bit wherever they
     cut K at the same places (profiles/r04_pp3_vs_ring.txt)"""
     M, N, Kd = shape
-    assert -(-M // 192) * 192 * 27 < -(-M // 256) * 256 * 25          # dispatch takes the 192-row variant
     a, w = rnd(M, Kd, dtype=torch.bfloat16, seed=25), rnd(N, Kd, dtype=torch.bfloat16, seed=26, scale=0.1)
+    kernel = nt_step(a, w, f32out, seeds=(27, 28))["kernel"]           # dispatch takes the 192-row variant
+    assert kernel.startswith(ROWS_192[shape]) and (kernel.startswith("pp3<") or kernel.startswith("t128<") or kernel.endswith(",192>")), kernel
     ref = a.double() @ w.double().t()
     for rep in range(2):
         if f32out:
@@ -1146,19 +1173,33 @@ def test_sumsq_ranges():
 
 
 # ------------------------------------------------------------------- few-row NT kernel (128x128 tiles, M <= 1024)
+# shape -> (kernel family dxa_gemm_plan gives it, pieces the few-row kernel cuts K into)
+FEW_ROWS = {(543, 4608, 3584): ("t128", 1), (543, 3584, 18944): ("pp3", 0), (514, 1024, 4096): ("t128", 4), (514, 4096, 1024): ("t128", 1),
+            (64, 64, 64): ("skinny_bf16", 0), (130, 300, 64): ("pp3", 0), (1024, 200, 128): ("pp", 0), (700, 136, 192): ("pp", 0),
+            (543, 37888, 3584): ("pp3", 0), (514, 1024, 1024): ("t128", 2), (640, 1000, 2048): ("t128", 4), (400, 1536, 3072): ("t128", 4)}
+
+
 @pytest.mark.parametrize("shape", [(543, 4608, 3584), (543, 3584, 18944), (514, 1024, 4096), (514, 4096, 1024), (64, 64, 64),
                                    (130, 300, 64), (1024, 200, 128), (700, 136, 192), (543, 37888, 3584), (514, 1024, 1024),
                                    (640, 1000, 2048), (400, 1536, 3072)])
 def test_gemm_few_rows_t128(shape):
     """bf16 NT products on a few hundred rows (batch-1 prefill S = 543, ViT on 2 x 257 tokens): 128x128-tile LDS-DMA ring
-    kernel; 1, 2, 3, 4 and many K tiles (the ring has 4 stages), split-K over 2 / 3 / 4 slices where few tiles meet a deep K
-    (40 tiles x K 4096 / 1024, 40 x 2048, 48 x 3072), ragged M / N, the whole epilogue menu (bias, residual,
+    kernel; 1, 2, 3, 4 and many K tiles (the ring has 4 stages), split-K over 2 / 4 slices where few tiles meet a deep K
+    (40 tiles x K 1024 / 4096, 40 x 2048, 48 x 3072; 3 slices: test_gemm_routes_gpu.py), and the shapes around the kernel's
+    limits that FEW_ROWS gives to its neighbours, ragged M / N, the whole epilogue menu (bias, residual,
     activation + pre-activation copy, activation gradient, fp32 accumulate), every element against fp64, repetitions bitwise"""
     M, N, Kd = shape
     a, w = rnd(M, Kd, dtype=torch.bfloat16, seed=91), rnd(N, Kd, dtype=torch.bfloat16, seed=92, scale=0.1)
     ref = a.double() @ w.double().t()
     rtol, atol = tol_for(torch.bfloat16, Kd)
     bias, res = rnd(N, dtype=torch.bfloat16, seed=93), rnd(M, N, dtype=torch.bfloat16, seed=94)
+    # dispatch, from the planner, of the four products below: the few-row kernel with the K cut the docstring names, or (the
+    # shapes around its limits: fewer than 32 or more than 256 tiles, K beyond 4096, 64 rows) the kernel that takes over there
+    want, split = FEW_ROWS[shape]
+    for odt, kw in ((torch.bfloat16, dict(bias=bias, residual=res)), (torch.float32, dict(accumulate=True)),
+                    (torch.bfloat16, dict(bias=bias, act=3, aux_out=res)), (torch.bfloat16, dict(mulgrad=res, act=3))):
+        step = tensor_route(L, "nt", a, w, odt, **kw)["steps"][0]
+        assert gemm_family(step["kernel"]) == want and (want != "t128" or step["split_s"] == split), (kw.keys(), step)
     first = None
     for rep in range(3):
         out = K.mm_nt(a, w, bias=bias, residual=res)
