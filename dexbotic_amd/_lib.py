@@ -270,6 +270,9 @@ SIGNATURES = {
     "dxa_dit_sample_bf16_per_fwd": (_int, [_vp] * 9 + [_int, _int, _int, _int, _f32, _vp, _vp, _int, _int, _int, _int, _int, _int, _int, _f32, _vp, _sz, _vp]),
     "dxa_dit_sample_bf16_workspace": (_sz, [_int, _int, _int]),
     "dxa_dit_sample_bf16_fwd": (_int, [_vp] * 9 + [_int, _int, _int, _int, _f32, _vp, _int, _int, _int, _int, _int, _int, _f32, _vp, _sz, _vp]),
+    "dxa_dit_sample_bf16_batched_workspace": (_sz, [_int, _int, _int, _int]),
+    "dxa_dit_sample_bf16_batched_fwd": (_int, [_vp] * 9 + [_int, _int, _int, _int, _int, _f32, _vp, _int, _int, _int, _int, _int, _int, _f32, _vp, _sz, _vp]),
+    "dxa_dit_sample_bf16_per_batched_fwd": (_int, [_vp] * 9 + [_int, _int, _int, _int, _int, _f32, _vp, _vp, _int, _int, _int, _int, _int, _int, _int, _f32, _vp, _sz, _vp]),
     "dxa_decode_step_workspace": (_sz, [_int, _int, _int, _int, _int]),
     "dxa_decode_step": (_int, [C.POINTER(DecodeDesc), _vp]),
     "dxa_decode_status": (_int, [_vp, _vp]),

@@ -742,7 +742,8 @@ enum { BF_QKV = 0, BF_FC1 = 1, BF_RES = 2 };
 // gelu, out -> ab tiles;  BF_RES: A = ob / ab, S K-slices folded by the last arrival (as in gemm_phase), out -> h += ..., hb, stats.
 template <int KIND, int U>
 __device__ __forceinline__ void gemm_bf_u(const DitBfP& p, Smem& s, const BfBufs& b, const Buf& A, int K, const bf16_t* Wp,
-                                          const float* bias, const float* wsum, int Nout, int S, unsigned* cnt, unsigned cnt_target) {
+                                          const float* bias, const float* wsum, int Nout, int S, unsigned* cnt, unsigned cnt_target,
+                                          int wg) {
   constexpr bool LN = KIND != BF_RES;
   constexpr uint32_t OOB = 0x80000000u;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -762,7 +763,7 @@ __device__ __forceinline__ void gemm_bf_u(const DitBfP& p, Smem& s, const BfBufs
   const __amdgpu_buffer_rsrc_t Br = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(bias), 0, Nout * 4, 0x00020000);
   const __amdgpu_buffer_rsrc_t Sr = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(LN ? (const void*)wsum : (const void*)bias), 0, Nout * 4, 0x00020000);
   const int ncb = Nout / 16, npc = K / 32, per = npc / S, ntile = K / 16, nq = ntile / 2;
-  for (int item = blockIdx.x; item < ncb * S; item += gridDim.x) {
+  for (int item = wg; item < ncb * S; item += gridDim.x) {      // wg: blockIdx.x, or rotated by the request group (for_groups)
     const int cb = item % ncb, ks = item / ncb, n0 = cb * 16;
     const int pc_lo = ks * per, pc_hi = pc_lo + per;
     const uint32_t woff = (uint32_t)(((size_t)cb * npc * 16 + l16) * 64 + lg * 16);
@@ -874,20 +875,20 @@ __device__ __forceinline__ void gemm_bf_u(const DitBfP& p, Smem& s, const BfBufs
 
 template <int KIND>
 __device__ __forceinline__ void gemm_bf(const DitBfP& p, Smem& s, const BfBufs& b, const Buf& A, int K, const void* Wp, const void* bias,
-                                        const void* wsum, int Nout, int S, unsigned* cnt, unsigned cnt_target) {
+                                        const void* wsum, int Nout, int S, unsigned* cnt, unsigned cnt_target, int wg) {
   const int per = K / 32 / S;
   const bf16_t* W = reinterpret_cast<const bf16_t*>(Wp);
   const float *bi = reinterpret_cast<const float*>(bias), *ws = reinterpret_cast<const float*>(wsum);
-  if (per <= 8) gemm_bf_u<KIND, 1>(p, s, b, A, K, W, bi, ws, Nout, S, cnt, cnt_target);
-  else if (per <= 16) gemm_bf_u<KIND, 2>(p, s, b, A, K, W, bi, ws, Nout, S, cnt, cnt_target);
-  else gemm_bf_u<KIND, 3>(p, s, b, A, K, W, bi, ws, Nout, S, cnt, cnt_target);
+  if (per <= 8) gemm_bf_u<KIND, 1>(p, s, b, A, K, W, bi, ws, Nout, S, cnt, cnt_target, wg);
+  else if (per <= 16) gemm_bf_u<KIND, 2>(p, s, b, A, K, W, bi, ws, Nout, S, cnt, cnt_target, wg);
+  else gemm_bf_u<KIND, 3>(p, s, b, A, K, W, bi, ws, Nout, S, cnt, cnt_target, wg);
 }
 
 // attention_phase with the output written as bf16 operand tiles (ob): the A operand of the output projection
-__device__ __forceinline__ void attention_bf(const DitBfP& p, Smem& s, const BfBufs& b) {
+__device__ __forceinline__ void attention_bf(const DitBfP& p, Smem& s, const BfBufs& b, int wg) {
   const int tid = threadIdx.x, T1 = p.T1, ld = 3 * p.H;
   constexpr uint32_t OOB = 0x80000000u;
-  for (int pr = blockIdx.x; pr < p.N * p.heads; pr += gridDim.x) {
+  for (int pr = wg; pr < p.N * p.heads; pr += gridDim.x) {
     const int n = pr / p.heads, hd = pr - n * p.heads;
     const size_t base = (size_t)n * T1 * ld + hd * HD;
     float4 ld_[3];
@@ -957,8 +958,9 @@ constexpr int PER_MAXT = 24;        // tokens per sample with perceptual attenti
 // work item = (sample, head, group of <= 8 query rows).  The row groups of one (sample, head) read the same keys / values: they are
 // dealt to workgroups whose ids are congruent mod 8 — one XCD, one L2 (workgroups go round-robin over the 8 XCDs) — and to workgroups
 // that have no tile of the query projection (the first H / 16 have one): those request their keys / values while the projection runs.
-__device__ __forceinline__ int per_first_item(const DitBfP& p) {
-  const int shift = (p.H / 16) % (int)gridDim.x;
+// `extra`: work items dealt before this request group's (0 in a single-request launch)
+__device__ __forceinline__ int per_first_item(const DitBfP& p, int extra) {
+  const int shift = (p.H / 16 + extra) % (int)gridDim.x;
   return ((int)blockIdx.x + (int)gridDim.x - shift) % (int)gridDim.x;
 }
 __device__ __forceinline__ int per_items(const DitBfP& p) { return ((p.N * p.heads + 7) & ~7) * ((p.T1 + PER_TP - 1) / PER_TP); }
@@ -982,7 +984,7 @@ __device__ __forceinline__ void per_load(const DitBfP& p, const float* __restric
 }
 
 __device__ __forceinline__ void per_attention_bf(const DitBfP& p, Smem& s, const BfBufs& b, const float* __restrict__ kv,
-                                                 PerOperands& ops, bool preloaded) {
+                                                 PerOperands& ops, bool preloaded, int first) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int KW = p.P >> 3, T1 = p.T1;                           // KW = keys per wave: 8 .. 32
   // LDS: the phase owns everything in front of Smem::last — [ q: TP x 64 | (max, sum): 8 x TP x 2 | A: scores / probabilities 8 x 32 x TP,
@@ -994,7 +996,6 @@ __device__ __forceinline__ void per_attention_bf(const DitBfP& p, Smem& s, const
   static_assert(32 * PER_TP <= PER_TP * HD, "per_attention_bf: the probabilities fit under the partial outputs");
   float* const pw = sA + wave * 32 * PER_TP;
   const int key = lane & 31, half = lane >> 5;
-  const int first = per_first_item(p);
   for (int item = first; item < per_items(p); item += gridDim.x) {
     int n, hd, r0, nr;
     if (!per_decode(p, item, n, hd, r0, nr)) continue;     // (uniform per workgroup)
@@ -1100,53 +1101,124 @@ __device__ __forceinline__ void per_attention_bf(const DitBfP& p, Smem& s, const
   }
 }
 
-__device__ __forceinline__ void walk_blocks_bf(const DitBfP& p, Smem& s, const BfBufs& b, unsigned& epoch, unsigned nblk, unsigned base) {
+// ---- request groups.  A launch of the batched sampler (MULTI) carries G requests; a GROUP is one request's rows exactly as a
+// single launch lays them out (M = N T1 <= 48 rows, its own h, qkv, stats, part, hb, ob, ab, x ping-pong and eps `ws_gs` bytes after
+// the previous group's, its own x, z_emb and keys / values, its own split-K tile counters).  Weights, t_emb, pos and coef are shared.
+// Every phase walks the groups INSIDE the phase, with the per-group view of the parameters a single launch would have been given, so
+// a group's instruction sequence and summation order are the single launch's: same bits.  The device-wide barriers stay outside the
+// group loops: 620 per request become 620 per launch.  Group g's work items are dealt to the workgroups starting where group g - 1's
+// ended (rotated workgroup id), so a phase with fewer items than workgroups (48 tiles of the output projection on 192 workgroups)
+// runs several groups side by side; nothing in a tile's arithmetic depends on the workgroup that computes it.
+struct DitGroups {
+  int G;
+  size_t ws_gs;          // bytes between two groups' workspaces
+  size_t kv_gs;          // floats between two groups' keys / values inside one block's [G][N][P][2][H]
+};
+// group g's split-K tile counters: behind arrival counter g of the sync block (its 4 KiB page is otherwise padding), a KiB away from
+// the word the barrier polls.  NCTR pages: at most NCTR groups.
+constexpr unsigned SYNC_GROUP_PROJ = 256, SYNC_GROUP_FC2 = 320;
+constexpr int MAXG = (int)NCTR;
+static_assert(SYNC_GROUP_FC2 + SYNC_NTILE <= SYNC_CTR_WORDS && SYNC_GROUP_PROJ + SYNC_NTILE <= SYNC_GROUP_FC2, "group tile counters fit their page");
+
+template <bool MULTI>
+__device__ __forceinline__ DitBfP group_view(const DitBfP& p, const DitGroups& gr, int g) {
+  DitBfP q = p;
+  if (MULTI) {
+    const size_t d = (size_t)g * gr.ws_gs;
+    auto mv = [&](auto* ptr) { return reinterpret_cast<decltype(ptr)>(reinterpret_cast<char*>(ptr) + d); };
+    q.h = mv(p.h); q.qkv = mv(p.qkv); q.stats = mv(p.stats); q.part = mv(p.part); q.hb = mv(p.hb); q.ob = mv(p.ob); q.ab = mv(p.ab);
+    q.kv = p.kv + (size_t)g * gr.kv_gs;
+    q.cnt_proj = p.bar + sync_ctr((unsigned)g) + SYNC_GROUP_PROJ;
+    q.cnt_fc2 = p.bar + sync_ctr((unsigned)g) + SYNC_GROUP_FC2;
+  }
+  return q;
+}
+// blockIdx.x counted from the workgroup that takes work item `start` of a phase
+__device__ __forceinline__ int rotated_wg(int start) {
+  return ((int)blockIdx.x + (int)gridDim.x - start % (int)gridDim.x) % (int)gridDim.x;
+}
+// f(group's parameters, group's buffers, workgroup id for the group's items, g) for every group of the launch; `items` = work items
+// of the phase per group
+template <bool MULTI, typename F>
+__device__ __forceinline__ void for_groups(const DitBfP& p, const DitGroups& gr, int items, F f) {
+  if (!MULTI) {
+    f(p, BfBufs(p), (int)blockIdx.x, 0);
+  } else {
+    for (int g = 0; g < gr.G; ++g) {
+      const DitBfP pg = group_view<true>(p, gr, g);
+      f(pg, BfBufs(pg), rotated_wg(g * items), g);
+    }
+  }
+}
+
+template <bool MULTI>
+__device__ __forceinline__ void walk_blocks_bf(const DitBfP& p, const DitGroups& gr, Smem& s, unsigned& epoch, unsigned nblk, unsigned base) {
+  const int ncb = p.H / 16;
   for (int blk = 0; blk < p.depth; ++blk) {
     const void* const* w = p.w + blk * p.wstride;
     const bool per = p.P > 0;
     // the K-sliced output projections count arrivals per column block: with perceptual attention TWO products per block use cnt_proj
     const unsigned tgt_proj = per ? (2u * (base + (unsigned)blk) + 1u) * p.s_proj : (base + (unsigned)blk + 1u) * p.s_proj;
     DIT_STAMP(s, 0);
-    gemm_bf<BF_QKV>(p, s, b, b.hb, p.H, w[0], w[1], w[8], 3 * p.H, 1, nullptr, 0);
+    for_groups<MULTI>(p, gr, 3 * ncb, [&](const DitBfP& pg, const BfBufs& b, int wg, int) {
+      gemm_bf<BF_QKV>(pg, s, b, b.hb, p.H, w[0], w[1], w[8], 3 * p.H, 1, nullptr, 0, wg);
+    });
     DIT_STAMP(s, 3);
     phase_sync(p.bar, nblk, epoch, s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 0, 5);
     DIT_STAMP(s, 0);
-    attention_bf(p, s, b);
+    for_groups<MULTI>(p, gr, p.N * p.heads, [&](const DitBfP& pg, const BfBufs& b, int wg, int) { attention_bf(pg, s, b, wg); });
     DIT_STAMP(s, 1); DIT_STAMP(s, 2); DIT_STAMP(s, 3);
     phase_sync(p.bar, nblk, epoch, s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 1, 5);
     DIT_STAMP(s, 0);
-    gemm_bf<BF_RES>(p, s, b, b.ob, p.H, w[2], w[3], nullptr, p.H, p.s_proj, p.cnt_proj, tgt_proj);
+    for_groups<MULTI>(p, gr, ncb * p.s_proj, [&](const DitBfP& pg, const BfBufs& b, int wg, int) {
+      gemm_bf<BF_RES>(pg, s, b, b.ob, p.H, w[2], w[3], nullptr, p.H, p.s_proj, pg.cnt_proj, tgt_proj, wg);
+    });
     DIT_STAMP(s, 3);
     phase_sync(p.bar, nblk, epoch, s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 2, 5);
     if (per) {
       // x + MHA(norm3 x, per, per): q = (norm3 folded into the packed q rows of in_proj) | attention over the cached keys / values | out_proj
-      gemm_bf<BF_QKV>(p, s, b, b.hb, p.H, w[10], w[11], w[12], p.H, 1, nullptr, 0);
+      for_groups<MULTI>(p, gr, ncb, [&](const DitBfP& pg, const BfBufs& b, int wg, int) {
+        gemm_bf<BF_QKV>(pg, s, b, b.hb, p.H, w[10], w[11], w[12], p.H, 1, nullptr, 0, wg);
+      });
       // the keys / values of this workgroup's first attention item: in flight (or, for the workgroups without a projection tile,
-      // already here) when the barrier opens — a cold 128 KB of them costs 5 us after it (profiles/r06_memvla_sampler.txt)
-      const float* kvb = p.kv + (size_t)blk * p.N * p.P * 2 * p.H;
+      // already here) when the barrier opens — a cold 128 KB of them costs 5 us after it (profiles/r06_memvla_sampler.txt).
+      // With several groups: the first item of group 0 (the attention items start behind ALL groups' projection tiles).  (Requesting
+      // nothing ahead in the batched kernel takes it from 256 registers with 7 spilled to 212 and no scratch — and a group then misses
+      // its single launch's bits by 8.6e-4 after three steps: the two kernels are compiled separately and, it seems, this phase's
+      // sums are then contracted differently; not traced further.  The bits are the contract; the spills stay.)
+      const size_t kv_blk = (size_t)blk * (MULTI ? gr.G : 1) * p.N * p.P * 2 * p.H;
+      const int ahead = MULTI ? (gr.G - 1) * ncb : 0, nitem = per_items(p);
       PerOperands ops;
       bool pre = false;
       int n_, hd_, r0_, nr_;
-      if (per_decode(p, per_first_item(p), n_, hd_, r0_, nr_)) { per_load(p, kvb, n_, hd_, ops); pre = true; }
+      if (per_decode(p, per_first_item(p, ahead), n_, hd_, r0_, nr_)) { per_load(p, p.kv + kv_blk, n_, hd_, ops); pre = true; }
       phase_sync(p.bar, nblk, epoch, s);
       DIT_STAMP(s, 0);
-      per_attention_bf(p, s, b, kvb, ops, pre);
+      for_groups<MULTI>(p, gr, nitem, [&](const DitBfP& pg, const BfBufs& b, int, int g) {
+        per_attention_bf(pg, s, b, pg.kv + kv_blk, ops, pre && g == 0, per_first_item(p, ahead + g * nitem));
+      });
       DIT_STAMP(s, 5);
       phase_sync(p.bar, nblk, epoch, s);
       DIT_STAMP(s, 6); DIT_STAMP_FOLD(s, 5, 6);
-      gemm_bf<BF_RES>(p, s, b, b.ob, p.H, w[13], w[14], nullptr, p.H, p.s_proj, p.cnt_proj, tgt_proj + (unsigned)p.s_proj);
+      for_groups<MULTI>(p, gr, ncb * p.s_proj, [&](const DitBfP& pg, const BfBufs& b, int wg, int) {
+        gemm_bf<BF_RES>(pg, s, b, b.ob, p.H, w[13], w[14], nullptr, p.H, p.s_proj, pg.cnt_proj, tgt_proj + (unsigned)p.s_proj, wg);
+      });
       phase_sync(p.bar, nblk, epoch, s);
     }
     DIT_STAMP(s, 0);
-    gemm_bf<BF_FC1>(p, s, b, b.hb, p.H, w[4], w[5], w[9], p.I, 1, nullptr, 0);
+    for_groups<MULTI>(p, gr, p.I / 16, [&](const DitBfP& pg, const BfBufs& b, int wg, int) {
+      gemm_bf<BF_FC1>(pg, s, b, b.hb, p.H, w[4], w[5], w[9], p.I, 1, nullptr, 0, wg);
+    });
     DIT_STAMP(s, 3);
     phase_sync(p.bar, nblk, epoch, s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 3, 5);
     DIT_STAMP(s, 0);
-    gemm_bf<BF_RES>(p, s, b, b.ab, p.I, w[6], w[7], nullptr, p.H, p.s_fc2, p.cnt_fc2, (base + (unsigned)blk + 1u) * p.s_fc2);
+    for_groups<MULTI>(p, gr, ncb * p.s_fc2, [&](const DitBfP& pg, const BfBufs& b, int wg, int) {
+      gemm_bf<BF_RES>(pg, s, b, b.ab, p.I, w[6], w[7], nullptr, p.H, p.s_fc2, pg.cnt_fc2, (base + (unsigned)blk + 1u) * p.s_fc2, wg);
+    });
     DIT_STAMP(s, 3);
     phase_sync(p.bar, nblk, epoch, s);
     DIT_STAMP(s, 5); DIT_STAMP_FOLD(s, 4, 5);
@@ -1159,23 +1231,28 @@ struct DitSampleBfP {
   const float* coef; float* xpp; float* eps;
   int steps, A, nb, use_cfg;
   float cfg_scale;
+  DitGroups gr;              // MULTI: x [G][nb, T, A], ze [G][N, H]; xpp, eps and blk's arrays are group 0's
 };
 
+// MULTI = false: one request (dxa_dit_sample_bf16_fwd / _per_fwd).  MULTI = true: sp.gr.G request groups (the _batched entry points).
+template <bool MULTI>
 __global__ __launch_bounds__(512) void dit_sample_bf16_k(const DitSampleBfP sp) {
   __shared__ Smem s;
-  __shared__ float xs[MAXM * MAXA];
+  __shared__ float xs[MAXM * MAXA];              // the x of ONE group at a time
   const DitBfP& p = sp.blk;
   unsigned epoch = 0;
   const unsigned nblk = gridDim.x;
   const int T = p.T1 - 1, A = sp.A, H = p.H, nx = sp.nb * T * A;
-  const BfBufs b(p);
-  const Act xin(sp.x, (size_t)nx), xpp(sp.xpp, (size_t)2 * nx), epsg(sp.eps, (size_t)p.M * MAXA), hact(p.h, (size_t)p.M * p.H);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int G = MULTI ? sp.gr.G : 1;
 #if defined(DXA_DIT_STAMPS)
   if (threadIdx.x < 48) s.stamp[threadIdx.x / 8][threadIdx.x % 8] = 0ull;
   __syncthreads();
 #endif
-  auto load_x = [&](int step) {          // as in dit_sample_fused_k
+  // group g's x, x ping-pong and eps rows
+  auto group_f = [&](float* q, int g) { return reinterpret_cast<float*>(reinterpret_cast<char*>(q) + (MULTI ? (size_t)g * sp.gr.ws_gs : 0)); };
+  auto load_x = [&](int g, int step, bool writer) {          // as in dit_sample_fused_k; `writer`: this workgroup keeps the global copy
+    const Act xin(sp.x + (size_t)g * nx, (size_t)nx), xpp(group_f(sp.xpp, g), (size_t)2 * nx), epsg(group_f(sp.eps, g), (size_t)p.M * MAXA);
     if (tid < nx) {
       float xv;
       if (step == 0) {
@@ -1194,7 +1271,7 @@ __global__ __launch_bounds__(512) void dit_sample_bf16_k(const DitSampleBfP sp) 
         xv = x0 * sqrtf(ab_prev) + sqrtf(1.f - ab_prev - 0.f) * eps2;
       }
       xs[tid] = xv;
-      if (blockIdx.x == 0) {
+      if (writer) {
         if (step < sp.steps) xpp.st1((size_t)(step & 1) * nx + tid, xv);
         else xin.st1(tid, xv);
       }
@@ -1202,62 +1279,87 @@ __global__ __launch_bounds__(512) void dit_sample_bf16_k(const DitSampleBfP sp) 
     __syncthreads();
   };
   const int ntile = H / 16;
+  const int asm_items = (p.M * ntile + 127) / 128 * 128;      // (row, tile) pairs of the assemble loop, whole workgroups of them
   for (int step = 0; step < sp.steps; ++step) {
-    load_x(step);
-    // ---- assemble h = [t_emb + z_emb ; x W_x^T + b_x] + pos: four lanes per (row, 16-column tile), each four columns
-    for (int g = blockIdx.x * 512 + tid; (g >> 2) < ((p.M * ntile + 127) / 128) * 128; g += gridDim.x * 512) {
-      const int item = g >> 2, q = g & 3;
-      const bool valid = item < p.M * ntile;
-      const int m = valid ? item / ntile : 0, ct = valid ? item - m * ntile : 0, c = ct * 16 + 4 * q;
-      const int n = m / p.T1, t = m - n * p.T1;
-      float v[4];
+    for (int g = 0; g < G; ++g) {
+      const DitBfP pg = group_view<MULTI>(p, sp.gr, g);
+      const BfBufs b(pg);
+      const float* ze = sp.ze + (size_t)g * p.N * H;
+      const int wg = MULTI ? rotated_wg(g * (asm_items / 128)) : (int)blockIdx.x;
+      // several groups: only the workgroups that assemble rows of this group (and workgroup 0, which keeps x) compute its x
+      if (!MULTI || wg * 128 < asm_items || blockIdx.x == 0) load_x(g, step, blockIdx.x == 0);
+      // ---- assemble h = [t_emb + z_emb ; x W_x^T + b_x] + pos: four lanes per (row, 16-column tile), each four columns
+      for (int gi = wg * 512 + tid; (gi >> 2) < asm_items; gi += gridDim.x * 512) {
+        const int item = gi >> 2, q = gi & 3;
+        const bool valid = item < p.M * ntile;
+        const int m = valid ? item / ntile : 0, ct = valid ? item - m * ntile : 0, c = ct * 16 + 4 * q;
+        const int n = m / p.T1, t = m - n * p.T1;
+        float v[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if (t == 0) {
-          v[e] = sp.te[(size_t)step * H + c + e] + sp.ze[(size_t)n * H + c + e];
-        } else {
-          const float* xr = xs + ((n % sp.nb) * T + (t - 1)) * A;
-          float a = sp.xb[c + e];
-          for (int k = 0; k < A; ++k) a += xr[k] * sp.xw[(size_t)(c + e) * A + k];
-          v[e] = a;
+        for (int e = 0; e < 4; ++e) {
+          if (t == 0) {
+            v[e] = sp.te[(size_t)step * H + c + e] + ze[(size_t)n * H + c + e];
+          } else {
+            const float* xr = xs + ((n % sp.nb) * T + (t - 1)) * A;
+            float a = sp.xb[c + e];
+            for (int k = 0; k < A; ++k) a += xr[k] * sp.xw[(size_t)(c + e) * A + k];
+            v[e] = a;
+          }
+          v[e] += sp.pos[(size_t)t * H + c + e];
         }
-        v[e] += sp.pos[(size_t)t * H + c + e];
+        write_h(pg, b, m, c, make_float4(v[0], v[1], v[2], v[3]), valid, q == 0, 1, 2);
       }
-      write_h(p, b, m, c, make_float4(v[0], v[1], v[2], v[3]), valid, q == 0, 1, 2);
+      if (MULTI) __syncthreads();                // xs is the next group's from here
     }
     grid_sync(p.bar, nblk, epoch);
-    walk_blocks_bf(p, s, b, epoch, nblk, (unsigned)step * (unsigned)p.depth);
+    walk_blocks_bf<MULTI>(p, sp.gr, s, epoch, nblk, (unsigned)step * (unsigned)p.depth);
     // ---- final layer on the action tokens (fp32, from the fp32 residual stream): one wave per row
-    for (int m = blockIdx.x * 8 + wave; m < p.M; m += gridDim.x * 8) {
-      if (m % p.T1 == 0) continue;
-      float v[16];
-      float sx = 0.f, sxx = 0.f;
-      const int per = H / 64;
+    for (int g = 0; g < G; ++g) {
+      const Act hact(group_f(p.h, g), (size_t)p.M * p.H), epsg(group_f(sp.eps, g), (size_t)p.M * MAXA);
+      const int wg = MULTI ? rotated_wg(g * ((p.M + 7) / 8)) : (int)blockIdx.x;
+      for (int m = wg * 8 + wave; m < p.M; m += gridDim.x * 8) {
+        if (m % p.T1 == 0) continue;
+        float v[16];
+        float sx = 0.f, sxx = 0.f;
+        const int per = H / 64;
 #pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        v[j] = 0.f;
-        if (j < per) { v[j] = hact.ld1((size_t)m * H + j * 64 + lane); sx += v[j]; sxx += v[j] * v[j]; }
-      }
-      sx = wave_sum(sx); sxx = wave_sum(sxx);
-      const float mu = sx / (float)H;
-      const float rs = rsqrtf(fmaxf(sxx / (float)H - mu * mu, 0.f) + p.eps);
-      for (int k = 0; k < A; ++k) {
-        float d = 0.f;
+        for (int j = 0; j < 16; ++j) {
+          v[j] = 0.f;
+          if (j < per) { v[j] = hact.ld1((size_t)m * H + j * 64 + lane); sx += v[j]; sxx += v[j] * v[j]; }
+        }
+        sx = wave_sum(sx); sxx = wave_sum(sxx);
+        const float mu = sx / (float)H;
+        const float rs = rsqrtf(fmaxf(sxx / (float)H - mu * mu, 0.f) + p.eps);
+        for (int k = 0; k < A; ++k) {
+          float d = 0.f;
 #pragma unroll
-        for (int j = 0; j < 16; ++j)
-          if (j < per) d += (v[j] - mu) * rs * sp.fw[(size_t)k * H + j * 64 + lane];
-        d = wave_sum(d);
-        if (lane == 0) epsg.st1((size_t)m * MAXA + k, d + sp.fb[k]);
+          for (int j = 0; j < 16; ++j)
+            if (j < per) d += (v[j] - mu) * rs * sp.fw[(size_t)k * H + j * 64 + lane];
+          d = wave_sum(d);
+          if (lane == 0) epsg.st1((size_t)m * MAXA + k, d + sp.fb[k]);
+        }
       }
     }
     grid_sync(p.bar, nblk, epoch);
   }
-  if (blockIdx.x == 0) load_x(sp.steps);
+  // the last update, written to x: group g's by workgroup g
+  for (int g = 0; g < G; ++g)
+    if ((int)blockIdx.x == g % (int)gridDim.x) load_x(g, sp.steps, true);
 #if defined(DXA_DIT_STAMPS)
   __syncthreads();
   if (blockIdx.x == DXA_DIT_STAMPS && threadIdx.x < 48) g_dit_stamps[threadIdx.x / 8][threadIdx.x % 8] = s.stamp[threadIdx.x / 8][threadIdx.x % 8];
 #endif
-  leave_clean(p, nblk);
+  if (!MULTI) {
+    leave_clean(p, nblk);
+  } else {
+    grid_exit(p.bar, nblk, [&] {                 // as leave_clean, for the groups' tile counters
+      for (int g = 0; g < G; ++g)
+        for (int i = 0; i < ntile; ++i) {
+          __hip_atomic_store(p.bar + sync_ctr((unsigned)g) + SYNC_GROUP_PROJ + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __hip_atomic_store(p.bar + sync_ctr((unsigned)g) + SYNC_GROUP_FC2 + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    });
+  }
 }
 
 // ---- weight packing: one workgroup per (block, matrix, 16 output columns); thread (r = tid / 16, t = tid % 16) walks row nb * 16 + r
@@ -1389,10 +1491,15 @@ extern "C" size_t dxa_dit_sample_bf16_workspace(int M, int H, int I) {
 }
 
 namespace {
-int sample_bf16_launch(const char* who, float* x, const float* z_emb, const float* t_emb, const float* pos, const float* x_w,
-                       const float* x_b, const float* final_w, const float* final_b, const float* coef, int steps, int A,
-                       int nb, int use_cfg, float cfg_scale, const void* const* packed_table, const float* per_kv, int P, int depth, int N,
-                       int T1, int H, int heads, int I, float eps, void* workspace, size_t workspace_bytes, dxa_stream_t stream) {
+// MULTI = false: the single-request kernel (G == 1).  MULTI = true: G request groups — x [G][nb, T, A], z_emb [G][N, H], per_kv
+// [depth][G][N][P][2][H], the workspace G single-request workspaces one after the other; N, nb, T1 are ONE group's.
+template <bool MULTI>
+int sample_bf16_launch_groups(const char* who, float* x, const float* z_emb, const float* t_emb, const float* pos, const float* x_w,
+                              const float* x_b, const float* final_w, const float* final_b, const float* coef, int steps, int A, int G,
+                              int nb, int use_cfg, float cfg_scale, const void* const* packed_table, const float* per_kv, int P,
+                              int depth, int N, int T1, int H, int heads, int I, float eps, void* workspace, size_t workspace_bytes,
+                              dxa_stream_t stream) {
+  DXA_CHECK_ARG(G >= 1 && G <= MAXG, "%s: 1 <= G <= %d request groups a launch (got %d)", who, MAXG, G);
   DXA_CHECK_ARG(P == 0 || (per_kv && P % 64 == 0 && P >= 64 && P <= 256 && T1 <= PER_MAXT),
                 "%s: perceptual attention needs 64 <= P <= 256, P %% 64 == 0, at most %d tokens per sample and the keys / values", who, PER_MAXT);
   DXA_CHECK_ARG(x && z_emb && t_emb && pos && x_w && x_b && final_w && final_b && coef && workspace && packed_table, "%s: null buffer", who);
@@ -1404,7 +1511,8 @@ int sample_bf16_launch(const char* who, float* x, const float* z_emb, const floa
   DXA_CHECK_ARG(H % 64 == 0 && I % 64 == 0 && H == heads * HD && H <= 1024, "%s: needs head width 64, H <= 1024 and H, I %% 64 == 0", who);
   DXA_CHECK_ARG(nb * (T1 - 1) * A <= 512 && nb * (T1 - 1) * A <= MAXM * MAXA, "%s: the sample has too many elements", who);
   size_t off[8];
-  DXA_CHECK_ARG(workspace_bytes >= bf_ws_bytes(M, H, I, off), "%s: workspace too small", who);
+  const size_t group_bytes = bf_ws_bytes(M, H, I, off);
+  DXA_CHECK_ARG(workspace_bytes >= (size_t)G * group_bytes, "%s: workspace too small", who);
   DXA_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) % 256) == 0, "%s: the workspace must be 256-byte aligned", who);
   hipStream_t st = (hipStream_t)stream;
   DitSampleBfP sp;
@@ -1422,11 +1530,17 @@ int sample_bf16_launch(const char* who, float* x, const float* z_emb, const floa
   int grid = I / 16;
   if (3 * H / 16 > grid) grid = 3 * H / 16;
   Residency r;
-  if (int rc = residency(reinterpret_cast<const void*>(&dit_sample_bf16_k), 0, &r)) return rc;
+  if (int rc = residency(reinterpret_cast<const void*>(&dit_sample_bf16_k<false>), 0, &r)) return rc;
   const int resident = r.per_cu * r.cus;
   DXA_CHECK_ARG(resident >= 1, "%s: the kernel does not fit on this device", who);
   if (grid > resident) grid = resident;
-  p.s_fc2 = pick_slices(H / 16, I / 64, grid);
+  p.s_fc2 = pick_slices(H / 16, I / 64, grid);      // from ONE group's shape and the single-request grid: a group's bits are a single launch's
+  if (MULTI) {
+    Residency rg;
+    if (int rc = residency(reinterpret_cast<const void*>(&dit_sample_bf16_k<true>), 0, &rg)) return rc;
+    DXA_CHECK_ARG(rg.per_cu * rg.cus >= 1, "%s: the kernel does not fit on this device", who);
+    if (grid > rg.per_cu * rg.cus) grid = rg.per_cu * rg.cus;
+  }
   // the output projection is NOT K-sliced here: with bf16 operands a workgroup's whole K = 768 slab is 25 KB of weights + 52 KB of
   // activations (the qkv phase's load), while a sliced product pays the partial exchange — store, acknowledge, tile counter, gather by
   // the last arrival — after its MFMAs: 3.90 ms per sample with 4 slices, 3.82 with 2, 3.70 with 1 (profiles/r04_proj_slices.txt)
@@ -1434,7 +1548,8 @@ int sample_bf16_launch(const char* who, float* x, const float* z_emb, const floa
   sp.x = x; sp.ze = z_emb; sp.te = t_emb; sp.pos = pos; sp.xw = x_w; sp.xb = x_b; sp.fw = final_w; sp.fb = final_b; sp.coef = coef;
   sp.steps = steps; sp.A = A; sp.nb = nb; sp.use_cfg = use_cfg; sp.cfg_scale = cfg_scale;
   sp.xpp = extra; sp.eps = extra + 2 * MAXM * MAXA;
-  hipLaunchKernelGGL(dit_sample_bf16_k, dim3(grid), dim3(512), 0, st, sp);
+  sp.gr.G = G; sp.gr.ws_gs = group_bytes; sp.gr.kv_gs = (size_t)N * P * 2 * H;
+  hipLaunchKernelGGL(dit_sample_bf16_k<MULTI>, dim3(grid), dim3(512), 0, st, sp);
   DXA_CHECK_LAUNCH();
   return DXA_OK;
 }
@@ -1444,8 +1559,9 @@ extern "C" int dxa_dit_sample_bf16_fwd(float* x, const float* z_emb, const float
                                        const float* x_b, const float* final_w, const float* final_b, const float* coef, int steps, int A,
                                        int nb, int use_cfg, float cfg_scale, const void* const* packed_table, int depth, int N, int T1,
                                        int H, int heads, int I, float eps, void* workspace, size_t workspace_bytes, dxa_stream_t stream) {
-  return sample_bf16_launch("dxa_dit_sample_bf16_fwd", x, z_emb, t_emb, pos, x_w, x_b, final_w, final_b, coef, steps, A, nb, use_cfg,
-                            cfg_scale, packed_table, nullptr, 0, depth, N, T1, H, heads, I, eps, workspace, workspace_bytes, stream);
+  return sample_bf16_launch_groups<false>("dxa_dit_sample_bf16_fwd", x, z_emb, t_emb, pos, x_w, x_b, final_w, final_b, coef, steps, A, 1, nb,
+                                          use_cfg, cfg_scale, packed_table, nullptr, 0, depth, N, T1, H, heads, I, eps, workspace,
+                                          workspace_bytes, stream);
 }
 
 extern "C" int dxa_dit_sample_bf16_per_fwd(float* x, const float* z_emb, const float* t_emb, const float* pos, const float* x_w,
@@ -1454,6 +1570,36 @@ extern "C" int dxa_dit_sample_bf16_per_fwd(float* x, const float* z_emb, const f
                                            const float* per_kv, int P, int depth, int N, int T1, int H, int heads, int I, float eps,
                                            void* workspace, size_t workspace_bytes, dxa_stream_t stream) {
   DXA_CHECK_ARG(per_kv != nullptr && P > 0, "dxa_dit_sample_bf16_per_fwd: needs the perceptual keys / values");
-  return sample_bf16_launch("dxa_dit_sample_bf16_per_fwd", x, z_emb, t_emb, pos, x_w, x_b, final_w, final_b, coef, steps, A, nb, use_cfg,
-                            cfg_scale, packed_table, per_kv, P, depth, N, T1, H, heads, I, eps, workspace, workspace_bytes, stream);
+  return sample_bf16_launch_groups<false>("dxa_dit_sample_bf16_per_fwd", x, z_emb, t_emb, pos, x_w, x_b, final_w, final_b, coef, steps, A, 1,
+                                          nb, use_cfg, cfg_scale, packed_table, per_kv, P, depth, N, T1, H, heads, I, eps, workspace,
+                                          workspace_bytes, stream);
+}
+
+// ---- G requests in one launch (request groups, above).  G single-request workspaces: 1.6 MB a group for DiT-B, 2.3 MB for DiT-L, so
+// the MAXG = 16 groups the sync block has tile counters for take 26 / 37 MB.
+extern "C" size_t dxa_dit_sample_bf16_batched_workspace(int G, int M, int H, int I) {
+  if (G < 1 || G > MAXG) return 0;
+  return (size_t)G * dxa_dit_sample_bf16_workspace(M, H, I);
+}
+
+extern "C" int dxa_dit_sample_bf16_batched_fwd(float* x, const float* z_emb, const float* t_emb, const float* pos, const float* x_w,
+                                               const float* x_b, const float* final_w, const float* final_b, const float* coef, int steps,
+                                               int A, int G, int nb, int use_cfg, float cfg_scale, const void* const* packed_table,
+                                               int depth, int N, int T1, int H, int heads, int I, float eps, void* workspace,
+                                               size_t workspace_bytes, dxa_stream_t stream) {
+  return sample_bf16_launch_groups<true>("dxa_dit_sample_bf16_batched_fwd", x, z_emb, t_emb, pos, x_w, x_b, final_w, final_b, coef, steps, A,
+                                         G, nb, use_cfg, cfg_scale, packed_table, nullptr, 0, depth, N, T1, H, heads, I, eps, workspace,
+                                         workspace_bytes, stream);
+}
+
+extern "C" int dxa_dit_sample_bf16_per_batched_fwd(float* x, const float* z_emb, const float* t_emb, const float* pos, const float* x_w,
+                                                   const float* x_b, const float* final_w, const float* final_b, const float* coef,
+                                                   int steps, int A, int G, int nb, int use_cfg, float cfg_scale,
+                                                   const void* const* packed_table, const float* per_kv, int P, int depth, int N, int T1,
+                                                   int H, int heads, int I, float eps, void* workspace, size_t workspace_bytes,
+                                                   dxa_stream_t stream) {
+  DXA_CHECK_ARG(per_kv != nullptr && P > 0, "dxa_dit_sample_bf16_per_batched_fwd: needs the perceptual keys / values");
+  return sample_bf16_launch_groups<true>("dxa_dit_sample_bf16_per_batched_fwd", x, z_emb, t_emb, pos, x_w, x_b, final_w, final_b, coef, steps,
+                                         A, G, nb, use_cfg, cfg_scale, packed_table, per_kv, P, depth, N, T1, H, heads, I, eps, workspace,
+                                         workspace_bytes, stream);
 }

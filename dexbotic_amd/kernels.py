@@ -2063,6 +2063,53 @@ def dit_sample_bf16_fwd(x: torch.Tensor, z_emb: torch.Tensor, t_emb: torch.Tenso
     return x
 
 
+DIT_SAMPLE_MAX_GROUPS = 16          # csrc/dit_fused.hip MAXG
+
+
+def dit_sample_bf16_groups_supported(G: int, Ng: int, T1: int, H: int, heads: int, I: int, P: int = 0) -> bool:
+    """G requests of ``Ng`` samples each (2 with guidance: conditional, unconditional) in one launch of the bf16 sampler"""
+    return 1 <= G <= DIT_SAMPLE_MAX_GROUPS and dit_sample_bf16_supported(Ng, T1, H, heads, I, P)
+
+
+def dit_sample_bf16_batched_fwd(x: torch.Tensor, z_emb: torch.Tensor, t_emb: torch.Tensor, pos: torch.Tensor, x_w: torch.Tensor,
+                                x_b: torch.Tensor, final_w: torch.Tensor, final_b: torch.Tensor, coef: torch.Tensor, use_cfg: bool,
+                                cfg_scale: float, packed_table: torch.Tensor, depth: int, T1: int, H: int, heads: int, I: int,
+                                eps: float, per_kv: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dit_sample_bf16_fwd for G requests in ONE persistent launch (dxa_dit_sample_bf16_batched_fwd / _per_batched_fwd): x [G, T1-1, A]
+    fp32 is updated in place, z_emb [G, Ng, H] (Ng = 2 with guidance: the request's conditional row, then its unconditional one),
+    ``per_kv`` [depth, G, Ng, P, 2, H].  Request g of the result has the bits dit_sample_bf16_fwd(x[g:g+1], z_emb[g], ...,
+    per_kv=per_kv[:, g]) gives."""
+    steps, A = t_emb.shape[0], x.shape[-1]
+    for t in (x, z_emb, t_emb, pos, x_w, x_b, final_w, final_b, coef):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda
+    assert x.dim() == 3 and z_emb.dim() == 3
+    G, Ng = x.shape[0], z_emb.shape[1]
+    if z_emb.shape[0] != G:
+        raise L.DxaError(f"dit_sample_bf16_batched_fwd: x holds {G} requests but z_emb {z_emb.shape[0]}")
+    assert Ng == (2 if use_cfg else 1)
+    assert x.shape == (G, T1 - 1, A) and z_emb.shape == (G, Ng, H) and t_emb.shape == (steps, H) and coef.shape == (steps, 4)
+    assert pos.shape == (T1, H) and x_w.shape == (H, A) and final_w.shape == (A, H)
+    assert packed_table.dtype == torch.int64 and packed_table.numel() == depth * (10 if per_kv is None else 16) and packed_table.is_cuda
+    P_ = 0 if per_kv is None else per_kv.shape[3]
+    if not dit_sample_bf16_groups_supported(G, Ng, T1, H, heads, I, P_):
+        raise L.DxaError(f"dit_sample_bf16_batched_fwd: unsupported shape (G={G}, Ng={Ng}, T1={T1}, H={H}, heads={heads}, I={I}, P={P_})")
+    nbytes = lib.dxa_dit_sample_bf16_batched_workspace(G, Ng * T1, H, I)
+    ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    if per_kv is not None:
+        assert per_kv.dtype == torch.float32 and per_kv.is_contiguous() and per_kv.shape == (depth, G, Ng, P_, 2, H)
+        L.check(lib.dxa_dit_sample_bf16_per_batched_fwd(_ptr(x), _ptr(z_emb), _ptr(t_emb), _ptr(pos), _ptr(x_w), _ptr(x_b),
+                                                        _ptr(final_w), _ptr(final_b), _ptr(coef), steps, A, G, 1, int(use_cfg),
+                                                        float(cfg_scale), _ptr(packed_table), _ptr(per_kv), P_, depth, Ng, T1, H,
+                                                        heads, I, float(eps), _ptr(ws), nbytes, _stream()),
+                "dxa_dit_sample_bf16_per_batched_fwd")
+        return x
+    L.check(lib.dxa_dit_sample_bf16_batched_fwd(_ptr(x), _ptr(z_emb), _ptr(t_emb), _ptr(pos), _ptr(x_w), _ptr(x_b), _ptr(final_w),
+                                                _ptr(final_b), _ptr(coef), steps, A, G, 1, int(use_cfg), float(cfg_scale),
+                                                _ptr(packed_table), depth, Ng, T1, H, heads, I, float(eps), _ptr(ws), nbytes,
+                                                _stream()), "dxa_dit_sample_bf16_batched_fwd")
+    return x
+
+
 def dit_blocks_timed_out(stream: Optional["torch.cuda.Stream"] = None) -> bool:
     """True if a fused DiT launch on `stream` (default: the current one) gave up at a device-wide barrier since the last
     call (its result is garbage and the request must be re-run unfused).  Synchronises the stream."""

@@ -329,11 +329,27 @@ class DiT(nn.Module):
         return tabs[key]
 
     # ---- the whole sampler in one launch ---------------------------------------------------------------------------
-    def fused_sampler_ok(self, N: int, T1: int, P: int = 0) -> bool:
-        """``P``: perceptual keys per sample (MemVLA's DiT: only the bf16 sampler has the perceptual-attention phases)"""
+    # requests per launch the batched sampler is routed to (scripts/dit_batch_bench.py, profiles/dit_sampler_batched.txt): the G at
+    # which ONE launch of G request groups measured faster than both G single launches and the per-step path at batch G.  DiT-B:
+    # every G from 2 to the launch's 16 (5.2 ms against 7.4 / 25.1 at G = 2, 23.9 against 58.7 / 29.5 at G = 16).
+    BATCHED_GROUPS = range(2, 17)
+    # With perceptual attention (MemVLA's DiT-L) the launch beat G single launches from G = 2 on (19.3 ms against 28.6), but the
+    # per-step path at batch G does not exist to be measured before MemVLA batches episodes: not routed, as before.
+    BATCHED_GROUPS_PER = range(0)
+
+    def fused_sampler_ok(self, N: int, T1: int, P: int = 0, nb: int = 1) -> bool:
+        """``P``: perceptual keys per sample (MemVLA's DiT: only the bf16 sampler has the perceptual-attention phases).
+        ``nb`` > 1: N = nb requests (2 nb rows with guidance) — one launch of nb request groups, bf16 serving only."""
         from .... import kernels as K
         if self.in_channels > 8 or os.environ.get("DXA_DIT_SAMPLER", "1") == "0":
             return False
+        if nb > 1:
+            return (N % nb == 0 and nb in (self.BATCHED_GROUPS_PER if self.use_per_attn else self.BATCHED_GROUPS) and
+                    (P > 0) == bool(self.use_per_attn) and not torch.is_grad_enabled() and
+                    os.environ.get("DXA_DIT_FUSED", "1") != "0" and getattr(self, "allow_fused", True) and
+                    self.store.device.type == "cuda" and self.store.compute_dtype == torch.bfloat16 and
+                    os.environ.get("DXA_DIT_BF16", "1") != "0" and
+                    K.dit_sample_bf16_groups_supported(nb, N // nb, T1, self.hidden_size, self.num_heads, self.mlp_hidden, P))
         if self.use_per_attn:
             return (P > 0 and not torch.is_grad_enabled() and os.environ.get("DXA_DIT_FUSED", "1") != "0" and
                     getattr(self, "allow_fused", True) and self.store.device.type == "cuda" and
@@ -365,7 +381,9 @@ class DiT(nn.Module):
         launch (csrc/dit_fused.hip dit_sample_fused_k): noise [nb, T, A], z [N, 1, token] (N = 2 nb with guidance: [cond; uncond])
         -> the sample [nb, T, A].  What does not depend on x is prepared by three small launches: the z embedding and the
         timestep embeddings of the whole schedule.  ``per_token`` [N, P, per_token_size] (MemVLA): the perceptual keys / values of
-        every block are projected once (precompute_per_kv) and the launch attends them in its per-attention phases."""
+        every block are projected once (precompute_per_kv) and the launch attends them in its per-attention phases.
+        nb > 1 (fused_sampler_ok(..., nb=nb)): the nb requests go through ONE launch as nb request groups (csrc/dit_fused.hip);
+        request b's sample has the bits a call with noise[b:b+1] and its own rows of z gives."""
         from .... import kernels as K
         st = Fp32View(self.store)
         p, h = self.p, self.hidden_size
@@ -373,6 +391,8 @@ class DiT(nn.Module):
         nb, T, A = noise.shape
         anchor = self._anchor()
         tv, coef = self._sampler_tables(diffusion, noise.device)
+        if nb > 1:
+            return self._ddim_sample_groups(noise, z, tv, coef, cfg_scale, per_token)
         ze = Fn.LinearFn.apply(z.reshape(N, self.token_size).float().contiguous(), anchor, st, p + "z_embedder.linear.weight",
                                p + "z_embedder.linear.bias", L.ACT_NONE, None)
         tf = K.timestep_embedding(tv, self._timestep_freqs(noise.device))
@@ -403,6 +423,37 @@ class DiT(nn.Module):
                          st.w(p + "final_layer.linear.weight"), st.w(p + "final_layer.linear.bias"), coef, nb,
                          cfg_scale is not None, float(cfg_scale or 0.0), self._weight_table(st), self.depth, T + 1, h,
                          self.num_heads, self.mlp_hidden, 1e-6)
+        return x
+
+    def _ddim_sample_groups(self, noise, z, tv, coef, cfg_scale, per_token):
+        """ddim_sample_fused for nb > 1 requests: the caller's [cond x nb ; uncond x nb] rows of z (and per_token) regrouped request
+        by request — [cond_b ; uncond_b] is what a single request hands the sampler — and one launch for all of them.  The z
+        embedding runs per request on the two rows a single request embeds, so it cannot depend on the batch."""
+        from .... import kernels as K
+        st = Fp32View(self.store)
+        p, h = self.p, self.hidden_size
+        nb, T, A = noise.shape
+        Ng = z.shape[0] // nb
+        anchor = self._anchor()
+        zg = z.reshape(Ng, nb, self.token_size).transpose(0, 1).float().contiguous()             # [nb, Ng, token]
+        ze = torch.stack([Fn.LinearFn.apply(zg[b], anchor, st, p + "z_embedder.linear.weight", p + "z_embedder.linear.bias",
+                                            L.ACT_NONE, None) for b in range(nb)], 0)
+        tf = K.timestep_embedding(tv, self._timestep_freqs(noise.device))
+        te = Fn.MlpFn.apply(tf, anchor, st, p + "t_embedder.mlp.0.weight", p + "t_embedder.mlp.0.bias",
+                            p + "t_embedder.mlp.2.weight", p + "t_embedder.mlp.2.bias", L.ACT_SILU)
+        x = noise.float().contiguous().clone()
+        per_kv = None
+        if self.use_per_attn:
+            assert per_token is not None and per_token.shape[0] == Ng * nb
+            kv = self.precompute_per_kv(per_token, packed=True)                                  # [depth, Ng nb, P, 2, h]
+            per_kv = kv.view(self.depth, Ng, nb, *kv.shape[2:]).transpose(1, 2).contiguous()
+        self.used_fused = True
+        self.store.wait_pending()                  # the kernel reads the masters through raw pointers
+        K.dit_sample_bf16_batched_fwd(x, ze.contiguous(), te.contiguous(), st.w(p + "positional_embedding").reshape(T + 1, h),
+                                      st.w(p + "x_embedder.linear.weight"), st.w(p + "x_embedder.linear.bias"),
+                                      st.w(p + "final_layer.linear.weight"), st.w(p + "final_layer.linear.bias"), coef,
+                                      cfg_scale is not None, float(cfg_scale or 0.0), self._packed_table(st), self.depth, T + 1, h,
+                                      self.num_heads, self.mlp_hidden, 1e-6, per_kv=per_kv)
         return x
 
     def forward_with_cfg(self, x, t, z, cfg_scale=None, per_token=None, per_kv=None):

@@ -129,7 +129,7 @@ class CogACTForCausalLM(DexboticForCausalLM, ActionOutputForCausalLM):
             sample_fn = head.net.forward
         N_rows = noise.shape[0]
         if not return_trajectory and hasattr(head.net, "fused_sampler_ok") and \
-                head.net.fused_sampler_ok(N_rows, self.config.chunk_size + 1):
+                head.net.fused_sampler_ok(N_rows, self.config.chunk_size + 1, nb=B):
             # all DDIM steps in ONE persistent launch (embedders, blocks, final layer, guidance and update inside)
             return head.net.ddim_sample_fused(noise[:B], model_kwargs["z"], head.ddim_diffusion,
                                               cfg_scale if cfg_scale > 1.0 else None), None
@@ -147,10 +147,28 @@ class CogACTForCausalLM(DexboticForCausalLM, ActionOutputForCausalLM):
         the replay removes the launch gaps: p50 19.76 -> 19.46 ms (profiles/r04_infer_eager_vs_graph.txt; rounds 1-3 measured it
         level or slower and kept it off).  ``inference_args["use_graph"]=False`` or env DXA_INFER_GRAPH=0: eager launches.  At most
         ``MAX_INFER_GRAPHS`` request shapes keep a graph (least recently used dropped): instruction lengths vary in serving."""
+        host, samples, traj = self._infer_samples(input_ids, image_tensor, inference_args, kwargs.get("noise"),
+                                                  bool(kwargs.get("return_trajectory")))
+        actions = self._denorm(host[0], inference_args.get("action_norms")).tolist()
+        if traj is not None:
+            return actions, samples, traj
+        return actions
+
+    @torch.no_grad()
+    def inference_action_batch(self, input_ids, image_tensor, inference_args={}, noise=None) -> list:
+        """inference_action for B requests at once (input_ids [B, S], image_tensor [B, ...], ``noise`` [B, chunk, action_dim]):
+        the list of B de-normalised [chunk][action_dim] chunks.  One prefill at batch B; a model served in bfloat16 then samples all
+        B chunks in ONE launch of the persistent DiT sampler (B request groups, csrc/dit_fused.hip — chunk b has the bits that
+        sampler gives for row b's cognition feature alone), any other B or dtype on the per-step path.  Graph capture per
+        (shape, B), watchdog and fallback as inference_action."""
+        host, _, _ = self._infer_samples(input_ids, image_tensor, inference_args, noise, False)
+        norms = inference_args.get("action_norms")
+        return [self._denorm(host[b], norms).tolist() for b in range(host.shape[0])]
+
+    def _infer_samples(self, input_ids, image_tensor, inference_args, noise, return_traj):
+        """the request of inference_action / inference_action_batch: (samples on the host [B, chunk, action_dim], samples, trajectory)"""
         cfg_scale = inference_args.get("cfg_scale", 1.5)
         num_ddim_steps = inference_args.get("num_ddim_steps", 10)
-        action_norms = inference_args.get("action_norms")
-        return_traj = bool(kwargs.get("return_trajectory"))
         head = self.model.action_head
         if head.ddim_diffusion is None or head.ddim_diffusion.num_timesteps != num_ddim_steps:
             head.create_ddim(ddim_step=num_ddim_steps)
@@ -161,7 +179,6 @@ class CogACTForCausalLM(DexboticForCausalLM, ActionOutputForCausalLM):
                                      getattr(self.config, "tokenizer_model_max_length", None),
                                      getattr(self.config, "tokenizer_padding_side", "right"))
         B, S = plan.plan.shape
-        noise = kwargs.get("noise")
         if noise is None:
             noise = torch.randn(B, self.config.chunk_size, self.config.action_dim, device=dev, dtype=torch.float32)
         noise = noise.to(device=dev, dtype=torch.float32)
@@ -183,7 +200,7 @@ class CogACTForCausalLM(DexboticForCausalLM, ActionOutputForCausalLM):
             plan_t = plan.dev(dev)["plan"]
             samples, traj = self._sample_actions(images, plan_t, B, S, noise, float(cfg_scale), int(num_ddim_steps),
                                                  return_traj)
-        host = samples[0].cpu().numpy()
+        host = samples[:B].cpu().numpy()
         if dev.type == "cuda" and head.net.used_fused and K.dit_blocks_timed_out(graph_stream):
             # the persistent DiT kernel needs all its workgroups resident at once; something else held CUs for seconds
             # (another process on this GPU): this request is redone on the block-by-block kernels, which this process
@@ -192,11 +209,8 @@ class CogACTForCausalLM(DexboticForCausalLM, ActionOutputForCausalLM):
             self.__dict__.pop("_infer_graphs", None)      # every captured graph may hold the persistent kernel: re-capture
             samples, traj = self._sample_actions(images, plan.dev(dev)["plan"], B, S, noise, float(cfg_scale),
                                                  int(num_ddim_steps), return_traj)
-            host = samples[0].cpu().numpy()
-        actions = self._denorm(host, action_norms).tolist()
-        if traj is not None:
-            return actions, samples, traj
-        return actions
+            host = samples[:B].cpu().numpy()
+        return host, samples, traj
 
     MAX_INFER_GRAPHS = 8
 

@@ -5,7 +5,8 @@ dexbotic/exp/cogact_exp.py:146-177 (_get_response), dexbotic/client.py:33-61 (th
 Only PNG decoding and prompt formatting stay on the host; the frames go to the MI355X as uint8 and are padded,
 resized, cropped and normalised there (DexboticForCausalLM.process_images -> dxa_image_preprocess).
 
-``InferenceServer`` speaks the CogACT format (one sample, ``inference_action(ids, pix, args)``); ``FlowInferenceServer`` the batched
+``InferenceServer`` speaks the CogACT format (one sample, ``inference_action(ids, pix, args)``; with the optional ``batch_size``
+field several, ``inference_action_batch``); ``FlowInferenceServer`` the batched
 format of the flow-matching policies pi0 / pi0.5 / DM0 (``states`` and ``batch_size`` beside the frames, absent views masked)."""
 from __future__ import annotations
 
@@ -46,8 +47,12 @@ class InferenceServer:
         conv.append_message(conv.roles[1], self.assistant_stub)
         return conv.get_prompt()
 
-    def get_response(self, text: str, images: List) -> list:
-        """images: file-like objects / paths holding PNG (or anything PIL opens).  cogact_exp.py:146-177"""
+    def get_response(self, text, images: List, batch_size: Optional[int] = None) -> list:
+        """images: file-like objects / paths holding PNG (or anything PIL opens).  cogact_exp.py:146-177.
+        ``batch_size`` > 1: the request holds that many samples — images sample-major (as FlowInferenceServer), ``text`` one string
+        for all of them or a list (or JSON list) of ``batch_size`` strings — and the answer is [batch_size][chunk][action_dim]."""
+        if batch_size is not None and int(batch_size) > 1:
+            return self._get_response_batch(text, images, int(batch_size))
         from PIL import Image
         t0 = time.monotonic()
         stages = self.stage_ms if self.stage_ms is not None else None      # tuning: per-stage times (a device sync per stage)
@@ -78,6 +83,42 @@ class InferenceServer:
             self.log(f"process_frame: {len(frames)} view(s), {self.last_ms:.1f} ms")
         return out
 
+    def _get_response_batch(self, text, images: List, B: int) -> list:
+        """B samples in one request: one process_images call for all frames and inference_action_batch per prompt length (the
+        prefill takes no padding mask: samples whose prompts tokenise to the same length share a batch — always, with one text)"""
+        import json
+        from PIL import Image
+        t0 = time.monotonic()
+        if isinstance(text, str) and text.lstrip().startswith("["):
+            try:
+                parsed = json.loads(text)
+                text = parsed if isinstance(parsed, list) else text
+            except ValueError:
+                pass
+        texts = [text] * B if isinstance(text, str) else list(text)
+        if len(texts) != B or not all(isinstance(t, str) for t in texts):
+            raise ValueError(f"process_frame: batch_size {B} needs one text or a list of {B} strings, got {len(texts)} entries")
+        if len(images) == 0 or len(images) % B != 0:
+            raise ValueError(f"process_frame: {len(images)} image(s) do not divide into batch_size {B} samples")
+        views = len(images) // B
+        frames = [Image.open(f).convert("RGB") for f in images]
+        pix = self.model.process_images(frames).to(dtype=self.model.dtype)
+        if views > 1:
+            pix = pix.view(B, views, *pix.shape[1:])
+        ids = [tokenizer_image_token(self.build_prompt(t), self.tokenizer, IMAGE_TOKEN_INDEX, return_tensors="pt") for t in texts]
+        out = [None] * B
+        with torch.no_grad():
+            for n in sorted({int(i.numel()) for i in ids}):
+                rows = [b for b in range(B) if int(ids[b].numel()) == n]
+                chunks = self.model.inference_action_batch(torch.stack([ids[b] for b in rows], 0).to(self.model.device),
+                                                           pix[rows] if len(rows) < B else pix, dict(self.inference_args))
+                for b, c in zip(rows, chunks):
+                    out[b] = c.tolist() if hasattr(c, "tolist") else c
+        self.last_ms = 1e3 * (time.monotonic() - t0)
+        if self.log:
+            self.log(f"process_frame: {B} sample(s) x {views} view(s), {self.last_ms:.1f} ms")
+        return out
+
     def inference_single(self, image_path, prompt: str) -> list:
         """the exp scripts' ``--task inference_single`` (playground/benchmarks/libero/libero_cogact.py:70-72):
         ``_get_response(prompt, [image_path])`` on one image file (or a list of view files)"""
@@ -91,7 +132,8 @@ class InferenceServer:
 
         def process_frame():
             files = [io.BytesIO(f.read()) for f in request.files.getlist("image")]
-            return jsonify({"response": self.get_response(request.form.get("text"), files)})
+            bs = request.form.get("batch_size")
+            return jsonify({"response": self.get_response(request.form.get("text"), files, int(bs) if bs else None)})
 
         app.add_url_rule("/process_frame", "process_frame", process_frame, methods=["POST"])
         return app

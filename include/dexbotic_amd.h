@@ -986,6 +986,26 @@ int dxa_dit_sample_bf16_per_fwd(float* x, const float* z_emb, const float* t_emb
                                 float cfg_scale, const void* const* packed_table, const float* per_kv, int P, int depth, int N, int T1,
                                 int H, int heads, int I, float eps, void* workspace, size_t workspace_bytes, dxa_stream_t stream);
 
+/* G requests in ONE launch of the bf16 sampler.  A request GROUP is the rows of one request exactly as dxa_dit_sample_bf16_fwd lays
+ * them out (N = nb, or 2 nb with guidance: conditional rows, then unconditional; N*T1 <= 48 PER GROUP); the launch walks the groups
+ * inside every phase, between the same device-wide barriers, so G requests cost the barriers and the weight stream of one.  Group g
+ * of the result has the bits dxa_dit_sample_bf16_fwd / _per_fwd produces on that group's inputs alone.
+ *   x [G][nb, T1-1, A] in/out, z_emb [G][N, H], per_kv [depth][G][N][P][2][H]; t_emb, pos, coef and all weights are shared.
+ *   1 <= G <= 16 (DXA_ERR_INVALID_ARG outside; the workspace query then returns 0); the workspace is
+ *   dxa_dit_sample_bf16_batched_workspace(G, N*T1, H, I) = G * dxa_dit_sample_bf16_workspace(N*T1, H, I) bytes, 256-byte aligned.
+ *   Everything else — limits, co-residency contract, watchdog (dxa_dit_blocks_status) — as dxa_dit_sample_bf16_fwd. */
+size_t dxa_dit_sample_bf16_batched_workspace(int G, int M, int H, int I);
+int dxa_dit_sample_bf16_batched_fwd(float* x, const float* z_emb, const float* t_emb, const float* pos, const float* x_w,
+                                    const float* x_b, const float* final_w, const float* final_b, const float* coef, int steps, int A,
+                                    int G, int nb, int use_cfg, float cfg_scale, const void* const* packed_table, int depth, int N,
+                                    int T1, int H, int heads, int I, float eps, void* workspace, size_t workspace_bytes,
+                                    dxa_stream_t stream);
+int dxa_dit_sample_bf16_per_batched_fwd(float* x, const float* z_emb, const float* t_emb, const float* pos, const float* x_w,
+                                        const float* x_b, const float* final_w, const float* final_b, const float* coef, int steps,
+                                        int A, int G, int nb, int use_cfg, float cfg_scale, const void* const* packed_table,
+                                        const float* per_kv, int P, int depth, int N, int T1, int H, int heads, int I, float eps,
+                                        void* workspace, size_t workspace_bytes, dxa_stream_t stream);
+
 /* ---- KV-cached decode step in one persistent launch (csrc/decode_fused.hip) -------------------------------------------------
  * ONE new token of ONE sequence through every decoder layer and the final RMSNorm — the use_cache=True single-token pass of HF
  * Qwen2Model that GenerationMixin.generate drives for the discrete-action policies (dexbotic/model/discrete_vla/
