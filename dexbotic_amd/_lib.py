@@ -91,6 +91,24 @@ class AttnPlanInfo(C.Structure):
                 ("vec", _i32), ("workspace", C.c_uint64)]
 
 
+NORM_ENTRIES = ("rmsnorm_fwd", "rmsnorm_bwd", "layernorm_fwd", "layernorm_bwd", "add_layernorm_fwd", "add_layernorm_bwd", "colsum",
+                "downsample_layernorm_fwd", "downsample_layernorm_bwd", "adarms_fwd", "adarms_bwd", "gated_residual_fwd",
+                "gated_residual_bwd")     # enum dxa_norm_entry, in order
+
+
+class NormDesc(C.Structure):
+    _fields_ = [("entry", _i32), ("dtype", _i32), ("w_dtype", _i32), ("accumulate", _i32), ("rows", _i64), ("cols", _i64),
+                ("G", _i64), ("rows_per_sample", _i64), ("ld", _i64), ("gate_ld", _i64), ("dgate_ld", _i64),
+                ("partial_bytes", _sz)] + [(n, _vp) for n in ("x", "x2", "w", "b", "y", "dy", "dx", "residual", "partial", "mean",
+                                                             "rstd", "gate", "mod", "aux", "dgate", "dmod")] + \
+               [("have_counters", _i32), ("capturing", _i32)]
+
+
+class NormPlanInfo(C.Structure):
+    _fields_ = [("kernel", C.c_char_p), ("kernel2", C.c_char_p), ("mode", C.c_char_p), ("vec", _i32), ("grid", _i32 * 3),
+                ("block", _i32), ("lds", _i32), ("nsplit", _i32), ("trips", _i64)]
+
+
 class AdamWDesc(C.Structure):
     _fields_ = [
         ("p", _vp), ("g", _vp), ("m", _vp), ("v", _vp), ("shadow", _vp),
@@ -173,6 +191,8 @@ SIGNATURES = {
     "dxa_gated_residual_bwd": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _sz, _i64, _i64, _i64, _int, _vp]),
     "dxa_adarms_bwd_groups": (_int, [_i64]),
     "dxa_colsum": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _int, _vp, _sz, _vp]),
+    "dxa_norm_plan": (_int, [C.POINTER(NormDesc), C.POINTER(NormPlanInfo)]),
+    "dxa_norm_kernel_name": (C.c_char_p, [_int]),
     "dxa_rope_split": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _vp]),
     "dxa_rope_merge": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _vp]),
     "dxa_rope_split_at": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _int, _int, _vp]),

@@ -366,9 +366,6 @@ __global__ __launch_bounds__(256) void colsum_fused_k(const T* __restrict__ x, i
   out[c] = accumulate ? out[c] + s : s;
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
-
 // Fast backward (cols % 4 == 0, cols <= 4096): a wave owns whole rows, keeps its weight/bias-gradient partial
 // sums in REGISTERS (16 x 4 columns per lane) over all its rows; no LDS, no barriers, no serialisation between the
 // waves of a workgroup until the very end, where the four waves fold into ONE partial row; x/dy are read twice
@@ -721,41 +718,11 @@ __global__ __launch_bounds__(NS * 128, (NIT <= 4 ? NS : 2)) void rmsnorm_bwd_spl
 
 constexpr int NORM_BWD_MAX_BLOCKS = 512;
 constexpr int64_t NORM_BWD_FAST_MAX_COLS = 4096;
-
-template <bool LN>
-bool launch_norm_bwd_fast(const void* dy, const void* x, const void* w, const float* mean, const float* rstd, void* dx,
-                          const void* res, float* partial, int64_t rows, int64_t cols, int dtype, int w_dtype, bool vec_ok, hipStream_t st) {
-  int64_t g = (rows + 3) / 4;
-  if (g > NORM_BWD_MAX_BLOCKS) g = NORM_BWD_MAX_BLOCKS;
-  dim3 grid((unsigned)g);
-  // the row split between two waves (A/B against the one-wave-per-row kernels below: profiles/r05_norm_bwd_split.txt)
-  if (!LN && vec_ok && dtype == DXA_BF16 && cols % 16 == 0 && cols <= 8192 && (cols * 4) % 16 == 0 &&
-      (!partial || (reinterpret_cast<uintptr_t>(partial) & 15) == 0)) {
-    // four rows per workgroup pass (512 threads at 128 registers: a dozen spilled dwords); the three-row form (384 threads, 168
-    // registers, no spill) against it: profiles/r05_norm_bwd_split.txt
-#define LAUNCH_SPLIT(TW_, NIT_, NS_) hipLaunchKernelGGL((rmsnorm_bwd_split_k<TW_, NIT_, NS_>), grid, dim3(NS_ * 128), 0, st, (const bf16_t*)dy, (const bf16_t*)x, (const TW_*)w, rstd, (bf16_t*)dx, (const bf16_t*)res, partial, rows, cols)
-    if (w_dtype == DXA_BF16) { if (cols > 4096) LAUNCH_SPLIT(bf16_t, 8, 4); else LAUNCH_SPLIT(bf16_t, 4, 4); }
-    else { if (cols > 4096) LAUNCH_SPLIT(float, 8, 4); else LAUNCH_SPLIT(float, 4, 4); }
-#undef LAUNCH_SPLIT
-    return true;
-  }
-  if (!vec_ok || cols % 4 != 0 || cols > NORM_BWD_FAST_MAX_COLS) return false;
-  if (dtype == DXA_BF16 && cols % 8 == 0 && !LN) {   // RMSNorm: 16-byte accesses, one read of x and dy (LayerNorm's second
-                                                     // set of partial sums costs it the registers: measured 27 vs 24 us)
-    if (w_dtype == DXA_BF16)
-      hipLaunchKernelGGL((norm_bwd_fast8_k<bf16_t, LN>), grid, dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, mean, rstd, (bf16_t*)dx, (const bf16_t*)res, partial, rows, cols);
-    else
-      hipLaunchKernelGGL((norm_bwd_fast8_k<float, LN>), grid, dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, (const float*)w, mean, rstd, (bf16_t*)dx, (const bf16_t*)res, partial, rows, cols);
-    return true;
-  }
-  if (dtype == DXA_BF16 && w_dtype == DXA_BF16)
-    hipLaunchKernelGGL((norm_bwd_fast_k<bf16_t, bf16_t, LN>), grid, dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, mean, rstd, (bf16_t*)dx, (const bf16_t*)res, partial, rows, cols);
-  else if (dtype == DXA_BF16)
-    hipLaunchKernelGGL((norm_bwd_fast_k<bf16_t, float, LN>), grid, dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, (const float*)w, mean, rstd, (bf16_t*)dx, (const bf16_t*)res, partial, rows, cols);
-  else
-    hipLaunchKernelGGL((norm_bwd_fast_k<float, float, LN>), grid, dim3(256), 0, st, (const float*)dy, (const float*)x, (const float*)w, mean, rstd, (float*)dx, (const float*)res, partial, rows, cols);
-  return true;
-}
+constexpr size_t DS_LN_MAX_LDS = 60 * 1024;      // partial sums of rows up to 7680 columns stay in LDS (default 64 KB ceiling)
+constexpr int ADARMS_BWD_MAX_GROUPS = 128;
+// arrival counters of colsum_fused_k: COLSUM_CNT ints per (device, stream), zeroed once (the kernel leaves them zeroed),
+// allocated on first use; under capture before they exist the counters are null and the two-launch form, which needs none, runs
+constexpr int COLSUM_CNT = 4096;
 
 }  // namespace
 
@@ -768,12 +735,406 @@ extern "C" int dxa_norm_bwd_blocks(int64_t rows) {
   return (int)g;
 }
 
+extern "C" int dxa_adarms_bwd_groups(int64_t rows_per_sample) {
+  int64_t g = (rows_per_sample + 3) / 4;
+  if (g < 1) g = 1;
+  if (g > ADARMS_BWD_MAX_GROUPS) g = ADARMS_BWD_MAX_GROUPS;
+  return (int)g;
+}
+
 static int check_norm_dtypes(int dtype, int w_dtype, const char* who) {
   if (!(dtype == DXA_F32 || dtype == DXA_BF16) || !(w_dtype == DXA_F32 || w_dtype == DXA_BF16) ||
       (dtype == DXA_F32 && w_dtype == DXA_BF16)) {
     dxa_set_error("%s: unsupported dtype combination (%d,%d)", who, dtype, w_dtype);
     return DXA_ERR_UNSUPPORTED;
   }
+  return DXA_OK;
+}
+
+// ---- The route of a norm call: every choice between kernel instantiations of the entry points below is made in norm_plan, from
+// the call's sizes, dtypes, optional operands and pointer alignments alone (nothing is dereferenced and HIP is not touched, so
+// dxa_norm_plan answers without a GPU).  The launchers launch what the plan names and hold no condition of their own.
+// Within a group of instantiations the index is: + 2 * tw + (scalar) for the (T, TW) pairs tw = (bf16, bf16), (bf16, float),
+// (float, float) and the 4-/1-wide (ds: 16-byte/1-wide) forms; + 2 * av + gated for the adarms vector widths av (below).
+#define NORM_KERNELS(X)                                                                                                              \
+  X(K_RMS_FWD_FAST, "rmsnorm_fwd_fast_k<bf16>") X(K_RMS_FWD_FAST_F, "rmsnorm_fwd_fast_k<float>")                                     \
+  X(K_RMS_FWD, "rmsnorm_fwd_k<bf16,bf16,4>") X(K_RMS_FWD_1, "rmsnorm_fwd_k<bf16,bf16,1>")                                           \
+  X(K_RMS_FWD_BF4, "rmsnorm_fwd_k<bf16,float,4>") X(K_RMS_FWD_BF1, "rmsnorm_fwd_k<bf16,float,1>")                                   \
+  X(K_RMS_FWD_FF4, "rmsnorm_fwd_k<float,float,4>") X(K_RMS_FWD_FF1, "rmsnorm_fwd_k<float,float,1>")                                 \
+  X(K_RMS_SPLIT, "rmsnorm_bwd_split_k<bf16,4,4>") X(K_RMS_SPLIT_B8, "rmsnorm_bwd_split_k<bf16,8,4>")                                \
+  X(K_RMS_SPLIT_F4, "rmsnorm_bwd_split_k<float,4,4>") X(K_RMS_SPLIT_F8, "rmsnorm_bwd_split_k<float,8,4>")                           \
+  X(K_RMS_FAST8, "norm_bwd_fast8_k<bf16,false>") X(K_RMS_FAST8_F, "norm_bwd_fast8_k<float,false>")                                  \
+  X(K_RMS_FAST, "norm_bwd_fast_k<bf16,bf16,false>") X(K_RMS_FAST_BF, "norm_bwd_fast_k<bf16,float,false>")                           \
+  X(K_RMS_FAST_FF, "norm_bwd_fast_k<float,float,false>")                                                                            \
+  X(K_RMS_BWD, "rmsnorm_bwd_k<bf16,bf16,4>") X(K_RMS_BWD_1, "rmsnorm_bwd_k<bf16,bf16,1>")                                           \
+  X(K_RMS_BWD_BF4, "rmsnorm_bwd_k<bf16,float,4>") X(K_RMS_BWD_BF1, "rmsnorm_bwd_k<bf16,float,1>")                                   \
+  X(K_RMS_BWD_FF4, "rmsnorm_bwd_k<float,float,4>") X(K_RMS_BWD_FF1, "rmsnorm_bwd_k<float,float,1>")                                 \
+  X(K_LN_FWD, "layernorm_fwd_k<bf16,bf16,4>") X(K_LN_FWD_1, "layernorm_fwd_k<bf16,bf16,1>")                                         \
+  X(K_LN_FWD_BF4, "layernorm_fwd_k<bf16,float,4>") X(K_LN_FWD_BF1, "layernorm_fwd_k<bf16,float,1>")                                 \
+  X(K_LN_FWD_FF4, "layernorm_fwd_k<float,float,4>") X(K_LN_FWD_FF1, "layernorm_fwd_k<float,float,1>")                               \
+  X(K_LN_FAST, "norm_bwd_fast_k<bf16,bf16,true>") X(K_LN_FAST_BF, "norm_bwd_fast_k<bf16,float,true>")                               \
+  X(K_LN_FAST_FF, "norm_bwd_fast_k<float,float,true>")                                                                              \
+  X(K_LN_BWD, "layernorm_bwd_k<bf16,bf16,4>") X(K_LN_BWD_1, "layernorm_bwd_k<bf16,bf16,1>")                                         \
+  X(K_LN_BWD_BF4, "layernorm_bwd_k<bf16,float,4>") X(K_LN_BWD_BF1, "layernorm_bwd_k<bf16,float,1>")                                 \
+  X(K_LN_BWD_FF4, "layernorm_bwd_k<float,float,4>") X(K_LN_BWD_FF1, "layernorm_bwd_k<float,float,1>")                               \
+  X(K_ADDLN_FWD, "layernorm_fwd_k<bf16,bf16,4,true>") X(K_ADDLN_FWD_1, "layernorm_fwd_k<bf16,bf16,1,true>")                         \
+  X(K_ADDLN_FWD_BF4, "layernorm_fwd_k<bf16,float,4,true>") X(K_ADDLN_FWD_BF1, "layernorm_fwd_k<bf16,float,1,true>")                 \
+  X(K_ADDLN_FWD_FF4, "layernorm_fwd_k<float,float,4,true>") X(K_ADDLN_FWD_FF1, "layernorm_fwd_k<float,float,1,true>")               \
+  X(K_ADDLN_BWD, "layernorm_bwd_k<bf16,bf16,4,true>") X(K_ADDLN_BWD_1, "layernorm_bwd_k<bf16,bf16,1,true>")                         \
+  X(K_ADDLN_BWD_BF4, "layernorm_bwd_k<bf16,float,4,true>") X(K_ADDLN_BWD_BF1, "layernorm_bwd_k<bf16,float,1,true>")                 \
+  X(K_ADDLN_BWD_FF4, "layernorm_bwd_k<float,float,4,true>") X(K_ADDLN_BWD_FF1, "layernorm_bwd_k<float,float,1,true>")               \
+  X(K_CS_DIRECT, "colsum_stage1_k<bf16,true>") X(K_CS_DIRECT_F, "colsum_stage1_k<float,true>")                                      \
+  X(K_CS_FUSED, "colsum_fused_k<bf16>") X(K_CS_FUSED_F, "colsum_fused_k<float>")                                                    \
+  X(K_CS_STAGE1, "colsum_stage1_k<bf16,false>") X(K_CS_STAGE1_F, "colsum_stage1_k<float,false>")                                    \
+  X(K_CS_STAGE2, "colsum_stage2_k")                                                                                                 \
+  X(K_DS_FWD, "ds_layernorm_fwd_k<bf16,bf16,8>") X(K_DS_FWD_1, "ds_layernorm_fwd_k<bf16,bf16,1>")                                   \
+  X(K_DS_FWD_BF8, "ds_layernorm_fwd_k<bf16,float,8>") X(K_DS_FWD_BF1, "ds_layernorm_fwd_k<bf16,float,1>")                           \
+  X(K_DS_FWD_FF4, "ds_layernorm_fwd_k<float,float,4>") X(K_DS_FWD_FF1, "ds_layernorm_fwd_k<float,float,1>")                         \
+  X(K_DS_BWD, "ds_layernorm_bwd_k<bf16,bf16,8>") X(K_DS_BWD_1, "ds_layernorm_bwd_k<bf16,bf16,1>")                                   \
+  X(K_DS_BWD_BF8, "ds_layernorm_bwd_k<bf16,float,8>") X(K_DS_BWD_BF1, "ds_layernorm_bwd_k<bf16,float,1>")                           \
+  X(K_DS_BWD_FF4, "ds_layernorm_bwd_k<float,float,4>") X(K_DS_BWD_FF1, "ds_layernorm_bwd_k<float,float,1>")                         \
+  X(K_AR_FWD_FAST, "adarms_fwd_fast_k<false>") X(K_AR_FWD_FAST_G, "adarms_fwd_fast_k<true>")                                        \
+  X(K_AR_FWD, "adarms_fwd_k<bf16,8,false>") X(K_AR_FWD_B8G, "adarms_fwd_k<bf16,8,true>")                                            \
+  X(K_AR_FWD_B4, "adarms_fwd_k<bf16,4,false>") X(K_AR_FWD_B4G, "adarms_fwd_k<bf16,4,true>")                                         \
+  X(K_AR_FWD_B1, "adarms_fwd_k<bf16,1,false>") X(K_AR_FWD_B1G, "adarms_fwd_k<bf16,1,true>")                                         \
+  X(K_AR_FWD_F4, "adarms_fwd_k<float,4,false>") X(K_AR_FWD_F4G, "adarms_fwd_k<float,4,true>")                                       \
+  X(K_AR_FWD_F1, "adarms_fwd_k<float,1,false>") X(K_AR_FWD_F1G, "adarms_fwd_k<float,1,true>")                                       \
+  X(K_GR_FWD, "gated_residual_fwd_k<bf16,8>") X(K_GR_FWD_B4, "gated_residual_fwd_k<bf16,4>")                                        \
+  X(K_GR_FWD_B1, "gated_residual_fwd_k<bf16,1>") X(K_GR_FWD_F4, "gated_residual_fwd_k<float,4>")                                    \
+  X(K_GR_FWD_F1, "gated_residual_fwd_k<float,1>")                                                                                   \
+  X(K_AR_BWD, "adarms_bwd_k<bf16,8,false>") X(K_AR_BWD_B8G, "adarms_bwd_k<bf16,8,true>")                                            \
+  X(K_AR_BWD_B4, "adarms_bwd_k<bf16,4,false>") X(K_AR_BWD_B4G, "adarms_bwd_k<bf16,4,true>")                                         \
+  X(K_AR_BWD_B1, "adarms_bwd_k<bf16,1,false>") X(K_AR_BWD_B1G, "adarms_bwd_k<bf16,1,true>")                                         \
+  X(K_AR_BWD_F4, "adarms_bwd_k<float,4,false>") X(K_AR_BWD_F4G, "adarms_bwd_k<float,4,true>")                                       \
+  X(K_AR_BWD_F1, "adarms_bwd_k<float,1,false>") X(K_AR_BWD_F1G, "adarms_bwd_k<float,1,true>")                                       \
+  X(K_GR_BWD, "gated_residual_bwd_k<bf16,8>") X(K_GR_BWD_B4, "gated_residual_bwd_k<bf16,4>")                                        \
+  X(K_GR_BWD_B1, "gated_residual_bwd_k<bf16,1>") X(K_GR_BWD_F4, "gated_residual_bwd_k<float,4>")                                    \
+  X(K_GR_BWD_F1, "gated_residual_bwd_k<float,1>")                                                                                   \
+  X(K_FOLD, "adarms_fold_k<bf16>") X(K_FOLD_F, "adarms_fold_k<float>")
+
+namespace {
+#define NORM_KERNEL_ID(id, name) id,
+enum NormKernel { NORM_KERNELS(NORM_KERNEL_ID) K_NONE };
+#undef NORM_KERNEL_ID
+#define NORM_KERNEL_NAME(id, name) name,
+const char* const NORM_KERNEL_NAMES[] = {NORM_KERNELS(NORM_KERNEL_NAME)};
+#undef NORM_KERNEL_NAME
+
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
+struct NormPlan {
+  int k = K_NONE, k2 = K_NONE;   // the launch(es); K_NONE: nothing to launch (rows == 0)
+  const char* mode = nullptr;
+  int vec = 1;
+  dim3 grid{1, 1, 1}, grid2{1, 1, 1};
+  int block = 256, block2 = 256;
+  size_t lds = 0;
+  int use_lds = 0;               // ds_layernorm_bwd_k: the partial sums live in LDS
+  int nsplit = 0;
+  int64_t trips = 0;
+};
+
+int tw_index(int dtype, int w_dtype) { return dtype == DXA_F32 ? 2 : w_dtype == DXA_BF16 ? 0 : 1; }
+int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+int check_downsample_args(const char* who, int64_t N, int64_t G, int64_t C) {
+  DXA_CHECK_ARG(N >= 0 && G > 0 && C > 0 && G <= 4096 && C <= (1 << 20) && N <= (1ll << 31),
+                "%s: bad sizes N=%lld G=%lld C=%lld", who, (long long)N, (long long)G, (long long)C);
+  return DXA_OK;
+}
+
+// widest access every pointer and stride allows: 8 (bf16 only), 4 or 1 elements
+int adarms_vec(int dtype, int64_t cols, int64_t gate_ld, std::initializer_list<const void*> ptrs) {
+  const size_t es = dtype == DXA_BF16 ? 2 : 4;
+  int vec = dtype == DXA_BF16 ? 8 : 4;
+  for (; vec > 1; vec >>= 1) {
+    bool ok = cols % vec == 0 && gate_ld % vec == 0;
+    for (const void* p : ptrs) ok = ok && (reinterpret_cast<uintptr_t>(p) % (vec * es)) == 0;
+    if (ok) break;
+  }
+  return vec;
+}
+// index of an adarms / gated-residual vector width within its group: bf16 8, 4, 1, then fp32 4, 1
+int adarms_vidx(int dtype, int vec) { return dtype == DXA_BF16 ? (vec == 8 ? 0 : vec == 4 ? 1 : 2) : (vec == 4 ? 3 : 4); }
+
+int check_adarms(const char* who, int64_t rows, int64_t rps, int64_t cols, int dtype) {
+  DXA_CHECK_ARG(dtype == DXA_F32 || dtype == DXA_BF16, "%s: unsupported dtype %d", who, dtype);
+  DXA_CHECK_ARG(cols > 0 && rows >= 0 && rps > 0, "%s: bad sizes (rows %lld, rows_per_sample %lld, cols %lld)", who, (long long)rows,
+                (long long)rps, (long long)cols);
+  DXA_CHECK_ARG(rows % rps == 0, "%s: %lld rows are not a whole number of samples of %lld rows", who, (long long)rows, (long long)rps);
+  DXA_CHECK_ARG(rows / rps <= 65535, "%s: more than 65535 samples", who);
+  return DXA_OK;
+}
+
+// backward kernels with a grid-stride row loop: one workgroup per four rows up to NORM_BWD_MAX_BLOCKS
+void plan_bwd_grid(NormPlan* p, int64_t rows) {
+  p->grid = dim3((unsigned)dxa_norm_bwd_blocks(rows));
+  p->trips = cdiv(rows, (int64_t)p->grid.x * 4);
+}
+
+int plan_rmsnorm_fwd(const dxa_norm_desc* d, NormPlan* p) {
+  if (int rc = check_norm_dtypes(d->dtype, d->w_dtype, "dxa_rmsnorm_fwd")) return rc;
+  const int64_t rows = d->rows, cols = d->cols;
+  DXA_CHECK_ARG(d->x && d->y && rows >= 0 && cols > 0, "dxa_rmsnorm_fwd: bad args");
+  if (rows == 0) return DXA_OK;
+  const bool vec_ok = al16(d->x) && al16(d->y) && (!d->w || al16(d->w));
+  p->grid = dim3((unsigned)((rows + 3) / 4));
+  p->trips = 1;
+  if (d->dtype == DXA_BF16 && vec_ok && cols % 8 == 0 && cols <= 8192) {
+    p->k = K_RMS_FWD_FAST + (d->w_dtype == DXA_F32);
+    p->vec = 8;
+  } else {
+    p->vec = vec_ok && cols % 4 == 0 ? 4 : 1;
+    p->k = K_RMS_FWD + 2 * tw_index(d->dtype, d->w_dtype) + (p->vec == 1);
+  }
+  return DXA_OK;
+}
+
+// RMSNorm (LN = false) and LayerNorm backward
+int plan_norm_bwd(const dxa_norm_desc* d, NormPlan* p, bool LN) {
+  const char* who = LN ? "dxa_layernorm_bwd" : "dxa_rmsnorm_bwd";
+  if (int rc = check_norm_dtypes(d->dtype, d->w_dtype, who)) return rc;
+  const int64_t rows = d->rows, cols = d->cols;
+  if (LN) {
+    DXA_CHECK_ARG(d->dy && d->x && d->mean && d->rstd && d->dx && rows >= 0 && cols > 0, "dxa_layernorm_bwd: bad args");
+    DXA_CHECK_ARG(!d->w || d->partial, "dxa_layernorm_bwd: partial_dwdb required when w is given");
+  } else {
+    DXA_CHECK_ARG(d->dy && d->x && d->rstd && d->dx && rows >= 0 && cols > 0, "dxa_rmsnorm_bwd: bad args");
+    DXA_CHECK_ARG(!d->w || d->partial, "dxa_rmsnorm_bwd: partial_dw required when w is given");
+  }
+  if (rows == 0) return DXA_OK;
+  const bool vec_ok = al16(d->x) && al16(d->dy) && al16(d->dx) && (!d->w || al16(d->w)) && (!d->partial || al16(d->partial)) &&
+                      (!d->residual || al16(d->residual));
+  const int tw = tw_index(d->dtype, d->w_dtype);
+  plan_bwd_grid(p, rows);
+  if (!LN && vec_ok && d->dtype == DXA_BF16 && cols % 16 == 0 && cols <= 8192) {
+    // the row split between two waves (A/B against the one-wave-per-row kernels: profiles/r05_norm_bwd_split.txt); four rows
+    // per workgroup pass (512 threads at 128 registers: a dozen spilled dwords); the three-row form (384 threads, 168
+    // registers, no spill) against it: profiles/r05_norm_bwd_split.txt
+    p->k = K_RMS_SPLIT + 2 * (d->w_dtype == DXA_F32) + (cols > 4096);
+    p->vec = 8;
+    p->block = 4 * 128;
+  } else if (vec_ok && cols % 4 == 0 && cols <= NORM_BWD_FAST_MAX_COLS) {
+    if (!LN && d->dtype == DXA_BF16 && cols % 8 == 0) {   // RMSNorm: 16-byte accesses, one read of x and dy (LayerNorm's second
+                                                          // set of partial sums costs it the registers: measured 27 vs 24 us)
+      p->k = K_RMS_FAST8 + (d->w_dtype == DXA_F32);
+      p->vec = 8;
+    } else {
+      p->k = (LN ? K_LN_FAST : K_RMS_FAST) + tw;
+      p->vec = 4;
+    }
+  } else {
+    p->vec = vec_ok && cols % 4 == 0 ? 4 : 1;
+    p->k = (LN ? K_LN_BWD : K_RMS_BWD) + 2 * tw + (p->vec == 1);
+  }
+  return DXA_OK;
+}
+
+int plan_layernorm_fwd(const dxa_norm_desc* d, NormPlan* p) {
+  if (int rc = check_norm_dtypes(d->dtype, d->w_dtype, "dxa_layernorm_fwd")) return rc;
+  const int64_t rows = d->rows, cols = d->cols;
+  DXA_CHECK_ARG(d->x && d->y && rows >= 0 && cols > 0, "dxa_layernorm_fwd: bad args");
+  if (rows == 0) return DXA_OK;
+  const bool vec_ok = al16(d->x) && al16(d->y) && (!d->w || al16(d->w)) && (!d->b || al16(d->b));
+  p->grid = dim3((unsigned)((rows + 3) / 4));
+  p->trips = 1;
+  p->vec = vec_ok && cols % 4 == 0 ? 4 : 1;
+  p->k = K_LN_FWD + 2 * tw_index(d->dtype, d->w_dtype) + (p->vec == 1);
+  return DXA_OK;
+}
+
+int plan_add_layernorm_fwd(const dxa_norm_desc* d, NormPlan* p) {
+  if (int rc = check_norm_dtypes(d->dtype, d->w_dtype, "dxa_add_layernorm_fwd")) return rc;
+  const int64_t rows = d->rows, cols = d->cols;
+  DXA_CHECK_ARG(d->x && d->x2 && d->y, "dxa_add_layernorm_fwd: null x / res / y");
+  DXA_CHECK_ARG(rows >= 0 && cols > 0, "dxa_add_layernorm_fwd: bad sizes (rows %lld, cols %lld)", (long long)rows, (long long)cols);
+  if (rows == 0) return DXA_OK;
+  const bool vec = al16(d->x) && al16(d->x2) && al16(d->y) && (!d->w || al16(d->w)) && (!d->b || al16(d->b)) && cols % 4 == 0;
+  p->grid = dim3((unsigned)((rows + 3) / 4));
+  p->trips = 1;
+  p->vec = vec ? 4 : 1;
+  p->k = K_ADDLN_FWD + 2 * tw_index(d->dtype, d->w_dtype) + !vec;
+  return DXA_OK;
+}
+
+int plan_add_layernorm_bwd(const dxa_norm_desc* d, NormPlan* p) {
+  if (int rc = check_norm_dtypes(d->dtype, d->w_dtype, "dxa_add_layernorm_bwd")) return rc;
+  const int64_t rows = d->rows, cols = d->cols;
+  DXA_CHECK_ARG(d->dy && d->x && d->x2 && d->mean && d->rstd && d->dx, "dxa_add_layernorm_bwd: null dy / x / res / mean / rstd / dx");
+  DXA_CHECK_ARG(rows >= 0 && cols > 0, "dxa_add_layernorm_bwd: bad sizes (rows %lld, cols %lld)", (long long)rows, (long long)cols);
+  DXA_CHECK_ARG(!d->w || d->partial, "dxa_add_layernorm_bwd: partial_dwdb required when w is given");
+  if (rows == 0) return DXA_OK;
+  const bool vec = al16(d->x) && al16(d->x2) && al16(d->dy) && al16(d->dx) && (!d->w || al16(d->w)) && cols % 4 == 0;
+  plan_bwd_grid(p, rows);
+  p->vec = vec ? 4 : 1;
+  p->k = K_ADDLN_BWD + 2 * tw_index(d->dtype, d->w_dtype) + !vec;
+  return DXA_OK;
+}
+
+int plan_colsum(const dxa_norm_desc* d, NormPlan* p) {
+  const int64_t rows = d->rows, cols = d->cols;
+  DXA_CHECK_ARG(d->x && d->y && rows >= 0 && cols > 0 && d->ld >= cols, "dxa_colsum: bad args");
+  DXA_CHECK_ARG(d->dtype == DXA_F32 || d->dtype == DXA_BF16, "dxa_colsum: bad dtype");
+  // row splits of >= 32 rows, at most 64 of them: the <= 512 partial rows of a norm backward become 16 x 14 workgroups
+  int nsplit = (int)((rows + 31) / 32);
+  if (nsplit < 1) nsplit = 1;
+  if (nsplit > 64) nsplit = 64;
+  DXA_CHECK_ARG(d->partial && d->partial_bytes >= (size_t)nsplit * cols * sizeof(float),
+                "dxa_colsum: scratch too small (need %zu bytes)", (size_t)nsplit * cols * sizeof(float));
+  const size_t es = d->dtype == DXA_BF16 ? 2 : 4;
+  const int f32 = d->dtype == DXA_F32;
+  p->vec = ((reinterpret_cast<uintptr_t>(d->x) % (4 * es)) == 0) && (d->ld % 4 == 0) ? 4 : 1;
+  const unsigned gx = (unsigned)((cols + 255) / 256);
+  if (rows <= 32) {
+    // a handful of rows: one launch, the block's sums are the result
+    p->mode = "direct";
+    p->k = K_CS_DIRECT + f32;
+    p->nsplit = 1;
+  } else if (gx <= COLSUM_CNT && (d->have_counters || !d->capturing)) {
+    p->mode = "fused";
+    p->k = K_CS_FUSED + f32;
+    p->nsplit = nsplit;
+  } else {
+    p->mode = "two_launch";
+    p->k = K_CS_STAGE1 + f32;
+    p->nsplit = nsplit;
+    p->k2 = K_CS_STAGE2;     // one wave per 64 columns: 56 workgroups for 3584 columns instead of 14
+    p->grid2 = dim3((unsigned)((cols + 63) / 64));
+    p->block2 = 64;
+  }
+  p->grid = dim3(gx, (unsigned)p->nsplit);
+  p->trips = cdiv(cdiv(rows, p->nsplit), 4);
+  return DXA_OK;
+}
+
+int plan_downsample(const dxa_norm_desc* d, NormPlan* p, bool bwd) {
+  const char* who = bwd ? "dxa_downsample_layernorm_bwd" : "dxa_downsample_layernorm_fwd";
+  if (int rc = check_norm_dtypes(d->dtype, d->w_dtype, who)) return rc;
+  if (bwd) {
+    DXA_CHECK_ARG(d->dy && d->x && d->mean && d->rstd && d->dx, "dxa_downsample_layernorm_bwd: null dy / x / mean / rstd / dx");
+    DXA_CHECK_ARG(!d->w || d->partial, "dxa_downsample_layernorm_bwd: partial_dwdb required when w is given");
+  } else {
+    DXA_CHECK_ARG(d->x && d->y, "dxa_downsample_layernorm_fwd: null x / y");
+  }
+  const int64_t N = d->rows, G = d->G, C = d->cols;
+  if (int rc = check_downsample_args(who, N, G, C)) return rc;
+  const int h = (int)((G + 1) / 2);
+  const int64_t rows = N * h * h;
+  if (rows == 0) return DXA_OK;
+  const int vec = d->dtype == DXA_BF16 ? 8 : 4;              // 16 bytes per access
+  const bool vec_ok = bwd ? al16(d->x) && al16(d->dy) && al16(d->dx) && (!d->w || al16(d->w)) && C % vec == 0
+                          : al16(d->x) && al16(d->y) && (!d->w || al16(d->w)) && (!d->b || al16(d->b)) && C % vec == 0;
+  p->vec = vec_ok ? vec : 1;
+  p->k = (bwd ? K_DS_BWD : K_DS_FWD) + 2 * tw_index(d->dtype, d->w_dtype) + !vec_ok;
+  if (bwd) {
+    plan_bwd_grid(p, rows);
+    const size_t sums = d->w ? (size_t)8 * C * sizeof(float) : 0;
+    p->use_lds = sums > 0 && sums <= DS_LN_MAX_LDS;
+    p->lds = p->use_lds ? sums : 0;
+  } else {
+    p->grid = dim3((unsigned)((rows + 3) / 4));
+    p->trips = 1;
+  }
+  return DXA_OK;
+}
+
+int plan_adarms(const dxa_norm_desc* d, NormPlan* p, bool bwd, bool gated_residual) {
+  const char* who = gated_residual ? (bwd ? "dxa_gated_residual_bwd" : "dxa_gated_residual_fwd") : (bwd ? "dxa_adarms_bwd" : "dxa_adarms_fwd");
+  const int64_t rows = d->rows, cols = d->cols, rps = d->rows_per_sample;
+  const int dtype = d->dtype;
+  if (int rc = check_adarms(who, rows, rps, cols, dtype)) return rc;
+  const void* branch = d->x2;
+  if (!gated_residual && !bwd) {
+    DXA_CHECK_ARG(d->x && d->mod && d->y, "dxa_adarms_fwd: null x / mod / y");
+    DXA_CHECK_ARG(!branch || (d->gate && d->aux && d->gate_ld >= cols), "dxa_adarms_fwd: a branch needs gate_prev, r_out and gate_ld >= cols");
+  } else if (gated_residual && !bwd) {
+    DXA_CHECK_ARG(d->x && branch && d->gate && d->y && d->gate_ld >= cols, "dxa_gated_residual_fwd: null x / branch / gate / y, or gate_ld < cols");
+  } else if (!gated_residual) {
+    DXA_CHECK_ARG(d->dy && d->x && d->mod && d->rstd && d->dx && d->dmod && d->partial, "dxa_adarms_bwd: null dy / r / mod / rstd / dr / dmod / partial");
+    DXA_CHECK_ARG(!branch || (d->gate && d->aux && d->dgate && d->gate_ld >= cols && d->dgate_ld >= cols),
+                  "dxa_adarms_bwd: a branch needs gate_prev, dbranch, dgate_prev and gate_ld, dgate_ld >= cols");
+  } else {
+    DXA_CHECK_ARG(d->dy && branch && d->gate && d->dx && d->dgate && d->partial, "dxa_gated_residual_bwd: null dy / branch / gate / dbranch / dgate / partial");
+    DXA_CHECK_ARG(d->gate_ld >= cols && d->dgate_ld >= cols, "dxa_gated_residual_bwd: gate_ld / dgate_ld < cols");
+  }
+  if (rows == 0) return DXA_OK;
+  if (bwd) {
+    const int64_t B = rows / rps;
+    const int groups = dxa_adarms_bwd_groups(rps);
+    const int ns = gated_residual ? 1 : branch ? 3 : 2;
+    const size_t need = (size_t)B * groups * 4 * ns * cols * sizeof(float);
+    DXA_CHECK_ARG(d->partial_bytes >= need, "%s: partial too small (need %zu bytes)", who, need);
+    p->grid = dim3((unsigned)groups, (unsigned)B);
+    p->trips = cdiv(rps, (int64_t)groups * 4);
+    p->k2 = K_FOLD + (dtype == DXA_F32);
+    p->grid2 = dim3((unsigned)((ns * cols + 255) / 256), (unsigned)B);
+  } else {
+    p->grid = dim3((unsigned)((rows + 3) / 4));
+    p->trips = 1;
+  }
+  if (gated_residual) {
+    p->vec = bwd ? adarms_vec(dtype, cols, d->gate_ld, {d->dy, branch, d->gate, d->dx}) : adarms_vec(dtype, cols, d->gate_ld, {d->x, branch, d->gate, d->y});
+    p->k = (bwd ? K_GR_BWD : K_GR_FWD) + adarms_vidx(dtype, p->vec);
+  } else if (!bwd) {
+    p->vec = adarms_vec(dtype, cols, branch ? d->gate_ld : 0, {d->x, d->mod, d->y, branch, branch ? d->gate : nullptr, branch ? d->aux : nullptr});
+    p->k = dtype == DXA_BF16 && p->vec == 8 && cols <= 8192 ? K_AR_FWD_FAST + (branch != nullptr)
+                                                            : K_AR_FWD + 2 * adarms_vidx(dtype, p->vec) + (branch != nullptr);
+  } else {
+    p->vec = adarms_vec(dtype, cols, branch ? d->gate_ld : 0,
+                        {d->dy, d->x, d->mod, d->dx, d->residual, branch, branch ? d->gate : nullptr, branch ? d->aux : nullptr});
+    p->k = K_AR_BWD + 2 * adarms_vidx(dtype, p->vec) + (branch != nullptr);
+  }
+  if (p->vec == 2) p->vec = 1;       // a 2-wide fit runs on the scalar kernel (adarms_vidx)
+  return DXA_OK;
+}
+
+int norm_plan(const dxa_norm_desc* d, NormPlan* p) {
+  DXA_CHECK_ARG(d != nullptr, "dxa_norm_plan: null desc");
+  switch (d->entry) {
+    case DXA_NORM_RMSNORM_FWD: return plan_rmsnorm_fwd(d, p);
+    case DXA_NORM_RMSNORM_BWD: return plan_norm_bwd(d, p, false);
+    case DXA_NORM_LAYERNORM_FWD: return plan_layernorm_fwd(d, p);
+    case DXA_NORM_LAYERNORM_BWD: return plan_norm_bwd(d, p, true);
+    case DXA_NORM_ADD_LAYERNORM_FWD: return plan_add_layernorm_fwd(d, p);
+    case DXA_NORM_ADD_LAYERNORM_BWD: return plan_add_layernorm_bwd(d, p);
+    case DXA_NORM_COLSUM: return plan_colsum(d, p);
+    case DXA_NORM_DOWNSAMPLE_FWD: return plan_downsample(d, p, false);
+    case DXA_NORM_DOWNSAMPLE_BWD: return plan_downsample(d, p, true);
+    case DXA_NORM_ADARMS_FWD: return plan_adarms(d, p, false, false);
+    case DXA_NORM_ADARMS_BWD: return plan_adarms(d, p, true, false);
+    case DXA_NORM_GATED_RESIDUAL_FWD: return plan_adarms(d, p, false, true);
+    case DXA_NORM_GATED_RESIDUAL_BWD: return plan_adarms(d, p, true, true);
+  }
+  DXA_CHECK_ARG(false, "dxa_norm_plan: unknown entry point %d", d->entry);
+  return DXA_ERR_BAD_ARG;
+}
+
+// a plan named a kernel its entry point's launcher does not have: cannot happen while the two agree
+int unplanned(const char* who, int k) {
+  dxa_set_error("%s: no launch for planned kernel %d", who, k);
+  return DXA_ERR_UNSUPPORTED;
+}
+}  // namespace
+
+extern "C" const char* dxa_norm_kernel_name(int i) {
+  return i >= 0 && i < (int)K_NONE ? NORM_KERNEL_NAMES[i] : nullptr;
+}
+
+extern "C" int dxa_norm_plan(const dxa_norm_desc* d, dxa_norm_plan_info* out) {
+  DXA_CHECK_ARG(out != nullptr, "dxa_norm_plan: null output");
+  memset(out, 0, sizeof(*out));
+  NormPlan p;
+  if (int rc = norm_plan(d, &p)) return rc;
+  out->kernel = p.k == K_NONE ? nullptr : NORM_KERNEL_NAMES[p.k];
+  out->kernel2 = p.k2 == K_NONE || p.k == K_NONE ? nullptr : NORM_KERNEL_NAMES[p.k2];
+  out->mode = p.mode;
+  out->vec = p.k == K_NONE ? 0 : p.vec;
+  out->grid[0] = (int32_t)p.grid.x; out->grid[1] = (int32_t)p.grid.y; out->grid[2] = (int32_t)p.grid.z;
+  out->block = p.block;
+  out->lds = (int32_t)p.lds;
+  out->nsplit = p.nsplit;
+  out->trips = p.trips;
   return DXA_OK;
 }
 
@@ -832,28 +1193,26 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_fast_k(const bf16_t* __restri
 
 extern "C" int dxa_rmsnorm_fwd(const void* x, const void* w, void* y, float* rstd, int64_t rows, int64_t cols,
                                float eps, int dtype, int w_dtype, dxa_stream_t stream) {
-  if (int rc = check_norm_dtypes(dtype, w_dtype, "dxa_rmsnorm_fwd")) return rc;
-  DXA_CHECK_ARG(x && y && rows >= 0 && cols > 0, "dxa_rmsnorm_fwd: bad args");
-  if (rows == 0) return DXA_OK;
+  dxa_norm_desc d{};
+  d.entry = DXA_NORM_RMSNORM_FWD; d.dtype = dtype; d.w_dtype = w_dtype; d.rows = rows; d.cols = cols;
+  d.x = x; d.w = w; d.y = y; d.rstd = rstd;
+  NormPlan pl;
+  if (int rc = norm_plan(&d, &pl)) return rc;
+  if (pl.k == K_NONE) return DXA_OK;
   hipStream_t st = (hipStream_t)stream;
-  const bool vec_ok = al16(x) && al16(y) && (!w || al16(w));
-  dim3 grid((unsigned)((rows + 3) / 4));
-  if (dtype == DXA_BF16 && vec_ok && cols % 8 == 0 && cols <= 8192) {
-    if (w_dtype == DXA_BF16) hipLaunchKernelGGL((rmsnorm_fwd_fast_k<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, rstd, rows, cols, eps);
-    else hipLaunchKernelGGL((rmsnorm_fwd_fast_k<float>), grid, dim3(256), 0, st, (const bf16_t*)x, (const float*)w, (bf16_t*)y, rstd, rows, cols, eps);
-    DXA_CHECK_LAUNCH();
-    return DXA_OK;
+#define RMS_FWD(K_, T_, TW_) hipLaunchKernelGGL(K_, pl.grid, dim3(pl.block), 0, st, (const T_*)x, (const TW_*)w, (T_*)y, rstd, rows, cols, eps)
+  switch (pl.k) {
+    case K_RMS_FWD_FAST: RMS_FWD((rmsnorm_fwd_fast_k<bf16_t>), bf16_t, bf16_t); break;
+    case K_RMS_FWD_FAST_F: RMS_FWD((rmsnorm_fwd_fast_k<float>), bf16_t, float); break;
+    case K_RMS_FWD: RMS_FWD((rmsnorm_fwd_k<bf16_t, bf16_t, 4>), bf16_t, bf16_t); break;
+    case K_RMS_FWD_1: RMS_FWD((rmsnorm_fwd_k<bf16_t, bf16_t, 1>), bf16_t, bf16_t); break;
+    case K_RMS_FWD_BF4: RMS_FWD((rmsnorm_fwd_k<bf16_t, float, 4>), bf16_t, float); break;
+    case K_RMS_FWD_BF1: RMS_FWD((rmsnorm_fwd_k<bf16_t, float, 1>), bf16_t, float); break;
+    case K_RMS_FWD_FF4: RMS_FWD((rmsnorm_fwd_k<float, float, 4>), float, float); break;
+    case K_RMS_FWD_FF1: RMS_FWD((rmsnorm_fwd_k<float, float, 1>), float, float); break;
+    default: return unplanned("dxa_rmsnorm_fwd", pl.k);
   }
-  if (dtype == DXA_BF16 && w_dtype == DXA_BF16) {
-    if (vec_ok && cols % 4 == 0) hipLaunchKernelGGL((rmsnorm_fwd_k<bf16_t, bf16_t, 4>), grid, dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, rstd, rows, cols, eps);
-    else hipLaunchKernelGGL((rmsnorm_fwd_k<bf16_t, bf16_t, 1>), grid, dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, rstd, rows, cols, eps);
-  } else if (dtype == DXA_BF16) {
-    if (vec_ok && cols % 4 == 0) hipLaunchKernelGGL((rmsnorm_fwd_k<bf16_t, float, 4>), grid, dim3(256), 0, st, (const bf16_t*)x, (const float*)w, (bf16_t*)y, rstd, rows, cols, eps);
-    else hipLaunchKernelGGL((rmsnorm_fwd_k<bf16_t, float, 1>), grid, dim3(256), 0, st, (const bf16_t*)x, (const float*)w, (bf16_t*)y, rstd, rows, cols, eps);
-  } else {
-    if (vec_ok && cols % 4 == 0) hipLaunchKernelGGL((rmsnorm_fwd_k<float, float, 4>), grid, dim3(256), 0, st, (const float*)x, (const float*)w, (float*)y, rstd, rows, cols, eps);
-    else hipLaunchKernelGGL((rmsnorm_fwd_k<float, float, 1>), grid, dim3(256), 0, st, (const float*)x, (const float*)w, (float*)y, rstd, rows, cols, eps);
-  }
+#undef RMS_FWD
   DXA_CHECK_LAUNCH();
   return DXA_OK;
 }
@@ -861,27 +1220,37 @@ extern "C" int dxa_rmsnorm_fwd(const void* x, const void* w, void* y, float* rst
 extern "C" int dxa_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rstd, void* dx,
                                const void* residual, float* partial_dw, int64_t rows, int64_t cols, int dtype, int w_dtype,
                                dxa_stream_t stream) {
-  if (int rc = check_norm_dtypes(dtype, w_dtype, "dxa_rmsnorm_bwd")) return rc;
-  DXA_CHECK_ARG(dy && x && rstd && dx && rows >= 0 && cols > 0, "dxa_rmsnorm_bwd: bad args");
-  DXA_CHECK_ARG(!w || partial_dw, "dxa_rmsnorm_bwd: partial_dw required when w is given");
-  if (rows == 0) return DXA_OK;
+  dxa_norm_desc d{};
+  d.entry = DXA_NORM_RMSNORM_BWD; d.dtype = dtype; d.w_dtype = w_dtype; d.rows = rows; d.cols = cols;
+  d.dy = dy; d.x = x; d.w = w; d.rstd = rstd; d.dx = dx; d.residual = residual; d.partial = partial_dw;
+  NormPlan pl;
+  if (int rc = norm_plan(&d, &pl)) return rc;
+  if (pl.k == K_NONE) return DXA_OK;
   hipStream_t st = (hipStream_t)stream;
-  const bool vec_ok = al16(x) && al16(dy) && al16(dx) && (!w || al16(w)) && (!partial_dw || al16(partial_dw)) && (!residual || al16(residual));
-  if (launch_norm_bwd_fast<false>(dy, x, w, nullptr, rstd, dx, residual, w ? partial_dw : nullptr, rows, cols, dtype, w_dtype, vec_ok, st)) {
-    DXA_CHECK_LAUNCH();
-    return DXA_OK;
+  float* part = w ? partial_dw : nullptr;
+  // the fast kernels and the split kernel (dx only without a gain) take no slab without w; rmsnorm_bwd_k decides from w itself
+#define RMS_BWD(K_, T_, TW_, P_) hipLaunchKernelGGL(K_, pl.grid, dim3(pl.block), 0, st, (const T_*)dy, (const T_*)x, (const TW_*)w, rstd, (T_*)dx, (const T_*)residual, P_, rows, cols)
+#define RMS_FAST(K_, T_, TW_) hipLaunchKernelGGL(K_, pl.grid, dim3(pl.block), 0, st, (const T_*)dy, (const T_*)x, (const TW_*)w, (const float*)nullptr, rstd, (T_*)dx, (const T_*)residual, part, rows, cols)
+  switch (pl.k) {
+    case K_RMS_SPLIT: RMS_BWD((rmsnorm_bwd_split_k<bf16_t, 4, 4>), bf16_t, bf16_t, part); break;
+    case K_RMS_SPLIT_B8: RMS_BWD((rmsnorm_bwd_split_k<bf16_t, 8, 4>), bf16_t, bf16_t, part); break;
+    case K_RMS_SPLIT_F4: RMS_BWD((rmsnorm_bwd_split_k<float, 4, 4>), bf16_t, float, part); break;
+    case K_RMS_SPLIT_F8: RMS_BWD((rmsnorm_bwd_split_k<float, 8, 4>), bf16_t, float, part); break;
+    case K_RMS_FAST8: RMS_FAST((norm_bwd_fast8_k<bf16_t, false>), bf16_t, bf16_t); break;
+    case K_RMS_FAST8_F: RMS_FAST((norm_bwd_fast8_k<float, false>), bf16_t, float); break;
+    case K_RMS_FAST: RMS_FAST((norm_bwd_fast_k<bf16_t, bf16_t, false>), bf16_t, bf16_t); break;
+    case K_RMS_FAST_BF: RMS_FAST((norm_bwd_fast_k<bf16_t, float, false>), bf16_t, float); break;
+    case K_RMS_FAST_FF: RMS_FAST((norm_bwd_fast_k<float, float, false>), float, float); break;
+    case K_RMS_BWD: RMS_BWD((rmsnorm_bwd_k<bf16_t, bf16_t, 4>), bf16_t, bf16_t, partial_dw); break;
+    case K_RMS_BWD_1: RMS_BWD((rmsnorm_bwd_k<bf16_t, bf16_t, 1>), bf16_t, bf16_t, partial_dw); break;
+    case K_RMS_BWD_BF4: RMS_BWD((rmsnorm_bwd_k<bf16_t, float, 4>), bf16_t, float, partial_dw); break;
+    case K_RMS_BWD_BF1: RMS_BWD((rmsnorm_bwd_k<bf16_t, float, 1>), bf16_t, float, partial_dw); break;
+    case K_RMS_BWD_FF4: RMS_BWD((rmsnorm_bwd_k<float, float, 4>), float, float, partial_dw); break;
+    case K_RMS_BWD_FF1: RMS_BWD((rmsnorm_bwd_k<float, float, 1>), float, float, partial_dw); break;
+    default: return unplanned("dxa_rmsnorm_bwd", pl.k);
   }
-  dim3 grid((unsigned)dxa_norm_bwd_blocks(rows));
-  if (dtype == DXA_BF16 && w_dtype == DXA_BF16) {
-    if (vec_ok && cols % 4 == 0) hipLaunchKernelGGL((rmsnorm_bwd_k<bf16_t, bf16_t, 4>), grid, dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, rstd, (bf16_t*)dx, (const bf16_t*)residual, partial_dw, rows, cols);
-    else hipLaunchKernelGGL((rmsnorm_bwd_k<bf16_t, bf16_t, 1>), grid, dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, rstd, (bf16_t*)dx, (const bf16_t*)residual, partial_dw, rows, cols);
-  } else if (dtype == DXA_BF16) {
-    if (vec_ok && cols % 4 == 0) hipLaunchKernelGGL((rmsnorm_bwd_k<bf16_t, float, 4>), grid, dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, (const float*)w, rstd, (bf16_t*)dx, (const bf16_t*)residual, partial_dw, rows, cols);
-    else hipLaunchKernelGGL((rmsnorm_bwd_k<bf16_t, float, 1>), grid, dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, (const float*)w, rstd, (bf16_t*)dx, (const bf16_t*)residual, partial_dw, rows, cols);
-  } else {
-    if (vec_ok && cols % 4 == 0) hipLaunchKernelGGL((rmsnorm_bwd_k<float, float, 4>), grid, dim3(256), 0, st, (const float*)dy, (const float*)x, (const float*)w, rstd, (float*)dx, (const float*)residual, partial_dw, rows, cols);
-    else hipLaunchKernelGGL((rmsnorm_bwd_k<float, float, 1>), grid, dim3(256), 0, st, (const float*)dy, (const float*)x, (const float*)w, rstd, (float*)dx, (const float*)residual, partial_dw, rows, cols);
-  }
+#undef RMS_BWD
+#undef RMS_FAST
   DXA_CHECK_LAUNCH();
   return DXA_OK;
 }
@@ -889,22 +1258,24 @@ extern "C" int dxa_rmsnorm_bwd(const void* dy, const void* x, const void* w, con
 extern "C" int dxa_layernorm_fwd(const void* x, const void* w, const void* b, void* y, float* mean, float* rstd,
                                  int64_t rows, int64_t cols, float eps, int dtype, int w_dtype,
                                  dxa_stream_t stream) {
-  if (int rc = check_norm_dtypes(dtype, w_dtype, "dxa_layernorm_fwd")) return rc;
-  DXA_CHECK_ARG(x && y && rows >= 0 && cols > 0, "dxa_layernorm_fwd: bad args");
-  if (rows == 0) return DXA_OK;
+  dxa_norm_desc d{};
+  d.entry = DXA_NORM_LAYERNORM_FWD; d.dtype = dtype; d.w_dtype = w_dtype; d.rows = rows; d.cols = cols;
+  d.x = x; d.w = w; d.b = b; d.y = y; d.mean = mean; d.rstd = rstd;
+  NormPlan pl;
+  if (int rc = norm_plan(&d, &pl)) return rc;
+  if (pl.k == K_NONE) return DXA_OK;
   hipStream_t st = (hipStream_t)stream;
-  const bool vec_ok = al16(x) && al16(y) && (!w || al16(w)) && (!b || al16(b));
-  dim3 grid((unsigned)((rows + 3) / 4));
-  if (dtype == DXA_BF16 && w_dtype == DXA_BF16) {
-    if (vec_ok && cols % 4 == 0) hipLaunchKernelGGL((layernorm_fwd_k<bf16_t, bf16_t, 4>), grid, dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)b, (bf16_t*)y, mean, rstd, rows, cols, eps);
-    else hipLaunchKernelGGL((layernorm_fwd_k<bf16_t, bf16_t, 1>), grid, dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)b, (bf16_t*)y, mean, rstd, rows, cols, eps);
-  } else if (dtype == DXA_BF16) {
-    if (vec_ok && cols % 4 == 0) hipLaunchKernelGGL((layernorm_fwd_k<bf16_t, float, 4>), grid, dim3(256), 0, st, (const bf16_t*)x, (const float*)w, (const float*)b, (bf16_t*)y, mean, rstd, rows, cols, eps);
-    else hipLaunchKernelGGL((layernorm_fwd_k<bf16_t, float, 1>), grid, dim3(256), 0, st, (const bf16_t*)x, (const float*)w, (const float*)b, (bf16_t*)y, mean, rstd, rows, cols, eps);
-  } else {
-    if (vec_ok && cols % 4 == 0) hipLaunchKernelGGL((layernorm_fwd_k<float, float, 4>), grid, dim3(256), 0, st, (const float*)x, (const float*)w, (const float*)b, (float*)y, mean, rstd, rows, cols, eps);
-    else hipLaunchKernelGGL((layernorm_fwd_k<float, float, 1>), grid, dim3(256), 0, st, (const float*)x, (const float*)w, (const float*)b, (float*)y, mean, rstd, rows, cols, eps);
+#define LN_FWD(K_, T_, TW_) hipLaunchKernelGGL(K_, pl.grid, dim3(pl.block), 0, st, (const T_*)x, (const TW_*)w, (const TW_*)b, (T_*)y, mean, rstd, rows, cols, eps)
+  switch (pl.k) {
+    case K_LN_FWD: LN_FWD((layernorm_fwd_k<bf16_t, bf16_t, 4>), bf16_t, bf16_t); break;
+    case K_LN_FWD_1: LN_FWD((layernorm_fwd_k<bf16_t, bf16_t, 1>), bf16_t, bf16_t); break;
+    case K_LN_FWD_BF4: LN_FWD((layernorm_fwd_k<bf16_t, float, 4>), bf16_t, float); break;
+    case K_LN_FWD_BF1: LN_FWD((layernorm_fwd_k<bf16_t, float, 1>), bf16_t, float); break;
+    case K_LN_FWD_FF4: LN_FWD((layernorm_fwd_k<float, float, 4>), float, float); break;
+    case K_LN_FWD_FF1: LN_FWD((layernorm_fwd_k<float, float, 1>), float, float); break;
+    default: return unplanned("dxa_layernorm_fwd", pl.k);
   }
+#undef LN_FWD
   DXA_CHECK_LAUNCH();
   return DXA_OK;
 }
@@ -912,28 +1283,28 @@ extern "C" int dxa_layernorm_fwd(const void* x, const void* w, const void* b, vo
 extern "C" int dxa_layernorm_bwd(const void* dy, const void* x, const void* w, const float* mean,
                                  const float* rstd, void* dx, const void* residual, float* partial_dwdb, int64_t rows,
                                  int64_t cols, int dtype, int w_dtype, dxa_stream_t stream) {
-  if (int rc = check_norm_dtypes(dtype, w_dtype, "dxa_layernorm_bwd")) return rc;
-  DXA_CHECK_ARG(dy && x && mean && rstd && dx && rows >= 0 && cols > 0, "dxa_layernorm_bwd: bad args");
-  DXA_CHECK_ARG(!w || partial_dwdb, "dxa_layernorm_bwd: partial_dwdb required when w is given");
-  if (rows == 0) return DXA_OK;
+  dxa_norm_desc d{};
+  d.entry = DXA_NORM_LAYERNORM_BWD; d.dtype = dtype; d.w_dtype = w_dtype; d.rows = rows; d.cols = cols;
+  d.dy = dy; d.x = x; d.w = w; d.mean = mean; d.rstd = rstd; d.dx = dx; d.residual = residual; d.partial = partial_dwdb;
+  NormPlan pl;
+  if (int rc = norm_plan(&d, &pl)) return rc;
+  if (pl.k == K_NONE) return DXA_OK;
   hipStream_t st = (hipStream_t)stream;
-  const bool vec_ok = al16(x) && al16(dy) && al16(dx) && (!w || al16(w)) && (!partial_dwdb || al16(partial_dwdb)) && (!residual || al16(residual));
-  if (launch_norm_bwd_fast<true>(dy, x, w, mean, rstd, dx, residual, w ? partial_dwdb : nullptr, rows, cols, dtype, w_dtype, vec_ok, st)) {
-    DXA_CHECK_LAUNCH();
-    return DXA_OK;
-  }
-  dim3 grid((unsigned)dxa_norm_bwd_blocks(rows));
   float* part = w ? partial_dwdb : nullptr;
-  if (dtype == DXA_BF16 && w_dtype == DXA_BF16) {
-    if (vec_ok && cols % 4 == 0) hipLaunchKernelGGL((layernorm_bwd_k<bf16_t, bf16_t, 4>), grid, dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, mean, rstd, (bf16_t*)dx, (const bf16_t*)residual, part, rows, cols);
-    else hipLaunchKernelGGL((layernorm_bwd_k<bf16_t, bf16_t, 1>), grid, dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, mean, rstd, (bf16_t*)dx, (const bf16_t*)residual, part, rows, cols);
-  } else if (dtype == DXA_BF16) {
-    if (vec_ok && cols % 4 == 0) hipLaunchKernelGGL((layernorm_bwd_k<bf16_t, float, 4>), grid, dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, (const float*)w, mean, rstd, (bf16_t*)dx, (const bf16_t*)residual, part, rows, cols);
-    else hipLaunchKernelGGL((layernorm_bwd_k<bf16_t, float, 1>), grid, dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, (const float*)w, mean, rstd, (bf16_t*)dx, (const bf16_t*)residual, part, rows, cols);
-  } else {
-    if (vec_ok && cols % 4 == 0) hipLaunchKernelGGL((layernorm_bwd_k<float, float, 4>), grid, dim3(256), 0, st, (const float*)dy, (const float*)x, (const float*)w, mean, rstd, (float*)dx, (const float*)residual, part, rows, cols);
-    else hipLaunchKernelGGL((layernorm_bwd_k<float, float, 1>), grid, dim3(256), 0, st, (const float*)dy, (const float*)x, (const float*)w, mean, rstd, (float*)dx, (const float*)residual, part, rows, cols);
+#define LN_BWD(K_, T_, TW_) hipLaunchKernelGGL(K_, pl.grid, dim3(pl.block), 0, st, (const T_*)dy, (const T_*)x, (const TW_*)w, mean, rstd, (T_*)dx, (const T_*)residual, part, rows, cols)
+  switch (pl.k) {
+    case K_LN_FAST: LN_BWD((norm_bwd_fast_k<bf16_t, bf16_t, true>), bf16_t, bf16_t); break;
+    case K_LN_FAST_BF: LN_BWD((norm_bwd_fast_k<bf16_t, float, true>), bf16_t, float); break;
+    case K_LN_FAST_FF: LN_BWD((norm_bwd_fast_k<float, float, true>), float, float); break;
+    case K_LN_BWD: LN_BWD((layernorm_bwd_k<bf16_t, bf16_t, 4>), bf16_t, bf16_t); break;
+    case K_LN_BWD_1: LN_BWD((layernorm_bwd_k<bf16_t, bf16_t, 1>), bf16_t, bf16_t); break;
+    case K_LN_BWD_BF4: LN_BWD((layernorm_bwd_k<bf16_t, float, 4>), bf16_t, float); break;
+    case K_LN_BWD_BF1: LN_BWD((layernorm_bwd_k<bf16_t, float, 1>), bf16_t, float); break;
+    case K_LN_BWD_FF4: LN_BWD((layernorm_bwd_k<float, float, 4>), float, float); break;
+    case K_LN_BWD_FF1: LN_BWD((layernorm_bwd_k<float, float, 1>), float, float); break;
+    default: return unplanned("dxa_layernorm_bwd", pl.k);
   }
+#undef LN_BWD
   DXA_CHECK_LAUNCH();
   return DXA_OK;
 }
@@ -943,17 +1314,23 @@ extern "C" int dxa_layernorm_bwd(const void* dy, const void* x, const void* w, c
 extern "C" int dxa_add_layernorm_fwd(const void* x, const void* res, const void* w, const void* b, void* y, float* mean,
                                      float* rstd, int64_t rows, int64_t cols, float eps, int dtype, int w_dtype,
                                      dxa_stream_t stream) {
-  if (int rc = check_norm_dtypes(dtype, w_dtype, "dxa_add_layernorm_fwd")) return rc;
-  DXA_CHECK_ARG(x && res && y, "dxa_add_layernorm_fwd: null x / res / y");
-  DXA_CHECK_ARG(rows >= 0 && cols > 0, "dxa_add_layernorm_fwd: bad sizes (rows %lld, cols %lld)", (long long)rows, (long long)cols);
-  if (rows == 0) return DXA_OK;
+  dxa_norm_desc d{};
+  d.entry = DXA_NORM_ADD_LAYERNORM_FWD; d.dtype = dtype; d.w_dtype = w_dtype; d.rows = rows; d.cols = cols;
+  d.x = x; d.x2 = res; d.w = w; d.b = b; d.y = y; d.mean = mean; d.rstd = rstd;
+  NormPlan pl;
+  if (int rc = norm_plan(&d, &pl)) return rc;
+  if (pl.k == K_NONE) return DXA_OK;
   hipStream_t st = (hipStream_t)stream;
-  const bool vec = al16(x) && al16(res) && al16(y) && (!w || al16(w)) && (!b || al16(b)) && cols % 4 == 0;
-  dim3 grid((unsigned)((rows + 3) / 4));
-#define ADD_LN_FWD(T_, TW_, V_) hipLaunchKernelGGL((layernorm_fwd_k<T_, TW_, V_, true>), grid, dim3(256), 0, st, (const T_*)x, (const TW_*)w, (const TW_*)b, (T_*)y, mean, rstd, rows, cols, eps, (const T_*)res)
-  if (dtype == DXA_BF16 && w_dtype == DXA_BF16) { if (vec) ADD_LN_FWD(bf16_t, bf16_t, 4); else ADD_LN_FWD(bf16_t, bf16_t, 1); }
-  else if (dtype == DXA_BF16) { if (vec) ADD_LN_FWD(bf16_t, float, 4); else ADD_LN_FWD(bf16_t, float, 1); }
-  else { if (vec) ADD_LN_FWD(float, float, 4); else ADD_LN_FWD(float, float, 1); }
+#define ADD_LN_FWD(T_, TW_, V_) hipLaunchKernelGGL((layernorm_fwd_k<T_, TW_, V_, true>), pl.grid, dim3(pl.block), 0, st, (const T_*)x, (const TW_*)w, (const TW_*)b, (T_*)y, mean, rstd, rows, cols, eps, (const T_*)res)
+  switch (pl.k) {
+    case K_ADDLN_FWD: ADD_LN_FWD(bf16_t, bf16_t, 4); break;
+    case K_ADDLN_FWD_1: ADD_LN_FWD(bf16_t, bf16_t, 1); break;
+    case K_ADDLN_FWD_BF4: ADD_LN_FWD(bf16_t, float, 4); break;
+    case K_ADDLN_FWD_BF1: ADD_LN_FWD(bf16_t, float, 1); break;
+    case K_ADDLN_FWD_FF4: ADD_LN_FWD(float, float, 4); break;
+    case K_ADDLN_FWD_FF1: ADD_LN_FWD(float, float, 1); break;
+    default: return unplanned("dxa_add_layernorm_fwd", pl.k);
+  }
 #undef ADD_LN_FWD
   DXA_CHECK_LAUNCH();
   return DXA_OK;
@@ -962,73 +1339,63 @@ extern "C" int dxa_add_layernorm_fwd(const void* x, const void* res, const void*
 extern "C" int dxa_add_layernorm_bwd(const void* dy, const void* x, const void* res, const void* w, const float* mean,
                                      const float* rstd, void* dx, float* partial_dwdb, int64_t rows, int64_t cols, int dtype,
                                      int w_dtype, dxa_stream_t stream) {
-  if (int rc = check_norm_dtypes(dtype, w_dtype, "dxa_add_layernorm_bwd")) return rc;
-  DXA_CHECK_ARG(dy && x && res && mean && rstd && dx, "dxa_add_layernorm_bwd: null dy / x / res / mean / rstd / dx");
-  DXA_CHECK_ARG(rows >= 0 && cols > 0, "dxa_add_layernorm_bwd: bad sizes (rows %lld, cols %lld)", (long long)rows, (long long)cols);
-  DXA_CHECK_ARG(!w || partial_dwdb, "dxa_add_layernorm_bwd: partial_dwdb required when w is given");
-  if (rows == 0) return DXA_OK;
+  dxa_norm_desc d{};
+  d.entry = DXA_NORM_ADD_LAYERNORM_BWD; d.dtype = dtype; d.w_dtype = w_dtype; d.rows = rows; d.cols = cols;
+  d.dy = dy; d.x = x; d.x2 = res; d.w = w; d.mean = mean; d.rstd = rstd; d.dx = dx; d.partial = partial_dwdb;
+  NormPlan pl;
+  if (int rc = norm_plan(&d, &pl)) return rc;
+  if (pl.k == K_NONE) return DXA_OK;
   hipStream_t st = (hipStream_t)stream;
-  const bool vec = al16(x) && al16(res) && al16(dy) && al16(dx) && (!w || al16(w)) && cols % 4 == 0;
-  dim3 grid((unsigned)dxa_norm_bwd_blocks(rows));
   float* part = w ? partial_dwdb : nullptr;
-#define ADD_LN_BWD(T_, TW_, V_) hipLaunchKernelGGL((layernorm_bwd_k<T_, TW_, V_, true>), grid, dim3(256), 0, st, (const T_*)dy, (const T_*)x, (const TW_*)w, mean, rstd, (T_*)dx, (const T_*)nullptr, part, rows, cols, (const T_*)res)
-  if (dtype == DXA_BF16 && w_dtype == DXA_BF16) { if (vec) ADD_LN_BWD(bf16_t, bf16_t, 4); else ADD_LN_BWD(bf16_t, bf16_t, 1); }
-  else if (dtype == DXA_BF16) { if (vec) ADD_LN_BWD(bf16_t, float, 4); else ADD_LN_BWD(bf16_t, float, 1); }
-  else { if (vec) ADD_LN_BWD(float, float, 4); else ADD_LN_BWD(float, float, 1); }
+#define ADD_LN_BWD(T_, TW_, V_) hipLaunchKernelGGL((layernorm_bwd_k<T_, TW_, V_, true>), pl.grid, dim3(pl.block), 0, st, (const T_*)dy, (const T_*)x, (const TW_*)w, mean, rstd, (T_*)dx, (const T_*)nullptr, part, rows, cols, (const T_*)res)
+  switch (pl.k) {
+    case K_ADDLN_BWD: ADD_LN_BWD(bf16_t, bf16_t, 4); break;
+    case K_ADDLN_BWD_1: ADD_LN_BWD(bf16_t, bf16_t, 1); break;
+    case K_ADDLN_BWD_BF4: ADD_LN_BWD(bf16_t, float, 4); break;
+    case K_ADDLN_BWD_BF1: ADD_LN_BWD(bf16_t, float, 1); break;
+    case K_ADDLN_BWD_FF4: ADD_LN_BWD(float, float, 4); break;
+    case K_ADDLN_BWD_FF1: ADD_LN_BWD(float, float, 1); break;
+    default: return unplanned("dxa_add_layernorm_bwd", pl.k);
+  }
 #undef ADD_LN_BWD
   DXA_CHECK_LAUNCH();
   return DXA_OK;
 }
 
 namespace {
-// arrival counters of colsum_fused_k: COLSUM_CNT ints per (device, stream), zeroed once (the kernel leaves them zeroed),
-// allocated on first use; under capture before they exist the counters are null and the two-launch form, which needs none, runs
-constexpr int COLSUM_CNT = 4096;
 StreamBlock colsum_counters(COLSUM_CNT * sizeof(int));
 }  // namespace
 
 extern "C" int dxa_colsum(const void* x, int64_t ld, float* out, int64_t rows, int64_t cols, int dtype,
                           int accumulate, float* scratch, size_t scratch_bytes, dxa_stream_t stream) {
-  DXA_CHECK_ARG(x && out && rows >= 0 && cols > 0 && ld >= cols, "dxa_colsum: bad args");
-  DXA_CHECK_ARG(dtype == DXA_F32 || dtype == DXA_BF16, "dxa_colsum: bad dtype");
+  dxa_norm_desc d{};
+  d.entry = DXA_NORM_COLSUM; d.dtype = dtype; d.rows = rows; d.cols = cols; d.ld = ld; d.accumulate = accumulate;
+  d.x = x; d.y = out; d.partial = scratch; d.partial_bytes = scratch_bytes;
+  d.have_counters = 1;                     // planned as if they existed; their absence is learnt below, where it can be
+  NormPlan pl;
+  if (int rc = norm_plan(&d, &pl)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  // row splits of >= 32 rows, at most 64 of them: the <= 512 partial rows of a norm backward become 16 x 14 workgroups
-  int nsplit = (int)((rows + 31) / 32);
-  if (nsplit < 1) nsplit = 1;
-  if (nsplit > 64) nsplit = 64;
-  DXA_CHECK_ARG(scratch && scratch_bytes >= (size_t)nsplit * cols * sizeof(float),
-                "dxa_colsum: scratch too small (need %zu bytes)", (size_t)nsplit * cols * sizeof(float));
-  dim3 grid((unsigned)((cols + 255) / 256), (unsigned)nsplit);
-  const size_t es = dtype == DXA_BF16 ? 2 : 4;
-  const int vec = ((reinterpret_cast<uintptr_t>(x) % (4 * es)) == 0) && (ld % 4 == 0);
-  if (rows <= 32) {
-    // a handful of rows: one launch, the block's sums are the result
-    dim3 g1((unsigned)((cols + 255) / 256), 1);
-    if (dtype == DXA_BF16)
-      hipLaunchKernelGGL((colsum_stage1_k<bf16_t, true>), g1, dim3(256), 0, st, (const bf16_t*)x, ld, out, rows, cols, vec, accumulate);
-    else
-      hipLaunchKernelGGL((colsum_stage1_k<float, true>), g1, dim3(256), 0, st, (const float*)x, ld, out, rows, cols, vec, accumulate);
-    DXA_CHECK_LAUNCH();
-    return DXA_OK;
-  }
   int* cnt = nullptr;
-  if (grid.x <= COLSUM_CNT) {
+  if (pl.k == K_CS_FUSED || pl.k == K_CS_FUSED_F) {
     if (int rc = colsum_counters.get(st, &cnt)) return rc;
+    if (cnt == nullptr) {                  // not allocated yet and the stream is capturing
+      d.have_counters = 0;
+      d.capturing = 1;
+      if (int rc = norm_plan(&d, &pl)) return rc;
+    }
   }
-  if (cnt != nullptr) {
-    if (dtype == DXA_BF16)
-      hipLaunchKernelGGL((colsum_fused_k<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)x, ld, scratch, out, rows, cols, vec, accumulate, cnt);
-    else
-      hipLaunchKernelGGL((colsum_fused_k<float>), grid, dim3(256), 0, st, (const float*)x, ld, scratch, out, rows, cols, vec, accumulate, cnt);
-    DXA_CHECK_LAUNCH();
-    return DXA_OK;
+  const int vec = pl.vec == 4;
+  switch (pl.k) {
+    case K_CS_DIRECT: hipLaunchKernelGGL((colsum_stage1_k<bf16_t, true>), pl.grid, dim3(pl.block), 0, st, (const bf16_t*)x, ld, out, rows, cols, vec, accumulate); break;
+    case K_CS_DIRECT_F: hipLaunchKernelGGL((colsum_stage1_k<float, true>), pl.grid, dim3(pl.block), 0, st, (const float*)x, ld, out, rows, cols, vec, accumulate); break;
+    case K_CS_FUSED: hipLaunchKernelGGL((colsum_fused_k<bf16_t>), pl.grid, dim3(pl.block), 0, st, (const bf16_t*)x, ld, scratch, out, rows, cols, vec, accumulate, cnt); break;
+    case K_CS_FUSED_F: hipLaunchKernelGGL((colsum_fused_k<float>), pl.grid, dim3(pl.block), 0, st, (const float*)x, ld, scratch, out, rows, cols, vec, accumulate, cnt); break;
+    case K_CS_STAGE1: hipLaunchKernelGGL((colsum_stage1_k<bf16_t>), pl.grid, dim3(pl.block), 0, st, (const bf16_t*)x, ld, scratch, rows, cols, vec); break;
+    case K_CS_STAGE1_F: hipLaunchKernelGGL((colsum_stage1_k<float>), pl.grid, dim3(pl.block), 0, st, (const float*)x, ld, scratch, rows, cols, vec); break;
+    default: return unplanned("dxa_colsum", pl.k);
   }
-  if (dtype == DXA_BF16)
-    hipLaunchKernelGGL((colsum_stage1_k<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)x, ld, scratch, rows, cols, vec);
-  else
-    hipLaunchKernelGGL((colsum_stage1_k<float>), grid, dim3(256), 0, st, (const float*)x, ld, scratch, rows, cols, vec);
-  hipLaunchKernelGGL(colsum_stage2_k, dim3((unsigned)((cols + 63) / 64)), dim3(64), 0, st, scratch, out, nsplit,
-                     cols, accumulate);    // one wave per 64 columns: 56 workgroups for 3584 columns instead of 14
+  if (pl.k2 == K_CS_STAGE2)
+    hipLaunchKernelGGL(colsum_stage2_k, pl.grid2, dim3(pl.block2), 0, st, scratch, out, pl.nsplit, cols, accumulate);
   DXA_CHECK_LAUNCH();
   return DXA_OK;
 }
@@ -1235,33 +1602,30 @@ __global__ __launch_bounds__(256) void ds_layernorm_bwd_k(const T* __restrict__ 
     for (int64_t c = threadIdx.x; c < 2 * cols; c += 256) slab[c] = ds_sums[c];
 }
 
-constexpr size_t DS_LN_MAX_LDS = 60 * 1024;      // partial sums of rows up to 7680 columns stay in LDS (default 64 KB ceiling)
-
-int check_downsample_args(const char* who, int64_t N, int64_t G, int64_t C) {
-  DXA_CHECK_ARG(N >= 0 && G > 0 && C > 0 && G <= 4096 && C <= (1 << 20) && N <= (1ll << 31),
-                "%s: bad sizes N=%lld G=%lld C=%lld", who, (long long)N, (long long)G, (long long)C);
-  return DXA_OK;
-}
-
 }  // namespace
 
 extern "C" int dxa_downsample_layernorm_fwd(const void* x, const void* w, const void* b, void* y, float* mean, float* rstd,
                                             int64_t N, int64_t G, int64_t C, float eps, int dtype, int w_dtype,
                                             dxa_stream_t stream) {
-  if (int rc = check_norm_dtypes(dtype, w_dtype, "dxa_downsample_layernorm_fwd")) return rc;
-  DXA_CHECK_ARG(x && y, "dxa_downsample_layernorm_fwd: null x / y");
-  if (int rc = check_downsample_args("dxa_downsample_layernorm_fwd", N, G, C)) return rc;
+  dxa_norm_desc d{};
+  d.entry = DXA_NORM_DOWNSAMPLE_FWD; d.dtype = dtype; d.w_dtype = w_dtype; d.rows = N; d.G = G; d.cols = C;
+  d.x = x; d.w = w; d.b = b; d.y = y; d.mean = mean; d.rstd = rstd;
+  NormPlan pl;
+  if (int rc = norm_plan(&d, &pl)) return rc;
+  if (pl.k == K_NONE) return DXA_OK;
   const int h = (int)((G + 1) / 2);
   const int64_t rows = N * h * h;
-  if (rows == 0) return DXA_OK;
   hipStream_t st = (hipStream_t)stream;
-  const int vec = dtype == DXA_BF16 ? 8 : 4;              // 16 bytes per access
-  const bool vec_ok = al16(x) && al16(y) && (!w || al16(w)) && (!b || al16(b)) && C % vec == 0;
-  dim3 grid((unsigned)((rows + 3) / 4));
-#define DS_FWD(T_, TW_, V_) hipLaunchKernelGGL((ds_layernorm_fwd_k<T_, TW_, V_>), grid, dim3(256), 0, st, (const T_*)x, (const TW_*)w, (const TW_*)b, (T_*)y, mean, rstd, rows, (int)G, h, (int)C, eps)
-  if (dtype == DXA_BF16 && w_dtype == DXA_BF16) { if (vec_ok) DS_FWD(bf16_t, bf16_t, 8); else DS_FWD(bf16_t, bf16_t, 1); }
-  else if (dtype == DXA_BF16) { if (vec_ok) DS_FWD(bf16_t, float, 8); else DS_FWD(bf16_t, float, 1); }
-  else { if (vec_ok) DS_FWD(float, float, 4); else DS_FWD(float, float, 1); }
+#define DS_FWD(T_, TW_, V_) hipLaunchKernelGGL((ds_layernorm_fwd_k<T_, TW_, V_>), pl.grid, dim3(pl.block), 0, st, (const T_*)x, (const TW_*)w, (const TW_*)b, (T_*)y, mean, rstd, rows, (int)G, h, (int)C, eps)
+  switch (pl.k) {
+    case K_DS_FWD: DS_FWD(bf16_t, bf16_t, 8); break;
+    case K_DS_FWD_1: DS_FWD(bf16_t, bf16_t, 1); break;
+    case K_DS_FWD_BF8: DS_FWD(bf16_t, float, 8); break;
+    case K_DS_FWD_BF1: DS_FWD(bf16_t, float, 1); break;
+    case K_DS_FWD_FF4: DS_FWD(float, float, 4); break;
+    case K_DS_FWD_FF1: DS_FWD(float, float, 1); break;
+    default: return unplanned("dxa_downsample_layernorm_fwd", pl.k);
+  }
 #undef DS_FWD
   DXA_CHECK_LAUNCH();
   return DXA_OK;
@@ -1270,25 +1634,26 @@ extern "C" int dxa_downsample_layernorm_fwd(const void* x, const void* w, const 
 extern "C" int dxa_downsample_layernorm_bwd(const void* dy, const void* x, const void* w, const float* mean,
                                             const float* rstd, void* dx, float* partial_dwdb, int64_t N, int64_t G,
                                             int64_t C, int dtype, int w_dtype, dxa_stream_t stream) {
-  if (int rc = check_norm_dtypes(dtype, w_dtype, "dxa_downsample_layernorm_bwd")) return rc;
-  DXA_CHECK_ARG(dy && x && mean && rstd && dx, "dxa_downsample_layernorm_bwd: null dy / x / mean / rstd / dx");
-  DXA_CHECK_ARG(!w || partial_dwdb, "dxa_downsample_layernorm_bwd: partial_dwdb required when w is given");
-  if (int rc = check_downsample_args("dxa_downsample_layernorm_bwd", N, G, C)) return rc;
+  dxa_norm_desc d{};
+  d.entry = DXA_NORM_DOWNSAMPLE_BWD; d.dtype = dtype; d.w_dtype = w_dtype; d.rows = N; d.G = G; d.cols = C;
+  d.dy = dy; d.x = x; d.w = w; d.mean = mean; d.rstd = rstd; d.dx = dx; d.partial = partial_dwdb;
+  NormPlan pl;
+  if (int rc = norm_plan(&d, &pl)) return rc;
+  if (pl.k == K_NONE) return DXA_OK;
   const int h = (int)((G + 1) / 2);
   const int64_t rows = N * h * h;
-  if (rows == 0) return DXA_OK;
   hipStream_t st = (hipStream_t)stream;
-  const int vec = dtype == DXA_BF16 ? 8 : 4;
-  const bool vec_ok = al16(x) && al16(dy) && al16(dx) && (!w || al16(w)) && C % vec == 0;
   float* part = w ? partial_dwdb : nullptr;
-  const size_t sums = part ? (size_t)8 * C * sizeof(float) : 0;
-  const int use_lds = sums > 0 && sums <= DS_LN_MAX_LDS;
-  const size_t lds = use_lds ? sums : 0;
-  dim3 grid((unsigned)dxa_norm_bwd_blocks(rows));
-#define DS_BWD(T_, TW_, V_) hipLaunchKernelGGL((ds_layernorm_bwd_k<T_, TW_, V_>), grid, dim3(256), lds, st, (const T_*)dy, (const T_*)x, (const TW_*)w, mean, rstd, (T_*)dx, part, rows, (int)G, h, (int)C, use_lds)
-  if (dtype == DXA_BF16 && w_dtype == DXA_BF16) { if (vec_ok) DS_BWD(bf16_t, bf16_t, 8); else DS_BWD(bf16_t, bf16_t, 1); }
-  else if (dtype == DXA_BF16) { if (vec_ok) DS_BWD(bf16_t, float, 8); else DS_BWD(bf16_t, float, 1); }
-  else { if (vec_ok) DS_BWD(float, float, 4); else DS_BWD(float, float, 1); }
+#define DS_BWD(T_, TW_, V_) hipLaunchKernelGGL((ds_layernorm_bwd_k<T_, TW_, V_>), pl.grid, dim3(pl.block), pl.lds, st, (const T_*)dy, (const T_*)x, (const TW_*)w, mean, rstd, (T_*)dx, part, rows, (int)G, h, (int)C, pl.use_lds)
+  switch (pl.k) {
+    case K_DS_BWD: DS_BWD(bf16_t, bf16_t, 8); break;
+    case K_DS_BWD_1: DS_BWD(bf16_t, bf16_t, 1); break;
+    case K_DS_BWD_BF8: DS_BWD(bf16_t, float, 8); break;
+    case K_DS_BWD_BF1: DS_BWD(bf16_t, float, 1); break;
+    case K_DS_BWD_FF4: DS_BWD(float, float, 4); break;
+    case K_DS_BWD_FF1: DS_BWD(float, float, 1); break;
+    default: return unplanned("dxa_downsample_layernorm_bwd", pl.k);
+  }
 #undef DS_BWD
   DXA_CHECK_LAUNCH();
   return DXA_OK;
@@ -1573,78 +1938,59 @@ __global__ __launch_bounds__(256) void adarms_fold_k(const float* __restrict__ p
   else stf<T>(out_b + s * ld_b + (j - n_a), acc);
 }
 
-constexpr int ADARMS_BWD_MAX_GROUPS = 128;
-
-// widest access every pointer and stride allows: 8 (bf16 only), 4 or 1 elements
-int adarms_vec(int dtype, int64_t cols, int64_t gate_ld, std::initializer_list<const void*> ptrs) {
-  const size_t es = dtype == DXA_BF16 ? 2 : 4;
-  int vec = dtype == DXA_BF16 ? 8 : 4;
-  for (; vec > 1; vec >>= 1) {
-    bool ok = cols % vec == 0 && gate_ld % vec == 0;
-    for (const void* p : ptrs) ok = ok && (reinterpret_cast<uintptr_t>(p) % (vec * es)) == 0;
-    if (ok) break;
-  }
-  return vec;
-}
-
-int check_adarms(const char* who, int64_t rows, int64_t rps, int64_t cols, int dtype) {
-  DXA_CHECK_ARG(dtype == DXA_F32 || dtype == DXA_BF16, "%s: unsupported dtype %d", who, dtype);
-  DXA_CHECK_ARG(cols > 0 && rows >= 0 && rps > 0, "%s: bad sizes (rows %lld, rows_per_sample %lld, cols %lld)", who, (long long)rows,
-                (long long)rps, (long long)cols);
-  DXA_CHECK_ARG(rows % rps == 0, "%s: %lld rows are not a whole number of samples of %lld rows", who, (long long)rows, (long long)rps);
-  DXA_CHECK_ARG(rows / rps <= 65535, "%s: more than 65535 samples", who);
-  return DXA_OK;
-}
-
 }  // namespace
-
-extern "C" int dxa_adarms_bwd_groups(int64_t rows_per_sample) {
-  int64_t g = (rows_per_sample + 3) / 4;
-  if (g < 1) g = 1;
-  if (g > ADARMS_BWD_MAX_GROUPS) g = ADARMS_BWD_MAX_GROUPS;
-  return (int)g;
-}
 
 extern "C" int dxa_adarms_fwd(const void* x, const void* branch, const void* gate_prev, int64_t gate_ld, const void* mod,
                               void* r_out, void* y, float* rstd, int64_t rows, int64_t rows_per_sample, int64_t cols, float eps,
                               int dtype, dxa_stream_t stream) {
-  if (int rc = check_adarms("dxa_adarms_fwd", rows, rows_per_sample, cols, dtype)) return rc;
-  DXA_CHECK_ARG(x && mod && y, "dxa_adarms_fwd: null x / mod / y");
-  DXA_CHECK_ARG(!branch || (gate_prev && r_out && gate_ld >= cols), "dxa_adarms_fwd: a branch needs gate_prev, r_out and gate_ld >= cols");
-  if (rows == 0) return DXA_OK;
+  dxa_norm_desc d{};
+  d.entry = DXA_NORM_ADARMS_FWD; d.dtype = dtype; d.rows = rows; d.rows_per_sample = rows_per_sample; d.cols = cols; d.gate_ld = gate_ld;
+  d.x = x; d.x2 = branch; d.gate = gate_prev; d.mod = mod; d.aux = r_out; d.y = y; d.rstd = rstd;
+  NormPlan pl;
+  if (int rc = norm_plan(&d, &pl)) return rc;
+  if (pl.k == K_NONE) return DXA_OK;
   hipStream_t st = (hipStream_t)stream;
-  const int vec = adarms_vec(dtype, cols, branch ? gate_ld : 0, {x, mod, y, branch, branch ? gate_prev : nullptr, branch ? r_out : nullptr});
-  dim3 grid((unsigned)((rows + 3) / 4));
-#define ADARMS_FWD(K_, ...) do { \
-    if (branch) hipLaunchKernelGGL((K_<__VA_ARGS__ true>), grid, dim3(256), 0, st, (const T_*)x, (const T_*)branch, (const T_*)gate_prev, gate_ld, (const T_*)mod, (T_*)r_out, (T_*)y, rstd, rows, rows_per_sample, cols, eps); \
-    else hipLaunchKernelGGL((K_<__VA_ARGS__ false>), grid, dim3(256), 0, st, (const T_*)x, (const T_*)nullptr, (const T_*)nullptr, (int64_t)0, (const T_*)mod, (T_*)nullptr, (T_*)y, rstd, rows, rows_per_sample, cols, eps); } while (0)
-  if (dtype == DXA_BF16) {
-    typedef bf16_t T_;
-    if (vec == 8 && cols <= 8192) ADARMS_FWD(adarms_fwd_fast_k, );
-    else if (vec == 8) ADARMS_FWD(adarms_fwd_k, bf16_t, 8,);
-    else if (vec == 4) ADARMS_FWD(adarms_fwd_k, bf16_t, 4,);
-    else ADARMS_FWD(adarms_fwd_k, bf16_t, 1,);
-  } else {
-    typedef float T_;
-    if (vec == 4) ADARMS_FWD(adarms_fwd_k, float, 4,);
-    else ADARMS_FWD(adarms_fwd_k, float, 1,);
+#define ADARMS_FWD_G(K_, T_) hipLaunchKernelGGL(K_, pl.grid, dim3(pl.block), 0, st, (const T_*)x, (const T_*)branch, (const T_*)gate_prev, gate_ld, (const T_*)mod, (T_*)r_out, (T_*)y, rstd, rows, rows_per_sample, cols, eps)
+#define ADARMS_FWD(K_, T_) hipLaunchKernelGGL(K_, pl.grid, dim3(pl.block), 0, st, (const T_*)x, (const T_*)nullptr, (const T_*)nullptr, (int64_t)0, (const T_*)mod, (T_*)nullptr, (T_*)y, rstd, rows, rows_per_sample, cols, eps)
+  switch (pl.k) {
+    case K_AR_FWD_FAST: ADARMS_FWD((adarms_fwd_fast_k<false>), bf16_t); break;
+    case K_AR_FWD_FAST_G: ADARMS_FWD_G((adarms_fwd_fast_k<true>), bf16_t); break;
+    case K_AR_FWD: ADARMS_FWD((adarms_fwd_k<bf16_t, 8, false>), bf16_t); break;
+    case K_AR_FWD_B8G: ADARMS_FWD_G((adarms_fwd_k<bf16_t, 8, true>), bf16_t); break;
+    case K_AR_FWD_B4: ADARMS_FWD((adarms_fwd_k<bf16_t, 4, false>), bf16_t); break;
+    case K_AR_FWD_B4G: ADARMS_FWD_G((adarms_fwd_k<bf16_t, 4, true>), bf16_t); break;
+    case K_AR_FWD_B1: ADARMS_FWD((adarms_fwd_k<bf16_t, 1, false>), bf16_t); break;
+    case K_AR_FWD_B1G: ADARMS_FWD_G((adarms_fwd_k<bf16_t, 1, true>), bf16_t); break;
+    case K_AR_FWD_F4: ADARMS_FWD((adarms_fwd_k<float, 4, false>), float); break;
+    case K_AR_FWD_F4G: ADARMS_FWD_G((adarms_fwd_k<float, 4, true>), float); break;
+    case K_AR_FWD_F1: ADARMS_FWD((adarms_fwd_k<float, 1, false>), float); break;
+    case K_AR_FWD_F1G: ADARMS_FWD_G((adarms_fwd_k<float, 1, true>), float); break;
+    default: return unplanned("dxa_adarms_fwd", pl.k);
   }
 #undef ADARMS_FWD
+#undef ADARMS_FWD_G
   DXA_CHECK_LAUNCH();
   return DXA_OK;
 }
 
 extern "C" int dxa_gated_residual_fwd(const void* x, const void* branch, const void* gate, int64_t gate_ld, void* y, int64_t rows,
                                       int64_t rows_per_sample, int64_t cols, int dtype, dxa_stream_t stream) {
-  if (int rc = check_adarms("dxa_gated_residual_fwd", rows, rows_per_sample, cols, dtype)) return rc;
-  DXA_CHECK_ARG(x && branch && gate && y && gate_ld >= cols, "dxa_gated_residual_fwd: null x / branch / gate / y, or gate_ld < cols");
-  if (rows == 0) return DXA_OK;
+  dxa_norm_desc d{};
+  d.entry = DXA_NORM_GATED_RESIDUAL_FWD; d.dtype = dtype; d.rows = rows; d.rows_per_sample = rows_per_sample; d.cols = cols;
+  d.gate_ld = gate_ld; d.x = x; d.x2 = branch; d.gate = gate; d.y = y;
+  NormPlan pl;
+  if (int rc = norm_plan(&d, &pl)) return rc;
+  if (pl.k == K_NONE) return DXA_OK;
   hipStream_t st = (hipStream_t)stream;
-  const int vec = adarms_vec(dtype, cols, gate_ld, {x, branch, gate, y});
-  dim3 grid((unsigned)((rows + 3) / 4));
-#define GATED_FWD(T_, V_) hipLaunchKernelGGL((gated_residual_fwd_k<T_, V_>), grid, dim3(256), 0, st, (const T_*)x, (const T_*)branch, (const T_*)gate, gate_ld, (T_*)y, rows, rows_per_sample, cols)
-  if (dtype == DXA_BF16) { if (vec == 8) GATED_FWD(bf16_t, 8); else if (vec == 4) GATED_FWD(bf16_t, 4); else GATED_FWD(bf16_t, 1); }
-  else { if (vec == 4) GATED_FWD(float, 4); else GATED_FWD(float, 1); }
+#define GATED_FWD(T_, V_) hipLaunchKernelGGL((gated_residual_fwd_k<T_, V_>), pl.grid, dim3(pl.block), 0, st, (const T_*)x, (const T_*)branch, (const T_*)gate, gate_ld, (T_*)y, rows, rows_per_sample, cols)
+  switch (pl.k) {
+    case K_GR_FWD: GATED_FWD(bf16_t, 8); break;
+    case K_GR_FWD_B4: GATED_FWD(bf16_t, 4); break;
+    case K_GR_FWD_B1: GATED_FWD(bf16_t, 1); break;
+    case K_GR_FWD_F4: GATED_FWD(float, 4); break;
+    case K_GR_FWD_F1: GATED_FWD(float, 1); break;
+    default: return unplanned("dxa_gated_residual_fwd", pl.k);
+  }
 #undef GATED_FWD
   DXA_CHECK_LAUNCH();
   return DXA_OK;
@@ -1654,31 +2000,38 @@ extern "C" int dxa_adarms_bwd(const void* dy, const void* r, const void* mod, co
                               void* dmod, const void* branch, const void* gate_prev, int64_t gate_ld, void* dbranch,
                               void* dgate_prev, int64_t dgate_ld, float* partial, size_t partial_bytes, int64_t rows,
                               int64_t rows_per_sample, int64_t cols, int dtype, dxa_stream_t stream) {
-  if (int rc = check_adarms("dxa_adarms_bwd", rows, rows_per_sample, cols, dtype)) return rc;
-  DXA_CHECK_ARG(dy && r && mod && rstd && dr && dmod && partial, "dxa_adarms_bwd: null dy / r / mod / rstd / dr / dmod / partial");
-  DXA_CHECK_ARG(!branch || (gate_prev && dbranch && dgate_prev && gate_ld >= cols && dgate_ld >= cols),
-                "dxa_adarms_bwd: a branch needs gate_prev, dbranch, dgate_prev and gate_ld, dgate_ld >= cols");
-  if (rows == 0) return DXA_OK;
-  const int64_t B = rows / rows_per_sample;
-  const int groups = dxa_adarms_bwd_groups(rows_per_sample);
-  const int ns = branch ? 3 : 2;
-  const size_t need = (size_t)B * groups * 4 * ns * cols * sizeof(float);
-  DXA_CHECK_ARG(partial_bytes >= need, "dxa_adarms_bwd: partial too small (need %zu bytes)", need);
+  dxa_norm_desc d{};
+  d.entry = DXA_NORM_ADARMS_BWD; d.dtype = dtype; d.rows = rows; d.rows_per_sample = rows_per_sample; d.cols = cols;
+  d.gate_ld = gate_ld; d.dgate_ld = dgate_ld; d.partial_bytes = partial_bytes;
+  d.dy = dy; d.x = r; d.mod = mod; d.rstd = rstd; d.residual = residual; d.dx = dr; d.dmod = dmod; d.x2 = branch; d.gate = gate_prev;
+  d.aux = dbranch; d.dgate = dgate_prev; d.partial = partial;
+  NormPlan pl;
+  if (int rc = norm_plan(&d, &pl)) return rc;
+  if (pl.k == K_NONE) return DXA_OK;
   hipStream_t st = (hipStream_t)stream;
-  const int vec = adarms_vec(dtype, cols, branch ? gate_ld : 0, {dy, r, mod, dr, residual, branch, branch ? gate_prev : nullptr, branch ? dbranch : nullptr});
-  dim3 grid((unsigned)groups, (unsigned)B);
-#define ADARMS_BWD(T_, V_) do { \
-    if (branch) hipLaunchKernelGGL((adarms_bwd_k<T_, V_, true>), grid, dim3(256), 0, st, (const T_*)dy, (const T_*)r, (const T_*)mod, rstd, (const T_*)residual, (T_*)dr, (const T_*)branch, (const T_*)gate_prev, gate_ld, (T_*)dbranch, partial, rows_per_sample, cols); \
-    else hipLaunchKernelGGL((adarms_bwd_k<T_, V_, false>), grid, dim3(256), 0, st, (const T_*)dy, (const T_*)r, (const T_*)mod, rstd, (const T_*)residual, (T_*)dr, (const T_*)nullptr, (const T_*)nullptr, (int64_t)0, (T_*)nullptr, partial, rows_per_sample, cols); } while (0)
-  if (dtype == DXA_BF16) { if (vec == 8) ADARMS_BWD(bf16_t, 8); else if (vec == 4) ADARMS_BWD(bf16_t, 4); else ADARMS_BWD(bf16_t, 1); }
-  else { if (vec == 4) ADARMS_BWD(float, 4); else ADARMS_BWD(float, 1); }
+  const int nrow = (int)pl.grid.x * 4;
+#define ADARMS_BWD_G(T_, V_) hipLaunchKernelGGL((adarms_bwd_k<T_, V_, true>), pl.grid, dim3(pl.block), 0, st, (const T_*)dy, (const T_*)r, (const T_*)mod, rstd, (const T_*)residual, (T_*)dr, (const T_*)branch, (const T_*)gate_prev, gate_ld, (T_*)dbranch, partial, rows_per_sample, cols)
+#define ADARMS_BWD(T_, V_) hipLaunchKernelGGL((adarms_bwd_k<T_, V_, false>), pl.grid, dim3(pl.block), 0, st, (const T_*)dy, (const T_*)r, (const T_*)mod, rstd, (const T_*)residual, (T_*)dr, (const T_*)nullptr, (const T_*)nullptr, (int64_t)0, (T_*)nullptr, partial, rows_per_sample, cols)
+  switch (pl.k) {
+    case K_AR_BWD: ADARMS_BWD(bf16_t, 8); break;
+    case K_AR_BWD_B8G: ADARMS_BWD_G(bf16_t, 8); break;
+    case K_AR_BWD_B4: ADARMS_BWD(bf16_t, 4); break;
+    case K_AR_BWD_B4G: ADARMS_BWD_G(bf16_t, 4); break;
+    case K_AR_BWD_B1: ADARMS_BWD(bf16_t, 1); break;
+    case K_AR_BWD_B1G: ADARMS_BWD_G(bf16_t, 1); break;
+    case K_AR_BWD_F4: ADARMS_BWD(float, 4); break;
+    case K_AR_BWD_F4G: ADARMS_BWD_G(float, 4); break;
+    case K_AR_BWD_F1: ADARMS_BWD(float, 1); break;
+    case K_AR_BWD_F1G: ADARMS_BWD_G(float, 1); break;
+    default: return unplanned("dxa_adarms_bwd", pl.k);
+  }
 #undef ADARMS_BWD
-  const int64_t n = (int64_t)ns * cols;
-  dim3 fgrid((unsigned)((n + 255) / 256), (unsigned)B);
-  if (dtype == DXA_BF16)
-    hipLaunchKernelGGL((adarms_fold_k<bf16_t>), fgrid, dim3(256), 0, st, partial, groups * 4, n, (bf16_t*)dmod, 3 * cols, 2 * cols, (bf16_t*)dgate_prev, dgate_ld);
+#undef ADARMS_BWD_G
+  const int64_t n = (int64_t)(branch ? 3 : 2) * cols;
+  if (pl.k2 == K_FOLD)
+    hipLaunchKernelGGL((adarms_fold_k<bf16_t>), pl.grid2, dim3(pl.block2), 0, st, partial, nrow, n, (bf16_t*)dmod, 3 * cols, 2 * cols, (bf16_t*)dgate_prev, dgate_ld);
   else
-    hipLaunchKernelGGL((adarms_fold_k<float>), fgrid, dim3(256), 0, st, partial, groups * 4, n, (float*)dmod, 3 * cols, 2 * cols, (float*)dgate_prev, dgate_ld);
+    hipLaunchKernelGGL((adarms_fold_k<float>), pl.grid2, dim3(pl.block2), 0, st, partial, nrow, n, (float*)dmod, 3 * cols, 2 * cols, (float*)dgate_prev, dgate_ld);
   DXA_CHECK_LAUNCH();
   return DXA_OK;
 }
@@ -1686,26 +2039,29 @@ extern "C" int dxa_adarms_bwd(const void* dy, const void* r, const void* mod, co
 extern "C" int dxa_gated_residual_bwd(const void* dy, const void* branch, const void* gate, int64_t gate_ld, void* dbranch,
                                       void* dgate, int64_t dgate_ld, float* partial, size_t partial_bytes, int64_t rows,
                                       int64_t rows_per_sample, int64_t cols, int dtype, dxa_stream_t stream) {
-  if (int rc = check_adarms("dxa_gated_residual_bwd", rows, rows_per_sample, cols, dtype)) return rc;
-  DXA_CHECK_ARG(dy && branch && gate && dbranch && dgate && partial, "dxa_gated_residual_bwd: null dy / branch / gate / dbranch / dgate / partial");
-  DXA_CHECK_ARG(gate_ld >= cols && dgate_ld >= cols, "dxa_gated_residual_bwd: gate_ld / dgate_ld < cols");
-  if (rows == 0) return DXA_OK;
-  const int64_t B = rows / rows_per_sample;
-  const int groups = dxa_adarms_bwd_groups(rows_per_sample);
-  const size_t need = (size_t)B * groups * 4 * cols * sizeof(float);
-  DXA_CHECK_ARG(partial_bytes >= need, "dxa_gated_residual_bwd: partial too small (need %zu bytes)", need);
+  dxa_norm_desc d{};
+  d.entry = DXA_NORM_GATED_RESIDUAL_BWD; d.dtype = dtype; d.rows = rows; d.rows_per_sample = rows_per_sample; d.cols = cols;
+  d.gate_ld = gate_ld; d.dgate_ld = dgate_ld; d.partial_bytes = partial_bytes;
+  d.dy = dy; d.x2 = branch; d.gate = gate; d.dx = dbranch; d.dgate = dgate; d.partial = partial;
+  NormPlan pl;
+  if (int rc = norm_plan(&d, &pl)) return rc;
+  if (pl.k == K_NONE) return DXA_OK;
   hipStream_t st = (hipStream_t)stream;
-  const int vec = adarms_vec(dtype, cols, gate_ld, {dy, branch, gate, dbranch});
-  dim3 grid((unsigned)groups, (unsigned)B);
-#define GATED_BWD(T_, V_) hipLaunchKernelGGL((gated_residual_bwd_k<T_, V_>), grid, dim3(256), 0, st, (const T_*)dy, (const T_*)branch, (const T_*)gate, gate_ld, (T_*)dbranch, partial, rows_per_sample, cols)
-  if (dtype == DXA_BF16) { if (vec == 8) GATED_BWD(bf16_t, 8); else if (vec == 4) GATED_BWD(bf16_t, 4); else GATED_BWD(bf16_t, 1); }
-  else { if (vec == 4) GATED_BWD(float, 4); else GATED_BWD(float, 1); }
+  const int nrow = (int)pl.grid.x * 4;
+#define GATED_BWD(T_, V_) hipLaunchKernelGGL((gated_residual_bwd_k<T_, V_>), pl.grid, dim3(pl.block), 0, st, (const T_*)dy, (const T_*)branch, (const T_*)gate, gate_ld, (T_*)dbranch, partial, rows_per_sample, cols)
+  switch (pl.k) {
+    case K_GR_BWD: GATED_BWD(bf16_t, 8); break;
+    case K_GR_BWD_B4: GATED_BWD(bf16_t, 4); break;
+    case K_GR_BWD_B1: GATED_BWD(bf16_t, 1); break;
+    case K_GR_BWD_F4: GATED_BWD(float, 4); break;
+    case K_GR_BWD_F1: GATED_BWD(float, 1); break;
+    default: return unplanned("dxa_gated_residual_bwd", pl.k);
+  }
 #undef GATED_BWD
-  dim3 fgrid((unsigned)((cols + 255) / 256), (unsigned)B);
-  if (dtype == DXA_BF16)
-    hipLaunchKernelGGL((adarms_fold_k<bf16_t>), fgrid, dim3(256), 0, st, partial, groups * 4, cols, (bf16_t*)nullptr, (int64_t)0, (int64_t)0, (bf16_t*)dgate, dgate_ld);
+  if (pl.k2 == K_FOLD)
+    hipLaunchKernelGGL((adarms_fold_k<bf16_t>), pl.grid2, dim3(pl.block2), 0, st, partial, nrow, cols, (bf16_t*)nullptr, (int64_t)0, (int64_t)0, (bf16_t*)dgate, dgate_ld);
   else
-    hipLaunchKernelGGL((adarms_fold_k<float>), fgrid, dim3(256), 0, st, partial, groups * 4, cols, (float*)nullptr, (int64_t)0, (int64_t)0, (float*)dgate, dgate_ld);
+    hipLaunchKernelGGL((adarms_fold_k<float>), pl.grid2, dim3(pl.block2), 0, st, partial, nrow, cols, (float*)nullptr, (int64_t)0, (int64_t)0, (float*)dgate, dgate_ld);
   DXA_CHECK_LAUNCH();
   return DXA_OK;
 }

@@ -476,6 +476,28 @@ def norm_bwd_blocks(rows: int) -> int:
     return int(lib.dxa_norm_bwd_blocks(rows))
 
 
+def norm_plan(entry: str, **fields) -> dict:
+    """the launch dxa_norm_plan gives a call of dxa_<entry> (L.NORM_ENTRIES); ``fields`` are dxa_norm_desc's by name, a pointer
+    role as a tensor, an address (int) or None.  Host arithmetic only: answers without a GPU."""
+    d = L.NormDesc()
+    d.entry = L.NORM_ENTRIES.index(entry)
+    for k, v in fields.items():
+        setattr(d, k, _ptr(v) if isinstance(v, torch.Tensor) else v)
+    info = L.NormPlanInfo()
+    L.check(lib.dxa_norm_plan(C.byref(d), C.byref(info)), "dxa_norm_plan")
+    s = lambda p: p.decode() if p is not None else None
+    return {"kernel": s(info.kernel), "kernel2": s(info.kernel2), "mode": s(info.mode), "vec": info.vec, "grid": tuple(info.grid),
+            "block": info.block, "lds": info.lds, "nsplit": info.nsplit, "trips": info.trips}
+
+
+def norm_kernel_names() -> list:
+    """every instantiation the norm launchers can launch (dxa_norm_kernel_name)"""
+    names = []
+    while lib.dxa_norm_kernel_name(len(names)) is not None:
+        names.append(lib.dxa_norm_kernel_name(len(names)).decode())
+    return names
+
+
 def _residual2d(residual, x2):
     if residual is None:
         return None

@@ -400,6 +400,55 @@ int dxa_adarms_bwd_groups(int64_t rows_per_sample);
  * Deterministic two-stage reduction; scratch >= min(64, ceil(rows/32)) * cols floats. */
 int dxa_colsum(const void* x, int64_t ld, float* out, int64_t rows, int64_t cols, int dtype,
                int accumulate, float* scratch, size_t scratch_bytes, dxa_stream_t stream);
+/* What a norm entry point would launch, without launching it: its argument checks (same status, same dxa_last_error text) and
+ * the kernel instantiation the launcher takes.  Host arithmetic only: no pointer is dereferenced (they count by their alignment
+ * alone), nothing is allocated and no GPU is needed.  The entry points launch from this plan.  The descriptor holds the entry
+ * point's arguments by role; a role an entry point does not have is ignored. */
+enum dxa_norm_entry {
+  DXA_NORM_RMSNORM_FWD = 0, DXA_NORM_RMSNORM_BWD, DXA_NORM_LAYERNORM_FWD, DXA_NORM_LAYERNORM_BWD, DXA_NORM_ADD_LAYERNORM_FWD,
+  DXA_NORM_ADD_LAYERNORM_BWD, DXA_NORM_COLSUM, DXA_NORM_DOWNSAMPLE_FWD, DXA_NORM_DOWNSAMPLE_BWD, DXA_NORM_ADARMS_FWD,
+  DXA_NORM_ADARMS_BWD, DXA_NORM_GATED_RESIDUAL_FWD, DXA_NORM_GATED_RESIDUAL_BWD
+};
+typedef struct dxa_norm_desc {
+  int32_t entry;            /* dxa_norm_entry */
+  int32_t dtype, w_dtype;   /* w_dtype: the norms with a gain only */
+  int32_t accumulate;       /* dxa_colsum */
+  int64_t rows, cols;       /* downsample: N and C */
+  int64_t G;                /* downsample: the token grid */
+  int64_t rows_per_sample;  /* adarms / gated residual */
+  int64_t ld, gate_ld, dgate_ld; /* dxa_colsum's row stride; the gate strides of adarms / gated residual */
+  size_t partial_bytes;     /* dxa_colsum's scratch_bytes; adarms / gated residual backward */
+  const void* x;            /* adarms backward: r */
+  const void* x2;           /* add_layernorm: res; adarms / gated residual: branch */
+  const void* w;
+  const void* b;
+  const void* y;            /* dxa_colsum: out */
+  const void* dy;
+  const void* dx;           /* adarms backward: dr; gated residual backward: dbranch */
+  const void* residual;
+  const void* partial;      /* dxa_colsum: scratch */
+  const void* mean;
+  const void* rstd;
+  const void* gate;         /* adarms: gate_prev */
+  const void* mod;
+  const void* aux;          /* adarms forward: r_out; adarms backward: dbranch */
+  const void* dgate;        /* adarms backward: dgate_prev */
+  const void* dmod;
+  int32_t have_counters;    /* dxa_colsum: the stream's arrival counters of the fused kernel exist */
+  int32_t capturing;        /* dxa_colsum: the stream is capturing (the counters cannot be allocated) */
+} dxa_norm_desc;
+typedef struct dxa_norm_plan_info {
+  const char* kernel;       /* the instantiation, e.g. "rmsnorm_bwd_split_k<float,8,4>" (static storage); NULL: no launch */
+  const char* kernel2;      /* the second launch (colsum_stage2_k, adarms_fold_k<T>), else NULL */
+  const char* mode;         /* dxa_colsum: "direct", "fused" or "two_launch"; else NULL */
+  int32_t vec;              /* elements per access of the row operands */
+  int32_t grid[3], block, lds; /* of the first launch; lds: dynamic LDS bytes */
+  int32_t nsplit;           /* dxa_colsum: row splits */
+  int64_t trips;            /* trips of the row loop per wave (row slot); 1 where a wave owns one row */
+} dxa_norm_plan_info;
+int dxa_norm_plan(const dxa_norm_desc* d, dxa_norm_plan_info* out);
+/* name of entry i of the table dxa_norm_plan_info.kernel points into, NULL past its end */
+const char* dxa_norm_kernel_name(int i);
 
 /* ------------------------------------------------------------------------------------------------
  * RoPE (rotate-half, HF:qwen2/modeling_qwen2.py:107-140) fused with the QKV split into head-major

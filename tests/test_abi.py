@@ -38,7 +38,8 @@ def test_struct_layouts_match_header_field_order():
     for cname, cls in (("dxa_gemm_desc", L.GemmDesc), ("dxa_attn_desc", L.AttnDesc), ("dxa_adamw_desc", L.AdamWDesc),
                        ("dxa_decode_desc", L.DecodeDesc), ("dxa_split3_op", L.Split3Op),
                        ("dxa_gemm_step_info", L.GemmStepInfo), ("dxa_gemm_plan_info", L.GemmPlanInfo),
-                       ("dxa_attn_plan_info", L.AttnPlanInfo)):
+                       ("dxa_attn_plan_info", L.AttnPlanInfo), ("dxa_norm_desc", L.NormDesc),
+                       ("dxa_norm_plan_info", L.NormPlanInfo)):
         body = re.search(r"typedef struct " + cname + r" \{(.*?)\} " + cname, src, flags=re.S).group(1)
         body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
         names = []

@@ -31,6 +31,26 @@ def tol(dtype):
     return (1e-5, 1e-5) if dtype == torch.float32 else (1.0 / 64, 1e-2)
 
 
+# the path each width takes, as the docstring states it: bf16 forward kernel, then elements per access for bf16 and for fp32
+PATHS = {64: ("adarms_fwd_fast_k", 8, 4), 1024: ("adarms_fwd_fast_k", 8, 4), 20: ("adarms_fwd_k", 4, 4), 21: ("adarms_fwd_k", 1, 1),
+         8200: ("adarms_fwd_k", 8, 4)}
+
+
+def assert_path(entry, dtype, shape, gated, **ops):
+    """dxa_norm_plan of the call just made takes the path PATHS names for its width"""
+    B, rps, d = shape
+    fam, vb, vf = PATHS[d]
+    bf = dtype == torch.bfloat16
+    vec, T, g = (vb if bf else vf), ("bf16" if bf else "float"), ("true" if gated else "false")
+    want = {"adarms_fwd": (f"adarms_fwd_fast_k<{g}>" if bf and fam == "adarms_fwd_fast_k" else f"adarms_fwd_k<{T},{vec},{g}>"),
+            "adarms_bwd": f"adarms_bwd_k<{T},{vec},{g}>", "gated_residual_fwd": f"gated_residual_fwd_k<{T},{vec}>",
+            "gated_residual_bwd": f"gated_residual_bwd_k<{T},{vec}>"}[entry]
+    p = K.norm_plan(entry, dtype=1 if bf else 0, rows=B * rps, rows_per_sample=rps, cols=d, **ops)
+    assert p["kernel"] == want and p["vec"] == vec, (p, want)
+    if entry.endswith("_bwd"):
+        assert p["kernel2"] == f"adarms_fold_k<{T}>" and p["grid"][:2] == (K.lib.dxa_adarms_bwd_groups(rps), B)
+
+
 def per_row(t, rps):
     """[B, cols] per-sample vectors -> [B * rps, cols] fp64"""
     return t.double().repeat_interleave(rps, dim=0)
@@ -78,12 +98,14 @@ def test_adarms_forward_with_and_without_the_fused_gated_add(dtype, shape):
     x, branch, mod, mod_prev = make(shape, dtype, 100)
     y, rstd, r = K.adarms_fwd(x, mod, EPS)
     assert r is None
+    assert_path("adarms_fwd", dtype, shape, False, x=x, mod=mod, y=y, rstd=rstd)
     yr, rr = ref_fwd(x, mod, rps)
     assert_close(y, yr, rtol, atol, "adarms fwd")
     assert_close(rstd[:, None], torch.rsqrt(rr.pow(2).mean(-1, keepdim=True) + EPS), 1e-5, 1e-6, "adarms rstd")
     gate = mod_prev[:, 2 * d:]                                   # inside the wider tensor: row stride 3 d
     assert gate.stride(0) == 3 * d
     y2, rstd2, r2 = K.adarms_fwd(x, mod, EPS, branch=branch, gate_prev=gate)
+    assert_path("adarms_fwd", dtype, shape, True, x=x, x2=branch, gate=gate, gate_ld=3 * d, mod=mod, aux=r2, y=y2, rstd=rstd2)
     yr2, rr2 = ref_fwd(x, mod, rps, branch, gate)
     assert_close(r2, rr2, rtol, atol, "adarms fwd r")
     assert_close(y2, yr2, rtol, atol, "adarms fwd fused")
@@ -110,6 +132,8 @@ def test_adarms_backward_with_and_without_residual_and_branch(dtype, shape):
         dmod = torch.full_like(mod, 7.0)
         dr, dbr = K.adarms_bwd(dy, x, mod, rstd, dmod, residual=residual)
         assert dbr is None
+        assert_path("adarms_bwd", dtype, shape, False, dy=dy, x=x, mod=mod, rstd=rstd, residual=residual, dx=dr, dmod=dmod, partial=1 << 40,
+                    partial_bytes=1 << 40)
         assert_close(dr, want["dr"], rtol, atol * 2, "adarms dr")
         assert_close(dmod[:, :d], want["dscale"], rtol, atol * math.sqrt(rps), "adarms dscale")
         assert_close(dmod[:, d:2 * d], want["dshift"], rtol, atol * math.sqrt(rps), "adarms dshift")
@@ -122,6 +146,8 @@ def test_adarms_backward_with_and_without_residual_and_branch(dtype, shape):
         dmod, dmod_prev = torch.full_like(mod, 7.0), torch.full_like(mod_prev, 7.0)
         dr, dbr = K.adarms_bwd(dy, r, mod, rstd2, dmod, residual=residual, branch=branch, gate_prev=gate,
                                dgate_prev=dmod_prev[:, 2 * d:])
+        assert_path("adarms_bwd", dtype, shape, True, dy=dy, x=r, mod=mod, rstd=rstd2, residual=residual, dx=dr, dmod=dmod, x2=branch,
+                    gate=gate, gate_ld=3 * d, aux=dbr, dgate=dmod_prev[:, 2 * d:], dgate_ld=3 * d, partial=1 << 40, partial_bytes=1 << 40)
         assert_close(dr, want["dr"], rtol, atol * 2, "adarms dr (fused)")
         assert_close(dbr, want["dbranch"], rtol, atol * 2, "adarms dbranch")
         assert_close(dmod[:, :d], want["dscale"], rtol, atol * math.sqrt(rps), "adarms dscale (fused)")
@@ -142,12 +168,15 @@ def test_gated_residual_forward_and_backward(dtype, shape):
     dy = rnd(B * rps, d, dtype=dtype, seed=304)
     gate = mod[:, 2 * d:]
     y = K.gated_residual_fwd(x, branch, gate)
+    assert_path("gated_residual_fwd", dtype, shape, False, x=x, x2=branch, gate=gate, gate_ld=3 * d, y=y)
     assert_close(y, x.double() + branch.double() * per_row(gate, rps), rtol, atol, "gated residual fwd")
     assert torch.equal(K.gated_residual_fwd(x, branch, gate.contiguous()), y)
     runs = []
     for _ in range(2):
         dmod = torch.full_like(mod, 7.0)
         dbr = K.gated_residual_bwd(dy, branch, gate, dmod[:, 2 * d:])
+        assert_path("gated_residual_bwd", dtype, shape, False, dy=dy, x2=branch, gate=gate, gate_ld=3 * d, dx=dbr, dgate=dmod[:, 2 * d:],
+                    dgate_ld=3 * d, partial=1 << 40, partial_bytes=1 << 40)
         assert_close(dbr, dy.double() * per_row(gate, rps), rtol, atol * 2, "gated residual dbranch")
         assert_close(dmod[:, 2 * d:], (dy.double() * branch.double()).view(B, rps, d).sum(1), rtol, atol * math.sqrt(rps),
                      "gated residual dgate")

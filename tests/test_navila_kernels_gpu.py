@@ -57,6 +57,9 @@ DS_CASES = [  # N, G, C, dtype, weight dtype
     (1, 5, 12, torch.float32, torch.float32),          # 16-byte path on an odd grid; 9 rows: a workgroup with one live wave
     (2, 27, 1152, torch.bfloat16, torch.bfloat16),     # the real tower's grid: 196 output tokens of width 4608
 ]
+# the path of each case as its comment states it (dxa_norm_plan): the kernel's (T, TW, elements per access), both directions
+DS_PATHS = {0: "float,float,1", 1: "bf16,bf16,1", 2: "float,float,4", 3: "bf16,float,8", 4: "bf16,bf16,8", 5: "float,float,4",
+            6: "bf16,bf16,8"}
 
 
 @pytest.mark.parametrize("N,G,C_,dtype,wdtype", DS_CASES)
@@ -76,7 +79,13 @@ def test_downsample_layernorm(N, G, C_, dtype, wdtype):
     dx, part = K.downsample_layernorm_bwd(dy, x, w, mean, rstd, out=dx)
     assert dx.shape == x.shape and not torch.isnan(dx).any()
     assert part.shape == (K.norm_bwd_blocks(N * h * h), 8 * C_)
-    s = K.colsum(part)                                    # the fold dxa_layernorm_bwd's partials go through
+    path = DS_PATHS[DS_CASES.index((N, G, C_, dtype, wdtype))]
+    dts = dict(dtype=int(dtype == torch.bfloat16), w_dtype=int(wdtype == torch.bfloat16), rows=N, G=G, cols=C_)
+    pf = K.norm_plan("downsample_layernorm_fwd", x=x, w=w, b=b, y=y, mean=mean, rstd=rstd, **dts)
+    pb = K.norm_plan("downsample_layernorm_bwd", dy=dy, x=x, w=w, mean=mean, rstd=rstd, dx=dx, partial=part, **dts)
+    assert pf["kernel"] == f"ds_layernorm_fwd_k<{path}>" and pb["kernel"] == f"ds_layernorm_bwd_k<{path}>", (pf, pb)
+    assert pb["lds"] == 8 * C_ * 4 and pb["grid"][0] == K.norm_bwd_blocks(N * h * h)    # the partial sums in LDS
+    s = K.colsum(part)                                   # the fold dxa_layernorm_bwd's partials go through
     dw, db = s[:4 * C_], s[4 * C_:]
     rows = N * h * h
     if dtype == torch.float32:
