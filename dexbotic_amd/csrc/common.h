@@ -126,6 +126,21 @@ __device__ __forceinline__ float fast_tanhf(float u) {
 // bounds held).
 __device__ __forceinline__ float fast_sigmoidf(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 
+// logistic 1 / (1 + e^-x) and SiLU x / (1 + e^-x), bit for bit torch's fp32 formulas wherever e^-x is finite.  Below x = -88.72 e^-x
+// overflows and the quotients are 0, while SiLU's true value stays a normal float down to x = -91.8 (quick-GELU's to -54) and the
+// logistic (subnormal there) feeds products that are not (the gradients, d * u * s * ...): there e^x itself is taken (only the lanes
+// that need it branch).
+__device__ __forceinline__ float sigmoid_f(float x) {
+  const float e = expf(-x);
+  if (__builtin_expect(e == __builtin_inff(), 0)) return expf(x);
+  return 1.f / (1.f + e);
+}
+__device__ __forceinline__ float silu_f(float x, float a = 1.f) {      // x / (1 + e^-ax): a = 1.702 is quick-GELU
+  const float e = expf(-a * x);
+  if (__builtin_expect(e == __builtin_inff(), 0)) return x * expf(a * x);
+  return x / (1.f + e);
+}
+
 __device__ __forceinline__ float act_fwd(int act, float x) {
   switch (act) {
     case DXA_ACT_GELU_ERF: return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f));
@@ -133,10 +148,10 @@ __device__ __forceinline__ float act_fwd(int act, float x) {
       const float k = 0.79788456080286535588f;  // sqrt(2/pi)
       return 0.5f * x * (1.f + fast_tanhf(k * (x + 0.044715f * x * x * x)));
     }
-    case DXA_ACT_QUICK_GELU: return x / (1.f + expf(-1.702f * x));
-    case DXA_ACT_SILU: return x / (1.f + expf(-x));
+    case DXA_ACT_QUICK_GELU: return silu_f(x, 1.702f);
+    case DXA_ACT_SILU: return silu_f(x);
     case DXA_ACT_RELU: return x > 0.f ? x : 0.f;
-    case DXA_ACT_SIGMOID: return 1.f / (1.f + expf(-x));
+    case DXA_ACT_SIGMOID: return sigmoid_f(x);
     default: return x;
   }
 }
@@ -155,16 +170,16 @@ __device__ __forceinline__ float act_grad(int act, float x) {
       return 0.5f * (1.f + t) + 0.5f * x * (1.f - t * t) * du;
     }
     case DXA_ACT_QUICK_GELU: {
-      const float s = 1.f / (1.f + expf(-1.702f * x));
+      const float s = sigmoid_f(1.702f * x);
       return s + x * 1.702f * s * (1.f - s);
     }
     case DXA_ACT_SILU: {
-      const float s = 1.f / (1.f + expf(-x));
+      const float s = sigmoid_f(x);
       return s * (1.f + x * (1.f - s));
     }
     case DXA_ACT_RELU: return x > 0.f ? 1.f : 0.f;
     case DXA_ACT_SIGMOID: {
-      const float s = 1.f / (1.f + expf(-x));
+      const float s = sigmoid_f(x);
       return s * (1.f - s);
     }
     default: return 1.f;

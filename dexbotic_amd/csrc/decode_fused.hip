@@ -274,7 +274,7 @@ __device__ __forceinline__ void gemv_glu(DSmem& s, const bf16_t* W, int F, int K
 #pragma unroll
       for (int w = 0; w < 8; ++w) { g += s.red[w][2 * threadIdx.x]; u += s.red[w][2 * threadIdx.x + 1]; }
       g = rnd<bf16_t>(g); u = rnd<bf16_t>(u);
-      st_bf(rD, p0 + threadIdx.x, rnd<bf16_t>(g / (1.f + expf(-g))) * u);
+      st_bf(rD, p0 + threadIdx.x, rnd<bf16_t>(silu_f(g)) * u);
     }
     __syncthreads();
   }

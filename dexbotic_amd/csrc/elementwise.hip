@@ -48,11 +48,14 @@ __global__ __launch_bounds__(TPB) void rope_k(const T* __restrict__ tok, T* __re
       }
     }
     float x1[VEC], x2[VEC], o1[VEC], o2[VEC];
+    // every product rounded on its own, then one add (contract(off): no fma): the arithmetic of t * cos + rotate_half(t) * sin in T,
+    // and of its autograd backward
     if (!MERGE) {
       Vec<T, VEC>::ld(x1, tok + toff + d0);
       Vec<T, VEC>::ld(x2, tok + toff + d0 + half);
 #pragma unroll
       for (int i = 0; i < VEC; ++i) {
+#pragma clang fp contract(off)
         if (rot) {
           const float cc = rnd<T>(c[i]), ss = rnd<T>(sn[i]);
           o1[i] = rnd<T>(x1[i] * cc) + rnd<T>(-x2[i] * ss);
@@ -66,6 +69,7 @@ __global__ __launch_bounds__(TPB) void rope_k(const T* __restrict__ tok, T* __re
       Vec<T, VEC>::ld(x2, hm + d0 + half);
 #pragma unroll
       for (int i = 0; i < VEC; ++i) {
+#pragma clang fp contract(off)
         if (rot) {
           const float cc = rnd<T>(c[i]), ss = rnd<T>(sn[i]);
           o1[i] = x1[i] * cc + x2[i] * ss;
@@ -89,6 +93,11 @@ constexpr int QKN_MAX_BLOCKS = 1024;      // workgroups (= rows of weight-gradie
 __device__ __forceinline__ float group_sum(float v, int n) {      // sum over the n adjacent lanes (n = 2^j) this lane belongs to
   for (int o = n >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+// a * b + c * d as rope_k rotates: each product rounded on its own, then one rounded add (no contraction into an fma)
+__device__ __forceinline__ float rot_fma_free(float a, float b, float c, float d) {
+#pragma clang fp contract(off)
+  return a * b + c * d;
 }
 template <int VEC>
 __device__ __forceinline__ void rope_row(float (&c)[VEC], float (&sn)[VEC], const float* cos_t, const float* sin_t, int64_t off) {
@@ -143,6 +152,7 @@ __global__ __launch_bounds__(TPB) void qknorm_rope_split_k(const T* __restrict__
       rope_row<VEC>(c, sn, cos_t, sin_t, (int64_t)(pos ? pos[t] : s) * half + d0);
 #pragma unroll
       for (int i = 0; i < VEC; ++i) {
+#pragma clang fp contract(off)
         // Qwen3RMSNorm: normalised in fp32, cast to the input dtype, THEN times the weight; the rotation as rope_k does it
         const float y1 = rnd<T>(w1[i] * rnd<T>(x1[i] * rs)), y2 = rnd<T>(w2[i] * rnd<T>(x2[i] * rs));
         const float cc = rnd<T>(c[i]), sv = rnd<T>(sn[i]);
@@ -207,7 +217,7 @@ __global__ __launch_bounds__(TPB) void qknorm_rope_merge_k(const T* __restrict__
 #pragma unroll
       for (int i = 0; i < VEC; ++i) {
         const float cc = rnd<T>(c[i]), sv = rnd<T>(sn[i]);
-        const float dy1 = g1[i] * cc + g2[i] * sv, dy2 = g2[i] * cc - g1[i] * sv;      // gradient of the normalised, weighted head
+        const float dy1 = rot_fma_free(g1[i], cc, g2[i], sv), dy2 = rot_fma_free(g2[i], cc, -g1[i], sv);   // gradient of the normalised, weighted head
         x1[i] *= rs;
         x2[i] *= rs;
         const float a1 = live * dy1 * rnd<T>(x1[i]), a2 = live * dy2 * rnd<T>(x2[i]);
@@ -264,7 +274,7 @@ __global__ __launch_bounds__(TPB) void swiglu_fwd_k(const T* __restrict__ gu, T*
     Vec<T, VEC>::ld(g, gu + r * 2 * F + c);
     Vec<T, VEC>::ld(u, gu + r * 2 * F + F + c);
 #pragma unroll
-    for (int i = 0; i < VEC; ++i) o[i] = rnd<T>(g[i] / (1.f + expf(-g[i]))) * u[i];
+    for (int i = 0; i < VEC; ++i) o[i] = rnd<T>(silu_f(g[i])) * u[i];
     Vec<T, VEC>::st(out + r * F + c, o);
   }
 }
@@ -280,7 +290,7 @@ __global__ __launch_bounds__(TPB) void swiglu_bwd_k(const T* __restrict__ gu, co
     Vec<T, VEC>::ld(d, dout + r * F + c);
 #pragma unroll
     for (int i = 0; i < VEC; ++i) {
-      const float s = 1.f / (1.f + expf(-g[i]));
+      const float s = sigmoid_f(g[i]);
       du[i] = d[i] * rnd<T>(g[i] * s);
       dg[i] = d[i] * u[i] * (s * (1.f + g[i] * (1.f - s)));
     }

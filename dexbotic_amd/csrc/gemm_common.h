@@ -559,7 +559,9 @@ __device__ __forceinline__ void sk_epilogue_swiglu(const GemmP& p, typename AccL
         for (int e = 0; e < 4; ++e) {
           // (fast_sigmoidf — v_exp_f32 + v_rcp_f32 — where swiglu_fwd_k has expf and an IEEE division: the SiLUs of a product are VALU
           //  work nothing overlaps in an epilogue, one workgroup per CU; against swiglu_fwd_k a result may differ by one bf16 step in a
-          //  few values per million, none on the test data)
+          //  few values per million, none on the test data; and below g = -88.72, where e^-g overflows, this SiLU is 0 while
+          //  silu_f (common.h) of swiglu_fwd_k and the decode step returns g e^g, at most 2.7e-37 in magnitude there: the two
+          //  differ by that much for a gate no layer of the models produces, and the guard's branch would sit in the epilogue)
           o[e] = rnd<bf16_t>(g[e] * fast_sigmoidf(g[e])) * u[e];
         }
         const u32x2_t_ ov = {pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3])};

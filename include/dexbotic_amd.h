@@ -456,6 +456,11 @@ const char* dxa_norm_kernel_name(int i);
  * Qwen2RotaryEmbedding (:52-104); pos: [B*S] int32 row index into the tables (NULL -> s).
  * dxa_rope_split : qkv [B*S, (Hq+2Hkv)*D] token-major  ->  q [B,Hq,S,D], k [B,Hkv,S,D], v [B,Hkv,S,D]
  * dxa_rope_merge : inverse rotation (backward): dq,dk,dv head-major -> dqkv token-major
+ * The rotation rounds each product to the dtype, then adds once (no contraction): the arithmetic of HF's
+ * q * cos + rotate_half(q) * sin in that dtype, and of its autograd backward.
+ * Alignment (NOT checked by the host; a misaligned operand is undefined behaviour): qkv / dqkv, q, k, v
+ * (and dq, dk, dv) 16-byte aligned for fp32 and at least 8-byte aligned for bf16 (16-byte aligned bf16
+ * operands with D % 16 == 0 take the 16-byte path); cos_t / sin_t 16-byte aligned.
  * ---------------------------------------------------------------------------------------------- */
 int dxa_rope_split(const void* qkv, void* q, void* k, void* v, const float* cos_t, const float* sin_t,
                    const int32_t* pos, int B, int S, int Hq, int Hkv, int D, int dtype,
