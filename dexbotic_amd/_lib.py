@@ -249,6 +249,9 @@ SIGNATURES = {
     "dxa_bank_stage_bwd": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp]),
     "dxa_bank_append": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp]),
     "dxa_bank_consolidate_batched": (_int, [_vp, _vp, _vp, _int, _int, _int, _vp, _i64, _i64, _i64, _i64, _int, _vp]),
+    "dxa_bank_stage_fwd_at": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _vp]),
+    "dxa_bank_append_at": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _vp]),
+    "dxa_bank_consolidate_batched_at": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _vp, _i64, _i64, _i64, _i64, _i64, _int, _vp]),
     "dxa_add_rows": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _f32, _int, _vp]),
     "dxa_token_sum": (_int, [_vp, _vp, _i64, _i64, _i64, _f32, _int, _vp]),
     "dxa_mse_loss": (_int, [_vp, _vp, _vp, _vp, _i64, _f32, _vp]),

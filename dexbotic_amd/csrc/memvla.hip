@@ -8,6 +8,9 @@
 //                          'parallel_stream' (memvla_arch.py:340-361): batch slot b is its own episode, so the B banks of a role lie
 //                          side by side and staging what the retrieval reads, the append and the consolidation are one launch
 //                          (two for the token merge) over all B slots, lengths read from a device array of counts
+//   dxa_bank_stage_fwd_at, dxa_bank_append_at, dxa_bank_consolidate_batched_at
+//                          the same kernels on a chosen subset of the S slots of a bank, in any order: row r of the call works on
+//                          slot slot_ids[r] (served episodes tick at different rates, join and leave); the other slots are not touched
 #include "common.h"
 
 namespace {
@@ -114,6 +117,13 @@ __device__ __forceinline__ int bank_count(const int32_t* __restrict__ counts, in
   const int n = counts[b] + add;
   return n < 0 ? 0 : (n > cap ? cap : n);
 }
+// the slot row r of a launch works on: r itself ('parallel_stream', slot_ids = null: all B slots in slot order) or slot_ids[r] of a
+// bank of S slots (the _at entry points); an id read from the device that is outside [0, S) gives -1: the row touches no slot
+__device__ __forceinline__ int bank_slot(const int32_t* __restrict__ slot_ids, int r, int S) {
+  if (!slot_ids) return r;
+  const int s = slot_ids[r];
+  return (s < 0 || s >= S) ? -1 : s;
+}
 
 // what the retrieval of one step reads: mem [B, cap, E] = the slot's entries oldest first (no history: entry 0 = the slot's own
 // tokens, the frame retrieving from itself), zeros behind them; ts_eff [B, cap] the matching timesteps; kv_len [B] keys in use
@@ -122,17 +132,17 @@ __global__ __launch_bounds__(TPB) void bank_stage_k(const T* __restrict__ feat, 
                                                     const int32_t* __restrict__ counts, const T* __restrict__ tokens,
                                                     const float* __restrict__ timesteps, T* __restrict__ mem,
                                                     float* __restrict__ ts_eff, int32_t* __restrict__ kv_len, int cap, int64_t N,
-                                                    int64_t E) {
-  const int b = blockIdx.y;
-  const int n = bank_count(counts, b, 0, cap);
+                                                    int64_t E, const int32_t* __restrict__ slot_ids, int S) {
+  const int b = blockIdx.y, s = bank_slot(slot_ids, b, S);
+  const int n = s < 0 ? 0 : bank_count(counts, b, 0, cap);         // a row without a slot is staged as a slot without history
   const int64_t total = (int64_t)cap * E, live = (int64_t)(n > 0 ? n : 1) * E;
-  const T* src = n > 0 ? feat + (int64_t)b * total : tokens + (int64_t)b * E;
+  const T* src = n > 0 ? feat + (int64_t)s * total : tokens + (int64_t)b * E;
   T* dst = mem + (int64_t)b * total;
   for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < total; i += (int64_t)gridDim.x * TPB)
     dst[i] = i < live ? src[i] : (T)0.f;
   if (blockIdx.x == 0) {
     for (int i = threadIdx.x; i < cap; i += TPB)
-      ts_eff[(int64_t)b * cap + i] = n > 0 ? (i < n ? ts[(int64_t)b * cap + i] : 0.f) : (i == 0 ? timesteps[b] : 0.f);
+      ts_eff[(int64_t)b * cap + i] = n > 0 ? (i < n ? ts[(int64_t)s * cap + i] : 0.f) : (i == 0 ? timesteps[b] : 0.f);
     if (threadIdx.x == 0) kv_len[b] = (int32_t)((n > 0 ? n : 1) * N);
   }
 }
@@ -152,35 +162,38 @@ __global__ __launch_bounds__(TPB) void bank_stage_bwd_k(const T* __restrict__ dm
 template <typename T>
 __global__ __launch_bounds__(TPB) void bank_append_k(T* __restrict__ feat, float* __restrict__ ts, const int32_t* __restrict__ counts,
                                                      const T* __restrict__ src, const float* __restrict__ timesteps, int cap,
-                                                     int64_t E) {
-  const int b = blockIdx.y;
+                                                     int64_t E, const int32_t* __restrict__ slot_ids, int S) {
+  const int b = blockIdx.y, slot = bank_slot(slot_ids, b, S);
   const int n = bank_count(counts, b, 0, cap);
-  if (n >= cap) return;
-  T* dst = feat + ((int64_t)b * cap + n) * E;
+  if (slot < 0 || n >= cap) return;
+  T* dst = feat + ((int64_t)slot * cap + n) * E;
   const T* s = src + (int64_t)b * E;
   for (int64_t e = (int64_t)blockIdx.x * TPB + threadIdx.x; e < E; e += (int64_t)gridDim.x * TPB) dst[e] = s[e];
-  if (blockIdx.x == 0 && threadIdx.x == 0) ts[(int64_t)b * cap + n] = timesteps[b];
+  if (blockIdx.x == 0 && threadIdx.x == 0) ts[(int64_t)slot * cap + n] = timesteps[b];
 }
 
-// bank_sims_k / bank_merge_k over (pair, slot) / (elements, slot) for the slots whose length counts[b] + add exceeds mem_length;
+// bank_sims_k / bank_merge_k over (pair, slot) / (elements, slot) for the slots whose length counts[b] + add exceeds mem_length
+// (counts and the sims scratch are indexed by the launch's row b, the bank by the row's slot);
 // the other slots' blocks return at once (the test is uniform over a block, so the barrier inside bank_pair_sim is safe)
 template <typename T>
 __global__ __launch_bounds__(TPB) void bank_sims_batched_k(const T* __restrict__ feat, const int32_t* __restrict__ counts, int add,
-                                                           int mem_length, float* __restrict__ sims, int cap, int64_t N, int64_t D) {
-  const int b = blockIdx.y, i = blockIdx.x;
+                                                           int mem_length, float* __restrict__ sims, int cap, int64_t N, int64_t D,
+                                                           const int32_t* __restrict__ slot_ids, int S) {
+  const int b = blockIdx.y, i = blockIdx.x, slot = bank_slot(slot_ids, b, S);
   const int len = bank_count(counts, b, add, cap);
-  if (len <= mem_length || i >= len - 1) return;
-  const T* a = feat + ((int64_t)b * cap + i) * N * D;
+  if (slot < 0 || len <= mem_length || i >= len - 1) return;
+  const T* a = feat + ((int64_t)slot * cap + i) * N * D;
   bank_pair_sim<T>(a, a + N * D, sims + (int64_t)b * (cap - 1) + i, N, D);
 }
 template <typename T>
 __global__ __launch_bounds__(TPB) void bank_merge_batched_k(T* __restrict__ feat, float* __restrict__ ts,
                                                             const int32_t* __restrict__ counts, int add, int mem_length,
-                                                            const float* __restrict__ sims, int cap, int64_t E, int fifo) {
-  const int b = blockIdx.y;
+                                                            const float* __restrict__ sims, int cap, int64_t E, int fifo,
+                                                            const int32_t* __restrict__ slot_ids, int S) {
+  const int b = blockIdx.y, slot = bank_slot(slot_ids, b, S);
   const int len = bank_count(counts, b, add, cap);
-  if (len <= mem_length || len < 2) return;
-  bank_merge_slot<T>(feat + (int64_t)b * cap * E, ts + (int64_t)b * cap, sims + (int64_t)b * (cap - 1), len, E, fifo);
+  if (slot < 0 || len <= mem_length || len < 2) return;
+  bank_merge_slot<T>(feat + (int64_t)slot * cap * E, ts + (int64_t)slot * cap, sims + (int64_t)b * (cap - 1), len, E, fifo);
 }
 
 // out[r, n, c] = (x ? x[r, n, c] : 0) + alpha * g[r, c]: the timestep positional embedding added to every token of a bank entry
@@ -275,22 +288,29 @@ extern "C" int dxa_bank_consolidate(void* feat, float* ts, int len, int64_t N, i
     DXA_CHECK_ARG(dtype == DXA_F32 || dtype == DXA_BF16, name ": dtype must be fp32 or bf16");                           \
   } while (0)
 
-extern "C" int dxa_bank_stage_fwd(const void* feat, const float* ts, const int32_t* counts, const void* tokens,
-                                  const float* timesteps, void* mem, float* ts_eff, int32_t* kv_len, int64_t B, int64_t cap,
-                                  int64_t N, int64_t D, int dtype, dxa_stream_t stream) {
-  DXA_BANK_CHECK("dxa_bank_stage_fwd", feat && ts && counts && tokens && timesteps && mem && ts_eff && kv_len);
-  DXA_CHECK_ARG(cap * N <= INT32_MAX, "dxa_bank_stage_fwd: cap * N keys do not fit kv_len");
+static int bank_stage_launch(const void* feat, const float* ts, const int32_t* slot_ids, const int32_t* counts,
+                             const void* tokens, const float* timesteps, void* mem, float* ts_eff, int32_t* kv_len, int64_t B,
+                             int64_t S, int64_t cap, int64_t N, int64_t D, int dtype, dxa_stream_t stream) {
   const int64_t E = N * D;
   const dim3 grid(dxa_grid1d(cap * E, TPB, 1024), (unsigned)B);
   hipStream_t st = (hipStream_t)stream;
   if (dtype == DXA_BF16)
     hipLaunchKernelGGL((bank_stage_k<bf16_t>), grid, dim3(TPB), 0, st, (const bf16_t*)feat, ts, counts, (const bf16_t*)tokens,
-                       timesteps, (bf16_t*)mem, ts_eff, kv_len, (int)cap, N, E);
+                       timesteps, (bf16_t*)mem, ts_eff, kv_len, (int)cap, N, E, slot_ids, (int)S);
   else
     hipLaunchKernelGGL((bank_stage_k<float>), grid, dim3(TPB), 0, st, (const float*)feat, ts, counts, (const float*)tokens,
-                       timesteps, (float*)mem, ts_eff, kv_len, (int)cap, N, E);
+                       timesteps, (float*)mem, ts_eff, kv_len, (int)cap, N, E, slot_ids, (int)S);
   DXA_CHECK_LAUNCH();
   return DXA_OK;
+}
+
+extern "C" int dxa_bank_stage_fwd(const void* feat, const float* ts, const int32_t* counts, const void* tokens,
+                                  const float* timesteps, void* mem, float* ts_eff, int32_t* kv_len, int64_t B, int64_t cap,
+                                  int64_t N, int64_t D, int dtype, dxa_stream_t stream) {
+  DXA_BANK_CHECK("dxa_bank_stage_fwd", feat && ts && counts && tokens && timesteps && mem && ts_eff && kv_len);
+  DXA_CHECK_ARG(cap * N <= INT32_MAX, "dxa_bank_stage_fwd: cap * N keys do not fit kv_len");
+  return bank_stage_launch(feat, ts, nullptr, counts, tokens, timesteps, mem, ts_eff, kv_len, B, B, cap, N, D,
+                           dtype, stream);
 }
 
 extern "C" int dxa_bank_stage_bwd(const void* dmem, const int32_t* counts, void* dtokens, int64_t B, int64_t cap, int64_t N,
@@ -307,18 +327,47 @@ extern "C" int dxa_bank_stage_bwd(const void* dmem, const int32_t* counts, void*
   return DXA_OK;
 }
 
-extern "C" int dxa_bank_append(void* feat, float* ts, const int32_t* counts, const void* src, const float* timesteps, int64_t B,
-                               int64_t cap, int64_t N, int64_t D, int dtype, dxa_stream_t stream) {
-  DXA_BANK_CHECK("dxa_bank_append", feat && ts && counts && src && timesteps);
+static int bank_append_launch(void* feat, float* ts, const int32_t* slot_ids, const int32_t* counts, const void* src,
+                              const float* timesteps, int64_t B, int64_t S, int64_t cap, int64_t N, int64_t D, int dtype,
+                              dxa_stream_t stream) {
   const int64_t E = N * D;
   const dim3 grid(dxa_grid1d(E, TPB, 256), (unsigned)B);
   hipStream_t st = (hipStream_t)stream;
   if (dtype == DXA_BF16)
     hipLaunchKernelGGL((bank_append_k<bf16_t>), grid, dim3(TPB), 0, st, (bf16_t*)feat, ts, counts, (const bf16_t*)src, timesteps,
-                       (int)cap, E);
+                       (int)cap, E, slot_ids, (int)S);
   else
     hipLaunchKernelGGL((bank_append_k<float>), grid, dim3(TPB), 0, st, (float*)feat, ts, counts, (const float*)src, timesteps,
-                       (int)cap, E);
+                       (int)cap, E, slot_ids, (int)S);
+  DXA_CHECK_LAUNCH();
+  return DXA_OK;
+}
+
+extern "C" int dxa_bank_append(void* feat, float* ts, const int32_t* counts, const void* src, const float* timesteps, int64_t B,
+                               int64_t cap, int64_t N, int64_t D, int dtype, dxa_stream_t stream) {
+  DXA_BANK_CHECK("dxa_bank_append", feat && ts && counts && src && timesteps);
+  return bank_append_launch(feat, ts, nullptr, counts, src, timesteps, B, B, cap, N, D, dtype, stream);
+}
+
+static int bank_consolidate_launch(void* feat, float* ts, const int32_t* slot_ids, const int32_t* counts, int count_add,
+                                   int mem_length, int fifo, float* sims, int64_t B, int64_t S, int64_t cap, int64_t N, int64_t D,
+                                   int dtype, dxa_stream_t stream) {
+  const int64_t E = N * D;
+  const dim3 gs((unsigned)(cap - 1), (unsigned)B), gm(dxa_grid1d(E, TPB, 256), (unsigned)B);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == DXA_BF16) {
+    if (!fifo)
+      hipLaunchKernelGGL((bank_sims_batched_k<bf16_t>), gs, dim3(TPB), 0, st, (const bf16_t*)feat, counts, count_add, mem_length, sims,
+                         (int)cap, N, D, slot_ids, (int)S);
+    hipLaunchKernelGGL((bank_merge_batched_k<bf16_t>), gm, dim3(TPB), 0, st, (bf16_t*)feat, ts, counts, count_add, mem_length, sims,
+                       (int)cap, E, fifo, slot_ids, (int)S);
+  } else {
+    if (!fifo)
+      hipLaunchKernelGGL((bank_sims_batched_k<float>), gs, dim3(TPB), 0, st, (const float*)feat, counts, count_add, mem_length, sims,
+                         (int)cap, N, D, slot_ids, (int)S);
+    hipLaunchKernelGGL((bank_merge_batched_k<float>), gm, dim3(TPB), 0, st, (float*)feat, ts, counts, count_add, mem_length, sims,
+                       (int)cap, E, fifo, slot_ids, (int)S);
+  }
   DXA_CHECK_LAUNCH();
   return DXA_OK;
 }
@@ -329,22 +378,43 @@ extern "C" int dxa_bank_consolidate_batched(void* feat, float* ts, const int32_t
   DXA_BANK_CHECK("dxa_bank_consolidate_batched", feat && ts && counts && (sims || fifo));
   DXA_CHECK_ARG(mem_length >= 1 && mem_length < cap, "dxa_bank_consolidate_batched: mem_length must be in [1, cap)");
   DXA_CHECK_ARG(count_add >= 0 && count_add <= cap, "dxa_bank_consolidate_batched: count_add must be in [0, cap]");
-  const int64_t E = N * D;
-  const dim3 gs((unsigned)(cap - 1), (unsigned)B), gm(dxa_grid1d(E, TPB, 256), (unsigned)B);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == DXA_BF16) {
-    if (!fifo)
-      hipLaunchKernelGGL((bank_sims_batched_k<bf16_t>), gs, dim3(TPB), 0, st, (const bf16_t*)feat, counts, count_add, mem_length, sims,
-                         (int)cap, N, D);
-    hipLaunchKernelGGL((bank_merge_batched_k<bf16_t>), gm, dim3(TPB), 0, st, (bf16_t*)feat, ts, counts, count_add, mem_length, sims,
-                       (int)cap, E, fifo);
-  } else {
-    if (!fifo)
-      hipLaunchKernelGGL((bank_sims_batched_k<float>), gs, dim3(TPB), 0, st, (const float*)feat, counts, count_add, mem_length, sims,
-                         (int)cap, N, D);
-    hipLaunchKernelGGL((bank_merge_batched_k<float>), gm, dim3(TPB), 0, st, (float*)feat, ts, counts, count_add, mem_length, sims,
-                       (int)cap, E, fifo);
-  }
-  DXA_CHECK_LAUNCH();
-  return DXA_OK;
+  return bank_consolidate_launch(feat, ts, nullptr, counts, count_add, mem_length, fifo, sims, B, B, cap, N, D, dtype, stream);
+}
+
+// ---- the same three on rows slot_ids[0 .. R) of a bank of S slots (served episodes) --------------------------------------------
+// B of the shared checks is the number of rows R; the slot count S is checked here
+#define DXA_BANK_AT_CHECK(name)                                                                                          \
+  do {                                                                                                                   \
+    const int64_t B = R;                                                                                                 \
+    DXA_BANK_CHECK(name, true);                                                                                          \
+    DXA_CHECK_ARG(S > 0 && S <= INT32_MAX && R <= S, name ": R rows need 0 < R <= S slots");                             \
+  } while (0)
+
+extern "C" int dxa_bank_stage_fwd_at(const void* feat, const float* ts, const int32_t* slot_ids, const int32_t* counts,
+                                     const void* tokens, const float* timesteps, void* mem, float* ts_eff, int32_t* kv_len,
+                                     int64_t R, int64_t S, int64_t cap, int64_t N, int64_t D, int dtype, dxa_stream_t stream) {
+  DXA_CHECK_ARG(feat && ts && slot_ids && counts && tokens && timesteps && mem && ts_eff && kv_len,
+                "dxa_bank_stage_fwd_at: null pointer");
+  DXA_BANK_AT_CHECK("dxa_bank_stage_fwd_at");
+  DXA_CHECK_ARG(cap * N <= INT32_MAX, "dxa_bank_stage_fwd_at: cap * N keys do not fit kv_len");
+  return bank_stage_launch(feat, ts, slot_ids, counts, tokens, timesteps, mem, ts_eff, kv_len, R, S, cap, N,
+                           D, dtype, stream);
+}
+
+extern "C" int dxa_bank_append_at(void* feat, float* ts, const int32_t* slot_ids, const int32_t* counts, const void* src,
+                                  const float* timesteps, int64_t R, int64_t S, int64_t cap, int64_t N, int64_t D, int dtype,
+                                  dxa_stream_t stream) {
+  DXA_CHECK_ARG(feat && ts && slot_ids && counts && src && timesteps, "dxa_bank_append_at: null pointer");
+  DXA_BANK_AT_CHECK("dxa_bank_append_at");
+  return bank_append_launch(feat, ts, slot_ids, counts, src, timesteps, R, S, cap, N, D, dtype, stream);
+}
+
+extern "C" int dxa_bank_consolidate_batched_at(void* feat, float* ts, const int32_t* slot_ids, const int32_t* counts, int count_add,
+                                               int mem_length, int fifo, float* sims, int64_t R, int64_t S, int64_t cap, int64_t N,
+                                               int64_t D, int dtype, dxa_stream_t stream) {
+  DXA_CHECK_ARG(feat && ts && slot_ids && counts && (sims || fifo), "dxa_bank_consolidate_batched_at: null pointer");
+  DXA_BANK_AT_CHECK("dxa_bank_consolidate_batched_at");
+  DXA_CHECK_ARG(mem_length >= 1 && mem_length < cap, "dxa_bank_consolidate_batched_at: mem_length must be in [1, cap)");
+  DXA_CHECK_ARG(count_add >= 0 && count_add <= cap, "dxa_bank_consolidate_batched_at: count_add must be in [0, cap]");
+  return bank_consolidate_launch(feat, ts, slot_ids, counts, count_add, mem_length, fifo, sims, R, S, cap, N, D, dtype, stream);
 }

@@ -443,6 +443,64 @@ def bank_consolidate_batched(feat: torch.Tensor, ts: torch.Tensor, counts: torch
                                              _ptr(sims), B, cap, N, D, dt(feat), _stream()), "dxa_bank_consolidate_batched")
 
 
+def _bank_at_dims(feat: torch.Tensor, ts: torch.Tensor, slot_ids: torch.Tensor, counts: torch.Tensor):
+    """the _at calls: banks of S slots, R <= S rows.  ``slot_ids`` / ``counts`` [R] int32 on the device; the ids are DISTINCT —
+    the caller that owns the host list checks (a duplicate there is a ValueError), nothing is read back here"""
+    S, cap, N, D = feat.shape
+    R = slot_ids.shape[0]
+    assert feat.is_contiguous() and ts.is_contiguous() and ts.dtype == torch.float32 and ts.shape == (S, cap)
+    for t in (slot_ids, counts):
+        assert t.is_contiguous() and t.dtype == torch.int32 and t.shape == (R,) and t.device == feat.device
+    assert 0 < R <= S, (R, S)
+    return R, S, cap, N, D
+
+
+def distinct_slots(slots, S: int):
+    """host-side check of a slot list before it is uploaded for the _at calls: ints in [0, S), no duplicates (ValueError)"""
+    ids = [int(s) for s in slots]
+    if len(set(ids)) != len(ids):
+        raise ValueError(f"duplicate slot ids in one call: {ids}")
+    if any(s < 0 or s >= S for s in ids):
+        raise ValueError(f"slot ids {ids} outside [0, {S})")
+    return ids
+
+
+def bank_stage_fwd_at(feat: torch.Tensor, ts: torch.Tensor, slot_ids: torch.Tensor, counts: torch.Tensor, tokens: torch.Tensor,
+                      timesteps: torch.Tensor):
+    """bank_stage_fwd on rows ``slot_ids`` of feat [S, cap, N, D] / ts [S, cap]: counts [R], tokens [R, N, D], timesteps [R] ->
+    fresh (mem [R, cap, N, D], ts_eff [R, cap], kv_len [R]); row r reads slot slot_ids[r]"""
+    R, S, cap, N, D = _bank_at_dims(feat, ts, slot_ids, counts)
+    assert tokens.is_contiguous() and tokens.shape == (R, N, D) and tokens.dtype == feat.dtype
+    assert timesteps.is_contiguous() and timesteps.dtype == torch.float32 and timesteps.shape == (R,)
+    mem = torch.empty((R, cap, N, D), device=feat.device, dtype=feat.dtype)
+    ts_eff = torch.empty((R, cap), device=feat.device, dtype=torch.float32)
+    kv_len = torch.empty(R, device=feat.device, dtype=torch.int32)
+    L.check(lib.dxa_bank_stage_fwd_at(_ptr(feat), _ptr(ts), _ptr(slot_ids), _ptr(counts), _ptr(tokens), _ptr(timesteps), _ptr(mem),
+                                      _ptr(ts_eff), _ptr(kv_len), R, S, cap, N, D, dt(feat), _stream()), "dxa_bank_stage_fwd_at")
+    return mem, ts_eff, kv_len
+
+
+def bank_append_at(feat: torch.Tensor, ts: torch.Tensor, slot_ids: torch.Tensor, counts: torch.Tensor, src: torch.Tensor,
+                   timesteps: torch.Tensor) -> None:
+    """feat[slot_ids[r], counts[r]] = src[r], ts[slot_ids[r], counts[r]] = timesteps[r] in ONE launch; other slots untouched"""
+    R, S, cap, N, D = _bank_at_dims(feat, ts, slot_ids, counts)
+    assert src.is_contiguous() and src.shape == (R, N, D) and src.dtype == feat.dtype
+    assert timesteps.is_contiguous() and timesteps.dtype == torch.float32 and timesteps.shape == (R,)
+    L.check(lib.dxa_bank_append_at(_ptr(feat), _ptr(ts), _ptr(slot_ids), _ptr(counts), _ptr(src), _ptr(timesteps), R, S, cap, N, D,
+                                   dt(feat), _stream()), "dxa_bank_append_at")
+
+
+def bank_consolidate_batched_at(feat: torch.Tensor, ts: torch.Tensor, slot_ids: torch.Tensor, counts: torch.Tensor, count_add: int,
+                                mem_length: int, sims: Optional[torch.Tensor], fifo: bool = False) -> None:
+    """bank_consolidate_batched on rows ``slot_ids``: slot slot_ids[r] is consolidated when counts[r] + count_add exceeds
+    mem_length.  sims: R * (cap - 1) floats of scratch, indexed by the row (two rows never share it)."""
+    R, S, cap, N, D = _bank_at_dims(feat, ts, slot_ids, counts)
+    assert fifo or (sims is not None and sims.dtype == torch.float32 and sims.is_contiguous() and sims.numel() >= R * (cap - 1))
+    L.check(lib.dxa_bank_consolidate_batched_at(_ptr(feat), _ptr(ts), _ptr(slot_ids), _ptr(counts), int(count_add), int(mem_length),
+                                                int(fifo), _ptr(sims), R, S, cap, N, D, dt(feat), _stream()),
+            "dxa_bank_consolidate_batched_at")
+
+
 def add_rows(x: Optional[torch.Tensor], g: torch.Tensor, Nn: int, alpha: float = 1.0) -> torch.Tensor:
     """x [R, Nn, C] + alpha * g [R, C] broadcast over the tokens (x None: the broadcast alone)"""
     R, C_ = g.shape

@@ -205,6 +205,36 @@ class DiT(nn.Module):
                         bias=st.w(f"{p}blocks.{k}.per_attn.in_proj_bias")[h:]).view(N, P_, 2, H, h // H)
                 for k in range(self.depth)]
 
+    @torch.no_grad()
+    def precompute_per_kv_groups(self, per_token: torch.Tensor, nb: int, per_request: bool = True) -> torch.Tensor:
+        """precompute_per_kv(packed=True) for the nb request groups of one launch: ``per_token`` [Ng nb, P, token] in the caller's
+        [cond x nb ; uncond x nb] order -> [depth, nb, Ng, P, 2, h] group-major.  For a block k and a request b the destination is a
+        contiguous [Ng P, 2h] matrix, so every product writes straight into it (no transposing copy of the result; the small input
+        is regrouped instead).  ``per_request`` (the routed setting): request b's embedding and 24 projections are products on ITS
+        Ng P rows — the very launches a single request makes, hence its bits whatever the GEMM planner picks at another row count.
+        False: one product per block over all nb Ng P rows (scripts/memvla_batch_bench.py times both)."""
+        from .... import kernels as K
+        st = Fp32View(self.store)
+        p, h = self.p, self.hidden_size
+        N, P_ = per_token.shape[:2]
+        Ng = N // nb
+        assert N == Ng * nb, (N, nb)
+        rows = per_token.float().reshape(Ng, nb, P_, -1).transpose(0, 1).reshape(nb, Ng * P_, -1).contiguous()
+        kv = torch.empty((self.depth, nb, Ng * P_, 2 * h), device=rows.device, dtype=torch.float32)
+        we, be = st.w(p + "per_token_embedder.linear.weight"), st.w(p + "per_token_embedder.linear.bias")
+        wk = [(st.w(f"{p}blocks.{k}.per_attn.in_proj_weight")[h:], st.w(f"{p}blocks.{k}.per_attn.in_proj_bias")[h:])
+              for k in range(self.depth)]
+        if per_request:
+            for b in range(nb):
+                pe = K.mm_nt(rows[b], we, bias=be)
+                for k, (w, bias) in enumerate(wk):
+                    K.mm_nt(pe, w, bias=bias, out=kv[k, b])
+        else:
+            pe = K.mm_nt(rows.view(nb * Ng * P_, -1), we, bias=be)
+            for k, (w, bias) in enumerate(wk):
+                K.mm_nt(pe, w, bias=bias, out=kv[k].view(nb * Ng * P_, 2 * h))
+        return kv.view(self.depth, nb, Ng, P_, 2, h)
+
     def _use_fused_blocks(self, N: int, T1: int) -> bool:
         from .... import kernels as K
         # one persistent launch for all blocks of a single-request denoising call (csrc/dit_fused.hip);
@@ -333,9 +363,12 @@ class DiT(nn.Module):
     # which ONE launch of G request groups measured faster than both G single launches and the per-step path at batch G.  DiT-B:
     # every G from 2 to the launch's 16 (5.2 ms against 7.4 / 25.1 at G = 2, 23.9 against 58.7 / 29.5 at G = 16).
     BATCHED_GROUPS = range(2, 17)
-    # With perceptual attention (MemVLA's DiT-L) the launch beat G single launches from G = 2 on (19.3 ms against 28.6), but the
-    # per-step path at batch G does not exist to be measured before MemVLA batches episodes: not routed, as before.
-    BATCHED_GROUPS_PER = range(0)
+    # With perceptual attention (MemVLA's DiT-L, P = 256; scripts/memvla_batch_bench.py, profiles/memvla_batched_episodes.txt): the
+    # whole request of R running episodes (MemVLAForCausalLM.inference_action_batch) measured at every R from 2 to the launch's 16
+    # faster on ONE launch of R request groups than both R calls of inference_action and the per-step path at batch R — R = 2: 23.7 ms
+    # against 35.2 / 90.1, R = 3: 29.7 against 52.6 / 93.5, R = 8: 56.6 against 140.6 / 100.5, R = 16: 103.7 against 281.3 / 120.9
+    # (medians; every upper quartile of the launch under the lower quartiles of the other two).  R = 1 is the single-request launch.
+    BATCHED_GROUPS_PER = range(2, 17)
 
     def fused_sampler_ok(self, N: int, T1: int, P: int = 0, nb: int = 1) -> bool:
         """``P``: perceptual keys per sample (MemVLA's DiT: only the bf16 sampler has the perceptual-attention phases).
@@ -445,8 +478,7 @@ class DiT(nn.Module):
         per_kv = None
         if self.use_per_attn:
             assert per_token is not None and per_token.shape[0] == Ng * nb
-            kv = self.precompute_per_kv(per_token, packed=True)                                  # [depth, Ng nb, P, 2, h]
-            per_kv = kv.view(self.depth, Ng, nb, *kv.shape[2:]).transpose(1, 2).contiguous()
+            per_kv = self.precompute_per_kv_groups(per_token, nb)                                # [depth, nb, Ng, P, 2, h]
         self.used_fused = True
         self.store.wait_pending()                  # the kernel reads the masters through raw pointers
         K.dit_sample_bf16_batched_fwd(x, ze.contiguous(), te.contiguous(), st.w(p + "positional_embedding").reshape(T + 1, h),

@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
@@ -181,7 +181,13 @@ class PerCogMemBank(nn.Module):
     served episode of ``inference_action``) has nothing to batch and takes the serial walk on slot 0's bank: the same kernels as
     a 'group' model, hence the same bits.  The buffers are sized by the first batch after a reset(); another B raises ValueError.
     Deviation: a slot's bank while training and while evaluating are two buffers, so a TRAINING key (i, 0, 0) does not share
-    the bank of the evaluation key (i, 0, 0) as the reference's dictionary would."""
+    the bank of the evaluation key (i, 0, 0) as the reference's dictionary would.
+
+    Serving several running episodes from one model (independent of ``dataloader_type``: a 'group' or 'stream' checkpoint serves
+    them too): ``open_episode_slots(S)`` sizes S episode slots, ``step_episode_rows`` runs one frame of the episodes in slots
+    ``slot_ids`` — any subset, in any order, the other slots untouched (the _at kernels, csrc/memvla.hip).  Slot s's bank is
+    ``entries(role, ("episode", s))``.  The episode slots and the single episode of ``inference_action`` (key (0, 0)) share the
+    model but not an episode; ``reset()`` clears both."""
 
     def __init__(self, store: ParamStore, dataloader_type: str, group_size: int, per_token_size: int, cog_token_size: int,
                  mem_length: int = 16, retrieval_layers: int = 2, use_timestep_pe: bool = True, fusion_type: str = "gate",
@@ -222,6 +228,9 @@ class PerCogMemBank(nn.Module):
         # one set for training and one for evaluation, each remembering the key of every slot (prev_eids, :257)
         self.eid_stream: Dict[str, Optional[tuple]] = {r: None for r in self.roles}
         self.slot_banks: Dict[str, Dict[bool, "_SlotBanks"]] = {r: {} for r in self.roles}
+        # served episodes: S slots per role (sized by open_episode_slots, allocated on first use), and each slot's own time
+        self.episode_banks: Dict[str, "_SlotBanks"] = {}
+        self.episode_time: List[int] = []
 
     def entries(self, role: str, eid=(0, 0)) -> List[Tuple[torch.Tensor, torch.Tensor]]:
         """[(timestep, feat[N, D])] of one bank, oldest first (tests / inspection; the reference's list layout).  ``eid``: the
@@ -398,6 +407,77 @@ class PerCogMemBank(nn.Module):
                 s.n = min(s.n + 1, self.mem_length)
         return fused
 
+    # ---- served episodes: S slots, any subset of them per step ---------------------------------------------------------------
+    def open_episode_slots(self, S: int) -> None:
+        """size the serving-side slot set: S running episodes per role (buffers are allocated by the first step).  Another S
+        while slots are open raises ValueError: reset() first (it clears every episode)."""
+        S = int(S)
+        if S < 1:
+            raise ValueError(f"open_episode_slots: S = {S} slots")
+        if self.episode_time and len(self.episode_time) != S:
+            raise ValueError(f"the bank holds {len(self.episode_time)} episode slots; {S} were asked for — reset() before "
+                             f"changing the number of slots")
+        if not self.episode_time:
+            self.episode_time = [0] * S
+
+    def _episode_state(self, role: str, tokens: torch.Tensor) -> "_SlotBanks":
+        if not self.episode_time:
+            raise ValueError("no episode slots: open_episode_slots(S) first")
+        _, N, D = tokens.shape
+        sb = self.episode_banks.get(role)
+        if sb is None:
+            sb = self.episode_banks[role] = _SlotBanks(len(self.episode_time), self.mem_length + 1, N, D, tokens.dtype, tokens.device)
+            for s, view in enumerate(sb.slots):
+                self.banks[role][("episode", s)] = view
+        if (sb.N, sb.D, sb.feat.dtype) != (N, D, tokens.dtype):
+            raise ValueError(f"episode slots: the '{role}' banks hold [{sb.N}, {sb.D}] {sb.feat.dtype} tokens, this step has "
+                             f"[{N}, {D}] {tokens.dtype} — reset() before changing the token shape")
+        return sb
+
+    @torch.no_grad()
+    def step_episode_rows(self, role: str, tokens: torch.Tensor, slot_ids, timesteps: torch.Tensor, first_frame) -> torch.Tensor:
+        """one frame of the episodes in slots ``slot_ids`` (R distinct ints, any order): tokens [R, N, D], ``timesteps`` ONE fp32
+        device tensor [R], ``first_frame`` R bools — a first-frame row empties its slot (host count 0; nothing else is cleared).
+        The pass is _process_slots' on the _at kernels, rows instead of slots: stage -> timestep PE -> retrieval blocks with
+        kv_end -> gate fusion -> append -> consolidation.  Slot ids and counts travel in ONE pinned upload per role and step.
+        R == 1 takes the serial walk on that slot's bank: the bits of the single-episode path.  Inference only."""
+        st = self.store
+        R, N, D = tokens.shape
+        sb = self._episode_state(role, tokens)
+        ids = K.distinct_slots(slot_ids, sb.B)
+        if len(ids) != R or len(first_frame) != R:
+            raise ValueError(f"{R} rows of tokens, {len(ids)} slot ids, {len(first_frame)} first-frame flags")
+        for s, first in zip(ids, first_frame):
+            if first:
+                sb.slots[s].n = 0
+        if R == 1:
+            return self._walk(role, tokens, [("episode", ids[0])], timesteps)
+        counts_host = [sb.slots[s].n for s in ids]
+        assert max(counts_host) <= self.mem_length
+        rows = hostcpu.upload(torch.tensor([ids, counts_host], dtype=torch.int32), tokens.device)   # (pinned; one upload per step)
+        slots, counts = rows[0], rows[1]
+        gp = f"{BANK}gate_fusion_blocks.{role}."
+        cap = sb.cap
+        tokens = tokens.contiguous()
+        mem, ts_eff, kv_len = K.bank_stage_fwd_at(sb.feat, sb.ts, slots, counts, tokens, timesteps)
+        pe = self._encode_time(role, ts_eff.view(R * cap), tokens.dtype)                           # (R cap, D)
+        key = Fn.AddRowsFn.apply(mem.reshape(R * cap, N, D), pe).reshape(R, cap * N, D)
+        val = mem.reshape(R, cap * N, D)
+        q = tokens
+        for blk in self.blocks[role]:
+            q = blk(q, key, val, kv_end=kv_len)
+        q = q.reshape(R * N, D)
+        scale = _lin(st, Fn.CatLastFn.apply(tokens.reshape(R * N, D), q), gp + "proj.weight", gp + "proj.bias", L.ACT_SIGMOID)
+        fused = Fn.GateFuseFn.apply(scale, tokens.reshape(R * N, D), q).view(R, N, D)
+        src = (fused if self.update_fused else tokens).contiguous()
+        K.bank_append_at(sb.feat, sb.ts, slots, counts, src, timesteps)
+        if max(counts_host) + 1 > self.mem_length:
+            K.bank_consolidate_batched_at(sb.feat, sb.ts, slots, counts, 1, self.mem_length, sb.sims.view(-1),
+                                          fifo=self.consolidate_type == "fifo")
+        for s in ids:
+            sb.slots[s].n = min(sb.slots[s].n + 1, self.mem_length)
+        return fused
+
     def process_batch_per(self, per_tokens, episode_ids, timesteps):
         return self._process_batch("per", per_tokens, episode_ids, timesteps)
 
@@ -505,9 +585,6 @@ class MemVLAForCausalLM(CogACTForCausalLM):
     @torch.no_grad()
     def inference_action(self, input_ids, image_tensor, episode_first_frame, inference_args={}, **kwargs):
         """memvla_arch.py:666-746: one frame of a running episode ('True' on the first frame resets the memory)"""
-        cfg_scale = inference_args.get("cfg_scale", 1.5)
-        num_ddim_steps = inference_args.get("num_ddim_steps", 10)
-        action_norms = inference_args.get("action_norms")
         assert episode_first_frame in ("True", "False"), "episode_first_frame must be 'True' or 'False'"
         bank = self.model.per_cog_mem_bank
         if episode_first_frame == "True":
@@ -522,8 +599,18 @@ class MemVLAForCausalLM(CogACTForCausalLM):
         self.cur_timestep += 1
         cog = bank.process_batch_cog(cog, [(0, 0)], ts)
         per = bank.process_batch_per(per, [(0, 0)], ts)
+        host = self._sample_chunks(cog, per, kwargs.get("noise"), inference_args, 1, ("ddim",))
+        return self._denorm(host[0], inference_args.get("action_norms")).tolist()
+
+    def _sample_chunks(self, cog, per, noise, inference_args, nb: int, graph_key: tuple):
+        """the sampler of inference_action / inference_action_batch on what the bank returned (cog [B, 1, d], per [B, P, D]): the
+        B raw chunks on the host [B, chunk, action_dim].  ``nb`` = B > 1: bf16 serving samples the B requests as B request
+        groups of ONE launch where that is routed (DiT.fused_sampler_ok(..., nb=B)), else the per-step path at batch B."""
+        cfg_scale = inference_args.get("cfg_scale", 1.5)
+        num_ddim_steps = inference_args.get("num_ddim_steps", 10)
+        dev = self.store.device
+        B = cog.shape[0]
         head = self.model.action_head
-        noise = kwargs.get("noise")
         if noise is None:
             noise = torch.randn(B, self.config.chunk_size, self.config.action_dim, device=dev, dtype=torch.float32)
         noise = noise.to(device=dev, dtype=torch.float32)
@@ -543,7 +630,7 @@ class MemVLAForCausalLM(CogACTForCausalLM):
         cfg = model_kwargs.get("cfg_scale")
 
         fused = inference_args.get("fused_sampler", True) and inference_args.get("cache_per_kv", True) and \
-            head.net.fused_sampler_ok(noise.shape[0], self.config.chunk_size + 1, per_token.shape[1])
+            head.net.fused_sampler_ok(noise.shape[0], self.config.chunk_size + 1, per_token.shape[1], **({"nb": nb} if nb > 1 else {}))
         head.net.used_fused = bool(fused)
 
         def sample(noise, z, per_token):
@@ -565,14 +652,12 @@ class MemVLAForCausalLM(CogACTForCausalLM):
             if fused:
                 head.net.refresh_packed()          # the bf16 operand copy a captured launch reads: up to date before a replay
             run_stream = cache
-            samples = cache.run(("ddim", float(cfg_scale), int(num_ddim_steps), bool(fused)), sample,
+            samples = cache.run(graph_key + (float(cfg_scale), int(num_ddim_steps), bool(fused)), sample,
                                 dict(noise=noise, z=model_kwargs["z"].contiguous(), per_token=per_token.contiguous()))
         else:
             run_stream = None
             samples = sample(noise, model_kwargs["z"], per_token)
-        if cfg_scale > 1.0:
-            samples = samples[:B]
-        host = samples[0].cpu().numpy()
+        host = samples[:B].cpu().numpy()
         if fused and K.dit_blocks_timed_out(run_stream.stream if run_stream is not None else None):
             # the persistent launch gave up at a barrier (its workgroups were not co-resident: something else held CUs for seconds):
             # the frame is sampled again block by block, which this process keeps doing from now on.  The memory bank above was
@@ -581,8 +666,63 @@ class MemVLAForCausalLM(CogACTForCausalLM):
             self.__dict__.pop("_sampler_graphs", None)
             fused = False
             samples = sample(noise, model_kwargs["z"], per_token)
-            host = (samples[:B] if cfg_scale > 1.0 else samples)[0].cpu().numpy()
-        return self._denorm(host, action_norms).tolist()
+            host = samples[:B].cpu().numpy()
+        return host
+
+    @torch.no_grad()
+    def inference_action_batch(self, input_ids, image_tensor, episode_first_frame: Sequence[str], inference_args={}, *,
+                               slots: Optional[Sequence[int]] = None, num_slots: Optional[int] = None, noise=None) -> list:
+        """one frame of R running episodes from one model: input_ids [R, S_tok] (prompts of one tokenised length: the prefill takes
+        no padding mask), image_tensor [R, ...], ``episode_first_frame`` R strings 'True' / 'False', ``noise`` [R, chunk, action_dim]
+        -> the list of R de-normalised [chunk][action_dim] chunks, row r for the episode in slot ``slots[r]`` (default: slot r).
+
+        The episodes live in ``num_slots`` slots of the memory bank (default: as many as the first call needs; asking for more later
+        raises ValueError — reset() first).  A call may name any subset of the slots in any order; the others keep their memory
+        and their time.  Each slot counts its own timesteps, 'True' sets that slot's to 0 and empties its bank; ``cur_timestep``
+        of inference_action is not touched.  inference_action and this method share the model, not an episode — and
+        inference_action(..., 'True') resets the whole bank, these slots included.
+
+        One prefill at batch R, the bank stepped once on the R rows (PerCogMemBank.step_episode_rows), then the sampler: bf16
+        serving with R in DiT.BATCHED_GROUPS_PER samples the R chunks as R request groups of ONE launch (chunk r has the bits that
+        launch gives request r alone), otherwise the per-step path at batch R with the perceptual keys / values projected once.
+        Graph capture per (R, cfg, steps, fused); watchdog and block-by-block fallback as inference_action (the bank is not
+        stepped twice).  R == 1 has the bits of inference_action on the same frames."""
+        R = int(input_ids.shape[0])
+        flags = list(episode_first_frame)
+        if isinstance(episode_first_frame, str) or any(f not in ("True", "False") for f in flags):
+            raise ValueError("episode_first_frame: a sequence of 'True' / 'False' strings, one per row")
+        if len(flags) != R or image_tensor.shape[0] != R:
+            raise ValueError(f"{R} prompts, {image_tensor.shape[0]} image rows, {len(flags)} episode_first_frame entries")
+        bank = self.model.per_cog_mem_bank
+        ids = list(range(R)) if slots is None else [int(s) for s in slots]
+        if len(ids) != R:
+            raise ValueError(f"{R} prompts, {len(ids)} slots")
+        S = len(bank.episode_time) or int(num_slots if num_slots is not None else max(ids, default=0) + 1)
+        if num_slots is not None and int(num_slots) != S:
+            raise ValueError(f"the model serves {S} episode slots; num_slots = {num_slots} — reset() the memory bank before "
+                             f"changing the number of slots")
+        if bank.episode_time and max(ids, default=0) >= S:
+            raise ValueError(f"slot {max(ids)}: the model serves {S} episode slots (sized by the first call) — reset() the memory "
+                             f"bank before opening more")
+        ids = K.distinct_slots(ids, S)             # duplicates, ids outside [0, S): ValueError
+        bank.open_episode_slots(S)
+        first = [f == "True" for f in flags]
+        for s, f in zip(ids, first):
+            if f:
+                bank.episode_time[s] = 0
+        dev = self.store.device
+        hidden, vision_proj, _ = self._vlm(input_ids, None, image_tensor.to(device=dev, dtype=self.store.compute_dtype))
+        d = hidden.shape[-1]
+        cog = hidden[:, -1, :].unsqueeze(1).contiguous()
+        per = self.model.per_compr(vision_proj.reshape(R, -1, d))
+        ts = hostcpu.upload(torch.tensor([float(bank.episode_time[s]) for s in ids], dtype=torch.float32), dev)
+        for s in ids:
+            bank.episode_time[s] += 1
+        cog = bank.step_episode_rows("cog", cog, ids, ts, first)
+        per = bank.step_episode_rows("per", per, ids, ts, first)
+        host = self._sample_chunks(cog, per, noise, inference_args, R, ("ddim_batch", R))
+        norms = inference_args.get("action_norms")
+        return [self._denorm(host[r], norms).tolist() for r in range(R)]
 
 
 from ..dexbotic_arch import register_model_with_hf  # noqa: E402

@@ -7,7 +7,9 @@ resized, cropped and normalised there (DexboticForCausalLM.process_images -> dxa
 
 ``InferenceServer`` speaks the CogACT format (one sample, ``inference_action(ids, pix, args)``; with the optional ``batch_size``
 field several, ``inference_action_batch``); ``FlowInferenceServer`` the batched
-format of the flow-matching policies pi0 / pi0.5 / DM0 (``states`` and ``batch_size`` beside the frames, absent views masked)."""
+format of the flow-matching policies pi0 / pi0.5 / DM0 (``states`` and ``batch_size`` beside the frames, absent views masked);
+``MemVLAInferenceServer`` MemVLA's (``episode_first_frame`` beside the frames; with ``batch_size`` one frame of several running
+episodes, each in its own slot of the memory bank)."""
 from __future__ import annotations
 
 import io
@@ -140,6 +142,131 @@ class InferenceServer:
 
     def run(self) -> None:
         self.create_app().run(host="0.0.0.0", port=self.port, debug=False, threaded=False)
+
+
+def _json_list(value, n: int, what: str, kind) -> Optional[list]:
+    """a form field that is one value for all n samples or a list (or the JSON text of a list) of n: -> the list, or None when
+    ``value`` is a single value.  Malformed JSON, another length or entries that are no ``kind``: ValueError."""
+    import json
+    if isinstance(value, str):
+        if not value.lstrip().startswith("["):
+            return None
+        try:
+            value = json.loads(value)
+        except ValueError as e:
+            raise ValueError(f"process_frame: {what} is not a JSON list: {e}") from None
+    if not isinstance(value, (list, tuple)):
+        return None
+    if len(value) != n or not all(isinstance(v, kind) and not isinstance(v, bool) for v in value):
+        raise ValueError(f"process_frame: {what} needs {n} entries of {getattr(kind, '__name__', kind)}, got {list(value)!r}")
+    return list(value)
+
+
+class MemVLAInferenceServer(InferenceServer):
+    """POST /process_frame in MemVLA's wire format — MemVLAInferenceConfig (memvla_exp.py:309-358): form fields ``text``, ``image``
+    files and ``episode_first_frame`` ('True' on the first frame of an episode), answered {"response": [chunk][action_dim]} by
+    ``inference_action``: one frame of the ONE episode the model is running.
+
+    With the optional ``batch_size`` = R the request holds one frame of R running episodes (several robots or simulator instances
+    on one set of weights): images sample-major, ``text`` one string for all or a (JSON) list of R, ``episode_first_frame`` one
+    string for all or a (JSON) list of R, ``slots`` an optional (JSON) list of R distinct ints — the episode slot of each sample,
+    default 0 .. R-1 — and the answer is {"response": [R][chunk][action_dim]} in request order (MemVLAForCausalLM.
+    inference_action_batch).  The prefill takes no padding mask: samples whose prompts tokenise to different lengths are served
+    as one call per length, each on its own slot ids — a slot is stepped only by the call that names it.  ``num_slots``: how many
+    episodes the model holds (default: what the first batched request needs).  The single episode and the slots share the model,
+    not an episode, and a single-frame request with 'True' resets the whole memory bank, the slots included."""
+
+    def __init__(self, model, tokenizer, norm_stats: Optional[dict] = None, port: int = 7891, cfg_scale: float = 1.5,
+                 num_ddim_steps: int = 10, num_slots: Optional[int] = None, log: Optional[Callable[[str], None]] = None):
+        super().__init__(model, tokenizer, norm_stats, port, cfg_scale, num_ddim_steps, " ", log)
+        self.num_slots = num_slots
+
+    def parse_request(self, text, n_images: int, episode_first_frame, batch_size, slots=None):
+        """the host-only part of a batched request: -> (R, views per sample, R texts, R flags, R slot ids)"""
+        try:
+            R = int(batch_size)
+        except (TypeError, ValueError):
+            raise ValueError(f"process_frame: batch_size {batch_size!r} is not a number") from None
+        if R < 1 or n_images < R or n_images % R != 0:
+            raise ValueError(f"process_frame: {n_images} image(s) do not divide into batch_size {R} samples")
+        texts = _json_list(text, R, "text", str)
+        if texts is None:
+            if not isinstance(text, str):
+                raise ValueError(f"process_frame: text is one string or a list of {R} strings")
+            texts = [text] * R
+        flags = _json_list(episode_first_frame, R, "episode_first_frame", str)
+        if flags is None:
+            flags = [episode_first_frame] * R
+        if any(f not in ("True", "False") for f in flags):
+            raise ValueError(f"process_frame: episode_first_frame is 'True' or 'False' (one for all or a list of {R}), got {flags!r}")
+        ids = list(range(R)) if slots is None else _json_list(slots, R, "slots", int)
+        if ids is None:
+            raise ValueError(f"process_frame: slots is a list of {R} ints, got {slots!r}")
+        if len(set(ids)) != R or min(ids) < 0:
+            raise ValueError(f"process_frame: slots {ids} are not {R} distinct non-negative ints")
+        return R, n_images // R, texts, flags, ids
+
+    def get_response(self, text, images: List, episode_first_frame, batch_size=None, slots=None, noise=None) -> list:
+        """images: file-like objects / paths holding PNG (or anything PIL opens).  Without ``batch_size``: memvla_exp.py:317-358,
+        [chunk][action_dim].  With it: [batch_size][chunk][action_dim], see the class.  ``noise`` injects the sampler's initial
+        draw ([1 | batch_size, chunk, action_dim])."""
+        from PIL import Image
+        t0 = time.monotonic()
+        images = list(images)
+        kw = {} if noise is None else {"noise": noise}
+        if batch_size is None:
+            if episode_first_frame not in ("True", "False"):
+                raise ValueError(f"process_frame: episode_first_frame is 'True' or 'False', got {episode_first_frame!r}")
+            frames = [Image.open(f).convert("RGB") for f in images]
+            pix = self.model.process_images(frames).to(dtype=self.model.dtype)
+            if len(frames) > 1:
+                pix = pix.unsqueeze(0)                               # [1, views, 3, H, W]
+            ids = tokenizer_image_token(self.build_prompt(text), self.tokenizer, IMAGE_TOKEN_INDEX, return_tensors="pt")
+            with torch.no_grad():
+                out = self.model.inference_action(ids.unsqueeze(0).to(self.model.device), pix, episode_first_frame,
+                                                  dict(self.inference_args), **kw)
+            self.last_ms = 1e3 * (time.monotonic() - t0)
+            if self.log:
+                self.log(f"process_frame[memvla]: {len(frames)} view(s), first frame {episode_first_frame}, {self.last_ms:.1f} ms")
+            return out
+        R, views, texts, flags, slot_ids = self.parse_request(text, len(images), episode_first_frame, batch_size, slots)
+        frames = [Image.open(f).convert("RGB") for f in images]
+        pix = self.model.process_images(frames).to(dtype=self.model.dtype)
+        if views > 1:
+            pix = pix.view(R, views, *pix.shape[1:])
+        ids = [tokenizer_image_token(self.build_prompt(t), self.tokenizer, IMAGE_TOKEN_INDEX, return_tensors="pt") for t in texts]
+        out = [None] * R
+        with torch.no_grad():
+            for n in sorted({int(i.numel()) for i in ids}):        # one call per prompt length, each on its own slots
+                rows = [b for b in range(R) if int(ids[b].numel()) == n]
+                sub = {} if noise is None else {"noise": noise[rows]}
+                chunks = self.model.inference_action_batch(
+                    torch.stack([ids[b] for b in rows], 0).to(self.model.device), pix[rows] if len(rows) < R else pix,
+                    [flags[b] for b in rows], dict(self.inference_args), slots=[slot_ids[b] for b in rows],
+                    num_slots=self.num_slots, **sub)
+                for b, c in zip(rows, chunks):
+                    out[b] = c
+        self.last_ms = 1e3 * (time.monotonic() - t0)
+        if self.log:
+            self.log(f"process_frame[memvla]: {R} episode(s) x {views} view(s), slots {slot_ids}, {self.last_ms:.1f} ms")
+        return out
+
+    def inference_single(self, image_path, prompt: str, episode_first_frame: str = "True") -> list:
+        paths = [image_path] if isinstance(image_path, (str, bytes)) or hasattr(image_path, "read") else list(image_path)
+        return self.get_response(prompt, paths, episode_first_frame)
+
+    def create_app(self):
+        from flask import Flask, jsonify, request
+        app = Flask(__name__)
+
+        def process_frame():
+            files = [io.BytesIO(f.read()) for f in request.files.getlist("image")]
+            answer = self.get_response(request.form.get("text"), files, request.form.get("episode_first_frame"),
+                                       batch_size=request.form.get("batch_size"), slots=request.form.get("slots"))
+            return jsonify({"response": answer})
+
+        app.add_url_rule("/process_frame", "process_frame", process_frame, methods=["POST"])
+        return app
 
 
 def read_normalization_stats(path: Optional[str]) -> dict:

@@ -727,6 +727,22 @@ int dxa_bank_append(void* feat, float* ts, const int32_t* counts, const void* sr
  * Also refuses mem_length outside [1, cap). */
 int dxa_bank_consolidate_batched(void* feat, float* ts, const int32_t* counts, int count_add, int mem_length, int fifo,
                                  float* sims, int64_t B, int64_t cap, int64_t N, int64_t D, int dtype, dxa_stream_t stream);
+/* The same three steps on a chosen subset of the slots, in any order (served episodes tick at different rates, join and
+ * leave): feat [S, cap, N, D], ts [S, cap] are the banks of S slots; slot_ids [R] int32 (device), R <= S, DISTINCT (the host
+ * that owns the list checks).  Row r of the call reads / writes slot slot_ids[r]; counts [R], tokens / src [R, N, D],
+ * timesteps [R], mem [R, cap, N, D], ts_eff [R, cap], kv_len [R] and the scratch sims [R (cap - 1)] are indexed by the row.
+ * The device code is the code above (the slot lookup is the only difference): per row bit-identical to the call above on the
+ * gathered slots.  Slots not named are not touched.  An id outside [0, S) makes its row a no-op: nothing is appended or
+ * merged, and stage_fwd writes the row's outputs as for a slot without history.  Refusals as above, plus R > S and S <= 0. */
+int dxa_bank_stage_fwd_at(const void* feat, const float* ts, const int32_t* slot_ids, const int32_t* counts, const void* tokens,
+                          const float* timesteps, void* mem, float* ts_eff, int32_t* kv_len, int64_t R, int64_t S, int64_t cap,
+                          int64_t N, int64_t D, int dtype, dxa_stream_t stream);
+int dxa_bank_append_at(void* feat, float* ts, const int32_t* slot_ids, const int32_t* counts, const void* src,
+                       const float* timesteps, int64_t R, int64_t S, int64_t cap, int64_t N, int64_t D, int dtype,
+                       dxa_stream_t stream);
+int dxa_bank_consolidate_batched_at(void* feat, float* ts, const int32_t* slot_ids, const int32_t* counts, int count_add,
+                                    int mem_length, int fifo, float* sims, int64_t R, int64_t S, int64_t cap, int64_t N,
+                                    int64_t D, int dtype, dxa_stream_t stream);
 /* out[r,n,:] = (x ? x[r,n,:] : 0) + alpha g[r,:]: the timestep embedding added to every token of a bank entry
  * (memvla_arch.py:352-360); x = NULL: broadcast of a row over the tokens (backward of the token mean, :139-141) */
 int dxa_add_rows(const void* x, const void* g, void* out, int64_t R, int64_t Nn, int64_t C, float alpha, int dtype,
