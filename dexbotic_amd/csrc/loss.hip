@@ -2,7 +2,7 @@
 //   dxa_cross_entropy_fwd/bwd : HF ForCausalLMLoss (transformers/loss/loss_utils.py) as called from
 //                               dexbotic/model/dexbotic_arch.py:488 — logits upcast to fp32, mean over the
 //                               non-ignored (already shifted) labels.
-//   dxa_argmax_rows           : torch.argmax over the vocabulary (first index among equal maxima), the greedy
+//   dxa_argmax_rows           : torch.argmax over the vocabulary (first index among equal maxima, a NaN the maximum), the greedy
 //                               choice of GenerationMixin.generate(do_sample=False) (discrete_vla_arch.py:33-41).
 //   dxa_cross_entropy_rows_bwd, dxa_ce_sample_reduce, dxa_expectile_loss : MuVLA's per-sample normalised, reward-weighted loss and its
 //                               reward head's expectile regression (dexbotic/model/muvla/muvla_arch.py:559-592).
@@ -19,15 +19,19 @@ __global__ __launch_bounds__(256) void argmax_rows_k(const T* __restrict__ xin, 
                                                      int64_t cols) {
   __shared__ float red_v[4];
   __shared__ int64_t red_i[4];
+  __shared__ int red_n[4];
   const T* x = xin + (int64_t)blockIdx.x * ld;
   float best = -INFINITY;
   int64_t idx = INT64_MAX;
+  bool saw_nan = false;
   for (int64_t i = (int64_t)threadIdx.x * VEC; i < cols; i += 256 * VEC) {
     float v[VEC];
     Vec<T, VEC>::ld(v, x + i);
 #pragma unroll
-    for (int e = 0; e < VEC; ++e)
-      if (v[e] > best || (v[e] == best && i + e < idx)) { best = v[e]; idx = i + e; }
+    for (int e = 0; e < VEC; ++e) {
+      saw_nan |= (v[e] != v[e]);
+      if (v[e] > best) { best = v[e]; idx = i + e; }    // a thread meets its columns in ascending order: an equal later one never wins
+    }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -36,12 +40,36 @@ __global__ __launch_bounds__(256) void argmax_rows_k(const T* __restrict__ xin, 
     if (v2 > best || (v2 == best && i2 < idx)) { best = v2; idx = i2; }
   }
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) { red_v[w] = best; red_i[w] = idx; }
+  const bool wave_nan = __ballot(saw_nan) != 0;
+  if (lane == 0) { red_v[w] = best; red_i[w] = idx; red_n[w] = wave_nan; }
   __syncthreads();
+  if (red_n[0] | red_n[1] | red_n[2] | red_n[3]) {      // rare, uniform over the workgroup: NaN is the maximum, the FIRST one wins (torch)
+    int64_t first = INT64_MAX;
+    for (int64_t i = (int64_t)threadIdx.x * VEC; i < cols; i += 256 * VEC) {
+      float v[VEC];
+      Vec<T, VEC>::ld(v, x + i);
+#pragma unroll
+      for (int e = 0; e < VEC; ++e)
+        if (v[e] != v[e] && i + e < first) first = i + e;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const int64_t i2 = __shfl_xor(first, o, 64);
+      if (i2 < first) first = i2;
+    }
+    if (lane == 0) red_i[w] = first;                    // (no wave reads red_i on this path before the barrier below)
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int i = 1; i < 4; ++i)
+        if (red_i[i] < first) first = red_i[i];
+      out[blockIdx.x] = first;
+    }
+    return;
+  }
   if (threadIdx.x == 0) {
     for (int i = 1; i < 4; ++i)
       if (red_v[i] > best || (red_v[i] == best && red_i[i] < idx)) { best = red_v[i]; idx = red_i[i]; }
-    out[blockIdx.x] = idx == INT64_MAX ? 0 : idx;       // all -inf / NaN row: index 0 like torch
+    out[blockIdx.x] = idx == INT64_MAX ? 0 : idx;       // all -inf row: index 0 like torch
   }
 }
 
@@ -52,13 +80,17 @@ __global__ __launch_bounds__(1024) void argmax_rows_wide_k(const bf16_t* __restr
                                                            int cols) {
   __shared__ float red_v[16];
   __shared__ int red_i[16];
+  __shared__ int red_n[16];
   const bf16_t* x = xin + (int64_t)blockIdx.x * ld;
   float best = -INFINITY;
   int idx = INT_MAX;
+  bool saw_nan = false;
   auto take = [&](const float (&v)[8], int i) {
 #pragma unroll
-    for (int e = 0; e < 8; ++e)
-      if (v[e] > best || (v[e] == best && i + e < idx)) { best = v[e]; idx = i + e; }
+    for (int e = 0; e < 8; ++e) {
+      saw_nan |= (v[e] != v[e]);
+      if (v[e] > best) { best = v[e]; idx = i + e; }    // a thread meets its columns in ascending order: an equal later one never wins
+    }
   };
   int i = (int)threadIdx.x * 8;
   for (; i + 1024 * 8 < cols; i += 2 * 1024 * 8) {             // cols % 8 == 0: a thread's 8 columns are all inside or all outside
@@ -80,12 +112,35 @@ __global__ __launch_bounds__(1024) void argmax_rows_wide_k(const bf16_t* __restr
     if (v2 > best || (v2 == best && i2 < idx)) { best = v2; idx = i2; }
   }
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) { red_v[w] = best; red_i[w] = idx; }
+  const bool wave_nan = __ballot(saw_nan) != 0;
+  if (lane == 0) { red_v[w] = best; red_i[w] = idx; red_n[w] = wave_nan; }
   __syncthreads();
+  int any_nan = 0;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) any_nan |= red_n[k];
+  if (any_nan) {                                        // rare, uniform over the workgroup: NaN is the maximum, the FIRST one wins (torch)
+    int first = INT_MAX;
+    for (int j = (int)threadIdx.x * 8; j < cols; j += 1024 * 8) {
+      float v[8];
+      Vec<bf16_t, 8>::ld(v, x + j);
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (v[e] != v[e] && j + e < first) first = j + e;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o, 64));
+    if (lane == 0) red_i[w] = first;                    // (no wave reads red_i on this path before the barrier below)
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int k = 1; k < 16; ++k) first = min(first, red_i[k]);
+      out[blockIdx.x] = first;
+    }
+    return;
+  }
   if (threadIdx.x == 0) {
     for (int k = 1; k < 16; ++k)
       if (red_v[k] > best || (red_v[k] == best && red_i[k] < idx)) { best = red_v[k]; idx = red_i[k]; }
-    out[blockIdx.x] = idx == INT_MAX ? 0 : idx;         // all -inf / NaN row: index 0 like torch
+    out[blockIdx.x] = idx == INT_MAX ? 0 : idx;         // all -inf row: index 0 like torch
   }
 }
 
@@ -155,9 +210,10 @@ __global__ __launch_bounds__(256) void soft_ce_fwd_k(const T* __restrict__ logit
 #pragma unroll
     for (int e = 1; e < VEC; ++e) vm = fmaxf(vm, v[e]);
     const float mn = fmaxf(m, vm);
-    float acc = s * expf(m - mn);          // m = -inf on the first visit: s = 0, exp(-inf) = 0
+    const float sh = fmaxf(mn, -3.4028235e38f);  // (-FLT_MAX) nothing but -inf seen yet: a finite shift, so every term is exp(-inf) = 0, not exp(NaN)
+    float acc = s * expf(m - sh);          // m = -inf on the first visit: s = 0, exp(-inf) = 0
 #pragma unroll
-    for (int e = 0; e < VEC; ++e) acc += expf(v[e] - mn);
+    for (int e = 0; e < VEC; ++e) acc += expf(v[e] - sh);    // a NaN entry (fmaxf passes it by) makes s NaN for good
     m = mn; s = acc;
   }
   // fold (m, s) pairs: wave shuffle, then the 4 waves through LDS
@@ -165,7 +221,8 @@ __global__ __launch_bounds__(256) void soft_ce_fwd_k(const T* __restrict__ logit
   for (int o = 32; o > 0; o >>= 1) {
     const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
     const float mn = fmaxf(m, m2);
-    s = (mn == -INFINITY) ? 0.f : s * expf(m - mn) + s2 * expf(m2 - mn);
+    const float sh = (mn == -INFINITY) ? 0.f : mn;        // as in the loop above: 0 + 0, and a NaN sum stays NaN
+    s = s * expf(m - sh) + s2 * expf(m2 - sh);
     m = mn;
   }
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -175,7 +232,8 @@ __global__ __launch_bounds__(256) void soft_ce_fwd_k(const T* __restrict__ logit
     float M = red_m[0], S = red_s[0];
     for (int i = 1; i < 4; ++i) {
       const float mn = fmaxf(M, red_m[i]);
-      S = (mn == -INFINITY) ? 0.f : S * expf(M - mn) + red_s[i] * expf(red_m[i] - mn);
+      const float sh = (mn == -INFINITY) ? 0.f : mn;
+      S = S * expf(M - sh) + red_s[i] * expf(red_m[i] - sh);
       M = mn;
     }
     const float lse = M + logf(S);

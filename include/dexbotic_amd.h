@@ -826,11 +826,17 @@ int dxa_scale_dev(float* x, int64_t n, const float* s, dxa_stream_t stream);
  *   row r AFTER the one-position shift; rows with labels == ignore_index contribute nothing.
  *   fwd: row_loss[r] = logsumexp(logits[r]) - logits[r, label] (fp32 math on fp32 or bf16 logits), lse[r] saved.
  *        loss = sum(row_loss) / #non-ignored rows is taken by the caller (dxa_colsum).
+ *        Non-finite logits are torch's (F.cross_entropy, torch.logsumexp): a -inf entry has probability 0 and gradient 0 and
+ *        lse runs over the rest; a label on a -inf entry gives row_loss = +inf; a row of nothing but -inf has lse = -inf
+ *        (row_loss 0 and dlogits 0 when its label is ignored); a NaN anywhere in a row gives lse = NaN, and row_loss = NaN
+ *        unless the label is ignored, for that row only.
  *   bwd: dlogits[r, v] = (exp(logits[r, v] - lse[r]) - [v == label]) * gscale[0] * scale  (gscale: device scalar
  *        = upstream gradient or NULL for 1; scale = 1 / #non-ignored rows).  dlogits may alias logits.
  * dxa_argmax_rows: out[r] = first index of the row maximum — torch.argmax, the greedy choice inside
  *   GenerationMixin.generate(do_sample=False) that DiscreteVLAForCausalLM decodes with
- *   (dexbotic/model/discrete_vla/discrete_vla_arch.py:33-41).  Integer result, must equal the reference's.
+ *   (dexbotic/model/discrete_vla/discrete_vla_arch.py:33-41).  Integer result, must equal the reference's: a NaN counts as the
+ *   maximum (the first NaN's index when a row holds one, as torch.argmax and the bin argmax of oft.hip), -0 equals +0, and a row
+ *   of nothing but -inf gives 0.
  * ---------------------------------------------------------------------------------------------- */
 int dxa_cross_entropy_fwd(const void* logits, int64_t ld, const int64_t* labels, float* row_loss, float* lse,
                           int64_t rows, int64_t V, int64_t ignore_index, int dtype, dxa_stream_t stream);

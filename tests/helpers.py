@@ -1,5 +1,6 @@
 """Shared test helpers: build the PRODUCT policy (dexbotic_amd) at an OracleConfig shape with the
 deterministic synthetic weights of oracle/weights.py."""
+import ctypes as C
 import os
 
 import numpy as np
@@ -87,3 +88,32 @@ def build_lm_product(cfg: O.OracleConfig, weights, compute_dtype="float32", devi
     m = (cls or DexboticForCausalLM)(dc, device=device, train=train)
     m.load_state_dict({k: torch.from_numpy(v) for k, v in weights.items()}, strict=True)
     return m
+
+
+# ------------------------------------------------------------- the kernel a captured launch holds (route tests)
+class KernelNodeParams(C.Structure):
+    _fields_ = [("blockDim", C.c_uint * 3), ("extra", C.c_void_p), ("func", C.c_void_p), ("gridDim", C.c_uint * 3),
+                ("kernelParams", C.c_void_p), ("sharedMemBytes", C.c_uint)]
+
+
+def _hip():
+    hip = C.CDLL("libamdhip64.so")            # torch's copy (already mapped: same soname)
+    hip.hipKernelNameRefByPtr.restype = C.c_char_p
+    hip.hipKernelNameRefByPtr.argtypes = [C.c_void_p, C.c_void_p]
+    return hip
+
+
+def _captured_kernel(graph, stream):
+    """(name, gridDim.x) of the single kernel node of a captured graph"""
+    hip = _hip()
+    n = C.c_size_t(0)
+    assert hip.hipGraphGetNodes(C.c_void_p(graph), None, C.byref(n)) == 0
+    nodes = (C.c_void_p * max(1, n.value))()
+    assert hip.hipGraphGetNodes(C.c_void_p(graph), nodes, C.byref(n)) == 0
+    assert n.value == 1, f"{n.value} nodes captured"
+    t = C.c_int(-1)
+    assert hip.hipGraphNodeGetType(C.c_void_p(nodes[0]), C.byref(t)) == 0 and t.value == 0      # hipGraphNodeTypeKernel
+    prm = KernelNodeParams()
+    assert hip.hipGraphKernelNodeGetParams(C.c_void_p(nodes[0]), C.byref(prm)) == 0
+    name = hip.hipKernelNameRefByPtr(C.c_void_p(prm.func), C.c_void_p(stream))
+    return (name.decode() if name else None), int(prm.gridDim[0])

@@ -19,6 +19,7 @@ import torch
 
 from tests import elementwise_cases as E
 from tests import elementwise_ref as R
+from tests.helpers import _captured_kernel
 
 pytestmark = pytest.mark.gpu
 
@@ -158,34 +159,6 @@ def _call(case, o, stream):
     if e == "permute":
         return lib.dxa_permute_bshd(a("src"), a("dst"), p["B"], p["S"], p["H"], p["D"], p["to_head"], t, stream)
     raise AssertionError(e)
-
-
-class KernelNodeParams(C.Structure):
-    _fields_ = [("blockDim", C.c_uint * 3), ("extra", C.c_void_p), ("func", C.c_void_p), ("gridDim", C.c_uint * 3),
-                ("kernelParams", C.c_void_p), ("sharedMemBytes", C.c_uint)]
-
-
-def _hip():
-    hip = C.CDLL("libamdhip64.so")            # torch's copy (already mapped: same soname)
-    hip.hipKernelNameRefByPtr.restype = C.c_char_p
-    hip.hipKernelNameRefByPtr.argtypes = [C.c_void_p, C.c_void_p]
-    return hip
-
-
-def _captured_kernel(graph, stream):
-    """(name, gridDim.x) of the single kernel node of a captured graph"""
-    hip = _hip()
-    n = C.c_size_t(0)
-    assert hip.hipGraphGetNodes(C.c_void_p(graph), None, C.byref(n)) == 0
-    nodes = (C.c_void_p * max(1, n.value))()
-    assert hip.hipGraphGetNodes(C.c_void_p(graph), nodes, C.byref(n)) == 0
-    assert n.value == 1, f"{n.value} nodes captured"
-    t = C.c_int(-1)
-    assert hip.hipGraphNodeGetType(C.c_void_p(nodes[0]), C.byref(t)) == 0 and t.value == 0      # hipGraphNodeTypeKernel
-    prm = KernelNodeParams()
-    assert hip.hipGraphKernelNodeGetParams(C.c_void_p(nodes[0]), C.byref(prm)) == 0
-    name = hip.hipKernelNameRefByPtr(C.c_void_p(prm.func), C.c_void_p(stream))
-    return (name.decode() if name else None), int(prm.gridDim[0])
 
 
 def _capture(case, ops, side):
